@@ -6,6 +6,9 @@
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
     python bench.py --gpus N --workload cfg3               (cfg2 network, bf16 operands: BASELINE cfg3)
     python bench.py --gpus N --workload cfg4               (sliding-window inference, tiles sharded over the ranks)
+    python bench.py ... --dump-outputs DIR                 (also write what the last timed step computed, DIR/<name>.npy:
+                                                             the same arguments give the same inputs, so two builds
+                                                             can be compared output for output)
 
 A "step" is one iteration of the reference's training loop (segmentation_trainer.py:162-180:
 train() -> forward -> criterion -> zero_grad -> backward -> optimizer.step -> eval()) on one
@@ -202,6 +205,34 @@ def roofline_of(prof, precision, full_prof=None, traffic=True):
     return out
 
 
+# --dump-outputs: at most 64 MB in all; an output with more elements than DUMP_MAX_ELEMS is written as a sample of that
+# many elements at fixed flat indices (seeded, sorted), the parameters as a smaller sample of the same kind
+DUMP_BUDGET_BYTES = 64 << 20
+DUMP_MAX_ELEMS = 6 << 20
+DUMP_PARAM_ELEMS = 1 << 20
+
+
+def dump_sample(t, n=DUMP_MAX_ELEMS):
+    """t flattened, or its elements at n fixed flat indices (the same indices for the same numel) when it has more"""
+    flat = t.detach().reshape(-1)
+    if flat.numel() <= n:
+        return t.detach()
+    idx = torch.randperm(flat.numel(), generator=torch.Generator().manual_seed(0))[:n].sort().values
+    return flat[idx.to(flat.device)]
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: name -> tensor as dirname/<name>.npy (float64 stays float64, everything else becomes float32)"""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    host = {k: (v.detach().double() if v.dtype == torch.float64 else v.detach().float()).cpu().numpy() for k, v in arrays.items()}
+    total = sum(a.nbytes for a in host.values())
+    assert total <= DUMP_BUDGET_BYTES, f"--dump-outputs: {total} bytes exceed the {DUMP_BUDGET_BYTES} byte budget"
+    for k, a in host.items():
+        np.save(os.path.join(dirname, k + ".npy"), a)
+    print(f"bench.py: wrote {len(host)} arrays ({total / 2**20:.1f} MiB) to {dirname}", file=sys.stderr)
+
+
 def _timed(fn, warmup=1, reps=3):
     """BASELINE.md section 3 / SURVEY section 8d protocol for the CPU leg: `warmup` untimed + `reps` timed iterations -> (mean s, last result)"""
     out = None
@@ -307,8 +338,15 @@ def parse_args(argv=None):
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-infer", action="store_true")
     ap.add_argument("--no-cfg3", action="store_true", help="skip the extra bf16 (BASELINE cfg3) and fp32_mfma measurements of the cfg2 / fp32 line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy "
+                         "(float32 / float64, rank 0; outputs above %d elements as a fixed, seeded sample)" % DUMP_MAX_ELEMS)
     ap.add_argument("--launch-probe", default=None, help=argparse.SUPPRESS)   # tests: each rank writes its env here and exits
     args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
     if args.workload == "cfg3":
         args.workload, args.precision = "cfg2", args.precision or "bf16"
     args.precision = args.precision or "fp32"
@@ -469,10 +507,20 @@ def run_train(args, rank, world, device, force_ddp, precision=None):
     barrier()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        loss_dict, _ = train_step(runner, crit, opt, predictor, batch, device)
+        loss_dict, step_batch = train_step(runner, crit, opt, predictor, batch, device)
     barrier()
     elapsed = time.perf_counter() - t0
     prof, ops.CONV_PROFILE = ops.CONV_PROFILE, None
+    # --dump-outputs: what the last timed step returned (loss terms, probabilities) and the parameters it left behind,
+    # taken before the phase-breakdown steps below update them again
+    dump = None
+    if args.dump_outputs and not extra and rank == 0:
+        dump = {f"train_{k}": v for k, v in loss_dict.items() if torch.is_tensor(v) and v.is_floating_point()}
+        dump["train_y_pred"] = dump_sample(step_batch["y_pred"])
+        dump["train_params_sample"] = dump_sample(torch.cat([p.detach().reshape(-1) for p in model.parameters()]),
+                                                  DUMP_PARAM_ELEMS)
+        dump = {k: v.cpu() for k, v in dump.items()}
+    del step_batch
     elapsed = max_over_ranks(elapsed, device)
     value = world * args.batch * args.steps / elapsed
 
@@ -501,9 +549,12 @@ def run_train(args, rank, world, device, force_ddp, precision=None):
             barrier()
             t0 = time.perf_counter()
             for _ in range(args.steps):
-                model(x)
+                p_inf = model(x)
             barrier()
             ti = time.perf_counter() - t0
+            if dump is not None:
+                dump["infer_y_pred"] = dump_sample(p_inf).cpu()
+            del p_inf
             # roofline of the inference path: the same K forwards once more with the dominant kernel's launches
             # event-timed (outside the timed loop: in the 16-bit modes ~20 launches of a 2.3 ms forward carry events)
             ops.CONV_PROFILE = [] if rank == 0 else None
@@ -518,6 +569,8 @@ def run_train(args, rank, world, device, force_ddp, precision=None):
     gc.unfreeze()
     if rank != 0:
         return None
+    if dump is not None:
+        dump_outputs(args.dump_outputs, dump)
     # ---- roofline of the dominant conv kernel of the timed train region (and of the inference region) ----
     roofline = roofline_of(prof, precision, prof_w)
     if infer is not None and prof_inf:
@@ -624,6 +677,9 @@ def run_window(args, rank, world, device):
     digest = float(out_vol.double().sum())     # identical on every rank count (aggregation is in grid order)
     if rank != 0:
         return None
+    if args.dump_outputs:
+        # (the volume of the last timed step: the phase-table passes above write their own output)
+        dump_outputs(args.dump_outputs, {"window_y_pred": dump_sample(out_vol)})
     phases = {k: v / 2 * 1e3 for k, v in timings.items()}
     serial = sum(v for k, v in phases.items() if k in ("exchange", "accumulate", "finalize", "aggregate"))
     out = {
