@@ -106,9 +106,10 @@ __global__ __launch_bounds__(256) void norm_bwd_apply_c8_kernel(
     const float* __restrict__ x, const float* __restrict__ dy, const float* __restrict__ mean,
     const float* __restrict__ rstd, const float* __restrict__ gamma, const float* __restrict__ beta,
     const float* __restrict__ stat_m, float* __restrict__ dx, HT* __restrict__ dx16, int C, int64_t S, int groups,
-    int act, float slope, int64_t xbs, int64_t ybs, int64_t dx16bs) {
+    int act, float slope, int64_t xbs, int64_t ybs, int64_t dx16bs, int* __restrict__ oflag) {
   using hx8 = typename H16<HT>::x8;
   const int cb = blockIdx.y, n = blockIdx.z;
+  bool sat = false;   // fp16: the c8 twin of a loss-scaled dx had to be clamped (reported at the end)
   const int c0 = cb * 8, nc = min(8, C - c0);
   float m[8], r[8], g[8], sc[8], sh[8], m1[8], m2[8];
 #pragma unroll
@@ -152,12 +153,13 @@ __global__ __launch_bounds__(256) void norm_bwd_apply_c8_kernel(
         const float pre = fmaf(xv[u][j], sc[j], sh[j]);
         const float gg = dv[u][j] * act16_grad(pre, act, slope) * g[j];
         const float v = r[j] * (gg - m1[j] - xh * m2[j]);
-        o[j] = (HT)(j < nc ? v : 0.f);
+        o[j] = to_h16_sat<HT>(j < nc ? v : 0.f, sat);
         if (j < nc) op[(int64_t)j * S + i] = v;
       }
       dst[i] = o;
     }
   }
+  report_saturation(sat, oflag);
 }
 
 int launch_norm_bwd_apply_c8(const float* x, const float* dy, const float* mean, const float* rstd, const float* gamma,
@@ -168,10 +170,10 @@ int launch_norm_bwd_apply_c8(const float* x, const float* dy, const float* mean,
   dim3 grid(bx, (unsigned)c8_blocks(C), (unsigned)N);
   if (compute == M355_COMPUTE_BF16)
     hipLaunchKernelGGL(norm_bwd_apply_c8_kernel<__bf16>, grid, dim3(256), 0, st, x, dy, mean, rstd, gamma, beta, stat_m, dx,
-                       (__bf16*)dx16, C, S, groups, act, slope, xbs, ybs, dx16bs);
+                       (__bf16*)dx16, C, S, groups, act, slope, xbs, ybs, dx16bs, nullptr);
   else
     hipLaunchKernelGGL(norm_bwd_apply_c8_kernel<_Float16>, grid, dim3(256), 0, st, x, dy, mean, rstd, gamma, beta, stat_m,
-                       dx, (_Float16*)dx16, C, S, groups, act, slope, xbs, ybs, dx16bs);
+                       dx, (_Float16*)dx16, C, S, groups, act, slope, xbs, ybs, dx16bs, overflow_flag());
   return check_launch("norm_bwd_apply_c8");
 }
 

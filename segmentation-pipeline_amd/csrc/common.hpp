@@ -90,8 +90,12 @@ int num_cus();
 // zero-initialised, self-resetting work-queue state (16 ints) of this (device, stream): abi.cpp
 int* queue_state(hipStream_t st);
 // fp16 training flow: the caller's overflow word of the current device (m355_overflow_flag_set), or null.  Kernels that
-// round a loss-scaled gradient to fp16 OR bit 0 into it when a value had to be clamped to +-65504 (to_h16_sat), the
-// epilogues that remove the loss scale from a parameter gradient OR bit 1 when the result is not finite.
+// round a loss-scaled gradient to fp16 (the c8 data gradients of conv and conv-transpose included) OR bit 0 into it when
+// a value had to be clamped to +-65504 (to_h16_sat; a NaN is not clamped: it stays NaN and sets no bit there), the
+// epilogues that remove the loss scale from a parameter gradient OR bit 1 when the result is not finite -- whenever the
+// word is installed, whatever the unscale factor (1.0 included).  fp16 FORWARD activations of the c8 conv epilogue
+// saturate the same way but are not reported: the word is about the loss scale, and lowering it cannot bring a forward
+// value back into range.  bf16 neither clamps nor reports.
 int* overflow_flag();
 
 }  // namespace m355

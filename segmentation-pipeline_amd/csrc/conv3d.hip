@@ -1529,10 +1529,10 @@ static void launch_slab_reduce_t(const float* slab, float* dw, int Cin, int Cout
   for (int c = 0; c < 4; ++c) max_ns = std::max(max_ns, k.ns[c]);
   if ((int64_t)Cout * ctiles < 2 * (int64_t)num_cus() && max_ns >= 16)
     hipLaunchKernelGGL(slab_reduce_tap_kernel, dim3((unsigned)Cout, (unsigned)ctiles, 27u), dim3(256), 0, st, slab, dw, Cin,
-                       Cout, k, scale, scale != 1.f ? overflow_flag() : nullptr);
+                       Cout, k, scale, overflow_flag());
   else
     hipLaunchKernelGGL(slab_reduce_t_kernel, dim3((unsigned)Cout, (unsigned)ctiles), dim3(256), 0, st, slab, dw, Cin, Cout,
-                       k, scale, scale != 1.f ? overflow_flag() : nullptr);
+                       k, scale, overflow_flag());
 }
 
 // ------------------------------------------- bwd-weight, tiny channel count on one side
@@ -2151,8 +2151,9 @@ static int run_mfma_conv(const float* in, const float* w, bool transpose, int Co
                          int mout, int D, int H, int W, int64_t in_bs, int64_t out_bs, void* ws,
                          size_t ws_bytes, hipStream_t st, int compute = M355_COMPUTE_F32, float* stat = nullptr,
                          const void* in16 = nullptr, int64_t in16_bs = 0, const void* prepacked = nullptr,
-                         bool out16 = false, bool softmax = false) {
+                         bool out16 = false, bool softmax = false, int* oflag = nullptr) {
   // prepacked: weights already packed for this plan by m355_conv3d_pack (M355_CONV_W_PACKED); `w` is then unused
+  // oflag: overflow word of a c8 data gradient (fp16 only: the stores saturate and report there, common.hpp)
   const FwdPlan p = plan_mfma(N, kin, mout, D, H, W, compute);
   M355_REQUIRE(!stat || p.ksplit == 1 || !is16(compute) || out16, M355_EINVALID_ARG,
                "conv3d_fwd_stats: no fused statistics for this plan (m355_conv3d_stats_slots() == 0)");
@@ -2170,7 +2171,7 @@ static int run_mfma_conv(const float* in, const float* w, bool transpose, int Co
       in16 = stage;
     }
     return run_h16_conv(p, compute, in16, in16_bs, w, transpose, Cout_w, Cin_w, bias, add, out, N, kin, mout, D, H, W,
-                        out_bs, ws, ws_bytes, st, stat, prepacked, out16, softmax);
+                        out_bs, ws, ws_bytes, st, stat, prepacked, out16, softmax, oflag);
   }
   M355_REQUIRE(!softmax, M355_EUNSUPPORTED, "conv3d: no fused softmax in the fp32 MFMA kernels");
   M355_REQUIRE(ws_bytes >= p.wp_bytes + p.slab_bytes, M355_EWORKSPACE,
@@ -2727,7 +2728,8 @@ extern "C" int m355_conv3d_bwd_data_h16_c8(const m355_conv3d_desc* d, const void
   return run_mfma_conv(nullptr, packed ? nullptr : w, true, d->Cout, d->Cin, nullptr, nullptr, (float*)dx16, d->N, d->Cout,
                        d->Cin, d->D, d->H, d->W, 0, dense_or(dx16_batch_stride, c8_blocks(d->Cin) * S * 8), workspace,
                        workspace_bytes, (hipStream_t)stream, d->compute, nullptr, dy16,
-                       dense_or(dy16_batch_stride, c8_blocks(d->Cout) * S * 8), packed ? w : nullptr, true);
+                       dense_or(dy16_batch_stride, c8_blocks(d->Cout) * S * 8), packed ? w : nullptr, true, false,
+                       d->compute == M355_COMPUTE_F16 ? overflow_flag() : nullptr);
 }
 
 extern "C" size_t m355_conv3d_bwd_weight_c8_workspace(const m355_conv3d_desc* d) {

@@ -258,9 +258,11 @@ template <typename HT>
 __global__ __launch_bounds__(256) void splitk_reduce_c8_kernel(const float* __restrict__ slab,
                                                                const float* __restrict__ bias, HT* __restrict__ y16,
                                                                int Cout, int64_t S, int ksplit, int64_t slab_stride,
-                                                               int64_t ybs16, float* __restrict__ stat) {
+                                                               int64_t ybs16, float* __restrict__ stat,
+                                                               int* __restrict__ oflag) {
   using hx8 = typename H16<HT>::x8;
   __shared__ float red[4][16];
+  bool sat = false;
   const int cb = blockIdx.y, n = blockIdx.z;
   const int c0 = cb * 8, nc = min(8, Cout - c0);
   const float* sp = slab + ((int64_t)n * Cout + c0) * S;
@@ -296,12 +298,13 @@ __global__ __launch_bounds__(256) void splitk_reduce_c8_kernel(const float* __re
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       const float t = j < nc ? v[j] + bv[j] : 0.f;
-      o[j] = (HT)t;
+      o[j] = to_h16_sat<HT>(t, sat);
       s1[j] += t;
       s2[j] = fmaf(t, t, s2[j]);
     }
     dst[i] = o;
   }
+  report_saturation(sat, oflag);
   if (!stat) return;
 #pragma unroll
   for (int j = 0; j < 8; ++j) {
@@ -381,7 +384,7 @@ __global__ __launch_bounds__(NW * 64, (NW == 8 ? 1 : (NTW <= 4 ? 2 : 1))) void c
     const float* __restrict__ add, float* __restrict__ y, float* __restrict__ slab, int CB, int Cout, int D, int H,
     int W, int cout_pad, int tz_tiles, int ty_tiles, int tx_tiles, int otiles, int nchunks, int ksplit, int nbatch,
     int64_t xbs16, int64_t ybs, int64_t slab_stride, float* __restrict__ stat, int* __restrict__ work_counter,
-    int stagger, int softmax, int order) {
+    int stagger, int softmax, int order, int* __restrict__ oflag) {
   using T = FwdTile<NTW, GX>;
   using hx8 = typename H16<HT>::x8;
   constexpr int GY = T::GY, TZ = NW, TY = T::TY, TX = T::TX, RS = T::RS, PS = T::PS, HV = (TZ + 2) * PS;
@@ -396,6 +399,7 @@ __global__ __launch_bounds__(NW * 64, (NW == 8 ? 1 : (NTW <= 4 ? 2 : 1))) void c
   __shared__ __attribute__((aligned(16))) hx8 xs[DB ? 2 : 1][XI];
   __shared__ __attribute__((aligned(16))) hx8 ws[DB ? 2 : 1][WI];
   __shared__ int next_item_s;
+  bool sat = false;                              // an fp16 c8 output value was clamped (store_conv_tile_c8)
 
 #ifdef M355_H16_STAMPS
   const unsigned long long r_entry = __builtin_amdgcn_s_memrealtime();
@@ -717,7 +721,7 @@ __global__ __launch_bounds__(NW * 64, (NW == 8 ? 1 : (NTW <= 4 ? 2 : 1))) void c
         float* st = stat ? stat + (((int64_t)cur.n * sp_tiles + cur.sp) * NW + wave) * Cout * 2 : nullptr;
         if constexpr (OUT16)
           store_conv_tile_c8<NTW, GY, HT>(acc, reinterpret_cast<HT*>(y) + (int64_t)cur.n * ybs, bias, cur.o0, Cout, z,
-                                          cur.y0, xg, ly, half, H, W, (int64_t)S, lane_ok, st);
+                                          cur.y0, xg, ly, half, H, W, (int64_t)S, lane_ok, st, sat);
         else if (softmax)   // (host: Cout <= 4, one channel tile, no residual, no statistics)
           store_conv_tile_softmax<NTW, GY>(acc, y + (int64_t)cur.n * ybs, bias, Cout, z, cur.y0, xg, ly, half, D, H, W,
                                            lane_ok);
@@ -748,6 +752,7 @@ __global__ __launch_bounds__(NW * 64, (NW == 8 ? 1 : (NTW <= 4 ? 2 : 1))) void c
     o[7] |= (unsigned long long)__builtin_amdgcn_s_getreg((3 << 11) | (0 << 6) | 20) << 32;   // HW_REG_XCC_ID
   }
 #endif
+  if constexpr (OUT16) report_saturation(sat, oflag);
   if constexpr (!ONE) queue_leave(work_counter);
 }
 
@@ -764,7 +769,7 @@ template <int NTW, typename HT>
 __global__ __launch_bounds__(256, 2) void conv3_c4_h16_kernel(
     const HT* __restrict__ x16, const HT* __restrict__ wp, const float* __restrict__ bias, HT* __restrict__ y16, int Cout,
     int D, int H, int W, int cout_pad, int tz_tiles, int ty_tiles, int tx_tiles, int otiles, int64_t xbs16, int64_t ybs16,
-    float* __restrict__ stat) {
+    float* __restrict__ stat, int* __restrict__ oflag) {
   using hx8 = typename H16<HT>::x8;
   constexpr int TZ = 4, TY = NTW, RS = 34, PS = (TY + 2) * RS, HV = (TZ + 2) * PS;
   __shared__ __attribute__((aligned(16))) uint2 xs[HV];        // channels 0..3 of every halo voxel
@@ -821,19 +826,22 @@ __global__ __launch_bounds__(256, 2) void conv3_c4_h16_kernel(
   }
   const int z = z0 + wave, xg = x0 + l32;
   float* st = stat ? stat + (((int64_t)n * sp_tiles + sp) * 4 + wave) * Cout * 2 : nullptr;
+  bool sat = false;
   store_conv_tile_c8<NTW, 1, HT>(acc, y16 + (int64_t)n * ybs16, bias, ot * 32, Cout, z, y0, xg, 0, half, H, W, S,
-                                 z < D && xg < W, st);
+                                 z < D && xg < W, st, sat);
+  report_saturation(sat, oflag);
 }
 
 template <typename HT>
 static bool launch_c4_h16(const FwdPlan& p, const HT* x16, int64_t xbs16, const HT* wp, const float* bias, HT* y16, int N,
-                          int mout, int D, int H, int W, int64_t ybs16, hipStream_t st, float* stat) {
+                          int mout, int D, int H, int W, int64_t ybs16, hipStream_t st, float* stat, int* oflag) {
   const int64_t items = (int64_t)p.tz_tiles * p.ty_tiles * p.tx_tiles * p.otiles * N;
   if (items <= 0 || items >= (1ll << 31)) return false;
   const dim3 grid((unsigned)items);
 #define M355_C4(NTW)                                                                                                   \
   hipLaunchKernelGGL((conv3_c4_h16_kernel<NTW, HT>), grid, dim3(256), 0, st, x16, wp, bias, y16, mout, D, H, W, p.mout_pad, \
-                     p.tz_tiles, p.ty_tiles, p.tx_tiles, p.otiles, xbs16, ybs16, stat)
+                     p.tz_tiles, p.ty_tiles, p.tx_tiles, p.otiles, xbs16, ybs16, stat, \
+                     oflag)
   if (p.ntw == 4) M355_C4(4); else if (p.ntw == 2) M355_C4(2); else if (p.ntw == 1) M355_C4(1); else return false;
 #undef M355_C4
   return true;
@@ -1005,7 +1013,8 @@ static bool launch_cout4_h16(const FwdPlan& p, const HT* x16, int64_t xbs16, con
 template <int NTW, int GX, typename HT>
 static void launch_h16(const FwdPlan& p, const HT* x16, int64_t xbs16, const HT* wp, const float* bias,
                        const float* add, float* y, float* slab, int N, int kin, int mout, int D, int H, int W,
-                       int64_t ybs, hipStream_t st, float* stat, int* work_counter, bool out16, int softmax) {
+                       int64_t ybs, hipStream_t st, float* stat, int* work_counter, bool out16, int softmax,
+                       int* oflag) {
   const int64_t items = (int64_t)p.tz_tiles * p.ty_tiles * p.tx_tiles * p.otiles * N * p.ksplit;
   const int64_t slots = tuning().conv_slots ? tuning().conv_slots : (p.nw == 8 ? 1 : (NTW <= 4 ? 2 : 1)) * num_cus();
   const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(items, slots));
@@ -1016,11 +1025,11 @@ static void launch_h16(const FwdPlan& p, const HT* x16, int64_t xbs16, const HT*
       if (out16 && p.ksplit == 1)
         hipLaunchKernelGGL((conv3_h16_kernel<NTW, GX, HT, true, 4, true>), dim3(g1), dim3(256), 0, st, x16, wp, bias, add, y,
                            slab, (int)c8_blocks(kin), mout, D, H, W, p.mout_pad, p.tz_tiles, p.ty_tiles, p.tx_tiles,
-                           p.otiles, p.nchunks, p.ksplit, N, xbs16, ybs, slab_stride, stat, work_counter, tuning().h16_xcd, softmax, tuning().h16_order);
+                           p.otiles, p.nchunks, p.ksplit, N, xbs16, ybs, slab_stride, stat, work_counter, tuning().h16_xcd, softmax, tuning().h16_order, oflag);
       else
         hipLaunchKernelGGL((conv3_h16_kernel<NTW, GX, HT, false, 4, true>), dim3(g1), dim3(256), 0, st, x16, wp, bias, add, y,
                            slab, (int)c8_blocks(kin), mout, D, H, W, p.mout_pad, p.tz_tiles, p.ty_tiles, p.tx_tiles,
-                           p.otiles, p.nchunks, p.ksplit, N, xbs16, ybs, slab_stride, stat, work_counter, tuning().h16_xcd, softmax, tuning().h16_order);
+                           p.otiles, p.nchunks, p.ksplit, N, xbs16, ybs, slab_stride, stat, work_counter, tuning().h16_xcd, softmax, tuning().h16_order, oflag);
       return;
     }
   }
@@ -1029,22 +1038,22 @@ static void launch_h16(const FwdPlan& p, const HT* x16, int64_t xbs16, const HT*
       if (out16 && p.ksplit == 1)
         hipLaunchKernelGGL((conv3_h16_kernel<NTW, GX, HT, true, 8>), dim3(grid), dim3(512), 0, st, x16, wp, bias, add, y,
                            slab, (int)c8_blocks(kin), mout, D, H, W, p.mout_pad, p.tz_tiles, p.ty_tiles, p.tx_tiles,
-                           p.otiles, p.nchunks, p.ksplit, N, xbs16, ybs, slab_stride, stat, work_counter, 0, softmax, tuning().h16_order);
+                           p.otiles, p.nchunks, p.ksplit, N, xbs16, ybs, slab_stride, stat, work_counter, 0, softmax, tuning().h16_order, oflag);
       else
         hipLaunchKernelGGL((conv3_h16_kernel<NTW, GX, HT, false, 8>), dim3(grid), dim3(512), 0, st, x16, wp, bias, add, y,
                            slab, (int)c8_blocks(kin), mout, D, H, W, p.mout_pad, p.tz_tiles, p.ty_tiles, p.tx_tiles,
-                           p.otiles, p.nchunks, p.ksplit, N, xbs16, ybs, slab_stride, stat, work_counter, 0, softmax, tuning().h16_order);
+                           p.otiles, p.nchunks, p.ksplit, N, xbs16, ybs, slab_stride, stat, work_counter, 0, softmax, tuning().h16_order, oflag);
       return;
     }
   }
   if (out16 && p.ksplit == 1)
     hipLaunchKernelGGL((conv3_h16_kernel<NTW, GX, HT, true>), dim3(grid), dim3(256), 0, st, x16, wp, bias, add, y, slab,
                        (int)c8_blocks(kin), mout, D, H, W, p.mout_pad, p.tz_tiles, p.ty_tiles, p.tx_tiles, p.otiles,
-                       p.nchunks, p.ksplit, N, xbs16, ybs, slab_stride, stat, work_counter, tuning().h16_stagger, softmax, tuning().h16_order);
+                       p.nchunks, p.ksplit, N, xbs16, ybs, slab_stride, stat, work_counter, tuning().h16_stagger, softmax, tuning().h16_order, oflag);
   else
     hipLaunchKernelGGL((conv3_h16_kernel<NTW, GX, HT, false>), dim3(grid), dim3(256), 0, st, x16, wp, bias, add, y, slab,
                        (int)c8_blocks(kin), mout, D, H, W, p.mout_pad, p.tz_tiles, p.ty_tiles, p.tx_tiles, p.otiles,
-                       p.nchunks, p.ksplit, N, xbs16, ybs, slab_stride, stat, work_counter, tuning().h16_stagger, softmax, tuning().h16_order);
+                       p.nchunks, p.ksplit, N, xbs16, ybs, slab_stride, stat, work_counter, tuning().h16_stagger, softmax, tuning().h16_order, oflag);
 }
 
 template <typename HT>
@@ -1067,8 +1076,9 @@ template <typename HT>
 static int run_h16_conv_t(const FwdPlan& p, const HT* in16, int64_t in16_bs, const float* w, bool transpose,
                           int Cout_w, int Cin_w, const float* bias, const float* add, float* out, int N, int kin,
                           int mout, int D, int H, int W, int64_t out_bs, void* ws, size_t ws_bytes, hipStream_t st,
-                          float* stat, const void* prepacked, bool out16, bool softmax) {
+                          float* stat, const void* prepacked, bool out16, bool softmax, int* oflag) {
   // out16: `out` is a c8 tensor of the same 16-bit type (out_bs in elements of it); `add` must be null
+  // oflag: the overflow word the c8 stores report a saturated fp16 value to (null: saturate silently)
   M355_REQUIRE(ws_bytes >= p.wp_bytes + p.slab_bytes, M355_EWORKSPACE,
                "conv3d(16-bit operands): workspace too small (%zu < %zu)", ws_bytes, p.wp_bytes + p.slab_bytes);
   M355_REQUIRE(((uintptr_t)ws & 15) == 0 && ((uintptr_t)in16 & 15) == 0 && (in16_bs % 8) == 0, M355_EINVALID_ARG,
@@ -1090,7 +1100,7 @@ static int run_h16_conv_t(const FwdPlan& p, const HT* in16, int64_t in16_bs, con
   const float* ka = p.ksplit == 1 ? add : nullptr;
   // edge layers with <= 4 K-channels and a c8 output: four taps per k-step (conv3_c4_h16_kernel)
   if (kin <= 4 && out16 && p.ksplit == 1 && p.gx == 32 && p.nw == 4 && !softmax && !tuning().no_small &&
-      launch_c4_h16<HT>(p, in16, in16_bs, wpb, kb, (HT*)out, N, mout, D, H, W, out_bs, st, stat))
+      launch_c4_h16<HT>(p, in16, in16_bs, wpb, kb, (HT*)out, N, mout, D, H, W, out_bs, st, stat, oflag))
     return check_launch("conv3_c4_h16");
   // output convolution (<= 4 M-channels, fp32 result, optional softmax): tap rows folded onto the MFMA's M side
   if (mout <= 4 && !out16 && !ka && !stat && p.ksplit == 1 && p.gx == 32 && p.nw == 4 && p.ntw == 4 && p.otiles == 1 &&
@@ -1099,7 +1109,7 @@ static int run_h16_conv_t(const FwdPlan& p, const HT* in16, int64_t in16_bs, con
 #define M355_H16_CASE(NTW, GX)                                                                               \
   if (p.ntw == NTW && p.gx == GX) {                                                                          \
     launch_h16<NTW, GX, HT>(p, in16, in16_bs, wpb, kb, ka, out, slab, N, kin, mout, D, H, W, out_bs, st,       \
-                            p.ksplit == 1 ? stat : nullptr, work_counter, out16, softmax ? 1 : 0);                                                          \
+                            p.ksplit == 1 ? stat : nullptr, work_counter, out16, softmax ? 1 : 0, oflag);                                                        \
   } else
   M355_H16_CASE(4, 32) M355_H16_CASE(2, 32) M355_H16_CASE(1, 32)
   M355_H16_CASE(4, 16) M355_H16_CASE(2, 16) M355_H16_CASE(1, 16)
@@ -1112,7 +1122,7 @@ static int run_h16_conv_t(const FwdPlan& p, const HT* in16, int64_t in16_bs, con
     const int64_t S = (int64_t)D * H * W;
     dim3 grid((unsigned)splitk_c8_slots(S), (unsigned)c8_blocks(mout), (unsigned)N);
     hipLaunchKernelGGL(splitk_reduce_c8_kernel<HT>, grid, dim3(256), 0, st, slab, bias, (HT*)out, mout, S, p.ksplit,
-                       (int64_t)N * mout * S, out_bs, stat);
+                       (int64_t)N * mout * S, out_bs, stat, oflag);
   } else if (p.ksplit > 1) {
     const int64_t S = (int64_t)D * H * W;
     const int64_t total = (int64_t)N * mout * S;
@@ -1126,12 +1136,12 @@ static int run_h16_conv_t(const FwdPlan& p, const HT* in16, int64_t in16_bs, con
 int run_h16_conv(const FwdPlan& p, int compute, const void* in16, int64_t in16_bs, const float* w, bool transpose,
                  int Cout_w, int Cin_w, const float* bias, const float* add, float* out, int N, int kin, int mout,
                  int D, int H, int W, int64_t out_bs, void* ws, size_t ws_bytes, hipStream_t st, float* stat,
-                 const void* prepacked, bool out16, bool softmax) {
+                 const void* prepacked, bool out16, bool softmax, int* oflag) {
   if (compute == M355_COMPUTE_BF16)
     return run_h16_conv_t<__bf16>(p, (const __bf16*)in16, in16_bs, w, transpose, Cout_w, Cin_w, bias, add, out, N, kin,
-                                  mout, D, H, W, out_bs, ws, ws_bytes, st, stat, prepacked, out16, softmax);
+                                  mout, D, H, W, out_bs, ws, ws_bytes, st, stat, prepacked, out16, softmax, nullptr);
   return run_h16_conv_t<_Float16>(p, (const _Float16*)in16, in16_bs, w, transpose, Cout_w, Cin_w, bias, add, out, N,
-                                  kin, mout, D, H, W, out_bs, ws, ws_bytes, st, stat, prepacked, out16, softmax);
+                                  kin, mout, D, H, W, out_bs, ws, ws_bytes, st, stat, prepacked, out16, softmax, oflag);
 }
 
 

@@ -687,7 +687,7 @@ __global__ void convt_dx_reduce_kernel(const float* __restrict__ slab, float* __
 template <typename HT, int MTW>
 __global__ __launch_bounds__(256) void convt_k2s2_bwd_data_h16_kernel(
     const HT* __restrict__ dy16, const float* __restrict__ w, HT* __restrict__ dx16, int Cin, int Cout, int D, int H, int W,
-    int64_t ybs16, int64_t xbs16, int mt_per_wg) {
+    int64_t ybs16, int64_t xbs16, int mt_per_wg, int* __restrict__ oflag) {
   using hx8 = typename H16<HT>::x8;
   extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
   hx8* afrag = reinterpret_cast<hx8*>(lds_raw);  // [m-tile of this workgroup][k-step][lane]
@@ -736,6 +736,7 @@ __global__ __launch_bounds__(256) void convt_k2s2_bwd_data_h16_kernel(
   const int OH = 2 * H, OW = 2 * W;
   const int64_t OS = (int64_t)S * 8;
   const hx8 zero = {};
+  bool sat = false;   // fp16: a scaled dx value was clamped to +-65504 (reported at the end)
   for (int vt = blockIdx.x; (int64_t)vt * 128 < S; vt += gridDim.x) {
     const int v = vt * 128 + wave * 32 + l32;
     const bool vok = v < S;
@@ -784,13 +785,14 @@ __global__ __launch_bounds__(256) void convt_k2s2_bwd_data_h16_kernel(
           if (cb < CBin) {
             hx8 o;
 #pragma unroll
-            for (int j = 0; j < 8; ++j) o[j] = (HT)(cb * 8 + j < Cin ? acc[q][u * 8 + j] : 0.f);
+            for (int j = 0; j < 8; ++j) o[j] = to_h16_sat<HT>(cb * 8 + j < Cin ? acc[q][u * 8 + j] : 0.f, sat);
             xo[(int64_t)cb * S + v] = o;
           }
         }
       }
     }
   }
+  report_saturation(sat, oflag);
 }
 
 // ---- weight gradient  dW[c, o, t] = sum_v X[c, v] * dY[o, 2v + t]:  M = Cin, N = Cout (per t), K = voxels.
@@ -1429,7 +1431,8 @@ extern "C" int m355_conv_transpose3d_bwd_data_h16(const m355_conv3d_desc* d, con
   const size_t lds = (size_t)mt_per_wg * nks * 1024;
 #define M355_CTBD(HT, MTW)                                                                                            \
   hipLaunchKernelGGL((convt_k2s2_bwd_data_h16_kernel<HT, MTW>), grid, dim3(256), lds, st, (const HT*)dy16, w, (HT*)dx16, \
-                     d->Cin, d->Cout, d->D, d->H, d->W, ybs, xbs, mt_per_wg)
+                     d->Cin, d->Cout, d->D, d->H, d->W, ybs, xbs, mt_per_wg,                                      \
+                     compute == M355_COMPUTE_F16 ? overflow_flag() : nullptr)
 #define M355_CTBD_T(HT)                                                  \
   if (mt_per_wg == 1) M355_CTBD(HT, 1); else if (mt_per_wg == 2) M355_CTBD(HT, 2); else M355_CTBD(HT, 4);
   if (compute == M355_COMPUTE_BF16) { M355_CTBD_T(__bf16) } else { M355_CTBD_T(_Float16) }
@@ -1470,7 +1473,7 @@ extern "C" int m355_conv_transpose3d_bwd_weight_h16(const m355_conv3d_desc* d, c
 #undef M355_CTBW
   const int64_t total = (int64_t)d->Cin * d->Cout * 8;
   hipLaunchKernelGGL(convt_slab_reduce_t_kernel, dim3((unsigned)ceil_div(total, 64)), dim3(256), 0, st, slab, dw, d->Cin,
-                     d->Cout, nsplit, grad_unscale, grad_unscale != 1.f ? overflow_flag() : nullptr);
+                     d->Cout, nsplit, grad_unscale, overflow_flag());
   if (dbias) {
     const size_t slab_b = (size_t)round_up((int64_t)nsplit * 8 * d->Cin * d->Cout * 4, 256);
     if (int rc = launch_dbias_c8(dy16, ybs, dbias, d->N, d->Cout, S * 8, compute, grad_unscale, (char*)workspace + slab_b, st))

@@ -41,8 +41,9 @@ __device__ __forceinline__ __bf16 to_h16_sat<__bf16>(float v) { return (__bf16)v
 template <>
 __device__ __forceinline__ _Float16 to_h16_sat<_Float16>(float v) {
   // a scaled gradient past the fp16 range saturates instead of becoming inf (which would turn every downstream sum
-  // into NaN); NaN stays NaN
-  return (_Float16)fminf(fmaxf(v, -65504.f), 65504.f);
+  // into NaN); NaN stays NaN -- a select, not fminf / fmaxf, which return the other operand of a NaN (v_max_f32 /
+  // v_min_f32: a NaN gradient came out as -65504, finite and unreported)
+  return (_Float16)(fabsf(v) > 65504.f ? copysignf(65504.f, v) : v);
 }
 
 // the same, remembering in `sat` that a value was clamped (the kernel ORs bit 0 into the overflow word at its end)
@@ -52,8 +53,9 @@ template <>
 __device__ __forceinline__ __bf16 to_h16_sat<__bf16>(float v, bool&) { return (__bf16)v; }
 template <>
 __device__ __forceinline__ _Float16 to_h16_sat<_Float16>(float v, bool& sat) {
-  sat = sat || fabsf(v) > 65504.f;
-  return (_Float16)fminf(fmaxf(v, -65504.f), 65504.f);
+  const bool big = fabsf(v) > 65504.f;   // (false for NaN: a NaN is not clamped, it stays NaN)
+  sat = sat || big;
+  return (_Float16)(big ? copysignf(65504.f, v) : v);
 }
 __device__ __forceinline__ void report_saturation(bool sat, int* __restrict__ oflag) {
   if (sat && oflag) atomicOr(oflag, 1);

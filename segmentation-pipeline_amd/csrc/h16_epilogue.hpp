@@ -11,13 +11,15 @@ namespace m355 {
 // lanes: block q, upper lanes: block q+1) and stores it with a single 16-byte instruction: 8 store
 // instructions per lane and tile (NTW = 4) instead of the 64 dword stores of the fp32 NCDHW epilogue, which
 // was the largest fixed cost of a short-K item (store-issue bound, ~9k cycles of a ~24k-cycle item).
+// fp16: values past +-65504 are stored saturated and remembered in `sat` (to_h16_sat; bf16: the plain rounding) -- the
+// kernel reports it once at its end, when the launcher handed it the overflow word (data gradients only, common.hpp).
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 template <int NTW, int GY, typename HT>
 __device__ __forceinline__ void store_conv_tile_c8(const f32x16 (&acc)[NTW], HT* __restrict__ dst16,
                                                    const float* __restrict__ bias, int o0, int Cout, int z, int y0,
                                                    int xg, int ly, int half, int H, int W, int64_t S, bool lane_ok,
-                                                   float* __restrict__ stat) {
+                                                   float* __restrict__ stat, bool& sat) {
   // Round 4: this tail is pure vector-ALU work (a wave64 instruction costs 4 cycles, and the edge-layer kernel -- 28 MFMAs
   // per tile -- spent most of its time here): bias add, statistics and the out-of-volume mask run on register PAIRS
   // (v_pk_add_f32 / v_pk_mul_f32 / v_pk_fma_f32: half the instructions, the same roundings), the mask is a multiply by
@@ -59,8 +61,8 @@ __device__ __forceinline__ void store_conv_tile_c8(const f32x16 (&acc)[NTW], HT*
       hx4 lo, hi;                     // this lane's 4 channels of block 2qp and of block 2qp + 1
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        lo[j] = (HT)v[(8 * qp + j) >> 1][(8 * qp + j) & 1];
-        hi[j] = (HT)v[(8 * qp + 4 + j) >> 1][(8 * qp + 4 + j) & 1];
+        lo[j] = to_h16_sat<HT>(v[(8 * qp + j) >> 1][(8 * qp + j) & 1], sat);
+        hi[j] = to_h16_sat<HT>(v[(8 * qp + 4 + j) >> 1][(8 * qp + 4 + j) & 1], sat);
       }
       uint2 X = __builtin_bit_cast(uint2, lo), Y = __builtin_bit_cast(uint2, hi);
       auto r0 = __builtin_amdgcn_permlane32_swap(X.x, Y.x, false, false);

@@ -626,7 +626,7 @@ int m355::launch_norm_bwd_reduce(const double* partial, const float* gamma, floa
   const int64_t count = groups == 0 ? (int64_t)N * S : (int64_t)(C / groups) * S;
   hipLaunchKernelGGL(norm_bwd_reduce_kernel, dim3((unsigned)std::max<int64_t>(nstats, C)), dim3(64), 0, st, partial, gamma,
                      dgamma, dbeta, stat_m, N, C, groups, nblk_c, count, training, count_ptr, grad_unscale,
-                     grad_unscale != 1.f ? overflow_flag() : nullptr);
+                     overflow_flag());
   return check_launch("norm_bwd_reduce");
 }
 

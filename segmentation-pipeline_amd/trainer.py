@@ -116,7 +116,7 @@ def train_step(model, criterion, optimizer, predictor, batch, device, timer: Opt
 class GraphedTrainStep:
     """One training iteration (train() -> forward -> criterion -> zero_grad -> backward -> optimizer.step, the order of
     segmentation_trainer.py:162-180) captured ONCE into a hipGraph and replayed: one launch per step instead of the
-    ~400 of a production architecture.  Where the step is host-bound -- msseg2 in the 16-bit modes: the GPU needs
+    ~400 of a production architecture.  Where the step is host-bound -- msseg2 in bf16: the GPU needs
     ~8 ms, the Python / ctypes enqueue ~10 ms -- the replay runs at GPU speed; where it is GPU-bound (cfg2, fp32
     anything) it changes nothing.  The loss trajectory is bit-identical to the plain eager loop, call by call (tests): the first
     `warmup` calls are eager steps on their own batches, the next call captures and replays.
@@ -128,7 +128,10 @@ class GraphedTrainStep:
     buffers.  Dropout3d is fine: its channel masks are drawn on the device with torch's CUDA generator, which advances its
     philox offset on every replay (a new mask per step; tools/graph_dropout_probe.py).  Not capturable (raises): BatchNorm
     with momentum=None (host read of num_batches_tracked), a PatchParallel wrapper (collectives); optimizers that read
-    state on the host need capturable=True (Adam)."""
+    state on the host need capturable=True (Adam).  Not for fp16 (raises): train_step skips the optimizer step when the
+    kernels raise the overflow word (ops.fp16_overflow / fp16_found_inf) and re-calibrates the loss scale; a replayed step
+    would apply an overflowed update to the weights and the optimizer state, and its loss scale is frozen at capture.
+    bf16 needs no loss scale and is captured as fp32 is."""
 
     def __init__(self, model, criterion, optimizer, warmup: int = 3):
         self.model, self.criterion, self.optimizer, self.warmup = model, criterion, optimizer, max(1, warmup)
@@ -142,6 +145,10 @@ class GraphedTrainStep:
         for m in self.model.modules():
             if isinstance(m, nn.BatchNorm3d) and m.momentum is None and m.track_running_stats:
                 raise NotImplementedError("GraphedTrainStep: BatchNorm3d(momentum=None) reads num_batches_tracked on the host")
+        if ops.get_precision() == "fp16":
+            raise NotImplementedError("GraphedTrainStep / SegmentedGraphTrainStep: fp16 steps are not captured -- a replay "
+                                      "cannot skip an overflowed optimizer step or re-calibrate the loss scale; use "
+                                      "trainer.train_step (or bf16)")
 
     def _eager(self, x, y):
         self.optimizer.zero_grad(set_to_none=True)
@@ -204,7 +211,8 @@ class SegmentedGraphTrainStep:
     wrapper).  `capture_collectives=True` (nccl only, default off until it has run on a multi-GPU box): ONE graph with
     the bucket hooks left on, the RCCL all-reduces recorded into it.
     Trajectory: the first `warmup` calls are eager train steps on their own batches (trainer.train_step order), like
-    GraphedTrainStep.  Not supported (raises): synchronised BatchNorm (its all-reduces sit inside the forward)."""
+    GraphedTrainStep.  Not supported (raises): synchronised BatchNorm (its all-reduces sit inside the forward), fp16 (the
+    overflow skip of train_step, see GraphedTrainStep)."""
 
     def __init__(self, ddp, criterion, optimizer, warmup: int = 3, capture_collectives: bool = False):
         if not isinstance(ddp, D.PatchParallel):

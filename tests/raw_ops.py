@@ -68,6 +68,36 @@ class RawOps:
             n = getattr(self.lib, "m355_" + qname)(C.byref(desc))
         return torch.empty(max(int(n), 16), dtype=torch.uint8, device=self.device)
 
+    # ------------------------------------------------- fp16 overflow word
+    def overflow_word(self):
+        """Context manager: installs a zeroed int32 device word as the library's overflow word of the current device
+        (m355_overflow_flag_set) and yields a reader `take()` -> the word's value, which also clears it.  On exit the
+        package's own word (ops._overflow_words) is installed again, or none when it had none -- HIP library only."""
+        import contextlib
+        from segmentation_pipeline_amd import ops
+        assert self.backend == "hip"
+        lib = self.lib
+
+        @contextlib.contextmanager
+        def cm():
+            idx = torch.cuda.current_device()
+            word = torch.zeros(1, dtype=torch.int32, device="cuda")
+            torch.cuda.synchronize()
+            self._chk(lib.m355_overflow_flag_set(_p(word), idx), "overflow_flag_set")
+
+            def take():
+                torch.cuda.synchronize()
+                v = int(word.item())
+                word.zero_()
+                return v
+            try:
+                yield take
+            finally:
+                torch.cuda.synchronize()
+                prev = ops._overflow_words.get(idx)
+                self._chk(lib.m355_overflow_flag_set(_p(prev), idx), "overflow_flag_set(restore)")
+        return cm()
+
     # ------------------------------------------------------------------ conv
     @staticmethod
     def conv_desc(x_shape, Cout, k, stride, pad, out_pad=0, xbs=0, ybs=0, compute=0):

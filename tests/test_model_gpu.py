@@ -190,6 +190,36 @@ def test_adam_trajectory_matches_reference(golden):
     np.testing.assert_allclose(ea[big], g["exp_avg_norms"][big], rtol=1e-2)
 
 
+@pytest.mark.parametrize("stepper", ["graphed", "segmented"])
+def test_graph_steppers_refuse_fp16(stepper):
+    """fp16 steps are not captured: trainer.train_step skips the optimizer step when the overflow word is set and
+    re-calibrates the loss scale, a replay could do neither (it would apply an overflowed update to the weights and the
+    optimizer state, with the scale frozen at capture).  Both steppers raise on the first call -- before anything ran:
+    weights and optimizer state untouched -- and the same stepper still works in bf16."""
+    import segmentation_pipeline_amd as sp
+    from segmentation_pipeline_amd import distributed as D
+    from segmentation_pipeline_amd.trainer import GraphedTrainStep, SegmentedGraphTrainStep
+    torch.manual_seed(0)
+    m = ModularUNet(4, 3, [8, 16], 2, block_params=dict(GN8), **CONVT).cuda().train()
+    opt = torch.optim.SGD(m.parameters(), lr=1e-2, momentum=0.9)
+    if stepper == "graphed":
+        step = GraphedTrainStep(m, HybridLogisticDiceLoss(), opt, warmup=1)
+    else:
+        step = SegmentedGraphTrainStep(D.PatchParallel(m), HybridLogisticDiceLoss(), opt, warmup=1)
+    g = torch.Generator().manual_seed(5)
+    x = torch.randn((1, 4, 16, 16, 16), generator=g).cuda()
+    y = torch.nn.functional.one_hot(torch.randint(0, 3, (1, 16, 16, 16), generator=g), 3).permute(0, 4, 1, 2, 3).float().cuda()
+    before = {k: v.clone() for k, v in m.state_dict().items()}
+    with sp.precision("fp16"):
+        with pytest.raises(NotImplementedError, match="fp16"):
+            step({"X": x, "y": y})
+    assert all(torch.equal(v, before[k]) for k, v in m.state_dict().items())
+    assert not opt.state
+    with sp.precision("bf16"):
+        for _ in range(3):
+            assert torch.isfinite(step({"X": x, "y": y})["loss"]).all()
+
+
 @pytest.mark.parametrize("mode", ["fp32", "bf16"])
 def test_adam_through_graphed_train_step(golden, mode):
     """GraphedTrainStep needs Adam(capturable=True) (the step counter lives on the device): the replayed trajectory is
