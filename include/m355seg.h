@@ -655,6 +655,43 @@ int m355_ensemble_accumulate(const float* pred, float* acc, int32_t* votes, int3
 int m355_ensemble_finalize(const float* acc, const int32_t* votes, float* mean_out, int64_t* onehot_out, int32_t N,
                            int32_t C, int64_t S, int32_t members, int32_t mode, void* stream);
 
+/* ------------------------------------------ connected components + post-processing
+ * skimage.morphology.label / remove_small_holes / dilation and the np.unique / torch.unique counts under
+ * post_processing.py (keep_components, remove_holes, remove_small_components) and
+ * evaluators/instance_segmentation_evaluator.py (lesion-wise detection).  Volumes are one int32 [D,H,W] map with
+ * fewer than 2^31 voxels (more: M355_EINVALID_ARG).
+ *   m355_ccl_label        connected components: mode 0 = non-zero voxels, neighbours connect when they hold the SAME
+ *                         value (multi-class, as skimage); mode 1 = voxels <= 0, all connect (the holes of x > 0).
+ *                         connectivity 1 / 2 / 3 = 6 / 18 / 26 neighbours.  labels: 0 background, 1..n numbered in
+ *                         raster order of each component's first voxel (scipy.ndimage.label's numbering).  *n_out
+ *                         (device int32) = n, or -1 when a bounded find / union loop hit its bound (labels then
+ *                         undefined).  Workspace: m355_ccl_workspace(D, H, W) bytes.
+ *   m355_label_histogram  counts[k - lo] (int64 [nbins], zeroed by the call) = voxels whose key k lies in
+ *                         [lo, lo + nbins): k = a[v] (b == NULL) or a[v] * bstride + b[v] (overlap table of two label
+ *                         maps).  minmax (int32[2], may be NULL; 1-D keys) receives min and max of a.
+ *   m355_masked_dilate6   one Jacobi step of the 6-neighbour grey dilation (ndi.grey_dilation, cross footprint; the
+ *                         volume border adds nothing), src -> dst (src != dst), changed only where
+ *                         flag[labels[v]] != 0.  class_rank == NULL: such a voxel takes the max of src over itself and
+ *                         its neighbours.  Otherwise keys are class_rank[src - lo] (0 for masked voxels) and a masked
+ *                         voxel whose neighbours' largest key K is > 0 takes rank_class[K].  *changed (device int64) =
+ *                         voxels with dst != src.
+ *   m355_label_convert_in / _out  boundary casts: dtype 0 uint8/bool, 1 int8, 2 int16, 3 int32, 4 int64.  in: op 0
+ *                         copy (int64 outside int32 sets *status), 1 (x == 0), 2 (x > 0).  out: dst = zero_where ?
+ *                         (zero_where[v] ? 0 : orig[v]) : src[v].
+ */
+size_t m355_ccl_workspace(int32_t D, int32_t H, int32_t W);
+int m355_ccl_label(const int32_t* x, int32_t* labels, int32_t* n_out, int32_t D, int32_t H, int32_t W,
+                   int32_t connectivity, int32_t mode, void* workspace, size_t ws_bytes, void* stream);
+int m355_label_histogram(const int32_t* a, const int32_t* b, int64_t nvox, int64_t bstride, int64_t lo, int64_t nbins,
+                         int64_t* counts, int32_t* minmax, void* stream);
+int m355_masked_dilate6(const int32_t* src, int32_t* dst, int32_t D, int32_t H, int32_t W, const int32_t* labels,
+                        const int32_t* flag, const int32_t* class_rank, const int32_t* rank_class, int32_t lo,
+                        int64_t* changed, void* stream);
+int m355_label_convert_in(const void* src, int32_t dtype, int32_t op, int32_t* dst, int64_t n, int32_t* status,
+                          void* stream);
+int m355_label_convert_out(const int32_t* src, const int32_t* zero_where, const void* orig, void* dst, int32_t dtype,
+                           int64_t n, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -157,6 +157,12 @@ SIGNATURES = {
                                            _i32, _P]),
     "m355_ensemble_finalize": (C.c_int, [_P, _P, _P, _P, _i32, _i32, _i64, _i32, _i32, _P]),
     "m355_argmax_confusion": (C.c_int, [_P, _P, _P, _P, _i32, _i32, _i64, _P]),
+    "m355_ccl_workspace": (_sz, [_i32, _i32, _i32]),
+    "m355_ccl_label": (C.c_int, [_P, _P, _P, _i32, _i32, _i32, _i32, _i32, _P, _sz, _P]),
+    "m355_label_histogram": (C.c_int, [_P, _P, _i64, _i64, _i64, _i64, _P, _P, _P]),
+    "m355_masked_dilate6": (C.c_int, [_P, _P, _i32, _i32, _i32, _P, _P, _P, _P, _i32, _P, _P]),
+    "m355_label_convert_in": (C.c_int, [_P, _i32, _i32, _P, _i64, _P, _P]),
+    "m355_label_convert_out": (C.c_int, [_P, _P, _P, _P, _i32, _i64, _P]),
 }
 
 
