@@ -692,6 +692,63 @@ int m355_label_convert_in(const void* src, int32_t dtype, int32_t op, int32_t* d
 int m355_label_convert_out(const int32_t* src, const int32_t* zero_where, const void* orig, void* dst, int32_t dtype,
                            int64_t n, void* stream);
 
+/* ------------------------------------------ training augmentation
+ * The per-voxel work of the torchio augmentation chains of the reference's production configs
+ * (research/dmri_hippo/configs/main_config.py:86-100, research/msseg2/msseg2.py:44-57); parameters are drawn on the
+ * host (augmentation.py).  Volumes are float32 [C, D, H, W] (label maps of the resample: 1-, 4- or 8-byte
+ * elements) with fewer than 2^31 voxels per channel.
+ *   m355_aug_resample     y[c, p] = x[c] at q = M p + t + B d(p) (mat12 = [M | t] row-major, host; disp9 = B, host,
+ *                         NULL = identity), p an index of the output size out3, q an index of the input size in3.  d =
+ *                         the cubic B-spline displacement of the control grid (device float [K0][K1][K2][3], in input
+ *                         voxels before B; NULL = none; grid3 = K, each >= 4) at u = (p + 0.5)(K - 3) / out3.  q inside
+ *                         when -0.5 <= q < in3 - 0.5 on every axis, else pad[c] (device double per channel; NULL =
+ *                         pad_const; 1- and 8-byte elements pad with 0).  interp 0 nearest clamp(floor(q + 0.5)),
+ *                         1 trilinear (neighbours clamped), 2 cubic B-spline on coefficients (m355_aug_prefilter) with
+ *                         mirrored neighbours; 1- and 8-byte elements: nearest only.  x != y.
+ *   m355_aug_prefilter    cubic B-spline coefficients of x in place (scipy spline_filter order 3, mode 'mirror').
+ *   m355_aug_order_stats  out[q] (device double, q < nq <= 2) = lerp(v[ks[q]], v[ks[q] + 1], fracs[q]) (numpy's _lerp;
+ *                         ks[q] + 1 capped at n - 1), v = the sorted values of ALL channels of x after the stage list.
+ *                         Exact radix select; ranks {0, n - 1} with fracs 0 take one min / max pass.  Workspace:
+ *                         m355_aug_workspace() bytes.  ks and fracs are host arrays.
+ *   m355_aug_intensity    y = x after the stage list (in place allowed).
+ *   m355_aug_blur         one axis of scipy gaussian_filter (mode 'reflect', radius int(4 sigma + 0.5), sigma in voxels),
+ *                         then the stage list (no M355_AUG_RESCALE) as an epilogue: the host passes the bias / gamma /
+ *                         noise stages that follow a blur to its last axis.  x != y.
+ *   m355_aug_otsu_pad     pad[c] (device double) = mean of the face voxels of channel c whose OTSU_BINS = 128-bin
+ *                         histogram bin lies at or below the Otsu split (all face voxels when none).
+ *   m355_aug_channel_minmax  out[c] (device double) = min (which 0) or max (which 1) of channel c, all channels in one
+ *                         pass.  Workspace: >= 8 * C bytes (m355_aug_workspace() covers C <= 4096). */
+#define M355_AUG_MAX_STAGES 8
+enum {
+  M355_AUG_BIAS = 0,     /* v *= exp(sum vec[j] x^a y^b z^c), a + b + c <= order, torchio's term order and coordinates */
+  M355_AUG_RESCALE = 1,  /* lo, hi = (float) stats[0..1] (device); lo == hi: unchanged; else clip, (v - lo) / (hi - lo) * (b - a) + a */
+  M355_AUG_GAMMA = 2,    /* v = sign(v) |v|^vec[channel] */
+  M355_AUG_NOISE = 3     /* v += a + b * N(0, 1), Philox4x32-10 keyed by seed, counter = element index, Box-Muller */
+};
+typedef struct {
+  int32_t op;
+  int32_t order;
+  float a, b;
+  uint64_t seed;
+  const double* stats;
+  const float* vec;
+} m355_aug_stage;
+int m355_aug_resample(const void* x, void* y, int32_t C, const int32_t* in3, const int32_t* out3, int32_t elem_bytes,
+                      int32_t interp, const double* mat12, const double* disp9, const float* grid, const int32_t* grid3,
+                      const double* pad, double pad_const, void* stream);
+int m355_aug_prefilter(float* x, int32_t C, const int32_t* size3, void* stream);
+size_t m355_aug_workspace(void);
+int m355_aug_order_stats(const float* x, int32_t C, const int32_t* size3, const m355_aug_stage* stages, int32_t nstages,
+                         int32_t nq, const int64_t* ks, const double* fracs, double* out, void* workspace,
+                         size_t ws_bytes, void* stream);
+int m355_aug_intensity(const float* x, float* y, int32_t C, const int32_t* size3, const m355_aug_stage* stages,
+                       int32_t nstages, void* stream);
+int m355_aug_blur(const float* x, float* y, int32_t C, const int32_t* size3, int32_t axis, double sigma,
+                  const m355_aug_stage* stages, int32_t nstages, void* stream);
+int m355_aug_otsu_pad(const float* x, int32_t C, const int32_t* size3, double* pad, void* stream);
+int m355_aug_channel_minmax(const float* x, int32_t C, const int32_t* size3, int32_t which, double* out,
+                           void* workspace, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -44,10 +44,20 @@ class NormDesc(C.Structure):
     ]
 
 
+class AugStage(C.Structure):
+    """m355_aug_stage"""
+    _fields_ = [("op", C.c_int32), ("order", C.c_int32), ("a", C.c_float), ("b", C.c_float), ("seed", C.c_uint64),
+                ("stats", C.c_void_p), ("vec", C.c_void_p)]
+
+
+AUG_BIAS, AUG_RESCALE, AUG_GAMMA, AUG_NOISE = 0, 1, 2, 3
+AUG_MAX_STAGES = 8
+
 _P = C.c_void_p
 ABI_VERSION = 3   # M355_ABI_VERSION of include/m355seg.h this binding was written against
 _i32, _i64, _f32, _sz = C.c_int32, C.c_int64, C.c_float, C.c_size_t
 _CD, _ND = C.POINTER(ConvDesc), C.POINTER(NormDesc)
+_I3, _D, _AS = C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(AugStage)
 
 # name -> (restype, argtypes); mirrors include/m355seg.h one to one
 SIGNATURES = {
@@ -163,6 +173,14 @@ SIGNATURES = {
     "m355_masked_dilate6": (C.c_int, [_P, _P, _i32, _i32, _i32, _P, _P, _P, _P, _i32, _P, _P]),
     "m355_label_convert_in": (C.c_int, [_P, _i32, _i32, _P, _i64, _P, _P]),
     "m355_label_convert_out": (C.c_int, [_P, _P, _P, _P, _i32, _i64, _P]),
+    "m355_aug_resample": (C.c_int, [_P, _P, _i32, _I3, _I3, _i32, _i32, _D, _D, _P, _I3, _P, C.c_double, _P]),
+    "m355_aug_prefilter": (C.c_int, [_P, _i32, _I3, _P]),
+    "m355_aug_workspace": (_sz, []),
+    "m355_aug_order_stats": (C.c_int, [_P, _i32, _I3, _AS, _i32, _i32, C.POINTER(C.c_int64), _D, _P, _P, _sz, _P]),
+    "m355_aug_intensity": (C.c_int, [_P, _P, _i32, _I3, _AS, _i32, _P]),
+    "m355_aug_blur": (C.c_int, [_P, _P, _i32, _I3, _i32, C.c_double, _AS, _i32, _P]),
+    "m355_aug_otsu_pad": (C.c_int, [_P, _i32, _I3, _P, _P]),
+    "m355_aug_channel_minmax": (C.c_int, [_P, _i32, _I3, _i32, _P, _P, _sz, _P]),
 }
 
 
