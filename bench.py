@@ -9,13 +9,19 @@
     python bench.py ... --dump-outputs DIR                 (also write what the last timed step computed, DIR/<name>.npy:
                                                              the same arguments give the same inputs, so two builds
                                                              can be compared output for output)
+    python bench.py ... --full                             (also everything beyond the headline: see below)
 
 A "step" is one iteration of the reference's training loop (segmentation_trainer.py:162-180:
 train() -> forward -> criterion -> zero_grad -> backward -> optimizer.step -> eval()) on one
 synthetic 1x4x128^3 patch per rank, with the 5-level GroupNorm/ConvTranspose U-Net
 (18.08 M params, fp32).  `value` = patches/s over all ranks for the K timed train steps
-(inputs resident in HBM).  The no-grad inference forward is timed the same way and
-reported under "infer".  One JSON line on rank 0.
+(inputs resident in HBM).  One JSON line on rank 0.
+
+A plain run does only what that line needs: set-up, the W warm-up and K timed steps, --dump-outputs, the line.  --full
+adds what takes work of its own: the no-grad inference forward timed the same way ("infer", with its roofline), the
+per-phase breakdown ("phases_ms"), the cfg3 / fp32_mfma legs of a cfg2 / fp32 line, the cfg4 phase table and output
+checks, and the CPU baseline with the Dice comparison against it (--no-infer, --no-cfg3 and --no-cpu-baseline leave
+parts of that out).
 """
 import argparse
 import gc
@@ -335,9 +341,13 @@ def parse_args(argv=None):
                          "BASELINE cfg3 / cfg5)")
     ap.add_argument("--bucket-dtype", default="fp32", choices=["fp32", "bf16"],
                     help="wire type of the gradient all-reduce buckets (bf16 halves the RCCL volume; fp32 master gradients)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-infer", action="store_true")
-    ap.add_argument("--no-cfg3", action="store_true", help="skip the extra bf16 (BASELINE cfg3) and fp32_mfma measurements of the cfg2 / fp32 line")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline: inference forwards, phase breakdown, the "
+                         "cfg3 / fp32_mfma legs, the CPU baseline and the Dice comparison with it (off: the headline only)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline and the Dice comparison")
+    ap.add_argument("--no-infer", action="store_true", help="skip the inference forwards (--dump-outputs then writes no infer_y_pred)")
+    ap.add_argument("--no-cfg3", action="store_true", help="with --full: skip the extra bf16 (BASELINE cfg3) and fp32_mfma measurements "
+                                                           "of the cfg2 / fp32 line")
     ap.add_argument("--dump-outputs", default=None, metavar="DIR",
                     help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy "
                          "(float32 / float64, rank 0; outputs above %d elements as a fixed, seeded sample)" % DUMP_MAX_ELEMS)
@@ -393,7 +403,7 @@ def main():
         out = run_window(args, rank, world, device)
     else:
         out = run_train(args, rank, world, device, force_ddp)
-        if args.workload == "cfg2" and args.precision == "fp32" and not args.no_cfg3:
+        if args.full and args.workload == "cfg2" and args.precision == "fp32" and not args.no_cfg3:
             # BASELINE cfg3 (same net, bf16 operands) under the same clock as the headline: K train steps + K forwards
             torch.cuda.empty_cache()
             c3 = run_train(args, rank, world, device, force_ddp, precision="bf16")
@@ -413,7 +423,7 @@ def main():
         return
     # The CPU leg runs on rank 0 after the process group is gone (the other ranks have left; no collective can time
     # out behind ~30 s of host work) and for every N, so each line of a scaling run carries its own baseline.
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         finish = out.pop("_cpu_leg")
         finish(out)
     out.pop("_cpu_leg", None)
@@ -475,13 +485,14 @@ def run_train(args, rank, world, device, force_ddp, precision=None):
     batch = {"X": x, "y": y}
 
     # ---- Dice vs CPU reference: first forward from the seed-0 weights, before any update ----
+    # (a plain run takes the device half too: the warm-up and timed steps start from the same state either way)
     model.eval()
     with torch.no_grad():
         p0 = model(x)
     am, counts = ops.argmax_confusion(p0, lab.to(torch.int32))
     gpu_dice0 = float(crit(p0, y)["dice_loss"])
     hard0 = hard_dice_from_counts(counts)[0].tolist()
-    p0_cpu, am_cpu_gpu, lab_cpu = (p0.cpu(), am.cpu().long(), lab.cpu()) if rank == 0 else (None, None, None)
+    p0_cpu, am_cpu_gpu, lab_cpu = (p0.cpu(), am.cpu().long(), lab.cpu()) if rank == 0 and args.full else (None, None, None)
 
     # The last warm-up step is event-timed launch by launch (per-op summary + which kernel dominates); inside the
     # timed region only the dominant kernel's launches carry timing events (the roofline measurement), so the
@@ -524,17 +535,26 @@ def run_train(args, rank, world, device, force_ddp, precision=None):
     elapsed = max_over_ranks(elapsed, device)
     value = world * args.batch * args.steps / elapsed
 
-    # per-phase breakdown (TorchTimer semantics: a sync per stamp), outside the timed region
+    # per-phase breakdown (TorchTimer semantics: a sync per stamp), outside the timed region.  The inference output
+    # --dump-outputs writes is that of the weights these two steps leave, so a plain run that dumps takes them too.
     phases = None
-    if not extra:
+    if not extra and (args.full or args.dump_outputs):
         timer = PhaseTimer(device)
         for _ in range(2):
             train_step(runner, crit, opt, predictor, batch, device, timer)
-        phases = {k: v / 2 * 1e3 for k, v in timer.timestamps.items()}
+        if args.full:
+            phases = {k: v / 2 * 1e3 for k, v in timer.timestamps.items()}
 
-    # ---- inference: K no-grad forwards ----
+    # ---- inference: K no-grad forwards (--full) ----
     infer, prof_inf = None, None
-    if not args.no_infer:
+    if not args.full:
+        if dump is not None and not args.no_infer:
+            # a plain run: the one forward whose output --dump-outputs writes (the same weights and input as the K
+            # timed forwards of --full)
+            model.eval()
+            with torch.no_grad():
+                dump["infer_y_pred"] = dump_sample(model(x)).cpu()
+    elif not args.no_infer:
         model.eval()
         with torch.no_grad():
             ops.CONV_PROFILE_KEYS, ops.CONV_PROFILE_EVERY = None, 1
@@ -608,7 +628,7 @@ def run_train(args, rank, world, device, force_ddp, precision=None):
         "final_loss": float(loss_dict["loss"].detach()),
         "dice": {"gpu_soft_dice_loss_step0": gpu_dice0, "gpu_hard_dice_step0": hard0},
     }
-    if args.workload == "cfg2" and precision == "fp32" and not args.no_cfg3:
+    if args.full and args.workload == "cfg2" and precision == "fp32" and not args.no_cfg3:
         out["_p0"] = p0   # compared with the fp32_mfma leg's first forward (main)
 
     def cpu_leg(out):
@@ -667,21 +687,24 @@ def run_window(args, rank, world, device):
         prof, ops.CONV_PROFILE = ops.CONV_PROFILE, None
         ops.CONV_PROFILE_KEYS = None
         elapsed = max_over_ranks(elapsed, device)
-        # phase table (a device synchronisation per stamp), outside the timed region
+        # phase table (a device synchronisation per stamp), outside the timed region (--full)
         timings = {}
-        pt = PatchPredict(patch_batch_size=1, patch_size=CFG4["patch"], patch_overlap=CFG4["overlap"], timings=timings)
-        for _ in range(2):
-            pt.predict_volume(model, vol)
-    s = out_vol.sum(0)
-    sum_err = float((s - 1).abs().max())
-    digest = float(out_vol.double().sum())     # identical on every rank count (aggregation is in grid order)
+        if args.full:
+            pt = PatchPredict(patch_batch_size=1, patch_size=CFG4["patch"], patch_overlap=CFG4["overlap"], timings=timings)
+            for _ in range(2):
+                pt.predict_volume(model, vol)
+    checks = None
+    if args.full:
+        s = out_vol.sum(0)
+        checks = {"max_abs_sum_p_minus_1": float((s - 1).abs().max()),
+                  "sum_of_probabilities": float(out_vol.double().sum())}   # identical on every rank count (grid order)
     if rank != 0:
         return None
     if args.dump_outputs:
         # (the volume of the last timed step: the phase-table passes above write their own output)
         dump_outputs(args.dump_outputs, {"window_y_pred": dump_sample(out_vol)})
-    phases = {k: v / 2 * 1e3 for k, v in timings.items()}
-    serial = sum(v for k, v in phases.items() if k in ("exchange", "accumulate", "finalize", "aggregate"))
+    phases = {k: v / 2 * 1e3 for k, v in timings.items()} if args.full else None
+    serial = sum(v for k, v in phases.items() if k in ("exchange", "accumulate", "finalize", "aggregate")) if phases else None
     out = {
         "metric": METRIC, "value": n_tiles * args.steps / elapsed, "unit": "patches/s", "n_gpus": world, "steps": args.steps,
         "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True,
@@ -693,7 +716,7 @@ def run_window(args, rank, world, device):
         "phases_ms": phases, "serial_ms_per_volume": serial,
         "roofline": roofline_of(prof, args.precision, traffic=False) if prof else None,
         "rccl": rccl_info(world),
-        "checks": {"max_abs_sum_p_minus_1": sum_err, "sum_of_probabilities": digest},
+        "checks": checks,
     }
 
     def cpu_leg(out):

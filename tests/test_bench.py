@@ -40,6 +40,31 @@ def test_steps_must_be_positive():
         bench.parse_args(["--steps", "0"])
 
 
+def test_full_is_off_by_default():
+    assert not bench.parse_args([]).full
+    assert bench.parse_args(["--full"]).full
+
+
+@pytest.mark.gpu
+def test_full_adds_what_a_plain_run_leaves_out():
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--workload", "cfg2-64"]
+    lines = []
+    for extra in ([], ["--full"]):
+        r = subprocess.run(cmd + extra, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-4000:]
+        lines.append(json.loads(r.stdout.strip().splitlines()[-1]))
+    plain, full = lines
+    for line in lines:
+        assert {"metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"} <= set(line)
+        assert line["steps"] == 2 and line["warmup"] == 1 and line["value"] > 0
+    assert plain["infer"] is None and plain["phases_ms"] is None and "cpu_baseline" not in plain
+    assert full["infer"]["ms_per_step"] > 0 and full["phases_ms"]
+    assert full["cpu_baseline"]["value"] > 0 and "max_abs_prob_diff_vs_cpu" in full["dice"]
+    # --full adds work after the timed steps, never changes them
+    assert abs(plain["final_loss"] - full["final_loss"]) <= 1e-5 * max(1.0, abs(full["final_loss"]))
+    assert abs(plain["dice"]["gpu_soft_dice_loss_step0"] - full["dice"]["gpu_soft_dice_loss_step0"]) <= 1e-6
+
+
 @pytest.mark.gpu
 def test_bench_dumps_the_last_timed_step(tmp_path):
     out = tmp_path / "out"

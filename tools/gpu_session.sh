@@ -25,7 +25,7 @@ for s in $STEPS; do
     tests) run tests 900 python -m pytest tests -m gpu -q -x --timeout=600 ${PYTEST_ARGS:-} ;;
     tests_all) run tests 900 python -m pytest tests -m gpu -q --timeout=600 ${PYTEST_ARGS:-} ;;
     smoke) run smoke 300 python -c "import __graft_entry__ as g; g.smoke()" ;;
-    bench) run bench 600 python bench.py --steps ${BENCH_STEPS:-5} --warmup 2 ${BENCH_ARGS:-} ;;
+    bench) run bench 600 python bench.py --full --steps ${BENCH_STEPS:-5} --warmup 2 ${BENCH_ARGS:-} ;;
     benchq) run benchq 300 python bench.py --steps 3 --warmup 1 --no-cpu-baseline ${BENCH_ARGS:-} ;;
     arch) run arch 600 python tools/arch_bench.py ;;
     archprof) run archprof 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/archprof -- python tools/arch_bench.py

@@ -12,7 +12,7 @@ timeout -k 10 400 python tools/c8_train_probe.py cfg2 cfg5 > $O/probe2.log 2>&1;
 grep -v Warning $O/probe2.log | tail -n 40
 [ $rc -ge 124 ] && exit $rc
 for prec in bf16 fp16; do
-  timeout -k 10 300 python bench.py --precision $prec --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_$prec.json 2> $O/bench_$prec.err; rc=$?
+  timeout -k 10 300 python bench.py --full --precision $prec --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_$prec.json 2> $O/bench_$prec.err; rc=$?
   python - <<P
 import json
 d=json.loads(open("$O/bench_$prec.json").read().strip().splitlines()[-1])

@@ -1,10 +1,11 @@
 #!/bin/bash
-# the driver's command (default flags), output under gpurun_out/r04
-cd "${GRAFT_REPO_ROOT:-/root/repo}"; mkdir -p gpurun_out/r04
-timeout -k 10 900 python bench.py "$@" > gpurun_out/r04/bench_default.json 2> gpurun_out/r04/bench_default.err; echo "bench rc=$?"; tail -3 gpurun_out/r04/bench_default.err
-python - <<'PY'
-import json
-d=json.load(open("gpurun_out/r04/bench_default.json"))
+# the driver's command with --full, then a digest of its line: tools/r04/bench_run.sh [bench.py args]; the line and the
+# log go to $BENCH_OUT (default bench_out/)
+cd "$(dirname "$0")/../.."; O=${BENCH_OUT:-bench_out}; mkdir -p "$O"
+timeout -k 10 900 python bench.py --full "$@" > "$O/bench_default.json" 2> "$O/bench_default.err"; echo "bench rc=$?"; tail -3 "$O/bench_default.err"
+python - "$O/bench_default.json" <<'PY'
+import json, sys
+d=json.load(open(sys.argv[1]))
 print("headline", d["ms_per_step"], d["infer"]["ms_per_step"], d["dtype"][:40], d["roofline"])
 print("conv", d["conv_kernels"])
 print("dice", d["dice"])

@@ -8,15 +8,15 @@ step() { local name=$1 to=$2; shift 2; echo "=== $name" ; timeout -k 10 "$to" "$
 stats() { local name=$1; shift; step $name 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/$name -o s -- "$@"; find $O/$name -name "s_kernel_stats.csv" | head -1 | xargs -r -I{} cp {} $O/${name}_kernel_stats.csv; }
 case "${1:-a}" in
   a)
-    step bench_fp32 600 python bench.py --steps 20 --warmup 5
-    step bench_bf16 300 python bench.py --steps 20 --warmup 5 --precision bf16
-    step bench_fp16 300 python bench.py --steps 20 --warmup 5 --precision fp16 --no-cpu-baseline
-    step bench_cfg4 300 python bench.py --workload cfg4 --steps 3 --warmup 1
-    step bench_cfg4_bf16 300 python bench.py --workload cfg4 --steps 5 --warmup 1 --precision bf16 --no-cpu-baseline
-    M355_FORCE_DDP=1 step bench_cfg3_rccl1 300 python bench.py --workload cfg3 --bucket-dtype bf16 --steps 20 --warmup 5 --no-cpu-baseline
-    stats prof_fp32 python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-cfg3
-    stats prof_fp32_mfma python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-cfg3 --precision fp32_mfma
-    stats prof_bf16 python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline --precision bf16
+    step bench_fp32 600 python bench.py --full --steps 20 --warmup 5
+    step bench_bf16 300 python bench.py --full --steps 20 --warmup 5 --precision bf16
+    step bench_fp16 300 python bench.py --full --steps 20 --warmup 5 --precision fp16 --no-cpu-baseline
+    step bench_cfg4 300 python bench.py --full --workload cfg4 --steps 3 --warmup 1
+    step bench_cfg4_bf16 300 python bench.py --full --workload cfg4 --steps 5 --warmup 1 --precision bf16 --no-cpu-baseline
+    M355_FORCE_DDP=1 step bench_cfg3_rccl1 300 python bench.py --full --workload cfg3 --bucket-dtype bf16 --steps 20 --warmup 5 --no-cpu-baseline
+    stats prof_fp32 python3 bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-cfg3
+    stats prof_fp32_mfma python3 bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-cfg3 --precision fp32_mfma
+    stats prof_bf16 python3 bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --precision bf16
     stats prof_bf16_infer python3 tools/infer_profile.py bf16 20
     ;;
   b)
