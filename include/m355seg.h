@@ -749,6 +749,73 @@ int m355_aug_otsu_pad(const float* x, int32_t C, const int32_t* size3, double* p
 int m355_aug_channel_minmax(const float* x, int32_t C, const int32_t* size3, int32_t which, double* out,
                            void* workspace, size_t ws_bytes, void* stream);
 
+/* ------------------------------------------ preprocessing
+ * The deterministic torchio preprocessing transforms of the reference's production configs
+ * (research/dmri_hippo/configs/main_config.py:78-120, research/msseg2/msseg2.py:36-80): preprocessing.py, DESIGN §4.11.
+ * Volumes are [C, V0, V1, V2] with fewer than 2^31 voxels per channel; element types are the M355_PRE_* codes
+ * (bool is one byte, 0 or 1).
+ *   m355_pre_bbox         bbox[0..6] (device int32, zeroed here) of the voxels of channel `channel` of `map` where
+ *                         pred 0: v != 0, pred 1: v == value.  bbox[a] = V_a - min_a, bbox[3 + a] = max_a + 1 (a < 3),
+ *                         bbox[6] = the count; all zero when no voxel matches.  One integer atomic per workgroup and value.
+ *   m355_pre_crop_or_pad_offsets  offsets[a] (device int32) = torchio 0.18.45 CropOrPad's begin of a box `bbox`
+ *                         (m355_pre_bbox) of an in3 volume cropped / padded to target3: the mask-centred window, or the
+ *                         centred one (ceil(n / 2) in front) when the box is empty.  One single-workgroup launch.
+ *   m355_pre_min_tables   np.pad(mode='minimum') lookup tables of x (after NaN -> nan_value when replace_nan): per
+ *                         channel the minimum over every non-empty subset of the three axes, the other coordinates
+ *                         fixed, as order-preserving uint64 keys.  m355_pre_min_tables_bytes(C, size3) bytes; one
+ *                         pass over x plus one small pass over the tables.
+ *   m355_pre_gather       y[c, p] (out3) = f(v[c, p + off]) with off = off_dev (device, when not NULL) or off3, v the
+ *                         in3 box of x (of size src3) at base3 (a crop folded in): in-bounds voxels take v (NaN ->
+ *                         nan_value when replace_nan); others the constant pad_value
+ *                         (pad_mode 0) or the np.pad 'minimum' value of the axes they leave (pad_mode 1, tables of x; the box is then all of x);
+ *                         then the simultaneous remap (every pair tests the value before any remap, the last match
+ *                         wins) where the mask holds, then the cast to out_dtype.  y may be a channel slice of a larger
+ *                         tensor (concatenation); x != y.
+ *   m355_pre_one_hot      y[k, p] = (trunc(x[0, p]) == k), k < K, in x's element type.  Labels outside [0, K) give an
+ *                         all-zero column and are counted into *bad (device int32, zeroed here).
+ *   m355_pre_image_from_labels  y[0, p] (float32) = 0, then per entry (in order) mode 0: y = weight where the label is
+ *                         `id`, mode 1: y += (label == id) * weight; the label is channel 0, or the first argmax over
+ *                         the channels of a one-hot map. */
+#define M355_PRE_MAX_REMAP 8
+#define M355_PRE_MAX_ENTRIES 8
+enum { M355_PRE_U8 = 0, M355_PRE_BOOL = 1, M355_PRE_I32 = 2, M355_PRE_I64 = 3, M355_PRE_F32 = 4 };
+enum { M355_PRE_MASK_NONE = 0, M355_PRE_MASK_HALF = 1, M355_PRE_MASK_MAP = 2 };
+typedef struct {
+  const void* x;
+  void* y;
+  int32_t in_dtype, out_dtype, C;
+  int32_t src3[3], base3[3], in3[3], out3[3], off3[3];
+  const int32_t* off_dev;      /* NULL: off3 */
+  int32_t pad_mode;            /* 0 constant pad_value, 1 per-line minimum (tables) */
+  double pad_value;
+  const void* tables;
+  int32_t replace_nan;
+  double nan_value;
+  int32_t nremap;
+  double remap_old[M355_PRE_MAX_REMAP], remap_new[M355_PRE_MAX_REMAP];
+  int32_t mask_kind;           /* M355_PRE_MASK_*: HALF = o[mask_axis] >= out3[mask_axis] / 2 (mask_upper) or < it */
+  int32_t mask_axis, mask_upper;
+  const void* mask_map;        /* MAP: nonzero voxels of an out3 map of mask_C (1 or C) channels */
+  int32_t mask_dtype, mask_C;
+} m355_pre_gather_desc;
+typedef struct {
+  const void* map;
+  int32_t dtype, C, one_hot;
+  float weight;
+  double id;
+} m355_pre_label_entry;
+int m355_pre_bbox(const void* map, int32_t dtype, int32_t C, const int32_t* size3, int32_t channel, int32_t pred,
+                  double value, int32_t* bbox, void* stream);
+int m355_pre_crop_or_pad_offsets(const int32_t* bbox, const int32_t* in3, const int32_t* target3, int32_t* offsets,
+                                 void* stream);
+size_t m355_pre_min_tables_bytes(int32_t C, const int32_t* size3);
+int m355_pre_min_tables(const void* x, int32_t dtype, int32_t C, const int32_t* size3, int32_t replace_nan,
+                        double nan_value, void* tables, size_t bytes, void* stream);
+int m355_pre_gather(const m355_pre_gather_desc* d, void* stream);
+int m355_pre_one_hot(const void* x, int32_t dtype, const int32_t* size3, int32_t K, void* y, int32_t* bad, void* stream);
+int m355_pre_image_from_labels(const m355_pre_label_entry* entries, int32_t n, const int32_t* size3, int32_t mode,
+                               float* y, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

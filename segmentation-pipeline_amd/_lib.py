@@ -53,6 +53,28 @@ class AugStage(C.Structure):
 AUG_BIAS, AUG_RESCALE, AUG_GAMMA, AUG_NOISE = 0, 1, 2, 3
 AUG_MAX_STAGES = 8
 
+PRE_U8, PRE_BOOL, PRE_I32, PRE_I64, PRE_F32 = 0, 1, 2, 3, 4
+PRE_MASK_NONE, PRE_MASK_HALF, PRE_MASK_MAP = 0, 1, 2
+PRE_MAX_REMAP = 8
+PRE_MAX_ENTRIES = 8
+
+
+class PreGatherDesc(C.Structure):
+    """m355_pre_gather_desc"""
+    _fields_ = [("x", C.c_void_p), ("y", C.c_void_p), ("in_dtype", C.c_int32), ("out_dtype", C.c_int32),
+                ("C", C.c_int32), ("src3", C.c_int32 * 3), ("base3", C.c_int32 * 3), ("in3", C.c_int32 * 3), ("out3", C.c_int32 * 3), ("off3", C.c_int32 * 3),
+                ("off_dev", C.c_void_p), ("pad_mode", C.c_int32), ("pad_value", C.c_double), ("tables", C.c_void_p),
+                ("replace_nan", C.c_int32), ("nan_value", C.c_double), ("nremap", C.c_int32),
+                ("remap_old", C.c_double * PRE_MAX_REMAP), ("remap_new", C.c_double * PRE_MAX_REMAP),
+                ("mask_kind", C.c_int32), ("mask_axis", C.c_int32), ("mask_upper", C.c_int32),
+                ("mask_map", C.c_void_p), ("mask_dtype", C.c_int32), ("mask_C", C.c_int32)]
+
+
+class PreLabelEntry(C.Structure):
+    """m355_pre_label_entry"""
+    _fields_ = [("map", C.c_void_p), ("dtype", C.c_int32), ("C", C.c_int32), ("one_hot", C.c_int32),
+                ("weight", C.c_float), ("id", C.c_double)]
+
 _P = C.c_void_p
 ABI_VERSION = 3   # M355_ABI_VERSION of include/m355seg.h this binding was written against
 _i32, _i64, _f32, _sz = C.c_int32, C.c_int64, C.c_float, C.c_size_t
@@ -181,6 +203,13 @@ SIGNATURES = {
     "m355_aug_blur": (C.c_int, [_P, _P, _i32, _I3, _i32, C.c_double, _AS, _i32, _P]),
     "m355_aug_otsu_pad": (C.c_int, [_P, _i32, _I3, _P, _P]),
     "m355_aug_channel_minmax": (C.c_int, [_P, _i32, _I3, _i32, _P, _P, _sz, _P]),
+    "m355_pre_bbox": (C.c_int, [_P, _i32, _i32, _I3, _i32, _i32, C.c_double, _P, _P]),
+    "m355_pre_crop_or_pad_offsets": (C.c_int, [_P, _I3, _I3, _P, _P]),
+    "m355_pre_min_tables_bytes": (_sz, [_i32, _I3]),
+    "m355_pre_min_tables": (C.c_int, [_P, _i32, _i32, _I3, _i32, C.c_double, _P, _sz, _P]),
+    "m355_pre_gather": (C.c_int, [C.POINTER(PreGatherDesc), _P]),
+    "m355_pre_one_hot": (C.c_int, [_P, _i32, _I3, _i32, _P, _P, _P]),
+    "m355_pre_image_from_labels": (C.c_int, [C.POINTER(PreLabelEntry), _i32, _I3, _i32, _P, _P]),
 }
 
 

@@ -59,7 +59,7 @@ def _percentile_rank(n, q):
 class _State:
     """A subject during one call: materialised tensors and, per name, the intensity stages not yet applied."""
 
-    def __init__(self, subject, label_maps, spacing, generator):
+    def __init__(self, subject, label_maps, spacing, generator, label_values=None):
         self.data = dict(subject)
         self.owned = set()
         self.labels = set(label_maps)
@@ -68,6 +68,12 @@ class _State:
         self.pending = {}
         self.blur = {}        # name -> sigmas in voxels of a blur not yet applied (it runs before pending[name])
         self.keep = []        # device parameter tensors of launches already enqueued
+        # metadata of the preprocessing transforms (preprocessing.py)
+        self.label_values = {k: dict(v) for k, v in (label_values or {}).items()}
+        self.one_hot = set()
+        # name -> preprocessing pass not yet launched into data[name] (already allocated with its final shape and dtype);
+        # it runs before blur[name] and pending[name]
+        self.deferred = {}
 
     def images(self, t, intensity):
         names = [k for k in self.data if (t.include is None or k in t.include) and k not in t.exclude]
@@ -80,6 +86,9 @@ class _State:
     def flush(self, name):
         """apply the deferred blur and the pending intensity stages of `name`.  The caller's tensors are never written:
         a name is `owned` only once it holds a tensor this call allocated."""
+        pre = self.deferred.pop(name, None)
+        if pre is not None:
+            pre.run(self)
         stages = self.pending.pop(name, None) or []
         sig = self.blur.pop(name, None)
         if sig is not None:
@@ -95,8 +104,13 @@ class _State:
             self.set(name, y)
 
     def flush_all(self):
-        for name in list(self.pending) + list(self.blur):
+        for name in list(self.deferred) + list(self.pending) + list(self.blur):
             self.flush(name)
+
+    def meta(self):
+        return {"spacing": self.spacing, "label_maps": sorted(k for k in self.labels if k in self.data),
+                "label_values": {k: dict(v) for k, v in self.label_values.items() if k in self.data},
+                "one_hot": sorted(k for k in self.one_hot if k in self.data)}
 
 
 # ---------------------------------------------------------------------------------------------- native calls
@@ -222,14 +236,18 @@ class Transform:
         self.include = None if include is None else ([include] if isinstance(include, str) else list(include))
         self.exclude = [] if exclude is None else ([exclude] if isinstance(exclude, str) else list(exclude))
         self.last_history = None
+        self.last_meta = None
 
-    def __call__(self, subject, label_maps=(), spacing=(1.0, 1.0, 1.0), generator=None):
+    def __call__(self, subject, label_maps=(), spacing=(1.0, 1.0, 1.0), generator=None, label_values=None):
+        """label_values: {label map name: {label name: id}} (the reference's per-map `label_values`); the resulting
+        metadata (spacing, label maps, label_values, one-hot maps) is published as `last_meta`"""
         for k, v in subject.items():
             if not isinstance(v, torch.Tensor) or not v.is_cuda or v.dim() != 4:
                 raise M355Error(f"{k}: expected a device tensor [C, V0, V1, V2]")
-        state = _State(subject, label_maps, spacing, generator)
+        state = _State(subject, label_maps, spacing, generator, label_values)
         self._run(state)
         state.flush_all()
+        self.last_meta = state.meta()
         return dict(state.data)
 
     def _rand(self, state, *shape):
