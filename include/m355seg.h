@@ -816,6 +816,50 @@ int m355_pre_one_hot(const void* x, int32_t dtype, const int32_t* size3, int32_t
 int m355_pre_image_from_labels(const m355_pre_label_entry* entries, int32_t n, const int32_t* size3, int32_t mode,
                                float* y, void* stream);
 
+/* ------------------------------------------ evaluation
+ * Confusion counts of the reference's SegmentationEvaluator / LabelMapEvaluator (evaluators.py).
+ * counts[subject][l][{TP, FP, FN}] (device uint64, zeroed here) for the L distinct label values labels[0 .. L)
+ * (1 <= L <= M355_EV_MAX_LABELS); TN = S - TP - FP - FN.  A voxel equals label v as torch's `data == v` decides: v is
+ * cast to the map's element type first (uint8: v mod 256, float32: float(v)); a voxel of no label counts for none.
+ * Without a target, FN = 0 and TP + FP is the label's volume.  Element types are the M355_EV_* codes (bool one byte).
+ * `nokey`: an int32 that is none of the labels' values in any element type (the host picks it); values no label can
+ * equal (non-integral floats, int64 outside int32) take it.  `descs` are host descriptors, copied to `dev_descs`
+ * (device, n descriptors) on the stream; all n subjects run in one launch, whatever their sizes.
+ *   m355_eval_confusion  label maps [S] of any M355_EV_* type up to float32; the target may be NULL.
+ *   m355_eval_scores     from scores [C, S] (float32, bfloat16 or float16; 1 <= C <= M355_EV_MAX_CHANNELS): the first
+ *                        maximum over the channels (a NaN is the maximum, the first NaN wins: torch.argmax), then the
+ *                        label value table[m * C + c] with m = 1 inside the mask, 0 outside (mask HALF: coordinate
+ *                        o[mask_axis] >= size3[mask_axis] / 2 when mask_upper, < it otherwise; MAP: the nonzero voxels
+ *                        of each subject's `mask` [S]).  Target: NONE, a one-hot [C, S] map (its argmax goes through
+ *                        the same table) or a label map [S].  pred_out / target_out (int64 [S], optional) receive the
+ *                        label maps; target_out only from a one-hot target. */
+#define M355_EV_MAX_LABELS 64
+#define M355_EV_MAX_CHANNELS 64
+enum { M355_EV_BOOL = 0, M355_EV_U8 = 1, M355_EV_I8 = 2, M355_EV_I16 = 3, M355_EV_I32 = 4, M355_EV_I64 = 5, M355_EV_F32 = 6,
+       M355_EV_BF16 = 7, M355_EV_F16 = 8 };
+enum { M355_EV_MASK_NONE = 0, M355_EV_MASK_HALF = 1, M355_EV_MASK_MAP = 2 };
+enum { M355_EV_TARGET_NONE = 0, M355_EV_TARGET_ONEHOT = 1, M355_EV_TARGET_MAP = 2 };
+typedef struct {
+  const void* pred;
+  const void* target;          /* NULL: no target */
+  int64_t S;
+  int32_t pred_dtype, target_dtype;
+} m355_eval_map_desc;
+typedef struct {
+  const void* scores;          /* [C, S] */
+  const void* target;          /* NULL, [C, S] one-hot or [S] label map */
+  const void* mask;            /* M355_EV_MASK_MAP: [S] */
+  int64_t* pred_out;           /* NULL: not written */
+  int64_t* target_out;
+  int32_t size3[3];
+  int32_t target_kind, target_dtype, mask_dtype;
+} m355_eval_scores_desc;
+int m355_eval_confusion(const m355_eval_map_desc* descs, int32_t n, void* dev_descs, const int32_t* labels, int32_t L,
+                        int32_t nokey, uint64_t* counts, void* stream);
+int m355_eval_scores(const m355_eval_scores_desc* descs, int32_t n, void* dev_descs, int32_t scores_dtype, int32_t C,
+                     const int32_t* table, int32_t mask_kind, int32_t mask_axis, int32_t mask_upper,
+                     const int32_t* labels, int32_t L, int32_t nokey, uint64_t* counts, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -75,6 +75,26 @@ class PreLabelEntry(C.Structure):
     _fields_ = [("map", C.c_void_p), ("dtype", C.c_int32), ("C", C.c_int32), ("one_hot", C.c_int32),
                 ("weight", C.c_float), ("id", C.c_double)]
 
+EV_BOOL, EV_U8, EV_I8, EV_I16, EV_I32, EV_I64, EV_F32, EV_BF16, EV_F16 = range(9)
+EV_MASK_NONE, EV_MASK_HALF, EV_MASK_MAP = 0, 1, 2
+EV_TARGET_NONE, EV_TARGET_ONEHOT, EV_TARGET_MAP = 0, 1, 2
+EV_MAX_LABELS = 64
+EV_MAX_CHANNELS = 64
+
+
+class EvalMapDesc(C.Structure):
+    """m355_eval_map_desc"""
+    _fields_ = [("pred", C.c_void_p), ("target", C.c_void_p), ("S", C.c_int64), ("pred_dtype", C.c_int32),
+                ("target_dtype", C.c_int32)]
+
+
+class EvalScoresDesc(C.Structure):
+    """m355_eval_scores_desc"""
+    _fields_ = [("scores", C.c_void_p), ("target", C.c_void_p), ("mask", C.c_void_p), ("pred_out", C.c_void_p),
+                ("target_out", C.c_void_p), ("size3", C.c_int32 * 3), ("target_kind", C.c_int32),
+                ("target_dtype", C.c_int32), ("mask_dtype", C.c_int32)]
+
+
 _P = C.c_void_p
 ABI_VERSION = 3   # M355_ABI_VERSION of include/m355seg.h this binding was written against
 _i32, _i64, _f32, _sz = C.c_int32, C.c_int64, C.c_float, C.c_size_t
@@ -210,6 +230,9 @@ SIGNATURES = {
     "m355_pre_gather": (C.c_int, [C.POINTER(PreGatherDesc), _P]),
     "m355_pre_one_hot": (C.c_int, [_P, _i32, _I3, _i32, _P, _P, _P]),
     "m355_pre_image_from_labels": (C.c_int, [C.POINTER(PreLabelEntry), _i32, _I3, _i32, _P, _P]),
+    "m355_eval_confusion": (C.c_int, [C.POINTER(EvalMapDesc), _i32, _P, _I3, _i32, _i32, _P, _P]),
+    "m355_eval_scores": (C.c_int, [C.POINTER(EvalScoresDesc), _i32, _P, _i32, _i32, _I3, _i32, _i32, _i32, _I3, _i32,
+                                   _i32, _P, _P]),
 }
 
 

@@ -1,4 +1,6 @@
-"""Lesion-wise detection statistics (the per-subject numbers of the reference's InstanceSegmentationEvaluator,
+"""The reference's evaluators (evaluators/segmentation_evaluator.py, label_map_evaluator.py,
+instance_segmentation_evaluator.py, labeled_tensor.py) with their counts taken on the device, and lesion-wise detection
+statistics (the per-subject numbers of the reference's InstanceSegmentationEvaluator,
 evaluators/instance_segmentation_evaluator.py) with the labelling and the overlap table on the device.
 
 The overlap table of N target and M predicted components is a dense int64 [N + 1, M + 1] histogram (component 0 is
@@ -6,12 +8,19 @@ the background of either map), built by one pass of m355_label_histogram over th
 above MAX_OVERLAP_ENTRIES entries.  The detection test and every statistic derived from the table run on the host in
 float32, the dtype of the reference's table (so N == 0 or M == 0 gives the same nan results).
 """
+import itertools
+from typing import Callable, Dict, Optional, Sequence
+
+import numpy as np
 import torch
 
+from . import ops
 from ._lib import M355Error
 from .post_processing import _OP_COPY, _OP_POSITIVE, _ccl, _connectivity, _device_volume, _histogram, _to_i32
 
-__all__ = ["overlap_histogram", "msseg_detection_test", "instance_segmentation_stats", "MAX_OVERLAP_ENTRIES", "STAT_NAMES"]
+__all__ = ["overlap_histogram", "msseg_detection_test", "instance_segmentation_stats", "MAX_OVERLAP_ENTRIES", "STAT_NAMES",
+           "LabeledTensor", "LabelMap", "Evaluator", "SegmentationEvaluator", "LabelMapEvaluator",
+           "InstanceSegmentationEvaluator", "label_counts"]
 
 MAX_OVERLAP_ENTRIES = 1 << 26   # (N + 1) * (M + 1): 512 MiB of int64 counts
 
@@ -109,3 +118,325 @@ def instance_segmentation_stats(pred, target, connectivity=2, detection_test=mss
         'precision': TP / (TP + FP), 'recall': TP / (TP + FN),
     }
     return {k: _item(stats[k]) for k in STAT_NAMES}
+
+
+# ---------------------------------------------------------------------------------------------- labelled tables
+def _listify(key):
+    if isinstance(key, (list, tuple)):
+        return list(key)
+    return [key]
+
+
+class LabeledTensor:
+    """A float32 host tensor whose dimensions are addressed by name (labeled_tensor.py, reference).  Keys: a string
+    (looked up in its dimension; a name given twice in a dimension addresses its last position), a list of keys, an
+    int or a slice, per dimension.  Ellipsis is refused."""
+
+    def __init__(self, dim_names: Sequence[str], dim_keys: Sequence[Sequence[str]]):
+        if len(dim_names) != len(dim_keys):
+            raise ValueError(f"The number of dimension names ({len(dim_names)}) "
+                             f"does not match the number of dimension keys ({len(dim_keys)}")
+        self.dim_names = dim_names
+        self.dim_keys = dim_keys
+        self.dim_key_map = [dict((k, i) for i, k in enumerate(keys)) for keys in dim_keys]
+        self.data = torch.zeros([len(keys) for keys in dim_keys])
+
+    def parse_key(self, key):
+        parts = _listify(key)
+        if any(k is Ellipsis for k in parts):
+            raise NotImplementedError("Elipsis indexing is not supported for LabeledTensors")
+        out = []
+        for k, lookup in zip(parts, self.dim_key_map):
+            if isinstance(k, str):
+                k = lookup[k]
+            elif isinstance(k, (list, tuple)):
+                k = [lookup[e] if isinstance(e, str) else e for e in k]
+            out.append(k)
+        return tuple(out) + tuple(parts[len(out):])
+
+    def __getitem__(self, key) -> torch.Tensor:
+        return self.data[self.parse_key(key)]
+
+    def __setitem__(self, key, value):
+        self.data[self.parse_key(key)] = value
+
+    def to_dataframe(self):
+        """one row per combination of the leading dimensions' keys, one column per key of the last dimension"""
+        import pandas as pd
+        lead, last = self.dim_names[:-1], self.dim_keys[-1]
+        columns = {name: [] for name in lead}
+        for k in last:
+            columns[k] = []
+        for combo in itertools.product(*self.dim_keys[:-1]):
+            for name, k in zip(lead, combo):
+                columns[name].append(k)
+            for k, v in zip(last, self[combo].tolist()):
+                columns[k].append(v)
+        return pd.DataFrame(columns)
+
+    def to_dict(self):
+        out = {}
+        for combo in itertools.product(*self.dim_keys):
+            node = out
+            for k in combo[:-1]:
+                node = node.setdefault(k, {})
+            node[combo[-1]] = self[combo].item()
+        return _fill_nested(self.dim_keys, out)
+
+    def compute_summary_stats(self, summary_stats_to_output):
+        funcs = LabeledTensor.get_summary_stat_funcs()
+        out = LabeledTensor(dim_names=["summary_stat", *self.dim_names[1:]],
+                            dim_keys=[summary_stats_to_output, *self.dim_keys[1:]])
+        for combo in itertools.product(*self.dim_keys[1:]):
+            column = self[(slice(None), *combo)]
+            for name in summary_stats_to_output:
+                out[(name, *combo)] = funcs[name](column).item()
+        return out
+
+    @staticmethod
+    def fix_tensor(x):
+        """the finite values of x, or [0.] when there are none"""
+        finite = x[x.isfinite()]
+        return finite if finite.shape[0] else torch.tensor([0.])
+
+    @staticmethod
+    def get_summary_stat_funcs(dim: int = 0):
+        fix = LabeledTensor.fix_tensor
+        return {
+            'mean': lambda x: torch.mean(fix(x), dim=dim),
+            'median': lambda x: torch.median(fix(x), dim=dim).values,
+            'mode': lambda x: torch.mode(fix(x), dim=dim).values,
+            'std': lambda x: torch.std(fix(x), dim=dim),
+            'min': lambda x: torch.min(fix(x), dim=dim).values,
+            'max': lambda x: torch.max(fix(x), dim=dim).values,
+        }
+
+
+def _fill_nested(dim_keys, filled):
+    """to_dict's layout: every key of every level present (the reference builds the nest first, then fills it)"""
+    def build(level):
+        if level == len(dim_keys):
+            return 0
+        return {k: build(level + 1) for k in dim_keys[level]}
+
+    def merge(skeleton, values):
+        for k, v in values.items():
+            if isinstance(v, dict):
+                merge(skeleton[k], v)
+            else:
+                skeleton[k] = v
+        return skeleton
+    return merge(build(0), filled)
+
+
+# ---------------------------------------------------------------------------------------------- subjects
+class LabelMap(dict):
+    """The part of a torchio LabelMap the evaluators read: `.data` ([1, D, H, W]) and item access to attributes such
+    as 'label_values'.  A real tio.LabelMap works in its place."""
+
+    def __init__(self, data=None, label_values=None, **attributes):
+        super().__init__(attributes)
+        if data is not None:
+            self['data'] = data
+        if label_values is not None:
+            self['label_values'] = dict(label_values)
+
+    @property
+    def data(self):
+        return self['data']
+
+
+class ScoreLabelMap(LabelMap):
+    """A label map that is the argmax of model scores through a channel -> label value table (prediction.
+    add_evaluation_labels).  Its `.data` (int64 [1, D, H, W]) is computed on first access; an evaluator given such
+    maps counts straight from the scores instead (ops.eval_scores), without writing them."""
+
+    def __init__(self, source, role, label_values=None):
+        super().__init__(None, label_values)
+        self.source, self.role = source, role
+
+    @property
+    def data(self):
+        if 'data' not in self:
+            self.source.materialise()
+        return self['data']
+
+    @property
+    def pending(self):
+        return 'data' not in self
+
+
+class Evaluator:
+    def __call__(self, subjects) -> dict:
+        raise NotImplementedError()
+
+    def __repr__(self):
+        args = ", ".join(f"{k}={v!r}" for k, v in vars(self).items() if not k.startswith("_"))
+        return f"{type(self).__name__}({args})"
+
+
+def _fused_sources(subjects, pred_name, target_name):
+    """the ScoreLabelMap sources when every prediction (and target) can be counted straight from scores, else None"""
+    preds = [s[pred_name] for s in subjects]
+    if not all(isinstance(p, ScoreLabelMap) and p.pending and p.role == "pred" for p in preds):
+        return None
+    sources = [p.source for p in preds]
+    if any(src.plan is not sources[0].plan for src in sources):
+        return None
+    if target_name is None:
+        return sources, None
+    targets = [s[target_name] for s in subjects]
+    own = [isinstance(t, ScoreLabelMap) and t.pending and t.role == "target" and t.source is src
+           for t, src in zip(targets, sources)]
+    if all(own):
+        return sources, "own"
+    if any(own):
+        return None
+    return sources, [t.data for t in targets]
+
+
+def label_counts(subjects, pred_name, target_name, values):
+    """int64 numpy [n, L, 3] (TP, FP, FN) per subject and label value, and the voxel count of each subject: one launch
+    (ops.eval_scores when the predictions are unwritten ScoreLabelMaps, ops.eval_confusion otherwise), one copy back."""
+    uniq = list(dict.fromkeys(int(v) for v in values))
+    fused = _fused_sources(subjects, pred_name, target_name)
+    if fused is not None:
+        sources, tmode = fused
+        plan = sources[0].plan
+        targets = None
+        if tmode == "own":
+            targets = [src.target for src in sources]
+        elif tmode is not None:
+            targets = tmode
+        counts, _, _ = ops.eval_scores([src.scores for src in sources], plan.tables(sources[0].scores.shape[0]), uniq, targets=targets,
+                                       masks=[src.mask for src in sources] if plan.mask_name is not None else None,
+                                       half=plan.half, one_hot_targets=tmode == "own")
+        sizes = [src.scores[0].numel() for src in sources]
+    else:
+        preds = [s[pred_name].data for s in subjects]
+        targets = [s[target_name].data for s in subjects] if target_name is not None else [None] * len(preds)
+        dev = next((t.device for t in preds if t.is_cuda), None) or torch.device("cuda", torch.cuda.current_device())
+        counts = ops.eval_confusion([p.to(dev) for p in preds], [None if t is None else t.to(dev) for t in targets], uniq)
+        sizes = [p.numel() for p in preds]
+    counts = counts.cpu().numpy()
+    pos = {v: i for i, v in enumerate(uniq)}
+    return counts[:, [pos[int(v)] for v in values], :], np.asarray(sizes, dtype=np.int64)
+
+
+def _subject_table(subjects, stats_to_output, second_keys):
+    subject_names = [subject['name'] for subject in subjects]
+    return LabeledTensor(dim_names=['subject', 'label', 'stat'], dim_keys=[subject_names, second_keys, stats_to_output])
+
+
+def _finish(subject_stats, summary_stats_to_output):
+    return {'subject_stats': subject_stats.to_dataframe(),
+            'summary_stats': subject_stats.compute_summary_stats(summary_stats_to_output)}
+
+
+class SegmentationEvaluator(Evaluator):
+    """Overlap statistics of a predicted against a target label map per subject and label (segmentation_evaluator.py,
+    reference): 'target_volume', 'prediction_volume', 'TP', 'FP', 'TN', 'FN', 'dice', 'jaccard', 'precision',
+    'recall', and their summary stats over the subjects.  The counts come from one device launch; the statistics are
+    the reference's float32 expressions on them (0 / 0 is nan, x / 0 inf)."""
+
+    def __init__(self, prediction_label_map_name: str, target_label_map_name: str,
+                 stats_to_output: Sequence[str] = ('target_volume', 'prediction_volume',
+                                                   'TP', 'FP', 'TN', 'FN', 'dice', 'precision', 'recall'),
+                 summary_stats_to_output: Sequence[str] = ('mean', 'std', 'min', 'max')):
+        self.prediction_label_map_name = prediction_label_map_name
+        self.target_label_map_name = target_label_map_name
+        self.stats_to_output = stats_to_output
+        self.summary_stats_to_output = summary_stats_to_output
+
+    @staticmethod
+    def _stats(tp, fp, fn, size):
+        TP, FP, FN = (torch.tensor([v], dtype=torch.int64).float() for v in (tp, fp, fn))
+        TN = torch.tensor([size - tp - fp - fn], dtype=torch.int64).float()
+        return {'target_volume': TP + FN, 'prediction_volume': TP + FP, 'TP': TP, 'FP': FP, 'TN': TN, 'FN': FN,
+                'dice': 2 * TP / (2 * TP + FP + FN), 'jaccard': TP / (TP + FP + FN),
+                'precision': TP / (TP + FP), 'recall': TP / (TP + FN)}
+
+    def __call__(self, subjects):
+        label_values = subjects[0][self.prediction_label_map_name]['label_values']
+        table = _subject_table(subjects, self.stats_to_output, list(label_values.keys()))
+        counts, sizes = label_counts(subjects, self.prediction_label_map_name, self.target_label_map_name,
+                                     list(label_values.values()))
+        for i, subject in enumerate(subjects):
+            for l, label_name in enumerate(label_values):
+                tp, fp, fn = (int(v) for v in counts[i, l])
+                stats = self._stats(tp, fp, fn, int(sizes[i]))
+                for stat_name in self.stats_to_output:
+                    table[subject['name'], label_name, stat_name] = stats[stat_name].item()
+        return _finish(table, self.summary_stats_to_output)
+
+
+CURVE_STATS = ('error', 'absolute_error', 'squared_error', 'percent_diff')
+
+
+class LabelMapEvaluator(Evaluator):
+    """Volume of every label per subject (label_map_evaluator.py, reference), and with `curve_params` (label name ->
+    polynomial coefficients, highest power first) and `curve_attribute` (a subject key, e.g. 'age') the deviation from
+    the curve: 'error', 'absolute_error', 'squared_error', 'percent_diff'.  Volumes come from one device launch."""
+
+    def __init__(self, label_map_name: str, curve_params: Optional[Dict[str, np.ndarray]] = None,
+                 curve_attribute: Optional[str] = None, stats_to_output: Sequence[str] = ('volume',),
+                 summary_stats_to_output: Sequence[str] = ('mean', 'std', 'min', 'max')):
+        self.label_map_name = label_map_name
+        self.curve_params = curve_params
+        self.curve_attribute = curve_attribute
+        self.stats_to_output = stats_to_output
+        self.summary_stats_to_output = summary_stats_to_output
+        if any(stat in CURVE_STATS for stat in stats_to_output):
+            if curve_params is None:
+                raise ValueError("curve_params must be provided")
+            if curve_attribute is None:
+                raise ValueError("curve_attribute must be provided")
+        self.poly_func = None
+        if curve_params is not None and curve_attribute is not None:
+            self.poly_func = {label: np.poly1d(param) for label, param in curve_params.items()}
+
+    def __call__(self, subjects):
+        label_values = subjects[0][self.label_map_name]['label_values']
+        table = _subject_table(subjects, self.stats_to_output, list(label_values.keys()))
+        counts, _ = label_counts(subjects, self.label_map_name, None, list(label_values.values()))
+        for i, subject in enumerate(subjects):
+            for l, label_name in enumerate(label_values):
+                volume = torch.tensor([int(counts[i, l, 0] + counts[i, l, 1])], dtype=torch.int64)
+                stats = {'volume': volume}
+                if self.poly_func is not None:
+                    expected = self.poly_func[label_name](subject[self.curve_attribute])
+                    error = volume - expected
+                    stats.update({'error': error, 'absolute_error': abs(error), 'squared_error': error ** 2,
+                                  'percent_diff': (error / expected) * 100})
+                for stat_name in self.stats_to_output:
+                    table[subject['name'], label_name, stat_name] = stats[stat_name].item()
+        return _finish(table, self.summary_stats_to_output)
+
+
+class InstanceSegmentationEvaluator(Evaluator):
+    """Lesion-wise detection and overlap statistics per subject (instance_segmentation_evaluator.py, reference), from
+    `instance_segmentation_stats` (components and overlap table on the device); a ['subject', 'stat'] table."""
+
+    def __init__(self, prediction_label_map_name: str, target_label_map_name: str,
+                 stats_to_output: Sequence[str] = STAT_NAMES,
+                 summary_stats_to_output: Sequence[str] = ('mean', 'std', 'min', 'max', 'median', 'mode'),
+                 connectivity: int = 2, detection_test: Callable = msseg_detection_test,
+                 detection_test_params: Optional[Dict] = None):
+        self.prediction_label_map_name = prediction_label_map_name
+        self.target_label_map_name = target_label_map_name
+        self.stats_to_output = stats_to_output
+        self.summary_stats_to_output = summary_stats_to_output
+        self.connectivity = connectivity
+        self.detection_test = detection_test
+        self.detection_test_params = {} if detection_test_params is None else detection_test_params
+
+    def __call__(self, subjects):
+        table = LabeledTensor(dim_names=['subject', 'stat'],
+                              dim_keys=[[s['name'] for s in subjects], self.stats_to_output])
+        for subject in subjects:
+            stats = instance_segmentation_stats(subject[self.prediction_label_map_name].data,
+                                                subject[self.target_label_map_name].data, self.connectivity,
+                                                self.detection_test, self.detection_test_params)
+            for stat_name in self.stats_to_output:
+                table[subject['name'], stat_name] = stats[stat_name]
+        return _finish(table, self.summary_stats_to_output)

@@ -10,6 +10,7 @@ import weakref
 from dataclasses import dataclass
 from typing import List, Optional, Sequence
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -2352,3 +2353,147 @@ def argmax_confusion(prob, target):
     check(L.m355_argmax_confusion(_p(prob), _p(target), _p(am), _p(counts), N, Cc, S, _stream()),
           "argmax_confusion")
     return am, counts
+
+
+# ----------------------------------------------------------------- evaluation counts (csrc/evaluate.hip)
+_EV_MAP_DTYPE = {torch.bool: _lib.EV_BOOL, torch.uint8: _lib.EV_U8, torch.int8: _lib.EV_I8, torch.int16: _lib.EV_I16,
+                 torch.int32: _lib.EV_I32, torch.int64: _lib.EV_I64, torch.float32: _lib.EV_F32}
+_EV_SCORE_DTYPE = {torch.float32: _lib.EV_F32, torch.bfloat16: _lib.EV_BF16, torch.float16: _lib.EV_F16}
+_EV_LABEL_LIMIT = 2 ** 31 - 128   # float32(v) of a label must stay inside int32
+
+
+def _ev_code(t, table, what):
+    if t.dtype not in table:
+        raise _lib.M355Error(f"{what}: element type {t.dtype} (one of {', '.join(str(d) for d in table)})")
+    if not t.is_cuda:
+        raise _lib.M355Error(f"{what}: expected a device tensor")
+    return table[t.dtype]
+
+
+def _ev_labels(labels):
+    """-> (int32 ctypes array, L, nokey).  nokey: an int32 that no label takes in any element type's cast"""
+    labels = [int(v) for v in labels]
+    if not 1 <= len(labels) <= _lib.EV_MAX_LABELS:
+        raise _lib.M355Error(f"{len(labels)} label values (1 .. {_lib.EV_MAX_LABELS})")
+    if len(set(labels)) != len(labels):
+        raise _lib.M355Error(f"label values {labels} are not distinct")
+    if any(abs(v) >= _EV_LABEL_LIMIT for v in labels):
+        raise _lib.M355Error(f"label values {labels}: |value| must be below {_EV_LABEL_LIMIT}")
+    keys = set()
+    for v in labels:
+        keys.update((v, v & 0xFF, (v + 128) % 256 - 128, (v + 32768) % 65536 - 32768, int(np.float32(v))))
+    nokey = -2 ** 31
+    while nokey in keys:
+        nokey += 1
+    return (C.c_int32 * len(labels))(*labels), len(labels), nokey
+
+
+def eval_confusion(preds, targets, labels):
+    """counts int64 [n, L, 3] = (TP, FP, FN) of label maps preds[i] against targets[i] (None: no target; TP + FP is
+    the volume) for the distinct int label values `labels`, every subject in one launch.  Maps: device tensors of
+    bool / (u)int8 / int16 / int32 / int64 / float32 holding integers, any shape, a target as many voxels as its
+    prediction.  `data == value` semantics of torch (the value cast to the map's type first)."""
+    if len(preds) != len(targets) or not preds:
+        raise _lib.M355Error("eval_confusion: one target (or None) per prediction, at least one subject")
+    arr, L, nokey = _ev_labels(labels)
+    n = len(preds)
+    descs = (_lib.EvalMapDesc * n)()
+    keep = []
+    dev = preds[0].device
+    for i, (p, t) in enumerate(zip(preds, targets)):
+        p = p.contiguous()
+        keep.append(p)
+        descs[i].pred, descs[i].S = p.data_ptr(), p.numel()
+        descs[i].pred_dtype = _ev_code(p, _EV_MAP_DTYPE, f"subject {i}: prediction")
+        if p.device != dev:
+            raise _lib.M355Error(f"subject {i} is on {p.device}, subject 0 on {dev}")
+        if t is not None:
+            t = t.contiguous()
+            keep.append(t)
+            if t.numel() != p.numel() or t.device != dev:
+                raise _lib.M355Error(f"subject {i}: target of {t.numel()} voxels on {t.device}, prediction of "
+                                     f"{p.numel()} on {dev}")
+            descs[i].target, descs[i].target_dtype = t.data_ptr(), _ev_code(t, _EV_MAP_DTYPE, f"subject {i}: target")
+    with torch.cuda.device(dev):
+        dev_descs = torch.empty(C.sizeof(descs), dtype=torch.uint8, device=dev)
+        counts = torch.empty((n, L, 3), dtype=torch.int64, device=dev)
+        check(_lib.lib().m355_eval_confusion(descs, n, _p(dev_descs), arr, L, nokey, _p(counts), _stream()),
+              "eval_confusion")
+    return counts
+
+
+def eval_scores(scores, table, labels, targets=None, masks=None, half=None, write_pred=False, write_target=False,
+                one_hot_targets=True):
+    """Counts straight from model scores.  scores: list of device tensors [C, *spatial] (float32 / bfloat16 /
+    float16, one type and one C for all).  Per voxel: c = torch.argmax over the channels (first maximum, NaN wins),
+    label = table[1][c] inside the mask, table[0][c] outside (table: two lists of C ints; without a mask only table[0]
+    is used).  Mask: `half` = (axis, upper) for a half-space of the spatial axes, or `masks` = one label map per
+    subject (its nonzero voxels).  targets[i]: None, a one-hot [C, *spatial] map (its argmax goes through the same
+    table; one_hot_targets=True) or a label map [1, *spatial] (one_hot_targets=False).
+    -> (counts int64 [n, L, 3], predicted label maps int64 [1, *spatial] or None, target label maps or None)."""
+    n = len(scores)
+    if n == 0:
+        raise _lib.M355Error("eval_scores: no subject")
+    targets = [None] * n if targets is None else list(targets)
+    Cc = scores[0].shape[0]
+    sd = _ev_code(scores[0], _EV_SCORE_DTYPE, "eval_scores: scores")
+    if not 1 <= Cc <= _lib.EV_MAX_CHANNELS:
+        raise _lib.M355Error(f"eval_scores: {Cc} channels (1 .. {_lib.EV_MAX_CHANNELS})")
+    outside = [int(v) for v in table[0]]
+    inside = [int(v) for v in table[1]] if (half is not None or masks is not None) else outside
+    if len(outside) != Cc or len(inside) != Cc:
+        raise _lib.M355Error(f"eval_scores: label table of {len(outside)} / {len(inside)} entries for {Cc} channels")
+    if half is not None and masks is not None:
+        raise _lib.M355Error("eval_scores: a half-space or mask maps, not both")
+    arr, L, nokey = _ev_labels(labels)
+    tab = (C.c_int32 * (2 * Cc))(*(outside + inside))
+    mask_kind, axis, upper = _lib.EV_MASK_NONE, 0, 0
+    if half is not None:
+        mask_kind, axis, upper = _lib.EV_MASK_HALF, int(half[0]), int(bool(half[1]))
+    elif masks is not None:
+        mask_kind = _lib.EV_MASK_MAP
+    descs = (_lib.EvalScoresDesc * n)()
+    keep, pred_outs, target_outs = [], [], []
+    dev = scores[0].device
+    for i, s in enumerate(scores):
+        if s.dim() != 4 or s.shape[0] != Cc or s.dtype != scores[0].dtype or s.device != dev:
+            raise _lib.M355Error(f"eval_scores: subject {i}: scores {tuple(s.shape)} {s.dtype} on {s.device}; expected "
+                                 f"[{Cc}, D, H, W] {scores[0].dtype} on {dev}")
+        s = s.contiguous()
+        sp = tuple(s.shape[1:])
+        keep.append(s)
+        d = descs[i]
+        d.scores = s.data_ptr()
+        d.size3[:] = sp
+        t = targets[i]
+        if t is not None:
+            t = t.contiguous()
+            keep.append(t)
+            if t.device != dev or tuple(t.shape[-3:]) != sp or t.dim() not in (3, 4):
+                raise _lib.M355Error(f"eval_scores: subject {i}: target {tuple(t.shape)} on {t.device} for scores "
+                                     f"{tuple(s.shape)}")
+            one_hot = bool(one_hot_targets)
+            if t.numel() != (Cc if one_hot else 1) * s[0].numel():
+                raise _lib.M355Error(f"eval_scores: subject {i}: {'one-hot' if one_hot else 'label map'} target "
+                                     f"{tuple(t.shape)} for scores {tuple(s.shape)}")
+            d.target, d.target_dtype = t.data_ptr(), _ev_code(t, _EV_MAP_DTYPE, f"subject {i}: target")
+            d.target_kind = _lib.EV_TARGET_ONEHOT if one_hot else _lib.EV_TARGET_MAP
+        if mask_kind == _lib.EV_MASK_MAP:
+            m = masks[i].contiguous()
+            keep.append(m)
+            if m.numel() != s[0].numel() or m.device != dev:
+                raise _lib.M355Error(f"eval_scores: subject {i}: mask {tuple(m.shape)} for scores {tuple(s.shape)}")
+            d.mask, d.mask_dtype = m.data_ptr(), _ev_code(m, _EV_MAP_DTYPE, f"subject {i}: mask")
+        po = torch.empty((1,) + sp, dtype=torch.int64, device=dev) if write_pred else None
+        to = None
+        if write_target and t is not None and d.target_kind == _lib.EV_TARGET_ONEHOT:
+            to = torch.empty((1,) + sp, dtype=torch.int64, device=dev)
+        d.pred_out, d.target_out = (po.data_ptr() if po is not None else None), (to.data_ptr() if to is not None else None)
+        pred_outs.append(po)
+        target_outs.append(to)
+    with torch.cuda.device(dev):
+        dev_descs = torch.empty(C.sizeof(descs), dtype=torch.uint8, device=dev)
+        counts = torch.empty((n, L, 3), dtype=torch.int64, device=dev)
+        check(_lib.lib().m355_eval_scores(descs, n, _p(dev_descs), sd, Cc, tab, mask_kind, axis, upper, arr, L, nokey,
+                                          _p(counts), _stream()), "eval_scores")
+    return counts, (pred_outs if write_pred else None), (target_outs if write_target else None)

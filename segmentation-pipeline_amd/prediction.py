@@ -10,13 +10,17 @@
   inside `distributed.unit_sharding()` the tiles are sharded over the ranks and
   returned by a single all_gather (distributed.gather_tiles).
 """
+import copy
 import itertools
 from typing import Optional, Sequence, Tuple
 
 import torch
 
 from . import distributed as D
+from . import evaluators as E
 from . import ops
+from . import preprocessing as P
+from ._lib import M355Error
 
 
 def split_and_flip(x: torch.Tensor) -> torch.Tensor:
@@ -247,3 +251,190 @@ class PatchPredict:
         preds = [self.predict_volume(model, v) for v in x]
         batch["y_pred"] = None if any(p is None for p in preds) else torch.stack(preds)
         return batch
+
+
+# ---------------------------------------------------------------------------------------------- evaluation labels
+class EvaluationPlan:
+    """The inverse of a preprocessing chain's label transforms (the reference's
+    `filter_transform(history, [LabelTransform, CopyProperty, RenameProperty, ConcatenateImages]).inverse()`,
+    prediction.py:155-170) for the image `name`, as a channel -> label value table: CustomOneHot^-1 is the argmax,
+    CustomRemapLabels^-1 the swapped remap under the same mask (named remaps restore their label_values entries),
+    renames follow the name back.  Built once per chain; `tables(C)` gives the [outside, inside] tables of C channels."""
+
+    def __init__(self, transform, name="y"):
+        steps = _label_steps(transform)
+        self.final_name = name
+        self.remaps = []            # (mapping, named pairs or None, masked) in application order
+        self.half, self.mask_name = None, None
+        masking = None
+        argmax = False
+        cur = name
+        for t, include, exclude in reversed(steps):
+            applies = (include is None or cur in include) and cur not in exclude
+            if isinstance(t, P.CustomOneHot):
+                if applies:
+                    if argmax:
+                        raise M355Error("evaluation labels: two CustomOneHot transforms act on one label map")
+                    argmax = True
+            elif isinstance(t, P.RenameProperty):
+                if cur == t.new_name:
+                    cur = t.old_name
+            elif isinstance(t, P.ConcatenateImages):
+                if cur == t.new_image_name:
+                    raise M355Error(f"evaluation labels: {cur} is a concatenation; splitting it is not supported")
+            elif isinstance(t, P.CustomRemapLabels):
+                if not applies:
+                    continue
+                if not argmax:
+                    raise M355Error("evaluation labels: a CustomRemapLabels after CustomOneHot cannot be inverted on "
+                                    "label values")
+                if not t.invertible:
+                    raise M355Error("evaluation labels: a CustomRemapLabels with invertible=False")
+                inverse = {}
+                for old, new in t.mapping.items():
+                    inverse[new] = old
+                named = None if t.named is None else [(label, new, old) for label, old, new in t.named]
+                if named is not None:
+                    inverse = {}
+                    for _, new, old in named:
+                        inverse[new] = old
+                mm = t.masking_method
+                if mm is not None:
+                    if masking is not None and masking != mm:
+                        raise M355Error(f"evaluation labels: remaps under two masks ({masking!r}, {mm!r})")
+                    masking = mm
+                self.remaps.append((inverse, named, mm is not None))
+        if not argmax:
+            raise M355Error(f"evaluation labels: no CustomOneHot produced {name}; nothing to take the argmax of")
+        self.source_name = cur
+        if masking is not None:
+            if isinstance(masking, str) and masking.title() in P._ANATOMICAL:
+                self.half = P._ANATOMICAL[masking.title()]
+            elif isinstance(masking, str):
+                self.mask_name = masking
+            else:
+                raise M355Error(f"evaluation labels: masking_method {masking!r}")
+
+    def tables(self, C):
+        outside, inside = list(range(C)), list(range(C))
+        for mapping, _, masked in self.remaps:
+            inside = [mapping.get(v, v) for v in inside]
+            if not masked:
+                outside = [mapping.get(v, v) for v in outside]
+        return outside, inside
+
+    def label_values(self, label_values):
+        """the label_values after the inverse chain (named remaps restore their entries)"""
+        if label_values is None:
+            return None
+        out = copy.deepcopy(dict(label_values))
+        for _, named, _ in self.remaps:
+            for label, _, old in named or ():
+                out[label] = old
+        return out
+
+
+def _label_steps(transform, include=None, exclude=(), gated=False):
+    """(label transform, effective include, effective exclude) in the order a Compose runs them; a label transform
+    under a probability below 1 or inside OneOf is refused"""
+    from . import augmentation as A
+    label_types = (P.CustomRemapLabels, P.CustomOneHot, P.RenameProperty, P.ConcatenateImages)
+    inc = transform.include if include is None else (
+        include if transform.include is None else [k for k in transform.include if k in include])
+    exc = list(exclude) + list(transform.exclude)
+    gated = gated or transform.probability < 1.0 or isinstance(transform, A.OneOf)
+    if isinstance(transform, A.Compose):
+        out = []
+        for t in transform.transforms:
+            out += _label_steps(t, inc, exc, gated)
+        return out
+    if isinstance(transform, label_types):
+        if gated:
+            raise M355Error(f"evaluation labels: {type(transform).__name__} runs under a probability gate or inside "
+                            "OneOf; its inverse is not defined")
+        return [(transform, inc, exc)]
+    return []
+
+
+class _ScoreSource:
+    def __init__(self, plan, scores, target, mask, label_values):
+        self.plan, self.scores, self.target, self.mask = plan, scores, target, mask
+        self.pred_map = E.ScoreLabelMap(self, "pred", label_values)
+        self.target_map = None if target is None else E.ScoreLabelMap(self, "target", label_values)
+
+    def materialise(self):
+        _materialise([self])
+
+
+def _materialise(sources):
+    plan = sources[0].plan
+    has_t = [s.target is not None for s in sources]
+    C = sources[0].scores.shape[0]
+    outside, inside = plan.tables(C)
+    _, preds, targets = ops.eval_scores(
+        [s.scores for s in sources], (outside, inside), [outside[0]],
+        targets=[s.target for s in sources] if all(has_t) else None,
+        masks=[s.mask for s in sources] if plan.mask_name is not None else None, half=plan.half,
+        write_pred=True, write_target=all(has_t))
+    for i, s in enumerate(sources):
+        s.pred_map['data'] = preds[i]
+        if s.target_map is not None:
+            if targets is None:
+                _materialise_one_target(s)
+            else:
+                s.target_map['data'] = targets[i]
+
+
+def _materialise_one_target(s):
+    outside, inside = s.plan.tables(s.scores.shape[0])
+    _, _, targets = ops.eval_scores([s.target.to(torch.float32)], (outside, inside), [outside[0]], targets=[s.target],
+                                    masks=[s.mask] if s.plan.mask_name is not None else None, half=s.plan.half,
+                                    write_target=True)
+    s.target_map['data'] = targets[0]
+
+
+def _tensor(v):
+    return v if torch.is_tensor(v) else v.data
+
+
+def add_evaluation_labels(subjects, transform, label_values=None, write=False, pred_name="y_pred", target_name="y"):
+    """Add 'y_pred_eval' / 'y_eval' label maps (evaluators.LabelMap: int64 [1, D, H, W] and 'label_values') to every
+    subject that has 'y_pred' scores ([C, D, H, W]) or a one-hot 'y', inverting the label transforms of `transform`,
+    the preprocessing Compose that produced 'y' (prediction.py:155-170 of the reference).  `label_values`: the training
+    target's {label name: value} after the chain (the reference's label_attributes); both maps take its inverse.
+    `subjects`: a list of dicts, or one batch dict of stacked [N, C, D, H, W] tensors (optionally 'name': a list),
+    which becomes a list of subject dicts.  The maps are computed on first access to `.data`; an evaluator counts
+    straight from the scores without writing them.  write=True: compute them now, in one launch.
+    A masked remap whose mask is a label map reads it from the subject under its name.  Returns the subjects."""
+    if isinstance(subjects, dict):
+        n = next(_tensor(v).shape[0] for k, v in subjects.items() if k in (pred_name, target_name))
+        names = subjects.get("name", [None] * n)
+        subjects = [{k: (_tensor(v)[i] if k in (pred_name, target_name) or
+                         (torch.is_tensor(v) and v.dim() == 5) else v)
+                     for k, v in subjects.items() if k != "name"} | ({"name": names[i]} if names[i] is not None else {})
+                    for i in range(n)]
+    plan = transform if isinstance(transform, EvaluationPlan) else EvaluationPlan(transform, target_name)
+    values = plan.label_values(label_values)
+    sources = []
+    for s in subjects:
+        scores = _tensor(s[pred_name]) if pred_name in s else None
+        target = _tensor(s[target_name]) if target_name in s else None
+        mask = None
+        if plan.mask_name is not None:
+            if plan.mask_name not in s:
+                raise M355Error(f"evaluation labels: the remap mask {plan.mask_name} is not in the subject")
+            mask = _tensor(s[plan.mask_name])
+        if scores is None and target is None:
+            continue
+        if scores is None:   # a target alone: the table applies to its argmax
+            src = _ScoreSource(plan, target.to(torch.float32), None, mask, values)
+            s["y_eval"] = src.pred_map
+            continue
+        src = _ScoreSource(plan, scores, target, mask, values)
+        s["y_pred_eval"] = src.pred_map
+        if src.target_map is not None:
+            s["y_eval"] = src.target_map
+        sources.append(src)
+    if write and sources:
+        _materialise(sources)
+    return subjects

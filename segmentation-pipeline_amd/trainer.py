@@ -6,7 +6,7 @@ import math
 import signal
 import threading
 import time
-from typing import Callable, Dict, Iterable, Optional
+from typing import Callable, Dict, Iterable, Optional, Sequence
 
 import torch
 
@@ -293,6 +293,29 @@ class SegmentedGraphTrainStep:
         return {k: v.clone() for k, v in ent["static"].items()}
 
 
+class ScheduledEvaluation:
+    """An evaluator run every `interval` iterations (segmentation_trainer.py:33-48, reference) on the validation
+    subjects of `cohorts` (logged as {log_name: {cohort: output}}) or on the subjects named in `subjects` (logged as
+    {log_name: output}); as a training evaluation, on the iteration's batch."""
+
+    def __init__(self, evaluator, log_name: str, cohorts: Sequence[str] = None, subjects: Sequence[str] = None,
+                 interval: int = 1):
+        assert not (cohorts and subjects), "One of cohorts or subjects may be provided, but not both."
+        self.evaluator = evaluator
+        self.log_name = log_name
+        self.cohorts = cohorts
+        self.subjects = subjects
+        self.interval = interval
+
+    def __repr__(self):
+        return (f"ScheduledEvaluation(evaluator={self.evaluator!r}, log_name={self.log_name!r}, cohorts={self.cohorts!r}, "
+                f"subjects={self.subjects!r}, interval={self.interval!r})")
+
+
+def _due(scheduled, iteration):
+    return [s for s in scheduled if iteration % s.interval == 0]
+
+
 class TrainLoop:
     """The iteration loop of SegmentationTrainer.train (segmentation_trainer.py:162-280) around
     `train_step`, without the torchio / logger plumbing: max_iterations, wall-clock budget with the
@@ -333,11 +356,69 @@ class TrainLoop:
             D.all_reduce_mean_scalars(vals)           # flags: mean > 0 <=> some rank raised it
         return bool(vals[0] > 0), bool(vals[1] > 0), float(vals[2])
 
+    def _training_evaluations(self, due, batch, label_transform, label_values):
+        from .prediction import add_evaluation_labels
+        if not due:
+            return {}
+        n = batch["y_pred"].shape[0]
+        names = batch.get("name") or [str(i) for i in range(n)]
+        subjects = add_evaluation_labels({"y_pred": batch["y_pred"].detach(), "y": batch["y"], "name": list(names)},
+                                         label_transform, label_values)
+        return {s.log_name: s.evaluator(subjects) for s in due}
+
+    def _validation_evaluations(self, due, model, device, validation_predictor, validation_subjects, label_transform,
+                                label_values):
+        """segmentation_trainer.py:193-241: predict every subject a due evaluator needs, then run the evaluators"""
+        from .prediction import add_evaluation_labels
+        if not due:
+            return {}
+        wanted = set()
+        for s in due:
+            if s.cohorts is not None:
+                for c in s.cohorts:
+                    wanted.update(id(x) for x in validation_subjects[c])
+            elif s.subjects is not None:
+                names = set(s.subjects)
+                wanted.update(id(x) for c in validation_subjects.values() for x in c if x["name"] in names)
+        evaluated = {}
+        with torch.no_grad():
+            for cohort in validation_subjects.values():
+                for subject in cohort:
+                    if id(subject) not in wanted or id(subject) in evaluated:
+                        continue
+                    batch = validation_predictor.predict(model, device, {"X": subject["X"][None]})
+                    out = {k: v for k, v in subject.items()}
+                    out["y_pred"] = batch["y_pred"][0]
+                    if torch.is_tensor(out.get("y")):
+                        out["y"] = out["y"].to(device)
+                    evaluated[id(subject)] = out
+        add_evaluation_labels(list(evaluated.values()), label_transform, label_values)
+        by_name = {s["name"]: s for s in evaluated.values()}
+        results = {}
+        for s in due:
+            if s.cohorts is not None:
+                results[s.log_name] = {c: s.evaluator([evaluated[id(x)] for x in validation_subjects[c]])
+                                       for c in s.cohorts}
+            elif s.subjects is not None:
+                results[s.log_name] = s.evaluator([by_name[name] for name in s.subjects])
+        return results
+
     def run(self, model, criterion, optimizer, predictor, batches: Iterable, device, max_iterations: int,
             max_training_time: Optional[float] = None, log_fn: Optional[Callable[[Dict], None]] = None,
-            timer: Optional[PhaseTimer] = None):
+            timer: Optional[PhaseTimer] = None, training_evaluators: Sequence[ScheduledEvaluation] = (),
+            validation_evaluators: Sequence[ScheduledEvaluation] = (), validation_predictor=None,
+            validation_subjects: Optional[Dict[str, list]] = None, label_transform=None,
+            label_values: Optional[Dict[str, int]] = None):
         """`batches`: iterator of dicts with stacked "X" / "y" tensors (the collate_subjects output,
-        utils/utils.py:75-85).  `max_training_time` in seconds.  Returns the last loss dict."""
+        utils/utils.py:75-85).  `max_training_time` in seconds.  Returns the last loss dict.
+
+        Scheduled evaluation (segmentation_trainer.py:181-241): `training_evaluators` run on the iteration's batch
+        (subject names from batch['name'] when present), `validation_evaluators` on `validation_subjects` (cohort name
+        -> list of subject dicts with 'name', 'X' [C, D, H, W] and the one-hot 'y'), predicted by
+        `validation_predictor` (default: `predictor`) under no_grad.  Both get 'y_pred_eval' / 'y_eval' from
+        prediction.add_evaluation_labels(label_transform, label_values): `label_transform` is the preprocessing
+        Compose that produced 'y', `label_values` the training target's label_values after it.  Outputs go into the
+        log dict (and so to `scoring_function`) under each evaluator's log_name."""
         if max_training_time is not None:
             save_buffer = min(int(max_training_time * 0.1), 5 * 60)
             stop_time = time.time() + max_training_time - save_buffer
@@ -350,6 +431,12 @@ class TrainLoop:
         for _ in range(max_iterations):
             loss_dict, _batch = train_step(model, criterion, optimizer, predictor, next(it), device, timer)
             log_dict = dict(loss_dict)
+            if training_evaluators or validation_evaluators:
+                log_dict.update(self._training_evaluations(_due(training_evaluators, self.iteration), _batch,
+                                                           label_transform, label_values))
+                log_dict.update(self._validation_evaluations(
+                    _due(validation_evaluators, self.iteration), model, device, validation_predictor or predictor,
+                    validation_subjects or {}, label_transform, label_values))
             score = None
             scoring = self.scoring_function is not None and self.iteration % self.scoring_interval == 0
             if scoring:
