@@ -816,6 +816,18 @@ int m355_pre_one_hot(const void* x, int32_t dtype, const int32_t* size3, int32_t
 int m355_pre_image_from_labels(const m355_pre_label_entry* entries, int32_t n, const int32_t* size3, int32_t mode,
                                float* y, void* stream);
 
+/* ------------------------------------------ mean diffusion-weighted image
+ * The per-voxel work of the reference's ReconstructMeanDWI / ReconstructMeanDWIClassic
+ * (segmentation_pipeline/transforms/reconstruct_mean_dwi.py); the channels are drawn on the host (augmentation.py,
+ * DESIGN §4.10).
+ *   m355_dwi_mean         y[v] (float32, one channel of size3) = (x[idx[0]][v] + x[idx[1]][v] + ... + x[idx[k-1]][v]) / k
+ *                         for x float32 [N, V0, V1, V2] (fewer than 2^31 voxels per channel): summed in fp32 in pick
+ *                         order, then one correctly rounded fp32 division by (float) k, as np.mean(x[idx], axis=0) and
+ *                         torch.mean(x[idx], 0) for float32.  idx: device int32 [k], k >= 1, duplicates allowed; an
+ *                         index outside [0, N) makes its voxels NaN (the host checks them before the upload).  One
+ *                         launch on `stream`, no synchronisation; x != y. */
+int m355_dwi_mean(const float* x, int32_t N, const int32_t* size3, const int32_t* idx, int32_t k, float* y, void* stream);
+
 /* ------------------------------------------ evaluation
  * Confusion counts of the reference's SegmentationEvaluator / LabelMapEvaluator (evaluators.py).
  * counts[subject][l][{TP, FP, FN}] (device uint64, zeroed here) for the L distinct label values labels[0 .. L)

@@ -230,6 +230,7 @@ SIGNATURES = {
     "m355_pre_gather": (C.c_int, [C.POINTER(PreGatherDesc), _P]),
     "m355_pre_one_hot": (C.c_int, [_P, _i32, _I3, _i32, _P, _P, _P]),
     "m355_pre_image_from_labels": (C.c_int, [C.POINTER(PreLabelEntry), _i32, _I3, _i32, _P, _P]),
+    "m355_dwi_mean": (C.c_int, [_P, _i32, _I3, _P, _i32, _P, _P]),
     "m355_eval_confusion": (C.c_int, [C.POINTER(EvalMapDesc), _i32, _P, _I3, _i32, _i32, _P, _P]),
     "m355_eval_scores": (C.c_int, [C.POINTER(EvalScoresDesc), _i32, _P, _i32, _i32, _I3, _i32, _i32, _i32, _I3, _i32,
                                    _i32, _P, _P]),

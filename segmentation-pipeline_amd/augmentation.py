@@ -13,6 +13,10 @@ per-voxel step runs in libm355seg.so (csrc/augment.hip).  A call never synchroni
 interpolation (intensity transforms skip them).  The input tensors are never modified.  Consecutive intensity
 transforms of one tensor are fused into one streaming pass (plus the statistics passes a rescale needs).
 `t.last_history` records the concrete parameters of the last call.  Semantics and every torchio assumption: DESIGN §4.10.
+
+`ReconstructMeanDWI` / `ReconstructMeanDWIClassic` (the reference's own transforms) replace `mean_dwi` with the mean of
+drawn channels of `full_dwi` (csrc/dwi.hip, through `MeanDWI`); they read full_dwi's gradient table from the call's
+`attributes={"full_dwi": {"grad": [N, 4] host table}}`.
 """
 import ctypes as C
 import math
@@ -27,7 +31,8 @@ from .ops import _p, _stream
 
 __all__ = ["Compose", "OneOf", "RandomFlip", "RandomPermuteDimensions", "RandomElasticDeformation", "RandomAffine",
            "RandomBiasField", "RescaleIntensity", "RandomGamma", "RandomBlur", "RandomNoise", "Flip", "PermuteDimensions",
-           "ElasticDeformation", "Affine", "BiasField", "Gamma", "Blur", "Noise"]
+           "ElasticDeformation", "Affine", "BiasField", "Gamma", "Blur", "Noise", "ReconstructMeanDWI",
+           "ReconstructMeanDWIClassic", "MeanDWI"]
 
 NEAREST, LINEAR, BSPLINE = 0, 1, 2
 _INTERP = {"nearest": NEAREST, "linear": LINEAR, "bspline": BSPLINE}
@@ -59,7 +64,7 @@ def _percentile_rank(n, q):
 class _State:
     """A subject during one call: materialised tensors and, per name, the intensity stages not yet applied."""
 
-    def __init__(self, subject, label_maps, spacing, generator, label_values=None):
+    def __init__(self, subject, label_maps, spacing, generator, label_values=None, attributes=None):
         self.data = dict(subject)
         self.owned = set()
         self.labels = set(label_maps)
@@ -74,6 +79,9 @@ class _State:
         # name -> preprocessing pass not yet launched into data[name] (already allocated with its final shape and dtype);
         # it runs before blur[name] and pending[name]
         self.deferred = {}
+        # per-image host attributes ({image name: {key: value}}, the reference's TensorLoader(belongs_to=...)), e.g.
+        # full_dwi's gradient table; None when the caller gave none
+        self.attributes = None if attributes is None else {k: dict(v) for k, v in attributes.items()}
 
     def images(self, t, intensity):
         names = [k for k in self.data if (t.include is None or k in t.include) and k not in t.exclude]
@@ -108,9 +116,12 @@ class _State:
             self.flush(name)
 
     def meta(self):
-        return {"spacing": self.spacing, "label_maps": sorted(k for k in self.labels if k in self.data),
-                "label_values": {k: dict(v) for k, v in self.label_values.items() if k in self.data},
-                "one_hot": sorted(k for k in self.one_hot if k in self.data)}
+        m = {"spacing": self.spacing, "label_maps": sorted(k for k in self.labels if k in self.data),
+             "label_values": {k: dict(v) for k, v in self.label_values.items() if k in self.data},
+             "one_hot": sorted(k for k in self.one_hot if k in self.data)}
+        if self.attributes is not None:
+            m["attributes"] = {k: dict(v) for k, v in self.attributes.items() if k in self.data}
+        return m
 
 
 # ---------------------------------------------------------------------------------------------- native calls
@@ -238,13 +249,16 @@ class Transform:
         self.last_history = None
         self.last_meta = None
 
-    def __call__(self, subject, label_maps=(), spacing=(1.0, 1.0, 1.0), generator=None, label_values=None):
+    def __call__(self, subject, label_maps=(), spacing=(1.0, 1.0, 1.0), generator=None, label_values=None,
+                 attributes=None):
         """label_values: {label map name: {label name: id}} (the reference's per-map `label_values`); the resulting
-        metadata (spacing, label maps, label_values, one-hot maps) is published as `last_meta`"""
+        metadata (spacing, label maps, label_values, one-hot maps) is published as `last_meta`.  attributes: host
+        values attached to an image, {image name: {key: value}} (the reference's TensorLoader(belongs_to=...)), e.g.
+        {"full_dwi": {"grad": [N, 4] table}} for ReconstructMeanDWI; published in `last_meta` only when given"""
         for k, v in subject.items():
             if not isinstance(v, torch.Tensor) or not v.is_cuda or v.dim() != 4:
                 raise M355Error(f"{k}: expected a device tensor [C, V0, V1, V2]")
-        state = _State(subject, label_maps, spacing, generator, label_values)
+        state = _State(subject, label_maps, spacing, generator, label_values, attributes)
         self._run(state)
         state.flush_all()
         self.last_meta = state.meta()
@@ -637,3 +651,193 @@ class RandomBlur(Transform):
             Blur(s, include=[name])._apply(state)
             hist[name] = s
         self.last_history = {"sigmas": hist}
+
+
+# ---------------------------------------------------------------------------------------------- diffusion
+def _grad_table(grad, num_channels=None):
+    """a host gradient table -> float64 [N, 4] (bvec x, y, z, bval); N must be the channel count of full_dwi"""
+    if isinstance(grad, torch.Tensor):
+        if grad.device.type != "cpu":
+            raise M355Error("the gradient table must be a host tensor or array (reading a device one would synchronise)")
+        grad = grad.numpy()
+    g = np.asarray(grad, dtype=np.float64)
+    if g.ndim != 2 or g.shape[1] != 4:
+        raise M355Error(f"gradient table of shape {g.shape}: expected [N, 4] (bvec, bval)")
+    if num_channels is not None and g.shape[0] != num_channels:
+        raise M355Error(f"gradient table of {g.shape[0]} rows for a full_dwi of {num_channels} channels")
+    return g
+
+
+def _eligible(g, bval_range):
+    """row indices whose bval lies strictly inside bval_range"""
+    lo, hi = bval_range
+    idx = np.nonzero((g[:, 3] > lo) & (g[:, 3] < hi))[0]
+    if idx.size == 0:
+        raise M355Error(f"no gradient with a bval strictly inside {tuple(bval_range)}")
+    return idx
+
+
+def _pair(v):
+    return isinstance(v, (tuple, list)) and len(v) == 2
+
+
+def _dwi_grad(state, full, key):
+    attrs = (state.attributes or {}).get(full, {})
+    if key not in attrs:
+        raise M355Error(f"{full}: no '{key}' gradient table: pass attributes={{'{full}': {{'{key}': [N, 4] table}}}}")
+    return _grad_table(attrs[key], state.data[full].shape[0])
+
+
+class MeanDWI(Transform):
+    """mean_dwi <- the mean of the channels `channels` (indices into full_dwi, in pick order, duplicates allowed) of
+    full_dwi: one launch of m355_dwi_mean.  full_dwi's deferred and pending work runs first; an existing mean_dwi is
+    replaced and its own deferred / pending work dropped (it belonged to the old data); a missing full_dwi is a no-op.
+    include / exclude are not consulted: the images are addressed by name."""
+
+    def __init__(self, channels, full_dwi_image_name="full_dwi", mean_dwi_image_name="mean_dwi", **kw):
+        super().__init__(**kw)
+        self.channels = [int(c) for c in np.atleast_1d(np.asarray(channels))]
+        if not self.channels or min(self.channels) < 0:
+            raise M355Error(f"MeanDWI: channels {self.channels}: at least one, none negative")
+        self.full_dwi_image_name = full_dwi_image_name
+        self.mean_dwi_image_name = mean_dwi_image_name
+
+    def _apply(self, state):
+        full, mean = self.full_dwi_image_name, self.mean_dwi_image_name
+        self.last_history = {"channels": list(self.channels)}
+        if full not in state.data:
+            return
+        state.flush(full)
+        x = state.data[full]
+        if x.dtype != torch.float32:
+            raise M355Error(f"{full}: images must be float32, got {x.dtype}")
+        N = x.shape[0]
+        if max(self.channels) >= N:
+            raise M355Error(f"MeanDWI: channel {max(self.channels)} of a {full} with {N} channels")
+        x = x.contiguous()
+        for pend in (state.deferred, state.blur, state.pending):
+            pend.pop(mean, None)
+        created = mean not in state.data
+        idx = _upload(self.channels, torch.int32, x.device)
+        y = torch.empty((1,) + tuple(x.shape[1:]), dtype=torch.float32, device=x.device)
+        check(_lib.lib().m355_dwi_mean(_p(x), N, _i3(x.shape[1:]), _p(idx), len(self.channels), _p(y), _stream()),
+              "dwi_mean")
+        state.keep += [x, idx]
+        state.set(mean, y)
+        if created and state.attributes is not None and full in state.attributes:
+            state.attributes[mean] = dict(state.attributes[full])   # the reference deep-copies full_dwi's image
+
+
+class ReconstructMeanDWI(Transform):
+    """the reference's ReconstructMeanDWI (segmentation_pipeline/transforms/reconstruct_mean_dwi.py): mean_dwi <- the
+    mean of num_dwis channels of full_dwi, drawn with replacement with probability proportional to
+    max_j |b_i . d_j|^directionality over m random unit directions d_j; only gradients whose bval lies strictly inside
+    bval_range are eligible.  The gradient table comes from the call's attributes[full_dwi_image_name][bvec_name].
+    Draw order and laws: `draw`; DESIGN §4.10."""
+
+    def __init__(self, full_dwi_image_name="full_dwi", mean_dwi_image_name="mean_dwi", bvec_name="grad", num_dwis=15,
+                 num_directions=1, directionality=4, bval_range=(1e-5, 501.0), p=1.0):
+        super().__init__(p)
+        self.full_dwi_image_name = full_dwi_image_name
+        self.mean_dwi_image_name = mean_dwi_image_name
+        self.bvec_name = bvec_name
+        for what, v in (("num_dwis", num_dwis), ("num_directions", num_directions)):
+            ok = (_pair(v) and all(isinstance(a, numbers.Integral) for a in v) and v[0] <= v[1]) or \
+                isinstance(v, numbers.Integral)
+            if not ok:
+                raise M355Error(f"ReconstructMeanDWI: {what} {v!r}: an int or a pair of ints (lo <= hi)")
+        if (min(num_dwis) if _pair(num_dwis) else num_dwis) < 1:
+            raise M355Error(f"ReconstructMeanDWI: num_dwis {num_dwis!r} can draw fewer than one image")
+        if _pair(num_directions) and num_directions[0] < 1:
+            raise M355Error(f"ReconstructMeanDWI: num_directions {num_directions!r} can draw no direction")
+        if isinstance(num_directions, numbers.Integral) and _pair(num_dwis):
+            # the reference returns num_dwis for an int num_directions: randn(3, (lo, hi)) raises there
+            raise M355Error("ReconstructMeanDWI: an int num_directions with a range of num_dwis (the reference fails)")
+        if not (isinstance(directionality, numbers.Number) or
+                (_pair(directionality) and all(isinstance(a, numbers.Number) for a in directionality))):
+            raise M355Error(f"ReconstructMeanDWI: directionality {directionality!r}: a number or a pair")
+        self.num_dwis = tuple(num_dwis) if _pair(num_dwis) else int(num_dwis)
+        self.num_directions = tuple(num_directions) if _pair(num_directions) else int(num_directions)
+        self.directionality = tuple(float(a) for a in directionality) if _pair(directionality) else float(directionality)
+        self.bval_range = tuple(float(a) for a in bval_range)
+
+    def draw(self, grad, generator=None, num_channels=None):
+        """the draws after the gate, on the host, from `generator`: num_dwis (int, or int(u^2 (hi - lo + 1) + lo) with
+        u ~ U[0, 1)), num_directions (uniform on the inclusive range; an int gives num_dwis, the reference's quirk),
+        directionality (U(a, b) for a pair), randn(3, m) directions with unit columns, then num_dwis picks with
+        replacement (torch.multinomial).  -> history; `channels` index full_dwi"""
+        g = _grad_table(grad, num_channels)
+        elig = _eligible(g, self.bval_range)
+        gen = generator
+
+        def rand():
+            return float(torch.rand(1, generator=gen, dtype=torch.float64)[0])
+
+        if isinstance(self.num_dwis, int):
+            n = self.num_dwis
+        else:
+            lo, hi = self.num_dwis
+            n = int(rand() ** 2 * (hi - lo + 1) + lo)
+        if isinstance(self.num_directions, int):
+            m = n                                   # the reference's quirk (num_dwis is an int here)
+        else:
+            m = int(torch.randint(self.num_directions[0], self.num_directions[1] + 1, (1,), generator=gen)[0])
+        if isinstance(self.directionality, float):
+            a = self.directionality
+        else:
+            a = self.directionality[0] + (self.directionality[1] - self.directionality[0]) * rand()
+        d = torch.randn(3, m, generator=gen, dtype=torch.float64).numpy()
+        d = d / np.linalg.norm(d, axis=0, keepdims=True)
+        prob = np.max(np.abs(g[elig, :3] @ d) ** a, axis=1)
+        if not np.isfinite(prob).all() or not prob.sum() > 0:
+            raise M355Error("ReconstructMeanDWI: every eligible gradient has probability zero (or a non-finite one)")
+        picks = torch.multinomial(torch.from_numpy(prob), n, replacement=True, generator=gen).numpy()
+        return {"num_dwis": n, "num_directions": m, "directionality": a, "directions": d,
+                "channels": [int(c) for c in elig[picks]]}
+
+    def _apply(self, state):
+        if self.full_dwi_image_name not in state.data:
+            return   # as the reference: nothing drawn, nothing changed
+        hist = self.draw(_dwi_grad(state, self.full_dwi_image_name, self.bvec_name), state.gen)
+        MeanDWI(hist["channels"], self.full_dwi_image_name, self.mean_dwi_image_name)._apply(state)
+        self.last_history = hist
+
+
+class ReconstructMeanDWIClassic(Transform):
+    """the reference's ReconstructMeanDWIClassic: a random eligible gradient, its subset_size nearest eligible gradients
+    (squared distance of the bvecs), and the mean of randint(1, subset_size) of them (a random permutation's first).
+    Draw order: `draw`; DESIGN §4.10."""
+
+    def __init__(self, full_dwi_image_name="full_dwi", mean_dwi_image_name="mean_dwi", bvec_name="grad", subset_size=15,
+                 bval_range=(1e-5, 501.0), p=1.0):
+        super().__init__(p)
+        if not isinstance(subset_size, numbers.Integral) or subset_size < 2:
+            raise M355Error(f"ReconstructMeanDWIClassic: subset_size {subset_size!r} < 2 (randint(1, subset_size))")
+        self.full_dwi_image_name = full_dwi_image_name
+        self.mean_dwi_image_name = mean_dwi_image_name
+        self.bvec_name = bvec_name
+        self.subset_size = int(subset_size)
+        self.bval_range = tuple(float(a) for a in bval_range)
+
+    def draw(self, grad, generator=None, num_channels=None):
+        """reference gradient (uniform over the eligible ones), the stable float64 squared-distance ranking (the
+        reference's argsort is unstable: ties may order differently there), number of selections randint(1,
+        subset_size) (upper bound excluded), then randperm of the candidates, whose first selections are taken"""
+        g = _grad_table(grad, num_channels)
+        elig = _eligible(g, self.bval_range)
+        gen = generator
+        r = int(torch.randint(0, elig.size, (1,), generator=gen)[0])
+        b = g[elig, :3]
+        dist = np.sum((b - b[r]) ** 2, axis=1)
+        cand = np.argsort(dist, kind="stable")[:self.subset_size]
+        nsel = int(torch.randint(1, self.subset_size, (1,), generator=gen)[0])
+        perm = torch.randperm(cand.size, generator=gen).numpy()[:nsel]
+        return {"reference": int(elig[r]), "subset": [int(c) for c in elig[cand]], "num_selections": nsel,
+                "channels": [int(c) for c in elig[cand[perm]]]}
+
+    def _apply(self, state):
+        if self.full_dwi_image_name not in state.data:
+            return
+        hist = self.draw(_dwi_grad(state, self.full_dwi_image_name, self.bvec_name), state.gen)
+        MeanDWI(hist["channels"], self.full_dwi_image_name, self.mean_dwi_image_name)._apply(state)
+        self.last_history = hist
