@@ -12,7 +12,14 @@
  *  - All tensors are float32 (M355_F32), NCDHW, spatial dims dense
  *    (stride of W == 1, H == W, D == H*W, C == D*H*W).  The batch stride is
  *    explicit (in elements) wherever a tensor may be a channel slice of a
- *    larger concat buffer; 0 means dense (C*D*H*W).
+ *    larger concat buffer; 0 means dense (C*D*H*W).  An fp32 tensor that
+ *    carries a batch stride needs no alignment beyond its element size, and
+ *    any stride is legal (the vector kernels are chosen from the pointers and
+ *    strides at hand), except where an entry point states a requirement and
+ *    rejects what misses it.  Everything else (weights, bias, statistics,
+ *    workspace, packed weights) is expected as an allocator hands it out:
+ *    16-byte aligned.  c8 tensors are made of 16-byte items: 16-byte aligned,
+ *    strides % 8 == 0.
  *  - Caller owns every buffer, including workspace.  The library never
  *    frees device memory and keeps no pointer to a tensor or workspace after a
  *    call returns.  The ONE piece of device state it keeps is the work-queue
@@ -314,7 +321,10 @@ int m355_norm_act_fwd(const m355_norm_desc* d, const float* x, const float* mean
 /* normalise + activation with nn.AvgPool3d(2, 2) of the result as a second output (an encoder block's output
  * continues into the skip connection and, pooled, into the next level: models/modular_unet.py:90-92).  y as in
  * m355_norm_act_fwd (no residual add); pooled: fp32 [N, C, D/2, H/2, W/2] with its own batch stride (0 = dense).
- * D * H * W must equal desc->S, all even.  Bit-identical to m355_norm_act_fwd followed by m355_avgpool3d_2x_fwd. */
+ * D * H * W must equal desc->S, all even.  Bit-identical to m355_norm_act_fwd followed by m355_avgpool3d_2x_fwd.
+ * Alignment: x and y 8-byte aligned, desc->x_batch_stride and desc->y_batch_stride even (the kernel moves x pairs);
+ * M355_EINVALID_ARG otherwise, nothing is launched.  Channel slices of an aligned concat buffer always qualify (S is a
+ * multiple of 8). */
 int m355_norm_act_pool_fwd(const m355_norm_desc* d, const float* x, const float* mean, const float* rstd,
                            const float* gamma, const float* beta, float* y, float* pooled, int64_t pooled_batch_stride,
                            int32_t D, int32_t H, int32_t W, void* stream);
@@ -543,7 +553,9 @@ int m355_add(const float* a, const float* b, float* y, int64_t n, void* stream);
  *   d2s: the inverse; D,H,W below are always those of the FULL-resolution tensor.
  * They turn the reference's strided Blur convolutions (components.py:91-154: effective 4x4x4 kernel,
  * stride 2, padding 1) into stride-1 3x3x3 convolutions that run on the MFMA path:
- *   BlurConv3d:          conv3(s2d(x), W') ;   BlurConvTranspose3d: d2s(conv3(x, W'')). */
+ *   BlurConv3d:          conv3(s2d(x), W') ;   BlurConvTranspose3d: d2s(conv3(x, W'')).
+ * Alignment: the FULL-resolution tensor (x of s2d, y of d2s) 8-byte aligned with an even batch stride (the kernel moves
+ * x pairs); M355_EUNSUPPORTED otherwise, nothing is launched.  The packed tensor has no requirement. */
 int m355_space_to_depth2(const float* x, float* y, int32_t N, int32_t C, int32_t D, int32_t H, int32_t W,
                          int64_t x_batch_stride, int64_t y_batch_stride, void* stream);
 int m355_depth_to_space2(const float* x, float* y, int32_t N, int32_t C, int32_t D, int32_t H, int32_t W,

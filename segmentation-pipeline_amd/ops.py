@@ -156,6 +156,30 @@ def _dense_channels(t):
     return t, (st[0] if N > 1 else Cc * S)
 
 
+def _pairs_ok(t, bs):
+    """m355_norm_act_pool_fwd and the fp32 space-to-depth pair move x pairs: they want an 8-byte aligned pointer and an
+    even batch stride (m355seg.h).  Channel slices of an allocator-aligned buffer always qualify; a caller's view at an odd
+    element offset does not."""
+    return t.data_ptr() % 8 == 0 and (t.shape[0] == 1 or bs % 2 == 0)
+
+
+def _pairs_in(t, bs):
+    """(tensor, batch stride) of an INPUT of those kernels: a view they would reject is compacted first"""
+    if _pairs_ok(t, bs):
+        return t, bs
+    t = t.clone(memory_format=torch.contiguous_format)
+    return t, t[0].numel()
+
+
+def _pairs_out(y, bs):
+    """(tensor to write, batch stride) for an OUTPUT of those kernels: a destination they would reject is produced in a
+    fresh tensor, which the caller copies into `y` afterwards (`written is not y`)"""
+    if _pairs_ok(y, bs):
+        return y, bs
+    t = torch.empty(y.shape, dtype=y.dtype, device=y.device)
+    return t, t[0].numel()
+
+
 class OutSlot:
     """A destination inside a pre-allocated concat buffer.
 
@@ -1640,13 +1664,17 @@ class _NormActPoolFn(torch.autograd.Function):
         S = D * H * W
         if xbs != Cc * S:
             x, xbs = x.contiguous(), Cc * S
+        x, xbs = _pairs_in(x, xbs)
         y = _alloc_out(cfg.out, x.shape, x)
         y, ybs = _dense_channels(y)
+        yw, ywbs = _pairs_out(y, ybs)
         pooled = torch.empty((N, Cc, D // 2, H // 2, W // 2), dtype=x.dtype, device=x.device)
-        d = NormDesc(N, Cc, S, cfg.groups, cfg.act, cfg.eps, cfg.slope, xbs, ybs, 0)
+        d = NormDesc(N, Cc, S, cfg.groups, cfg.act, cfg.eps, cfg.slope, xbs, ywbs, 0)
         mean, rstd, use_batch = _norm_statistics(L, d, x, cfg, N, Cc)
-        check(L.m355_norm_act_pool_fwd(C.byref(d), _p(x), _p(mean), _p(rstd), _p(gamma), _p(beta), _p(y), _p(pooled), 0,
+        check(L.m355_norm_act_pool_fwd(C.byref(d), _p(x), _p(mean), _p(rstd), _p(gamma), _p(beta), _p(yw), _p(pooled), 0,
                                        D, H, W, _stream()), "norm_act_pool_fwd")
+        if yw is not y:
+            y.copy_(yw)
         ctx.desc, ctx.batch_stats, ctx.has_affine, ctx.dims = d, use_batch, gamma is not None, (D, H, W)
         ctx.sync = cfg.sync
         ctx.save_for_backward(x, mean, rstd, gamma, beta)
@@ -2075,9 +2103,17 @@ class _S2DFn(torch.autograd.Function):
             full = (N, Cc // 8, 2 * D, 2 * H, 2 * W)
             y = _alloc_out(out, full, x)
         y, ybs = _dense_channels(y)
+        # (the FULL-resolution side must be 8-byte aligned with an even stride: x of s2d, y of d2s)
+        yw, ywbs = y, ybs
+        if to_depth:
+            x, xbs = _pairs_in(x, xbs)
+        else:
+            yw, ywbs = _pairs_out(y, ybs)
         fn = L.m355_space_to_depth2 if to_depth else L.m355_depth_to_space2
-        check(fn(_p(x), _p(y), full[0], full[1], full[2], full[3], full[4], xbs, ybs, _stream()),
+        check(fn(_p(x), _p(yw), full[0], full[1], full[2], full[3], full[4], xbs, ywbs, _stream()),
               "space_to_depth2" if to_depth else "depth_to_space2")
+        if yw is not y:
+            y.copy_(yw)
         ctx.to_depth, ctx.full = to_depth, full
         return y
 
@@ -2091,6 +2127,7 @@ class _S2DFn(torch.autograd.Function):
             check(L.m355_depth_to_space2(_p(dy), _p(dx), N, Cf, D, H, W, dybs, 0, _stream()), "depth_to_space2")
         else:
             dx = torch.empty((N, Cf * 8, D // 2, H // 2, W // 2), dtype=dy.dtype, device=dy.device)
+            dy, dybs = _pairs_in(dy, dybs)
             check(L.m355_space_to_depth2(_p(dy), _p(dx), N, Cf, D, H, W, dybs, 0, _stream()), "space_to_depth2")
         return dx, None, None
 

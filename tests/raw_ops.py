@@ -29,8 +29,102 @@ def build_oracle():
     return ORACLE_LIB
 
 
+class Slot:
+    """A tensor embedded as a channel slice of a larger, canary-filled flat buffer -- what `ops.OutSlot` /
+    `ops._dense_channels` (fp32) and `ops.Act16.slot` (c8) hand to the library, plus guards a test can inspect.
+
+    `shape` is the logical tensor: fp32 [N, C, D, H, W], or c8 [N, CB, S, 8] (then the "channels" below are channel
+    blocks).  Flat layout, in elements, `unit` = elements of one channel:
+
+        guard | lead | n = 0: c_pre * unit | C * unit (the slot) | c_post * unit | extra | n = 1: ... | guard
+
+    so the batch stride is (c_pre + C + c_post) * unit + extra, and the pointer handed to the library sits
+    (lead + c_pre * unit) elements behind a 64-byte aligned address.  `guard` is at least one full channel and at least
+    64 elements, a multiple of 16 elements.  Everything that is not the slot holds one quiet-NaN bit pattern of the element
+    type (compared through an integer view: bit-exact); so does the inside of an output slot (`data` is None).  An
+    input slot holds `data`.  A kernel that reads outside its slot and uses the value turns its result NaN."""
+
+    CANARY = {torch.float32: (torch.int32, 0x7FC0BEEF), torch.bfloat16: (torch.int16, 0x7FC5),
+              torch.float16: (torch.int16, 0x7E55)}
+
+    def __init__(self, device, shape, c_pre=1, c_post=1, lead=0, extra=0, dtype=torch.float32, data=None):
+        if data is not None:
+            shape, dtype = tuple(data.shape), data.dtype
+        self.shape, self.dtype, self.device = torch.Size(shape), dtype, device
+        N, Cc = shape[0], shape[1]
+        unit = 1
+        for v in shape[2:]:
+            unit *= v
+        assert N >= 1 and Cc >= 1 and unit >= 1 and min(c_pre, c_post, lead, extra) >= 0
+        itype, self.canary = self.CANARY[dtype]
+        self.unit = unit
+        self.bs = (c_pre + Cc + c_post) * unit + extra
+        self.bs_arg = self.bs    # what the wrappers pass as batch stride (the harness self-test passes a wrong one on purpose)
+        guard = -(-max(unit, 64) // 16) * 16
+        self.off = guard + lead + c_pre * unit
+        self.ibuf = torch.full((guard + lead + N * self.bs + guard,), self.canary, dtype=itype, device=device)
+        assert self.ibuf.data_ptr() % 64 == 0, "allocator alignment the layout classes are built on"
+        self.ptr = self.ibuf.data_ptr() + self.off * self.ibuf.element_size()
+        self.is_input = data is not None
+        if data is not None:
+            self.view().copy_(data.to(device))
+        self.before = self.ibuf.clone()
+
+    def _strided(self, flat):
+        st, acc = [], 1
+        for v in reversed(self.shape[2:]):
+            st.append(acc)
+            acc *= v
+        return torch.as_strided(flat, self.shape, (self.bs, self.unit) + tuple(reversed(st)), self.off)
+
+    def view(self):
+        """the slot as a strided view of the buffer, in the element type"""
+        return self._strided(self.ibuf.view(self.dtype))
+
+    def numel(self):
+        return self.shape.numel()
+
+    def misalign(self, to=16):
+        """bytes the slot pointer is off a `to`-byte boundary"""
+        return self.ptr % to
+
+    def result(self):
+        return self.view().clone(memory_format=torch.contiguous_format)
+
+    def assert_guards_intact(self, what=""):
+        g = self.ibuf.clone()
+        self._strided(g).fill_(self.canary)
+        bad = (g != self.canary).nonzero().flatten()
+        assert bad.numel() == 0, (f"{what}: {bad.numel()} elements outside the slot were overwritten; first at flat offset "
+                                  f"{int(bad[0])} (slot starts at {self.off}, batch stride {self.bs}, channel {self.unit})")
+
+    def assert_fully_written(self, what=""):
+        left = (self._strided(self.ibuf) == self.canary)
+        assert not bool(left.any()), f"{what}: {int(left.sum())} of {self.numel()} output elements were never written"
+
+    def assert_unchanged(self, what=""):
+        assert torch.equal(self.ibuf, self.before), f"{what}: an input buffer was modified"
+
+    def assert_untouched(self, what=""):
+        """an output slot of a call the host function rejected: still all canary"""
+        assert bool((self.ibuf == self.canary).all()), f"{what}: a rejected call wrote to its output"
+
+    def check_output(self, what=""):
+        """guards intact and every element written -> the slot as a dense tensor"""
+        self.assert_guards_intact(what)
+        self.assert_fully_written(what)
+        return self.result()
+
+
 def _p(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
+    if t is None:
+        return None
+    return C.c_void_p(t.ptr if isinstance(t, Slot) else t.data_ptr())
+
+
+def _bs(t, dense=0):
+    """batch stride to pass for `t`: a Slot's own, else `dense` (0 = the ABI's "dense")"""
+    return t.bs_arg if isinstance(t, Slot) else dense
 
 
 class RawOps:
@@ -57,7 +151,26 @@ class RawOps:
             raise RuntimeError(f"{what} -> {rc} {msg}")
 
     def to(self, t):
+        if isinstance(t, Slot):
+            assert torch.device(t.device).type == self.device
+            return t
         return None if t is None else t.to(self.device).contiguous()
+
+    def slot(self, data_or_shape, dtype=torch.float32, **layout):
+        """Slot on this backend's device: an input slot holding a tensor, or an output slot of a shape
+        (layout: c_pre, c_post, lead, extra -- see Slot)"""
+        if isinstance(data_or_shape, torch.Tensor):
+            return Slot(self.device, None, data=data_or_shape, **layout)
+        return Slot(self.device, tuple(data_or_shape), dtype=dtype, **layout)
+
+    def _out(self, out, shape, dtype=torch.float32, fill=None):
+        """the output of a wrapper: the caller's Slot (shape-checked) or a fresh dense tensor"""
+        if out is not None:
+            assert isinstance(out, Slot) and tuple(out.shape) == tuple(shape) and out.dtype == dtype, (out.shape, shape)
+            return out
+        if fill is not None:
+            return torch.full(tuple(shape), fill, dtype=dtype, device=self.device)
+        return torch.empty(tuple(shape), dtype=dtype, device=self.device)
 
     def empty(self, *shape, dtype=torch.float32):
         return torch.empty(shape, dtype=dtype, device=self.device)
@@ -131,68 +244,75 @@ class RawOps:
         torch.cuda.synchronize()
         return bufs
 
-    def conv3d_fwd(self, x, w, bias=None, add=None, stride=1, pad=1, compute=0, packed=None, softmax=False):
+    def conv3d_fwd(self, x, w, bias=None, add=None, stride=1, pad=1, compute=0, packed=None, softmax=False, out=None):
         """packed: buffer from pack_weights(w, x.shape, 0) -> the call uses M355_CONV_W_PACKED;
-        softmax: M355_CONV_SOFTMAX (HIP library, descriptors with m355_conv3d_fuses_softmax != 0)"""
+        softmax: M355_CONV_SOFTMAX (HIP library, descriptors with m355_conv3d_fuses_softmax != 0);
+        x / add: tensors or Slots, out: an output Slot (returned) -- `add` shares y's batch stride"""
         x, w, bias, add = map(self.to, (x, w, bias, add))
         k = w.shape[2]
-        d = self.conv_desc(x.shape, w.shape[0], k, stride, pad, compute=compute)
+        od = lambda n: (n + 2 * pad - k) // stride + 1
+        y = self._out(out, (x.shape[0], w.shape[0], od(x.shape[2]), od(x.shape[3]), od(x.shape[4])))
+        assert _bs(add, _bs(y)) == _bs(y) and (add is None or isinstance(add, Slot) == isinstance(y, Slot) or x.shape[0] == 1)
+        d = self.conv_desc(x.shape, w.shape[0], k, stride, pad, xbs=_bs(x), ybs=_bs(y), compute=compute)
         if softmax:
             assert self.lib.m355_conv3d_fuses_softmax(C.byref(d)) == 1
             d.flags |= _lib.CONV_SOFTMAX
         if packed is not None:
             d.flags = _lib.CONV_W_PACKED
-            od = lambda n: (n + 2 * pad - k) // stride + 1
-            y = self.empty(x.shape[0], w.shape[0], od(x.shape[2]), od(x.shape[3]), od(x.shape[4]))
             ws = self._ws("conv3d_fwd_workspace", d)
             self._chk(self.fn("conv3d_fwd")(C.byref(d), _p(x), _p(packed), _p(bias), _p(add), _p(y), _p(ws), ws.numel(),
                                             self._stream()), "conv3d_fwd(packed)")
             return y
-        od = lambda n: (n + 2 * pad - k) // stride + 1
-        y = self.empty(x.shape[0], w.shape[0], od(x.shape[2]), od(x.shape[3]), od(x.shape[4]))
         ws = self._ws("conv3d_fwd_workspace", d)
         self._chk(self.fn("conv3d_fwd")(C.byref(d), _p(x), _p(w), _p(bias), _p(add), _p(y), _p(ws), ws.numel(),
                                         self._stream()), "conv3d_fwd")
         return y
 
     # ---- c8 tensors of the 16-bit compute modes (HIP library only; dtype: 1 = bf16, 2 = fp16) ----
-    def act16_pack(self, x, compute, pad_batch=0):
+    @staticmethod
+    def dt16(compute):
+        return torch.bfloat16 if compute == 1 else torch.float16
+
+    def act16_pack(self, x, compute, pad_batch=0, out=None):
         """fp32 [N,C,D,H,W] -> c8 tensor (torch 16-bit dtype, shape [N, CB (+pad), S, 8]); pad_batch > 0 leaves
-        that many unused channel blocks per sample (a non-dense batch stride)."""
+        that many unused channel blocks per sample (a non-dense batch stride).  x: tensor or Slot; out: a c8 Slot."""
         x = self.to(x)
         N, Cc = x.shape[:2]
-        S = x[0, 0].numel()
+        S = x.numel() // (N * Cc)
         CB = (Cc + 7) // 8
-        dt = torch.bfloat16 if compute == 1 else torch.float16
-        x16 = torch.full((N, CB + pad_batch, S, 8), 7.0, dtype=dt, device=self.device)
-        self._chk(self.fn("act16_pack")(_p(x), _p(x16), N, Cc, S, 0, (CB + pad_batch) * S * 8, compute, self._stream()),
-                  "act16_pack")
+        dt = self.dt16(compute)
+        x16 = self._out(out, (N, CB + pad_batch, S, 8), dt, fill=7.0)
+        self._chk(self.fn("act16_pack")(_p(x), _p(x16), N, Cc, S, _bs(x), _bs(x16, (CB + pad_batch) * S * 8), compute,
+                                        self._stream()), "act16_pack")
         return x16
 
-    def act16_unpack(self, x16, Cc, spatial, compute):
+    def act16_unpack(self, x16, Cc, spatial, compute, out=None):
         N, CBp, S, _ = x16.shape
-        x = self.empty(N, Cc, *spatial)
-        self._chk(self.fn("act16_unpack")(_p(x16), _p(x), N, Cc, S, CBp * S * 8, 0, compute, self._stream()), "act16_unpack")
+        x = self._out(out, (N, Cc) + tuple(spatial))
+        self._chk(self.fn("act16_unpack")(_p(x16), _p(x), N, Cc, S, _bs(x16, CBp * S * 8), _bs(x), compute, self._stream()),
+                  "act16_unpack")
         return x
 
-    def conv_plan(self, x_shape, Cout, compute=0, which=0):
+    def conv_plan(self, x_shape, Cout, compute=0, which=0, xbs=0, ybs=0):
         """(kernel family, NTW, GX, split-K) of the 3x3x3 kernel the library picks (m355_conv3d_plan)"""
-        d = self.conv_desc(x_shape, Cout, 3, 1, 1, compute=compute)
+        d = self.conv_desc(x_shape, Cout, 3, 1, 1, xbs=xbs, ybs=ybs, compute=compute)
         out = (C.c_int32 * 4)()
         self._chk(self.lib.m355_conv3d_plan(C.byref(d), which, out), "conv3d_plan")
         return tuple(out)
 
-    def conv3d_fwd_h16(self, x16, Cin, spatial, w, bias=None, add=None, compute=1, groups=None, eps=1e-5, softmax=False):
+    def conv3d_fwd_h16(self, x16, Cin, spatial, w, bias=None, add=None, compute=1, groups=None, eps=1e-5, softmax=False,
+                       out=None):
         """forward on a c8 input; groups != None also returns the fused statistics (mean, rstd); softmax: the
         M355_CONV_SOFTMAX epilogue (asserts that the library offers it for this descriptor)"""
         w, bias, add = map(self.to, (w, bias, add))
         N, CBp, S, _ = x16.shape
         Cout = w.shape[0]
-        d = self.conv_desc((N, Cin) + tuple(spatial), Cout, 3, 1, 1, compute=compute)
+        y = self._out(out, (N, Cout) + tuple(spatial))
+        assert add is None or _bs(add) == _bs(y)
+        d = self.conv_desc((N, Cin) + tuple(spatial), Cout, 3, 1, 1, ybs=_bs(y), compute=compute)
         if softmax:
             assert self.lib.m355_conv3d_fuses_softmax(C.byref(d)) == 1
             d.flags |= 2
-        y = self.empty(N, Cout, *spatial)
         n = self.lib.m355_conv3d_h16_workspace(C.byref(d), 0)
         ws = torch.empty(max(int(n), 16), dtype=torch.uint8, device=self.device)
         part = None
@@ -200,7 +320,7 @@ class RawOps:
             slots = self.fn("conv3d_stats_slots")(C.byref(d))
             assert slots > 0
             part = self.empty(N, slots, Cout, 2)
-        self._chk(self.fn("conv3d_fwd_h16")(C.byref(d), _p(x16), CBp * S * 8, _p(w), _p(bias), _p(add), _p(y), _p(part),
+        self._chk(self.fn("conv3d_fwd_h16")(C.byref(d), _p(x16), _bs(x16, CBp * S * 8), _p(w), _p(bias), _p(add), _p(y), _p(part),
                                             _p(ws), ws.numel(), self._stream()), "conv3d_fwd_h16")
         if groups is None:
             return y
@@ -213,13 +333,13 @@ class RawOps:
                   "norm_stats_from_partials")
         return y, mean, rstd
 
-    def conv3d_fwd_h16_c8(self, x16, Cin, spatial, w, bias=None, compute=1, with_stats=False):
+    def conv3d_fwd_h16_c8(self, x16, Cin, spatial, w, bias=None, compute=1, with_stats=False, out=None):
         """forward with c8 input AND c8 output; with_stats -> (y16, partials [N, P, Cout, 2])"""
         w, bias = self.to(w), self.to(bias)
         N, CBp, S, _ = x16.shape
         Cout = w.shape[0]
         d = self.conv_desc((N, Cin) + tuple(spatial), Cout, 3, 1, 1, compute=compute)
-        y16 = torch.zeros((N, (Cout + 7) // 8, S, 8), dtype=x16.dtype, device=self.device)
+        y16 = self._out(out, (N, (Cout + 7) // 8, S, 8), x16.dtype, fill=0.0)
         n = self.lib.m355_conv3d_h16_workspace(C.byref(d), 0)
         ws = torch.empty(max(int(n), 16), dtype=torch.uint8, device=self.device)
         part = None
@@ -227,35 +347,36 @@ class RawOps:
             slots = self.fn("conv3d_stats_slots_c8")(C.byref(d))
             assert slots > 0
             part = self.empty(N, slots, Cout, 2)
-        self._chk(self.fn("conv3d_fwd_h16_c8")(C.byref(d), _p(x16), CBp * S * 8, _p(w), _p(bias), _p(y16), 0, _p(part),
+        self._chk(self.fn("conv3d_fwd_h16_c8")(C.byref(d), _p(x16), _bs(x16, CBp * S * 8), _p(w), _p(bias), _p(y16), _bs(y16), _p(part),
                                                _p(ws), ws.numel(), self._stream()), "conv3d_fwd_h16_c8")
         return (y16, part) if with_stats else y16
 
-    def norm_act_fwd_c8(self, x16, Cc, mean, rstd, gamma, beta, groups, act, compute, add16=None, eps=1e-5, slope=0.01):
+    def norm_act_fwd_c8(self, x16, Cc, mean, rstd, gamma, beta, groups, act, compute, add16=None, eps=1e-5, slope=0.01,
+                        out=None):
         mean, rstd, gamma, beta = map(self.to, (mean, rstd, gamma, beta))
         N, CB, S, _ = x16.shape
         d = NormDesc(N, Cc, S, groups, act, eps, slope, 0, 0, 0)
-        y16 = torch.empty_like(x16)
-        self._chk(self.fn("norm_act_fwd_c8")(C.byref(d), _p(x16), 0, _p(mean), _p(rstd), _p(gamma), _p(beta), _p(add16), 0,
-                                             _p(y16), 0, compute, self._stream()), "norm_act_fwd_c8")
+        y16 = self._out(out, x16.shape, x16.dtype)
+        self._chk(self.fn("norm_act_fwd_c8")(C.byref(d), _p(x16), _bs(x16), _p(mean), _p(rstd), _p(gamma), _p(beta), _p(add16),
+                                             _bs(add16), _p(y16), _bs(y16), compute, self._stream()), "norm_act_fwd_c8")
         return y16
 
     def act16_channel_partials(self, x16, Cc, compute):
         N, CB, S, _ = x16.shape
         slots = int(self.lib.m355_act16_partials_slots(S))
         part = self.empty(N, slots, Cc, 2)
-        self._chk(self.fn("act16_channel_partials")(_p(x16), 0, N, Cc, S, compute, _p(part), self._stream()),
+        self._chk(self.fn("act16_channel_partials")(_p(x16), _bs(x16), N, Cc, S, compute, _p(part), self._stream()),
                   "act16_channel_partials")
         return part
 
-    def conv3d_bwd_data_h16(self, dy16, Cout, w, x_shape, compute=1):
+    def conv3d_bwd_data_h16(self, dy16, Cout, w, x_shape, compute=1, out=None):
         w = self.to(w)
         N, CBp, S, _ = dy16.shape
-        d = self.conv_desc(x_shape, Cout, 3, 1, 1, compute=compute)
-        dx = self.empty(*x_shape)
+        dx = self._out(out, x_shape)
+        d = self.conv_desc(x_shape, Cout, 3, 1, 1, xbs=_bs(dx), compute=compute)
         n = self.lib.m355_conv3d_h16_workspace(C.byref(d), 1)
         ws = torch.empty(max(int(n), 16), dtype=torch.uint8, device=self.device)
-        self._chk(self.fn("conv3d_bwd_data_h16")(C.byref(d), _p(dy16), CBp * S * 8, _p(w), _p(dx), _p(ws), ws.numel(),
+        self._chk(self.fn("conv3d_bwd_data_h16")(C.byref(d), _p(dy16), _bs(dy16, CBp * S * 8), _p(w), _p(dx), _p(ws), ws.numel(),
                                                  self._stream()), "conv3d_bwd_data_h16")
         return dx
 
@@ -266,48 +387,48 @@ class RawOps:
         dw, db = self.empty(Cout, Cin, 3, 3, 3), (self.empty(Cout) if with_bias else None)
         n = self.lib.m355_conv3d_bwd_weight_h16_workspace(C.byref(d))
         ws = torch.empty(max(int(n), 16), dtype=torch.uint8, device=self.device)
-        self._chk(self.fn("conv3d_bwd_weight_h16")(C.byref(d), _p(x16), 0, _p(dy16), 0, _p(self.to(dy)) if with_bias else None,
+        d.y_batch_stride = _bs(dy) if with_bias else 0
+        self._chk(self.fn("conv3d_bwd_weight_h16")(C.byref(d), _p(x16), _bs(x16), _p(dy16), _bs(dy16), _p(self.to(dy)) if with_bias else None,
                                                    _p(dw), _p(db), _p(ws), ws.numel(), self._stream()),
                   "conv3d_bwd_weight_h16")
         return dw, db
 
-    def conv_transpose3d_fwd_h16(self, x16, Cin, spatial, w, bias, compute):
+    def conv_transpose3d_fwd_h16(self, x16, Cin, spatial, w, bias, compute, out=None):
         """k2 s2 conv-transpose c8 -> c8; returns the c8 output [N, CBout, 8S, 8]"""
         w, bias = self.to(w), self.to(bias)
         N, CB, S, _ = x16.shape
         Cout = w.shape[1]
         d = self.conv_desc((N, Cin) + tuple(spatial), Cout, 2, 2, 0)
-        y16 = torch.empty((N, (Cout + 7) // 8, 8 * S, 8), dtype=x16.dtype, device=self.device)
-        self._chk(self.fn("conv_transpose3d_fwd_h16")(C.byref(d), _p(x16), 0, _p(w), _p(bias), _p(y16), 0, compute,
+        y16 = self._out(out, (N, (Cout + 7) // 8, 8 * S, 8), x16.dtype)
+        self._chk(self.fn("conv_transpose3d_fwd_h16")(C.byref(d), _p(x16), _bs(x16), _p(w), _p(bias), _p(y16), _bs(y16), compute,
                                                       self._stream()), "conv_transpose3d_fwd_h16")
         return y16
 
     # ---- c8-only training flow (round 3) ----
-    def act16_pack_scaled(self, x, compute, scale):
+    def act16_pack_scaled(self, x, compute, scale, out=None):
         x = self.to(x)
         N, Cc = x.shape[:2]
-        S = x[0, 0].numel()
-        dt = torch.bfloat16 if compute == 1 else torch.float16
-        x16 = torch.full((N, (Cc + 7) // 8, S, 8), 7.0, dtype=dt, device=self.device)
-        self._chk(self.fn("act16_pack_scaled")(_p(x), _p(x16), N, Cc, S, 0, 0, compute, float(scale), self._stream()),
-                  "act16_pack_scaled")
+        S = x.numel() // (N * Cc)
+        x16 = self._out(out, (N, (Cc + 7) // 8, S, 8), self.dt16(compute), fill=7.0)
+        self._chk(self.fn("act16_pack_scaled")(_p(x), _p(x16), N, Cc, S, _bs(x), _bs(x16), compute, float(scale),
+                                               self._stream()), "act16_pack_scaled")
         return x16
 
-    def act16_unpack_scaled(self, x16, Cc, spatial, compute, scale):
+    def act16_unpack_scaled(self, x16, Cc, spatial, compute, scale, out=None):
         N, CBp, S, _ = x16.shape
-        x = self.empty(N, Cc, *spatial)
-        self._chk(self.fn("act16_unpack_scaled")(_p(x16), _p(x), N, Cc, S, CBp * S * 8, 0, compute, float(scale),
-                                                 self._stream()), "act16_unpack_scaled")
+        x = self._out(out, (N, Cc) + tuple(spatial))
+        self._chk(self.fn("act16_unpack_scaled")(_p(x16), _p(x), N, Cc, S, _bs(x16, CBp * S * 8), _bs(x), compute,
+                                                 float(scale), self._stream()), "act16_unpack_scaled")
         return x
 
-    def conv3d_bwd_data_h16_c8(self, dy16, Cout, w, x_shape, compute=1):
+    def conv3d_bwd_data_h16_c8(self, dy16, Cout, w, x_shape, compute=1, out=None):
         w = self.to(w)
         N, CBp, S, _ = dy16.shape
         d = self.conv_desc(x_shape, Cout, 3, 1, 1, compute=compute)
-        dx16 = torch.full((N, (x_shape[1] + 7) // 8, S, 8), 7.0, dtype=dy16.dtype, device=self.device)
+        dx16 = self._out(out, (N, (x_shape[1] + 7) // 8, S, 8), dy16.dtype, fill=7.0)
         n = self.lib.m355_conv3d_h16_workspace(C.byref(d), 1)
         ws = torch.empty(max(int(n), 16), dtype=torch.uint8, device=self.device)
-        self._chk(self.fn("conv3d_bwd_data_h16_c8")(C.byref(d), _p(dy16), CBp * S * 8, _p(w), _p(dx16), 0, _p(ws), ws.numel(),
+        self._chk(self.fn("conv3d_bwd_data_h16_c8")(C.byref(d), _p(dy16), _bs(dy16, CBp * S * 8), _p(w), _p(dx16), _bs(dx16), _p(ws), ws.numel(),
                                                     self._stream()), "conv3d_bwd_data_h16_c8")
         return dx16
 
@@ -317,76 +438,78 @@ class RawOps:
         dw, db = self.empty(Cout, Cin, 3, 3, 3), (self.empty(Cout) if with_bias else None)
         n = self.lib.m355_conv3d_bwd_weight_c8_workspace(C.byref(d))
         ws = torch.empty(max(int(n), 16), dtype=torch.uint8, device=self.device)
-        self._chk(self.fn("conv3d_bwd_weight_c8")(C.byref(d), _p(x16), 0, _p(dy16), 0, _p(dw), _p(db), float(unscale), _p(ws),
+        self._chk(self.fn("conv3d_bwd_weight_c8")(C.byref(d), _p(x16), _bs(x16), _p(dy16), _bs(dy16), _p(dw), _p(db), float(unscale), _p(ws),
                                                   ws.numel(), self._stream()), "conv3d_bwd_weight_c8")
         return dw, db
 
     def norm_act_bwd_c8(self, x16, dy16, dpool16, Cc, spatial, mean, rstd, gamma, beta, groups, act, compute, training=1,
-                        unscale=1.0, eps=1e-5, slope=0.01):
+                        unscale=1.0, eps=1e-5, slope=0.01, out=None):
         """-> (dx16, dgamma, dbeta); dy16 / dpool16: c8 gradients (either may be None, not both)"""
         mean, rstd, gamma, beta = map(self.to, (mean, rstd, gamma, beta))
         N, S = x16.shape[0], x16.shape[2]
         D, H, W = spatial
         d = NormDesc(N, Cc, S, groups, act, eps, slope, 0, 0, 0)
-        dx16 = torch.full_like(x16, 7.0)
+        dx16 = self._out(out, x16.shape, x16.dtype, fill=7.0)
         dg = self.empty(Cc) if gamma is not None else None
         db = self.empty(Cc) if gamma is not None else None
         ws = self._ws("norm_workspace", d)
-        self._chk(self.fn("norm_act_bwd_c8")(C.byref(d), _p(x16), 0, _p(dy16), 0, _p(dpool16), 0, D, H, W, _p(mean), _p(rstd),
-                                             _p(gamma), _p(beta), _p(dx16), 0, _p(dg), _p(db), training, float(unscale),
+        self._chk(self.fn("norm_act_bwd_c8")(C.byref(d), _p(x16), _bs(x16), _p(dy16), _bs(dy16), _p(dpool16), _bs(dpool16), D, H, W,
+                                             _p(mean), _p(rstd),
+                                             _p(gamma), _p(beta), _p(dx16), _bs(dx16), _p(dg), _p(db), training, float(unscale),
                                              compute, _p(ws), ws.numel(), self._stream()), "norm_act_bwd_c8")
         return dx16, dg, db
 
-    def avgpool_bwd_h16(self, dpool16, dskip16, Cc, spatial, compute):
+    def avgpool_bwd_h16(self, dpool16, dskip16, Cc, spatial, compute, out=None):
         D, H, W = spatial
         N = dpool16.shape[0]
-        dx16 = torch.full((N, (Cc + 7) // 8, D * H * W, 8), 7.0, dtype=dpool16.dtype, device=self.device)
-        self._chk(self.fn("avgpool3d_2x_bwd_h16")(_p(dpool16), _p(dskip16), _p(dx16), N, Cc, D, H, W, 0, 0, 0, compute,
+        dx16 = self._out(out, (N, (Cc + 7) // 8, D * H * W, 8), dpool16.dtype, fill=7.0)
+        self._chk(self.fn("avgpool3d_2x_bwd_h16")(_p(dpool16), _p(dskip16), _p(dx16), N, Cc, D, H, W, _bs(dpool16), _bs(dskip16),
+                                                  _bs(dx16), compute,
                                                   self._stream()), "avgpool3d_2x_bwd_h16")
         return dx16
 
-    def upsample_trilinear2x_fwd_h16(self, x16, Cc, spatial, compute, pad_batch=0):
+    def upsample_trilinear2x_fwd_h16(self, x16, Cc, spatial, compute, pad_batch=0, out=None):
         """c8 -> c8 at twice the resolution; pad_batch: unused channel blocks per sample of the destination"""
         D, H, W = spatial
         N, CBp = x16.shape[:2]
         CB = (Cc + 7) // 8
-        y16 = torch.full((N, CB + pad_batch, 8 * D * H * W, 8), 7.0, dtype=x16.dtype, device=self.device)
-        self._chk(self.fn("upsample_trilinear2x_fwd_h16")(_p(x16), _p(y16), N, Cc, D, H, W, CBp * D * H * W * 8,
-                                                          (CB + pad_batch) * D * H * W * 64, compute, self._stream()),
+        y16 = self._out(out, (N, CB + pad_batch, 8 * D * H * W, 8), x16.dtype, fill=7.0)
+        self._chk(self.fn("upsample_trilinear2x_fwd_h16")(_p(x16), _p(y16), N, Cc, D, H, W, _bs(x16, CBp * D * H * W * 8),
+                                                          _bs(y16, (CB + pad_batch) * D * H * W * 64), compute, self._stream()),
                   "upsample_trilinear2x_fwd_h16")
         return y16
 
-    def upsample_trilinear2x_bwd_h16(self, dy16, Cc, spatial, compute):
+    def upsample_trilinear2x_bwd_h16(self, dy16, Cc, spatial, compute, out=None):
         """`spatial`: the LOW-resolution size"""
         D, H, W = spatial
         N, CBp = dy16.shape[:2]
-        dx16 = torch.full((N, (Cc + 7) // 8, D * H * W, 8), 7.0, dtype=dy16.dtype, device=self.device)
-        self._chk(self.fn("upsample_trilinear2x_bwd_h16")(_p(dy16), _p(dx16), N, Cc, D, H, W, CBp * D * H * W * 64, 0, compute,
-                                                          self._stream()), "upsample_trilinear2x_bwd_h16")
+        dx16 = self._out(out, (N, (Cc + 7) // 8, D * H * W, 8), dy16.dtype, fill=7.0)
+        self._chk(self.fn("upsample_trilinear2x_bwd_h16")(_p(dy16), _p(dx16), N, Cc, D, H, W, _bs(dy16, CBp * D * H * W * 64),
+                                                          _bs(dx16), compute, self._stream()), "upsample_trilinear2x_bwd_h16")
         return dx16
 
-    def act16_channel_scale(self, x16, scale, Cc, compute):
+    def act16_channel_scale(self, x16, scale, Cc, compute, out=None):
         scale = self.to(scale)
         N, CBp, S, _ = x16.shape
-        y16 = torch.full((N, (Cc + 7) // 8, S, 8), 7.0, dtype=x16.dtype, device=self.device)
-        self._chk(self.fn("act16_channel_scale")(_p(x16), _p(scale), _p(y16), N, Cc, S, CBp * S * 8, 0, compute,
+        y16 = self._out(out, (N, (Cc + 7) // 8, S, 8), x16.dtype, fill=7.0)
+        self._chk(self.fn("act16_channel_scale")(_p(x16), _p(scale), _p(y16), N, Cc, S, _bs(x16, CBp * S * 8), _bs(y16), compute,
                                                  self._stream()), "act16_channel_scale")
         return y16
 
-    def s2d_h16(self, x16, full_shape, compute, to_depth, pad_batch=0):
+    def s2d_h16(self, x16, full_shape, compute, to_depth, pad_batch=0, out=None):
         """space-to-depth (to_depth) / depth-to-space by 2, c8 -> c8; `full_shape` = (N, C, D, H, W) of the full-resolution
         tensor; pad_batch: unused channel blocks per sample of the destination"""
         N, Cc, D, H, W = full_shape
         S = D * H * W
         CBp = x16.shape[1]
         if to_depth:
-            y16 = torch.full((N, Cc + pad_batch, S // 8, 8), 7.0, dtype=x16.dtype, device=self.device)
-            xbs, ybs = CBp * S * 8, (Cc + pad_batch) * (S // 8) * 8
+            y16 = self._out(out, (N, Cc + pad_batch, S // 8, 8), x16.dtype, fill=7.0)
+            xbs, ybs = _bs(x16, CBp * S * 8), _bs(y16, (Cc + pad_batch) * (S // 8) * 8)
             fn = self.fn("space_to_depth2_h16")
         else:
             CB = (Cc + 7) // 8
-            y16 = torch.full((N, CB + pad_batch, S, 8), 7.0, dtype=x16.dtype, device=self.device)
-            xbs, ybs = CBp * (S // 8) * 8, (CB + pad_batch) * S * 8
+            y16 = self._out(out, (N, CB + pad_batch, S, 8), x16.dtype, fill=7.0)
+            xbs, ybs = _bs(x16, CBp * (S // 8) * 8), _bs(y16, (CB + pad_batch) * S * 8)
             fn = self.fn("depth_to_space2_h16")
         self._chk(fn(_p(x16), _p(y16), N, Cc, D, H, W, xbs, ybs, compute, self._stream()), "s2d_h16")
         return y16
@@ -395,13 +518,13 @@ class RawOps:
         d = self.conv_desc(x_shape, Cout, 2, 2, 0)
         return bool(self.lib.m355_conv_transpose3d_h16_bwd_supported(C.byref(d)))
 
-    def convt_bwd_data_h16(self, dy16, w, x_shape, compute):
+    def convt_bwd_data_h16(self, dy16, w, x_shape, compute, out=None):
         w = self.to(w)
         N, Cin = x_shape[:2]
         S = x_shape[2] * x_shape[3] * x_shape[4]
         d = self.conv_desc(x_shape, w.shape[1], 2, 2, 0)
-        dx16 = torch.full((N, (Cin + 7) // 8, S, 8), 7.0, dtype=dy16.dtype, device=self.device)
-        self._chk(self.fn("conv_transpose3d_bwd_data_h16")(C.byref(d), _p(dy16), 0, _p(w), _p(dx16), 0, compute,
+        dx16 = self._out(out, (N, (Cin + 7) // 8, S, 8), dy16.dtype, fill=7.0)
+        self._chk(self.fn("conv_transpose3d_bwd_data_h16")(C.byref(d), _p(dy16), _bs(dy16), _p(w), _p(dx16), _bs(dx16), compute,
                                                            self._stream()), "conv_transpose3d_bwd_data_h16")
         return dx16
 
@@ -411,23 +534,23 @@ class RawOps:
         db = self.empty(Cout) if with_bias else None
         n = self.lib.m355_conv_transpose3d_h16_bwd_workspace(C.byref(d))
         ws = torch.empty(max(int(n), 16), dtype=torch.uint8, device=self.device)
-        self._chk(self.fn("conv_transpose3d_bwd_weight_h16")(C.byref(d), _p(x16), 0, _p(dy16), 0, _p(dw), _p(db), float(unscale),
+        self._chk(self.fn("conv_transpose3d_bwd_weight_h16")(C.byref(d), _p(x16), _bs(x16), _p(dy16), _bs(dy16), _p(dw), _p(db), float(unscale),
                                                              compute, _p(ws), ws.numel(), self._stream()),
                   "conv_transpose3d_bwd_weight_h16")
         return dw, db
 
-    def conv3d_fwd_stats(self, x, w, bias=None, groups=0, eps=1e-5):
+    def conv3d_fwd_stats(self, x, w, bias=None, groups=0, eps=1e-5, compute=0, out=None):
         """fused conv + statistics: returns (y, mean, rstd) of the normalisation that follows the conv, or
         None when this backend has no fused statistics for the shape"""
         x, w = self.to(x), self.to(w)
         bias = self.to(bias) if bias is not None else None
         N, Cin, D, H, W = x.shape
         Cout = w.shape[0]
-        d = self.conv_desc(x.shape, Cout, 3, 1, 1)
+        y = self._out(out, (N, Cout, D, H, W))
+        d = self.conv_desc(x.shape, Cout, 3, 1, 1, xbs=_bs(x), ybs=_bs(y), compute=compute)
         slots = self.fn("conv3d_stats_slots")(C.byref(d))
         if slots <= 0:
             return None
-        y = self.empty(N, Cout, D, H, W)
         part = self.empty(N, slots, Cout, 2)
         ws = self._ws("conv3d_fwd_workspace", d)
         self._chk(self.fn("conv3d_fwd_stats")(C.byref(d), _p(x), _p(w), _p(bias), None, _p(y), _p(part), _p(ws),
@@ -441,10 +564,10 @@ class RawOps:
                   "norm_stats_from_partials")
         return y, mean, rstd
 
-    def conv3d_bwd_data(self, dy, w, x_shape, stride=1, pad=1, compute=0, packed=None):
+    def conv3d_bwd_data(self, dy, w, x_shape, stride=1, pad=1, compute=0, packed=None, out=None):
         dy, w = self.to(dy), self.to(w)
-        d = self.conv_desc(x_shape, w.shape[0], w.shape[2], stride, pad, compute=compute)
-        dx = self.empty(*x_shape)
+        dx = self._out(out, x_shape)
+        d = self.conv_desc(x_shape, w.shape[0], w.shape[2], stride, pad, xbs=_bs(dx), ybs=_bs(dy), compute=compute)
         ws = self._ws("conv3d_bwd_data_workspace", d)
         if packed is not None:
             d.flags, w = _lib.CONV_W_PACKED, packed
@@ -455,7 +578,7 @@ class RawOps:
     def conv3d_bwd_weight(self, x, dy, k, stride=1, pad=1, with_bias=True, compute=0):
         x, dy = self.to(x), self.to(dy)
         Cout = dy.shape[1]
-        d = self.conv_desc(x.shape, Cout, k, stride, pad, compute=compute)
+        d = self.conv_desc(x.shape, Cout, k, stride, pad, xbs=_bs(x), ybs=_bs(dy), compute=compute)
         dw = self.empty(Cout, x.shape[1], k, k, k)
         db = self.empty(Cout) if with_bias else None
         ws = self._ws("conv3d_bwd_weight_workspace", d)
@@ -463,21 +586,21 @@ class RawOps:
                                                self._stream()), "conv3d_bwd_weight")
         return dw, db
 
-    def convt_fwd(self, x, w, bias=None, stride=2, pad=0, out_pad=0, compute=0):
+    def convt_fwd(self, x, w, bias=None, stride=2, pad=0, out_pad=0, compute=0, out=None):
         x, w, bias = map(self.to, (x, w, bias))
         k = w.shape[2]
-        d = self.conv_desc(x.shape, w.shape[1], k, stride, pad, out_pad, compute=compute)
         od = lambda n: (n - 1) * stride - 2 * pad + k + out_pad
-        y = self.empty(x.shape[0], w.shape[1], od(x.shape[2]), od(x.shape[3]), od(x.shape[4]))
+        y = self._out(out, (x.shape[0], w.shape[1], od(x.shape[2]), od(x.shape[3]), od(x.shape[4])))
+        d = self.conv_desc(x.shape, w.shape[1], k, stride, pad, out_pad, xbs=_bs(x), ybs=_bs(y), compute=compute)
         ws = self._ws("conv_transpose3d_workspace", d)
         self._chk(self.fn("conv_transpose3d_fwd")(C.byref(d), _p(x), _p(w), _p(bias), _p(y), _p(ws), ws.numel(),
                                                   self._stream()), "convt_fwd")
         return y
 
-    def convt_bwd_data(self, dy, w, x_shape, stride=2, pad=0, out_pad=0):
+    def convt_bwd_data(self, dy, w, x_shape, stride=2, pad=0, out_pad=0, out=None):
         dy, w = self.to(dy), self.to(w)
-        d = self.conv_desc(x_shape, w.shape[1], w.shape[2], stride, pad, out_pad)
-        dx = self.empty(*x_shape)
+        dx = self._out(out, x_shape)
+        d = self.conv_desc(x_shape, w.shape[1], w.shape[2], stride, pad, out_pad, xbs=_bs(dx), ybs=_bs(dy))
         ws = self._ws("conv_transpose3d_workspace", d)
         self._chk(self.fn("conv_transpose3d_bwd_data")(C.byref(d), _p(dy), _p(w), _p(dx), _p(ws), ws.numel(),
                                                        self._stream()), "convt_bwd_data")
@@ -486,7 +609,7 @@ class RawOps:
     def convt_bwd_weight(self, x, dy, k, stride=2, pad=0, out_pad=0, with_bias=True):
         x, dy = self.to(x), self.to(dy)
         Cout = dy.shape[1]
-        d = self.conv_desc(x.shape, Cout, k, stride, pad, out_pad)
+        d = self.conv_desc(x.shape, Cout, k, stride, pad, out_pad, xbs=_bs(x), ybs=_bs(dy))
         dw = self.empty(x.shape[1], Cout, k, k, k)
         db = self.empty(Cout) if with_bias else None
         ws = self._ws("conv_transpose3d_workspace", d)
@@ -496,14 +619,14 @@ class RawOps:
 
     # ------------------------------------------------------------------ norm
     @staticmethod
-    def norm_desc(x, groups, act=0, eps=1e-5, slope=0.01):
+    def norm_desc(x, groups, act=0, eps=1e-5, slope=0.01, xbs=0, ybs=0, abs_=0):
         N, Cc = x.shape[:2]
         S = x.numel() // (N * Cc)
-        return NormDesc(N, Cc, S, groups, act, eps, slope, 0, 0, 0)
+        return NormDesc(N, Cc, S, groups, act, eps, slope, xbs, ybs, abs_)
 
     def norm_stats(self, x, groups, eps=1e-5, running=None, momentum=0.1):
         x = self.to(x)
-        d = self.norm_desc(x, groups, eps=eps)
+        d = self.norm_desc(x, groups, eps=eps, xbs=_bs(x))
         ns = self.fn("norm_num_stats")(C.byref(d))
         mean, rstd = self.empty(ns), self.empty(ns)
         rm = rv = None
@@ -514,40 +637,41 @@ class RawOps:
                                         ws.numel(), self._stream()), "norm_stats")
         return mean, rstd, rm, rv
 
-    def norm_act_fwd(self, x, mean, rstd, gamma, beta, groups, act, add=None, eps=1e-5, slope=0.01):
+    def norm_act_fwd(self, x, mean, rstd, gamma, beta, groups, act, add=None, eps=1e-5, slope=0.01, out=None):
         x, mean, rstd, gamma, beta, add = map(self.to, (x, mean, rstd, gamma, beta, add))
-        d = self.norm_desc(x, groups, act, eps, slope)
-        y = torch.empty_like(x)
+        y = self._out(out, x.shape)
+        d = self.norm_desc(x, groups, act, eps, slope, _bs(x), _bs(y), _bs(add))
         self._chk(self.fn("norm_act_fwd")(C.byref(d), _p(x), _p(mean), _p(rstd), _p(gamma), _p(beta), _p(add),
                                           _p(y), self._stream()), "norm_act_fwd")
         return y
 
     def norm_act_fwd_h16(self, x, mean, rstd, gamma, beta, groups, act, compute, add=None, want_f32=False, eps=1e-5,
-                         slope=0.01):
+                         slope=0.01, out16=None, out=None):
         """c8 output (torch 16-bit tensor [N, CB, S, 8]) and optionally the fp32 NCDHW output as well"""
         x, mean, rstd, gamma, beta, add = map(self.to, (x, mean, rstd, gamma, beta, add))
-        d = self.norm_desc(x, groups, act, eps, slope)
         N, Cc = x.shape[:2]
-        S = x[0, 0].numel()
-        y16 = torch.empty((N, (Cc + 7) // 8, S, 8), dtype=torch.bfloat16 if compute == 1 else torch.float16,
-                          device=self.device)
-        y = torch.empty_like(x) if want_f32 else None
+        S = x.numel() // (N * Cc)
+        y16 = self._out(out16, (N, (Cc + 7) // 8, S, 8), self.dt16(compute))
+        y = self._out(out, x.shape) if (want_f32 or out is not None) else None
+        d = self.norm_desc(x, groups, act, eps, slope, _bs(x), _bs(y), _bs(add))
         self._chk(self.fn("norm_act_fwd_h16")(C.byref(d), _p(x), _p(mean), _p(rstd), _p(gamma), _p(beta), _p(add), _p(y),
-                                              _p(y16), 0, compute, self._stream()), "norm_act_fwd_h16")
+                                              _p(y16), _bs(y16), compute, self._stream()), "norm_act_fwd_h16")
         return y16, y
 
-    def avgpool_fwd_h16(self, x16, Cc, spatial, compute):
+    def avgpool_fwd_h16(self, x16, Cc, spatial, compute, out=None):
         N, CB, S, _ = x16.shape
         D, H, W = spatial
-        y16 = torch.empty((N, CB, S // 8, 8), dtype=x16.dtype, device=self.device)
-        self._chk(self.fn("avgpool3d_2x_fwd_h16")(_p(x16), _p(y16), N, Cc, D, H, W, 0, 0, compute, self._stream()),
+        y16 = self._out(out, (N, CB, S // 8, 8), x16.dtype)
+        self._chk(self.fn("avgpool3d_2x_fwd_h16")(_p(x16), _p(y16), N, Cc, D, H, W, _bs(x16), _bs(y16), compute, self._stream()),
                   "avgpool3d_2x_fwd_h16")
         return y16
 
-    def norm_act_bwd(self, x, dy, mean, rstd, gamma, beta, groups, act, training=1, eps=1e-5, slope=0.01):
+    def norm_act_bwd(self, x, dy, mean, rstd, gamma, beta, groups, act, training=1, eps=1e-5, slope=0.01, out=None):
+        """x and dx share desc.x_batch_stride, dy has desc.y_batch_stride"""
         x, dy, mean, rstd, gamma, beta = map(self.to, (x, dy, mean, rstd, gamma, beta))
-        d = self.norm_desc(x, groups, act, eps, slope)
-        dx = torch.empty_like(x)
+        dx = self._out(out, x.shape)
+        assert _bs(dx) == _bs(x) or x.shape[0] == 1
+        d = self.norm_desc(x, groups, act, eps, slope, _bs(x), _bs(dy))
         dg = self.empty(x.shape[1]) if gamma is not None else None
         db = self.empty(x.shape[1]) if gamma is not None else None
         ws = self._ws("norm_workspace", d)
@@ -556,84 +680,105 @@ class RawOps:
                   "norm_act_bwd")
         return dx, dg, db
 
-    def norm_act_pool_fwd(self, x, mean, rstd, gamma, beta, groups, act, eps=1e-5, slope=0.01):
+    def norm_act_pool_fwd(self, x, mean, rstd, gamma, beta, groups, act, eps=1e-5, slope=0.01, out=None, out_pooled=None):
         """norm + activation with AvgPool3d(2, 2) of the result as second output -> (y, pooled)"""
         x, mean, rstd, gamma, beta = map(self.to, (x, mean, rstd, gamma, beta))
-        d = self.norm_desc(x, groups, act, eps, slope)
         N, Cc, D, H, W = x.shape
-        y, pooled = torch.empty_like(x), self.empty(N, Cc, D // 2, H // 2, W // 2)
+        y, pooled = self._out(out, x.shape), self._out(out_pooled, (N, Cc, D // 2, H // 2, W // 2))
+        d = self.norm_desc(x, groups, act, eps, slope, _bs(x), _bs(y))
         self._chk(self.fn("norm_act_pool_fwd")(C.byref(d), _p(x), _p(mean), _p(rstd), _p(gamma), _p(beta), _p(y), _p(pooled),
-                                               0, D, H, W, self._stream()), "norm_act_pool_fwd")
+                                               _bs(pooled), D, H, W, self._stream()), "norm_act_pool_fwd")
         return y, pooled
 
-    def norm_act_bwd_h16(self, x, dy, mean, rstd, gamma, beta, groups, act, compute, training=1, eps=1e-5, slope=0.01):
+    def norm_act_bwd_h16(self, x, dy, mean, rstd, gamma, beta, groups, act, compute, training=1, eps=1e-5, slope=0.01,
+                         out=None, out16=None):
         """norm backward that also emits dx as c8 -> (dx, dgamma, dbeta, dx16 [N, CB, S, 8])"""
         x, dy, mean, rstd, gamma, beta = map(self.to, (x, dy, mean, rstd, gamma, beta))
-        d = self.norm_desc(x, groups, act, eps, slope)
         N, Cc = x.shape[:2]
-        S = x[0, 0].numel()
-        dx = torch.empty_like(x)
+        S = x.numel() // (N * Cc)
+        dx = self._out(out, x.shape)
+        assert _bs(dx) == _bs(x) or N == 1
+        d = self.norm_desc(x, groups, act, eps, slope, _bs(x), _bs(dy))
         dg = self.empty(Cc) if gamma is not None else None
         db = self.empty(Cc) if gamma is not None else None
-        dx16 = torch.empty((N, (Cc + 7) // 8, S, 8), dtype=torch.bfloat16 if compute == 1 else torch.float16, device=self.device)
+        dx16 = self._out(out16, (N, (Cc + 7) // 8, S, 8), self.dt16(compute))
         ws = self._ws("norm_workspace", d)
         self._chk(self.fn("norm_act_bwd_h16")(C.byref(d), _p(x), _p(dy), _p(mean), _p(rstd), _p(gamma), _p(beta), _p(dx),
-                                              _p(dg), _p(db), training, _p(dx16), 0, compute, _p(ws), ws.numel(),
+                                              _p(dg), _p(db), training, _p(dx16), _bs(dx16), compute, _p(ws), ws.numel(),
                                               self._stream()), "norm_act_bwd_h16")
         return dx, dg, db, dx16
 
     # -------------------------------------------------- pool / upsample / softmax
-    def avgpool_fwd(self, x):
+    # (every tensor argument may be a Slot, `out` an output Slot: pointers and batch strides then come from the slots)
+    def avgpool_fwd(self, x, out=None):
         x = self.to(x)
         N, Cc, D, H, W = x.shape
-        y = self.empty(N, Cc, D // 2, H // 2, W // 2)
-        self._chk(self.fn("avgpool3d_2x_fwd")(_p(x), _p(y), N, Cc, D, H, W, 0, 0, self._stream()), "avgpool_fwd")
+        y = self._out(out, (N, Cc, D // 2, H // 2, W // 2))
+        self._chk(self.fn("avgpool3d_2x_fwd")(_p(x), _p(y), N, Cc, D, H, W, _bs(x), _bs(y), self._stream()), "avgpool_fwd")
         return y
 
-    def avgpool_bwd(self, dy, x_shape):
+    def avgpool_bwd(self, dy, x_shape, out=None):
         dy = self.to(dy)
         N, Cc, D, H, W = x_shape
-        dx = self.empty(*x_shape)
-        self._chk(self.fn("avgpool3d_2x_bwd")(_p(dy), _p(dx), N, Cc, D, H, W, 0, 0, self._stream()), "avgpool_bwd")
+        dx = self._out(out, x_shape)
+        self._chk(self.fn("avgpool3d_2x_bwd")(_p(dy), _p(dx), N, Cc, D, H, W, _bs(dy), _bs(dx), self._stream()), "avgpool_bwd")
         return dx
 
-    def avgpool_bwd_add(self, dy, add, x_shape):
+    def avgpool_bwd_add(self, dy, add, x_shape, out=None):
         dy, add = self.to(dy), self.to(add)
         N, Cc, D, H, W = x_shape
-        dx = self.empty(*x_shape)
-        self._chk(self.fn("avgpool3d_2x_bwd_add")(_p(dy), _p(add), _p(dx), N, Cc, D, H, W, 0, 0, 0, self._stream()),
-                  "avgpool_bwd_add")
+        dx = self._out(out, x_shape)
+        self._chk(self.fn("avgpool3d_2x_bwd_add")(_p(dy), _p(add), _p(dx), N, Cc, D, H, W, _bs(dy), _bs(add), _bs(dx),
+                                                  self._stream()), "avgpool_bwd_add")
         return dx
 
-    def upsample_fwd(self, x):
+    def upsample_fwd(self, x, out=None):
         x = self.to(x)
         N, Cc, D, H, W = x.shape
-        y = self.empty(N, Cc, 2 * D, 2 * H, 2 * W)
-        self._chk(self.fn("upsample_trilinear2x_fwd")(_p(x), _p(y), N, Cc, D, H, W, 0, 0, self._stream()),
+        y = self._out(out, (N, Cc, 2 * D, 2 * H, 2 * W))
+        self._chk(self.fn("upsample_trilinear2x_fwd")(_p(x), _p(y), N, Cc, D, H, W, _bs(x), _bs(y), self._stream()),
                   "upsample_fwd")
         return y
 
-    def upsample_bwd(self, dy, x_shape):
+    def upsample_bwd(self, dy, x_shape, out=None):
         dy = self.to(dy)
         N, Cc, D, H, W = x_shape
-        dx = self.empty(*x_shape)
-        self._chk(self.fn("upsample_trilinear2x_bwd")(_p(dy), _p(dx), N, Cc, D, H, W, 0, 0, self._stream()),
+        dx = self._out(out, x_shape)
+        self._chk(self.fn("upsample_trilinear2x_bwd")(_p(dy), _p(dx), N, Cc, D, H, W, _bs(dy), _bs(dx), self._stream()),
                   "upsample_bwd")
         return dx
 
-    def space_to_depth(self, x):
+    def space_to_depth(self, x, out=None):
         x = self.to(x)
         N, Cc, D, H, W = x.shape
-        y = self.empty(N, Cc * 8, D // 2, H // 2, W // 2)
-        self._chk(self.fn("space_to_depth2")(_p(x), _p(y), N, Cc, D, H, W, 0, 0, self._stream()), "space_to_depth2")
+        y = self._out(out, (N, Cc * 8, D // 2, H // 2, W // 2))
+        self._chk(self.fn("space_to_depth2")(_p(x), _p(y), N, Cc, D, H, W, _bs(x), _bs(y), self._stream()), "space_to_depth2")
         return y
 
-    def depth_to_space(self, x):
+    def depth_to_space(self, x, out=None):
         x = self.to(x)
         N, C8, D, H, W = x.shape
-        y = self.empty(N, C8 // 8, 2 * D, 2 * H, 2 * W)
-        self._chk(self.fn("depth_to_space2")(_p(x), _p(y), N, C8 // 8, 2 * D, 2 * H, 2 * W, 0, 0, self._stream()),
+        y = self._out(out, (N, C8 // 8, 2 * D, 2 * H, 2 * W))
+        self._chk(self.fn("depth_to_space2")(_p(x), _p(y), N, C8 // 8, 2 * D, 2 * H, 2 * W, _bs(x), _bs(y), self._stream()),
                   "depth_to_space2")
+        return y
+
+    def copy_channels(self, x, out=None):
+        x = self.to(x)
+        N, Cc = x.shape[:2]
+        S = x.numel() // (N * Cc)
+        y = self._out(out, x.shape)
+        self._chk(self.fn("copy_channels")(_p(x), _p(y), N, Cc, S, _bs(x), _bs(y), self._stream()), "copy_channels")
+        return y
+
+    def dwi_mean(self, x, idx, out=None):
+        """x: [1, channels, D, H, W] (tensor or Slot) -> [1, 1, D, H, W] mean over the channels `idx`, summed in that
+        order (m355_dwi_mean has no stride arguments: only the pointers move) -- HIP library only"""
+        x = self.to(x)
+        _, Cc, D, H, W = x.shape
+        y = self._out(out, (1, 1, D, H, W))
+        it = torch.tensor(list(idx), dtype=torch.int32, device=self.device)
+        self._chk(self.fn("dwi_mean")(_p(x), Cc, self._i3((D, H, W)), _p(it), len(idx), _p(y), self._stream()), "dwi_mean")
         return y
 
     def blur_weight_fwd(self, w, scale, standardize, transposed):

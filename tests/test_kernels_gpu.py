@@ -4,7 +4,9 @@ fp32 tolerance: the oracle accumulates in double; the kernels in fp32 (MFMA = k-
 fma chain).  Per-element bound used here: |err| <= 2e-5 * sum|terms| scale, written as
 rtol/atol on the output scale.  Edge cases: ragged sizes that do not divide the tiles,
 channels not multiple of 32 (and odd, for the MFMA k-pair), N > 1, tiny volumes, the
-split-K path, concat-slot batch strides.
+split-K path.  Every call here hands over dense, allocator-aligned tensors (batch stride 0), except a
+few c8 wrappers with a padded destination: concat-slot batch strides, misaligned pointers and writes
+outside a slot are tested kernel by kernel in test_strided_slots_gpu.py (raw_ops.Slot).
 """
 import ctypes as C
 

@@ -680,16 +680,32 @@ def test_wsconv3d_forward_and_gradients_golden(golden):
     assert ws.bias.grad is None
 
 
-def test_batch_stride_concat_path_n2_grads_flow(golden):
-    """N=2 makes every concat slot a strided (non-contiguous) channel slice."""
+@pytest.mark.parametrize("mode", ["fp32", "fp32_mfma", "bf16"])
+def test_batch_stride_concat_path_n2_grads_flow(golden, mode):
+    """N=2 makes every concat slot a strided (non-contiguous) channel slice: sample 1 of the batch equals its N=1 run,
+    and the parameter gradients of the batch equal the sum of the two N=1 runs' (GroupNorm: samples are independent;
+    the loss sum(p^2) is additive over samples) -- in M355_COMPUTE_F32X3 ("fp32"), exact fp32 and one 16-bit mode.
+    The kernel-level counterpart is test_strided_slots_gpu.py."""
+    import segmentation_pipeline_amd as sp
     g = golden("unet_gn_convt.npz")
     model = BUILDERS["unet_gn_convt.npz"][0]()
     model.load_state_dict(g.state_dict("m.sd."))
     model = model.cuda().train()
     x = g.t("x").cuda()
-    both = model(x)
-    one = model(x[1:2].contiguous())
+
+    def run(xb):
+        model.zero_grad(set_to_none=True)
+        p = model(xb)
+        (p * p).sum().backward()
+        return p.detach(), {k: v.grad.clone() for k, v in model.named_parameters()}
+
+    with sp.precision(mode):
+        both, g_both = run(x)
+        one, g_one = run(x[1:2].contiguous())
+        _, g_zero = run(x[0:1].contiguous())
     assert maxerr(both[1:2], one.cpu()) <= 1e-6  # GroupNorm: samples are independent
+    for k, v in g_both.items():
+        grad_close(v, (g_zero[k] + g_one[k]).cpu(), k)
 
 
 @pytest.mark.parametrize("dropout_p", [0.5])
