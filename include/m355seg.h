@@ -222,7 +222,8 @@ int m355_conv3d_bwd_weight_h16(const m355_conv3d_desc* d, const void* x16, int64
 /* Introspection for profiling: which kernel variant a 3x3x3 conv dispatches to.
  * which: 0 = forward, 1 = data gradient, 2 = weight gradient (of m355_conv3d_bwd_weight).  out[0] = kernel family:
  * 0 generic direct kernel, 1 MFMA implicit GEMM (one output tile per workgroup), 3 the same as a persistent kernel
- * (workgroups walk several tiles), 2 z-Toeplitz small-Cout kernel, 4 the 16-bit operand kernel (persistent), 5 its
+ * (workgroups walk several tiles), 2 the small-Cout forward (Cout <= 4: the packed-FMA kernel conv3_valu_smallcout_kernel, or
+ * with M355_SMALLCOUT_VALU=0 the z-Toeplitz MFMA kernel), 4 the 16-bit operand kernel (persistent), 5 its
  * 8-wave double-buffered variant, 6 its one-item-per-workgroup variant, 7 the split kernel of M355_COMPUTE_F32X3
  * (conv3_f32x3_kernel); weight gradient: 8 conv3_bww_x3_kernel, 9 conv3_mfma_bww2(c)_kernel, 10 the edge-layer kernel
  * conv3_mfma_bww_small_kernel, 11 the c8 kernel behind an operand pack (16-bit modes).  out[1] = voxel groups per wave

@@ -1,4 +1,5 @@
-// conv3d for gfx950: fp32 implicit-GEMM on v_mfma_f32_32x32x2_f32 (exact fp32,
+// conv3d kernels for gfx950 and their launcher (the host layer that resolves a descriptor to one of them, plans it and
+// carries the C ABI is conv3d_host.hip): fp32 implicit-GEMM on v_mfma_f32_32x32x2_f32 (exact fp32,
 // k-ordered fma chain) for the 3x3x3 / stride 1 / pad 1 convolutions that carry
 // ~97 % of the U-Net FLOPs, plus generic direct kernels for any other
 // kernel-size / stride / padding (the reference's BlurConv3d, k=4 s=2, reaches the
@@ -1523,7 +1524,7 @@ __global__ __launch_bounds__(256) void slab_reduce_tap_kernel(const float* __res
 }
 
 // picks the reduction by shape: per-tap blocks where the (o, c-tile) grid alone cannot fill the chip
-static void launch_slab_reduce_t(const float* slab, float* dw, int Cin, int Cout, int ctiles, const BwwClasses& k,
+void launch_slab_reduce_t(const float* slab, float* dw, int Cin, int Cout, int ctiles, const BwwClasses& k,
                                  float scale, hipStream_t st) {
   int max_ns = 1;
   for (int c = 0; c < 4; ++c) max_ns = std::max(max_ns, k.ns[c]);
@@ -1862,244 +1863,10 @@ __global__ __launch_bounds__(256) void conv3d_direct_bwd_weight_kernel(
   if (threadIdx.x == 0) dw[((int64_t)o * Cin + c) * k3 + tap] = (float)tot;
 }
 
-// ------------------------------------------------------------------ planning
-// Plan for a 3x3x3/s1/p1 conv with K-channels `kin` and M-channels `mout`.
-// Lanes along x per 32-voxel group: the widest of {32, 16, 8} unless a narrower one wastes noticeably
-// fewer padded voxels (W = 24: 16 -> 2 tiles = 32 columns, 8 -> 3 tiles = 24 columns).
-int pick_gx(int W) {
-  int best = 8;
-  int64_t best_pad = round_up(W, 8);
-  for (int gx : {16, 32}) {
-    const int64_t pad = round_up(W, gx);
-    if (W >= gx && pad * 100 <= best_pad * 108) {  // prefer the wider tile unless it pads > 8 % more
-      best = gx;
-      best_pad = std::min(best_pad, pad);
-    }
-  }
-  return best;
-}
-
-// M355_COMPUTE_F32X3 (conv3d_f32x3.hip): a 32-row tile must carry real rows, and the 8-channel slab of a sample must fit
-// the 31-bit byte offsets its loads add up.  Layers with 3..7 K-channels (4 -> 32 forward, 3 -> 32 data gradient @128^3:
-// one chunk, 4 / 3 of its 8 channels real) run 0.183 / 0.174 ms on the split kernel against 0.21 / 0.19 on the fp32 MFMA
-// (0.06 ms of that is the 268 MB they write, the rest the half-empty K of their MFMAs) -- behind M355_F32X3_EDGE=1, off
-// by default: with the FIRST layer of the net on the split kernel one voxel of the 2.1 M of the bench volume (a near-tie
-// of two class probabilities) takes the other side of the CPU reference's argmax; with it on the fp32 MFMA none does.
-static bool x3_layer(int kin, int mout, int D, int H, int W) {
-  return tuning().f32x3 && kin >= (tuning().f32x3_edge ? 3 : 8) && mout > 4 && (int64_t)D * H * W < (1ll << 26);
-}
-
-FwdPlan plan_mfma(int N, int kin, int mout, int D, int H, int W, int compute) {
-  FwdPlan p{};
-  p.mfma = true;
-  p.gx = pick_gx(W);
-  const int gy = 32 / p.gx;
-  const bool h16 = is16(compute);  // bf16 / fp16 operand modes share one plan
-  if (compute == M355_COMPUTE_F32 && tuning().f32x3 == 2) compute = M355_COMPUTE_F32X3;   // M355_F32X3=2: test hook
-  const bool x3 = compute == M355_COMPUTE_F32X3 && x3_layer(kin, mout, D, H, W);
-  if (!h16 && !x3) compute = M355_COMPUTE_F32;
-  p.x3 = x3 ? 1 : 0;
-  const int cc = h16 ? 16 : (x3 ? 8 : 4);  // input channels per LDS chunk
-  p.kin_pad = (int)round_up(kin, cc);
-  p.mout_pad = (int)round_up(mout, 32);
-  p.otiles = p.mout_pad / 32;
-  // fp32: a remainder of 1..16 channels runs as ONE 16-row tile on v_mfma_f32_16x16x4_f32 (half the MFMA time of a
-  // padded 32-row tile): 40 channels = 32 + 16 rows instead of 64, 80 = 64 + 16 instead of 96
-  p.tile16 = (!h16 && tuning().tile16 && mout % 32 >= 1 && mout % 32 <= 16) ? 1 : 0;   // (split kernels: conv3_f32x3_m16_kernel)
-  if (p.tile16) p.otiles -= 1;
-  const int wtiles = p.otiles + p.tile16;   // workgroup items per spatial tile
-  p.nchunks = p.kin_pad / cc;
-  p.nw = 4;
-  p.tz_tiles = (int)ceil_div(D, 4);
-  p.tx_tiles = (int)ceil_div(W, p.gx);
-  // Pick (voxel-tile height NTW, split-K) by a cost model instead of "fill the chip once":
-  // workgroups of one launch do equal work, so the time is rounds x (workgroups sharing a CU) x
-  // time of one workgroup, and a launch that needs 1.1 rounds costs as much as one that needs 2.
-  //   slots     NTW <= 4: 66.8 KB LDS -> two workgroups per CU (512); NTW = 8: one (256)
-  //   one chunk 54 x NTW MFMAs of 64 cycles per wave at ~2.04 GHz; + fill/epilogue (see `fixed`)
-  //   split-K   ks x out bytes written + read again by the reduce kernel (~4 TB/s) + a launch
-  const int64_t out_bytes = (int64_t)N * mout * D * H * W * 4;
-  const int force_ntw = tuning().conv_ntw;
-  const int force_ks = tuning().conv_ksplit;
-  const int cands[4] = {4, 8, 2, 1};
-  int chosen = 1, chosen_ks = 1;
-  double best = 1e30;
-  const int cus = num_cus();
-  const bool h16_one = h16 && tuning().h16_oneshot && tuning().h16_oneshot != 3;
-  if (h16_one) {
-    // 16-bit kernels, one item per workgroup (conv3_h16_kernel, ONE): cost model over (tile height, split-K).
-    //   time ~ residencies x (chunks per item x chunk time(NTW) x share + fixed(NTW)) + split-K reduction
-    // chunk time per workgroup with two resident per CU (measured: ~44 % of the MFMA rate at NTW = 4; narrower tiles
-    // re-read the weights more often), `share` < 1 when the launch leaves CUs with a single workgroup, the reduction
-    // pass ~12 us + its slab traffic.  Constants fitted on the cfg2 layers (tools/plan_sweep_h16.py).
-    double best_h = 1e30;
-    for (int ntw : {4, 2, 1}) {
-      if (p.gx == 8 && ntw == 4) continue;                 // not instantiated
-      if (force_ntw && ntw != force_ntw && force_ntw != 8 && !(p.gx == 8 && force_ntw == 4)) continue;
-      const int ty = ntw * gy;
-      if (ty > H && ntw > 1 && !force_ntw) continue;
-      const double chunk_us = ntw == 4 ? 5.8 : (ntw == 2 ? 3.5 : 2.8), fixed_us = ntw == 4 ? 6.0 : (ntw == 2 ? 3.5 : 2.5);
-      const int64_t nwg1 = (int64_t)p.tz_tiles * ceil_div(H, ty) * p.tx_tiles * p.otiles * N;
-      for (int ks = 1; ks <= std::min(p.nchunks, 8); ++ks) {
-        if (ks > 1 && (ks - 1) * ceil_div(p.nchunks, ks) >= p.nchunks) continue;   // an empty split
-        if (ks > 1 && ks * out_bytes > (128ll << 20)) break;
-        const int64_t nwg = nwg1 * ks;
-        const double per_cu = (double)nwg / cus;
-        const double share = 0.58 + 0.42 * std::min(1.0, std::max(0.0, per_cu - 1.0));
-        const double rounds = std::max(1.0, (double)ceil_div(nwg, 2 * (int64_t)cus));
-        double cost = rounds * ((double)ceil_div(p.nchunks, ks) * chunk_us * share + fixed_us);
-        if (ks > 1) cost += 14.0 + (double)(ks + 1) * (double)out_bytes / 2.5e6;
-        if (cost < best_h * 0.97) {
-          best_h = cost;
-          chosen = ntw;
-          chosen_ks = ks;
-        }
-      }
-    }
-  }
-  for (int i = 0; i < 4 && h16 && !h16_one; ++i) {
-    // 16-bit operand modes, queue-driven kernels (M355_H16_ONESHOT=0 / 3): fill the chip once, largest tile
-    // first; the instantiated tiles are NTW <= 4 (<= 2 for 8 lanes along x)
-    const int ntw = cands[i];
-    if (ntw == 8 || (p.gx == 8 && ntw == 4)) continue;
-    if (force_ntw && ntw != force_ntw && force_ntw != 8 && !(p.gx == 8 && force_ntw == 4)) continue;
-    const int ty = ntw * gy;
-    if (ty > H && ntw > 1 && !force_ntw) continue;
-    const int64_t nwg = (int64_t)p.tz_tiles * ceil_div(H, ty) * p.tx_tiles * p.otiles * N;
-    int64_t ks = std::max<int64_t>(1, std::min<int64_t>(ceil_div(512, nwg), std::min<int64_t>(p.nchunks, 8)));
-    while (ks > 1 && ks * out_bytes > (128ll << 20)) --ks;
-    while (ks > 1 && (ks - 1) * ceil_div(p.nchunks, ks) >= p.nchunks) --ks;
-    chosen = ntw;
-    chosen_ks = (int)ks;
-    if (nwg * ks * 4 >= 512 * 3) break;
-  }
-  if (x3) {
-    // conv3_f32x3_kernel: one item per workgroup, two workgroups per CU, NTW <= 4.  A chunk (8 channels) is 14 x 6 x NTW
-    // MFMAs of 32 cycles per wave at the ~1.6 GHz the bf16 pipe holds; split-K as for the fp32 kernels
-    double best3 = 1e30;
-    for (int ntw : {4, 2, 1}) {
-      if (force_ntw && ntw != force_ntw && force_ntw != 8) continue;
-      const int ty = ntw * gy;
-      if (ty > H && ntw > 1 && !force_ntw) continue;
-      const int64_t base_wg = (int64_t)p.tz_tiles * ceil_div(H, ty) * p.tx_tiles * (p.otiles + p.tile16) * N;   // (a 16-row item: half the time)
-      const double chunk_us = 14.0 * 6.0 * ntw * 32.0 / 1600.0 / (ntw >= 4 ? 1.0 : ntw == 2 ? 0.9 : 0.75);
-      for (int ks = 1; ks <= std::min(p.nchunks, 8); ++ks) {
-        if (ks > 1 && (ks - 1) * ceil_div(p.nchunks, ks) >= p.nchunks) continue;
-        if (ks > 1 && ks * out_bytes > (128ll << 20)) break;
-        const int64_t nwg = base_wg * ks;
-        const double rounds = (double)ceil_div(nwg, (int64_t)cus * 2);
-        const double share = nwg <= cus ? 1.0 / 0.8 : 2.0;
-        double cost = rounds * share * ((double)ceil_div(p.nchunks, ks) + 1.0) * chunk_us;
-        if (ks > 1) cost += (2.0 * ks + 1.0) * (double)out_bytes / 4.0e6 + 4.0;
-        if (cost < best3 * 0.98) {
-          best3 = cost;
-          chosen = ntw;
-          chosen_ks = ks;
-        }
-      }
-    }
-  }
-  for (int i = 0; i < 4 && !h16 && !x3; ++i) {
-    const int ntw = cands[i];
-    if (p.tile16 && ntw == 8) continue;              // the 16-row kernel is instantiated for NTW <= 4
-    if (force_ntw && ntw != force_ntw && !(p.tile16 && force_ntw == 8)) continue;
-    const int ty = ntw * gy;
-    if (ty > H && ntw > 1 && !force_ntw) continue;  // do not overhang H by a whole factor
-    const int64_t base_wg = (int64_t)p.tz_tiles * ceil_div(H, ty) * p.tx_tiles * wtiles * N;
-    const int per_cu = ntw <= 4 ? 2 : 1;
-    // narrow tiles re-read the weights from LDS more often per MFMA ((1 + NTW) / NTW reads each)
-    const double chunk_us = 54.0 * ntw * 64.0 / 2040.0 / (ntw >= 4 ? 1.0 : ntw == 2 ? 0.96 : 0.8);
-    for (int ks = 1; ks <= std::min(p.nchunks, 8); ++ks) {
-      if (ks > 1 && (ks - 1) * ceil_div(p.nchunks, ks) >= p.nchunks) continue;  // an empty split
-      if (ks > 1 && ks * out_bytes > (128ll << 20)) break;
-      const int64_t nwg = base_wg * ks;
-      const double rounds = (double)ceil_div(nwg, (int64_t)cus * per_cu);
-      // a lone workgroup on a CU has nothing to cover its barriers and LDS commits: measured ~0.8 of
-      // the paired rate for NTW <= 4 (u0.c0 pinned to one per CU: 111 vs 126 TFLOP/s), ~0.93 for NTW = 8
-      const bool lone = per_cu == 1 || nwg <= cus;
-      const double share = lone ? 1.0 / (per_cu == 1 ? 0.93 : 0.8) : (double)per_cu;
-      // fixed cost of an item: ~1 chunk for a one-shot workgroup, ~0.5 when the persistent kernel
-      // (more items than resident workgroups) prefetches across the item boundary
-      const double fixed = nwg > (int64_t)cus * per_cu ? 0.5 : 1.0;
-      double cost = rounds * share * ((double)ceil_div(p.nchunks, ks) + fixed) * chunk_us;
-      if (ks > 1) cost += (2.0 * ks + 1.0) * (double)out_bytes / 4.0e6 + 4.0;
-      if (cost < best * 0.98) {  // candidates come in order of preference: switch only for a real gain
-        best = cost;
-        chosen = ntw;
-        chosen_ks = ks;
-      }
-    }
-  }
-  if (h16 && !h16_one && p.gx == 32 && tuning().h16_w8 && D >= 8 && H >= 2) {
-    // 8-wave double-buffered variant (tile 8 x 2 x 32, one workgroup per CU) for SHORT items (<= 4 chunks = 64
-    // input channels) whose tiles fill the chip without split-K: there the single-buffered kernel spends as long
-    // on chunk boundaries and item switches as on MFMAs (32->32 @128^3: 0.194 -> 0.167 ms, 32->64 @64^3: 0.088 ->
-    // 0.058).  Long items stay on the 4-wave kernel: its 4-row wave tile needs 0.75 LDS fragment reads per MFMA,
-    // the 2-row tile of this variant 1.17, and at 6+ chunks that LDS traffic costs more than the boundaries
-    // (96->32 @128^3: 0.33 vs 0.41 ms).
-    const int64_t items8 = (int64_t)ceil_div(D, 8) * ceil_div(H, 2) * p.tx_tiles * p.otiles * N;
-    if (((items8 >= 2 * (int64_t)cus && p.nchunks <= 4) || tuning().h16_w8 == 2) && (!force_ntw || force_ntw == 2)) {   // 2: always (tests)
-      p.nw = 8;
-      p.tz_tiles = (int)ceil_div(D, 8);
-      chosen = 2;
-      chosen_ks = 1;
-    }
-  }
-  if (h16_one) p.oneshot = 1;
-  if (force_ks) {
-    chosen_ks = std::min(force_ks, p.nchunks);
-    while (chosen_ks > 1 && (chosen_ks - 1) * (int)ceil_div(p.nchunks, chosen_ks) >= p.nchunks)
-      --chosen_ks;
-  }
-  p.ntw = chosen;
-  p.ty_tiles = (int)ceil_div(H, p.ntw * gy);
-  p.ksplit = chosen_ks;
-  const int ksplit = chosen_ks;
-  {
-    // resident workgroups (LDS + registers: 2 per CU up to NTW = 4); the override exists for the tests
-    const int64_t slots = (tuning().conv_slots ? tuning().conv_slots : (p.nw == 8 ? 1 : (p.ntw <= 4 ? 2 : 1)) * num_cus());
-    const int64_t items = (int64_t)p.tz_tiles * p.ty_tiles * p.tx_tiles * p.otiles * N * p.ksplit;
-    // single-chunk items (Cin <= 4: the first conv of the network, the data gradient of the output conv) have no
-    // second chunk to hide the queue ticket's round trip or the next item's prefetch behind: the one-shot grid is
-    // faster there (4->32 @128^3: 0.187 vs 0.248 ms)
-    // ... and the queue only pays beyond two residencies of items: up to there the one-shot grid, whose workgroups
-    // the hardware hands out as CUs free up, is 3-7 % faster (192->64 @64^3, 2.0 residencies: 1.237 -> 1.195 ms;
-    // 128->384 @32^3, 1.5: 0.672 -> 0.628); from 3.4 residencies (40->40 @96^3) the queue wins by 7-9 %
-    p.persistent = compute == M355_COMPUTE_F32 && !x3 && items < (1ll << 31) && tuning().conv_persistent &&
-                   (tuning().conv_persistent > 1 ? items > slots
-                                                 : (items > 2 * slots && ceil_div(p.nchunks, p.ksplit) > 1));
-    (void)wtiles;
-  }
-  // packed weights + 256 B for the work counter of the persistent kernel
-  p.wp_bytes = (size_t)round_up((int64_t)p.kin_pad * 27 * p.mout_pad * (h16 ? 2 : 4), 256) + 256;
-  if (x3)   // [tile][chunk][pair][plane][lane] x 16 B, then the 16-row tile's [chunk][quad][plane][lane] x 16 B
-    p.wp_bytes = (size_t)p.otiles * p.nchunks * (14 * 3 * 1024) + (size_t)p.tile16 * p.nchunks * (7 * 3 * 1024) + 256;
-  p.slab_bytes = ksplit > 1 ? (size_t)ksplit * N * mout * D * H * W * 4 : 0;
-  return p;
-}
-
-// The MFMA kernels: 3x3x3, stride 1, padding 1, and a volume whose 4-channel slab fits the 32-bit byte
-// offsets of a buffer descriptor (< 2^27 voxels, i.e. below 512^3); anything else takes the generic
-// direct kernels (64-bit indexing).
-static bool is_k3s1p1(const m355_conv3d_desc* d) {
-  return d->k == 3 && d->stride == 1 && d->pad == 1 && (int64_t)d->D * d->H * d->W < (1ll << 27);
-}
-
-static int out_dim(int in, int k, int s, int p) { return (in + 2 * p - k) / s + 1; }
-
-// Cout <= 4 forward in exact fp32: z-Toeplitz packed rows instead of a mostly-empty 32-row tile
-static bool small_cout_fwd(const m355_conv3d_desc* d) {
-  return d->Cout <= 4 && !is16(d->compute) && d->W >= 32 && d->D >= 8 && d->Cin >= 8 &&
-         !tuning().no_small && (int64_t)std::max(d->Cin, d->Cout) * d->D * d->H * d->W < (1ll << 31);
-}
-static size_t small_cout_ws(const m355_conv3d_desc* d) {
-  return (size_t)round_up((int64_t)round_up(d->Cin, 2) * TZ_K * 32 * 4, 256);
-}
-static bool small_bww(const m355_conv3d_desc* d) {
-  // tap-on-lane kernel; a sample must fit the 32-bit byte offsets of a buffer descriptor
-  return (d->Cin <= 4 || d->Cout <= 4) && !tuning().no_small &&
-         (int64_t)std::max(d->Cin, d->Cout) * d->D * d->H * d->W < (1ll << 29);
-}
+// ------------------------------------------------------------------ launcher
+// Everything the host layer (conv3d_host.hip) starts from this file's kernels: it hands over a resolved route, nothing
+// here decides which kernel family runs.
+size_t smallcout_packed_bytes(int Cin) { return (size_t)round_up((int64_t)round_up(Cin, 2) * TZ_K * 32 * 4, 256); }
 
 template <int NTW, int GX>
 static void launch_fwd(const FwdPlan& p, const float* x, const float* wp, const float* bias,
@@ -2133,80 +1900,90 @@ static void launch_fwd(const FwdPlan& p, const float* x, const float* wp, const 
   }
 }
 
-// bytes of the c8 staging copy the fp32-input entry points make in 16-bit operand modes
-static size_t act16_staging_bytes(int N, int C, int D, int H, int W) {
-  return (size_t)round_up((int64_t)N * c8_blocks(C) * D * H * W * 16, 256);
-}
-
-static void launch_pack_w3(const FwdPlan& p, const float* w, float* wp, int Cout_w, int Cin_w, bool transpose,
-                           hipStream_t st) {
-  const int64_t total = (int64_t)p.kin_pad * 27 * p.mout_pad;
-  const int blocks = (int)std::min<int64_t>(ceil_div(total, 256), 2048);
-  hipLaunchKernelGGL(pack_w3_kernel, dim3(blocks), dim3(256), 0, st, w, wp, Cout_w, Cin_w, p.kin_pad, p.mout_pad,
-                     transpose ? 1 : 0, (int*)((char*)wp + p.wp_bytes - 256));
-}
-
-static int run_mfma_conv(const float* in, const float* w, bool transpose, int Cout_w, int Cin_w,
-                         const float* bias, const float* add, float* out, int N, int kin,
-                         int mout, int D, int H, int W, int64_t in_bs, int64_t out_bs, void* ws,
-                         size_t ws_bytes, hipStream_t st, int compute = M355_COMPUTE_F32, float* stat = nullptr,
-                         const void* in16 = nullptr, int64_t in16_bs = 0, const void* prepacked = nullptr,
-                         bool out16 = false, bool softmax = false, int* oflag = nullptr) {
-  // prepacked: weights already packed for this plan by m355_conv3d_pack (M355_CONV_W_PACKED); `w` is then unused
-  // oflag: overflow word of a c8 data gradient (fp16 only: the stores saturate and report there, common.hpp)
-  const FwdPlan p = plan_mfma(N, kin, mout, D, H, W, compute);
-  M355_REQUIRE(!stat || p.ksplit == 1 || !is16(compute) || out16, M355_EINVALID_ARG,
-               "conv3d_fwd_stats: no fused statistics for this plan (m355_conv3d_stats_slots() == 0)");
-  if (is16(compute)) {
-    if (!in16) {
-      // fp32 NCDHW input: one conversion pass into the c8 layout (the model path hands over c8 tensors that its
-      // normalisation / pooling passes wrote, m355_conv3d_fwd_h16)
-      const size_t base = p.wp_bytes + p.slab_bytes;
-      M355_REQUIRE(ws_bytes >= base + act16_staging_bytes(N, kin, D, H, W), M355_EWORKSPACE,
-                   "conv3d(16-bit operands): workspace too small (%zu < %zu)", ws_bytes,
-                   base + act16_staging_bytes(N, kin, D, H, W));
-      void* stage = (char*)ws + base;
-      in16_bs = c8_blocks(kin) * (int64_t)D * H * W * 8;
-      if (int rc = launch_pack_act16(in, stage, N, kin, (int64_t)D * H * W, in_bs, in16_bs, compute, st)) return rc;
-      in16 = stage;
+void launch_pack_weights(const ConvRoute& r, const m355_conv3d_desc* d, bool transpose, const float* w, void* packed,
+                         hipStream_t st) {
+  const FwdPlan& p = r.plan;
+  if (is_h16(r.kind)) return launch_pack_w3_h16(p, d->compute, w, packed, d->Cout, d->Cin, transpose, st);
+  switch (r.kind) {
+    case ConvKind::SmallCoutValu:
+      hipLaunchKernelGGL(pack_w3_valu_kernel, dim3((unsigned)ceil_div(d->Cin * 27 * 4, 256)), dim3(256), 0, st, w,
+                         (float*)packed, d->Cout, d->Cin);
+      break;
+    case ConvKind::SmallCoutToeplitz: {
+      const int kin_pad = (int)round_up(d->Cin, 2);
+      const int64_t total = (int64_t)kin_pad * TZ_K * 32;
+      hipLaunchKernelGGL(pack_w3_toeplitz_kernel, dim3((unsigned)std::min<int64_t>(ceil_div(total, 256), 2048)), dim3(256),
+                         0, st, w, (float*)packed, d->Cout, d->Cin, kin_pad);
+      break;
     }
-    return run_h16_conv(p, compute, in16, in16_bs, w, transpose, Cout_w, Cin_w, bias, add, out, N, kin, mout, D, H, W,
-                        out_bs, ws, ws_bytes, st, stat, prepacked, out16, softmax, oflag);
+    case ConvKind::X3:
+      launch_pack_w3_x3(p, w, packed, d->Cout, d->Cin, transpose, st);
+      break;
+    default: {
+      const int64_t total = (int64_t)p.kin_pad * 27 * p.mout_pad;
+      const int blocks = (int)std::min<int64_t>(ceil_div(total, 256), 2048);
+      hipLaunchKernelGGL(pack_w3_kernel, dim3(blocks), dim3(256), 0, st, w, (float*)packed, d->Cout, d->Cin, p.kin_pad,
+                         p.mout_pad, transpose ? 1 : 0, (int*)((char*)packed + p.wp_bytes - 256));
+    }
   }
-  M355_REQUIRE(!softmax, M355_EUNSUPPORTED, "conv3d: no fused softmax in the fp32 MFMA kernels");
-  M355_REQUIRE(ws_bytes >= p.wp_bytes + p.slab_bytes, M355_EWORKSPACE,
-               "conv3d: workspace too small (%zu < %zu)", ws_bytes, p.wp_bytes + p.slab_bytes);
-  M355_REQUIRE(((uintptr_t)ws & 15) == 0, M355_EINVALID_ARG, "conv3d: workspace not 16B aligned");
-  float* wp = prepacked ? (float*)prepacked : (float*)ws;
-  float* slab = (float*)((char*)ws + p.wp_bytes);
+}
+
+int launch_f32_conv(const ConvRoute& r, const ConvCall& c) {
+  const m355_conv3d_desc* d = c.d;
+  const FwdPlan& p = r.plan;
+  hipStream_t st = c.st;
+  const int D = d->D, H = d->H, W = d->W, N = d->N;
+  if (r.kind == ConvKind::Direct) {
+    const int OD = out_dim(D, d->k, d->stride, d->pad), OH = out_dim(H, d->k, d->stride, d->pad),
+              OW = out_dim(W, d->k, d->stride, d->pad);
+    const int64_t total = (int64_t)N * (c.transpose ? (int64_t)d->Cin * D * H * W : (int64_t)d->Cout * OD * OH * OW);
+    const int blocks = (int)std::min<int64_t>(ceil_div(total, 256), 65535);
+    if (c.transpose)   // in = dy, out = dx
+      hipLaunchKernelGGL(conv3d_direct_bwd_data_kernel, dim3(blocks), dim3(256), 0, st, c.in, c.w, c.out, N, d->Cin, d->Cout,
+                         D, H, W, OD, OH, OW, d->k, d->stride, d->pad, c.out_bs, c.in_bs);
+    else
+      hipLaunchKernelGGL(conv3d_direct_fwd_kernel, dim3(blocks), dim3(256), 0, st, c.in, c.w, c.bias, c.add, c.out, N,
+                         d->Cin, d->Cout, D, H, W, OD, OH, OW, d->k, d->stride, d->pad, c.in_bs, c.out_bs);
+    return check_launch(c.transpose ? "conv3d_direct_bwd_data" : "conv3d_direct_fwd");
+  }
+  float* wp = c.prepacked ? (float*)c.w : (float*)c.ws;
+  if (!c.prepacked) launch_pack_weights(r, d, c.transpose, c.w, wp, st);
+  if (r.kind == ConvKind::SmallCoutValu) {   // packed-FMA kernel (see conv3_valu_smallcout_kernel)
+    const int tyv = (int)ceil_div(H, VS_TY), txv = (int)ceil_div(W, VS_TX);
+    dim3 gv((unsigned)(ceil_div(D, VS_TZ) * tyv * txv), (unsigned)N);
+    hipLaunchKernelGGL(conv3_valu_smallcout_kernel, gv, dim3(256), 0, st, c.in, wp, c.bias, c.add, c.out, d->Cin, d->Cout,
+                       D, H, W, tyv, txv, c.in_bs, c.out_bs, c.softmax ? 1 : 0);
+    return check_launch("conv3_valu_smallcout");
+  }
+  if (r.kind == ConvKind::SmallCoutToeplitz) {
+    const int tyt = (int)ceil_div(H, 8), txt = (int)ceil_div(W, 32);
+    dim3 grid((unsigned)(ceil_div(D, 8) * tyt * txt), (unsigned)N);
+    hipLaunchKernelGGL(conv3_mfma_fwd_smallcout_kernel, grid, dim3(256), 0, st, c.in, wp, c.bias, c.add, c.out, d->Cin,
+                       d->Cout, D, H, W, tyt, txt, (int)round_up(d->Cin, 2) / 2, c.in_bs, c.out_bs);
+    return check_launch("conv3_mfma_fwd_smallcout");
+  }
+  const int kin = c.transpose ? d->Cout : d->Cin, mout = c.transpose ? d->Cin : d->Cout;
+  const float *in = c.in, *bias = c.bias, *add = c.add;
+  float *out = c.out, *stat = c.stat;
+  const int64_t in_bs = c.in_bs, out_bs = c.out_bs;
+  float* slab = (float*)((char*)c.ws + p.wp_bytes);
   int* work_counter = queue_state(st);   // per (device, stream): concurrent launches over one model never share it
   M355_REQUIRE(work_counter, M355_ELAUNCH, "conv3d: could not allocate the work-queue state");
   const float* kb = p.ksplit == 1 ? bias : nullptr;
   const float* ka = p.ksplit == 1 ? add : nullptr;
-  if (p.x3) {
-    if (!prepacked) launch_pack_w3_x3(p, w, wp, Cout_w, Cin_w, transpose, st);
+  if (r.kind == ConvKind::X3) {
     if (int rc = launch_x3_conv(p, in, wp, kb, ka, out, slab, N, kin, mout, D, H, W, in_bs, out_bs, st,
                                 p.ksplit == 1 ? stat : nullptr))
       return rc;
   } else {
-  if (!prepacked) launch_pack_w3(p, w, wp, Cout_w, Cin_w, transpose, st);
 #define M355_FWD_CASE(NTW, GX)                                                              \
   if (p.ntw == NTW && p.gx == GX) {                                                         \
     launch_fwd<NTW, GX>(p, in, wp, kb, ka, out, slab, N, kin, mout, D, H, W, in_bs, out_bs, \
                         st, p.ksplit == 1 ? stat : nullptr, work_counter);                  \
   } else
-  M355_FWD_CASE(8, 32)
-  M355_FWD_CASE(4, 32)
-  M355_FWD_CASE(2, 32)
-  M355_FWD_CASE(1, 32)
-  M355_FWD_CASE(8, 16)
-  M355_FWD_CASE(4, 16)
-  M355_FWD_CASE(2, 16)
-  M355_FWD_CASE(1, 16)
-  M355_FWD_CASE(8, 8)
-  M355_FWD_CASE(4, 8)
-  M355_FWD_CASE(2, 8)
-  M355_FWD_CASE(1, 8) {
+  M355_FWD_CASE(8, 32) M355_FWD_CASE(4, 32) M355_FWD_CASE(2, 32) M355_FWD_CASE(1, 32)
+  M355_FWD_CASE(8, 16) M355_FWD_CASE(4, 16) M355_FWD_CASE(2, 16) M355_FWD_CASE(1, 16)
+  M355_FWD_CASE(8, 8) M355_FWD_CASE(4, 8) M355_FWD_CASE(2, 8) M355_FWD_CASE(1, 8) {
     set_error("conv3d: no kernel for ntw=%d gx=%d", p.ntw, p.gx);
     return M355_EUNSUPPORTED;
   }
@@ -2227,703 +2004,39 @@ static int run_mfma_conv(const float* in, const float* w, bool transpose, int Co
   return check_launch("conv3d_mfma");
 }
 
-struct BwwPlan {
-  int gx, tz_tiles, ty_tiles, tx_tiles, otiles, ctiles, nsplit;
-  size_t slab_bytes;
-  bool classes;     // a 1..16 channel remainder on either side: conv3_mfma_bww2c_kernel (needs the gen-2 conditions)
-  BwwClasses k;     // always filled: without remainders one class with ns[*] = nsplit
-  int class_wgs;    // grid of the class kernel
-};
+// The choice of the MFMA weight-gradient kernel that a descriptor cannot make.  vec: float4 interior rows need 16-byte
+// aligned rows.  gen2: the second-generation kernels need float4 rows, and a sample must fit the 32-bit byte offsets of a
+// buffer descriptor (the hardware zero-fills what lies past it); otherwise conv3_mfma_bww_kernel<GX, vec>.
+struct BwwVariant { bool vec, gen2; };
+static BwwVariant bww_variant(const m355_conv3d_desc* d, const float* x, const float* dy, int64_t xbs) {
+  const int64_t spatial = (int64_t)d->D * d->H * d->W;
+  const bool vec = (d->W % 4 == 0) && (xbs % 4 == 0) && (((uintptr_t)x) & 15) == 0;
+  const bool gen2 = vec && ((uintptr_t)dy & 3) == 0 && (int64_t)d->Cin * spatial < (1ll << 29) &&
+                    (int64_t)d->Cout * spatial < (1ll << 29) && tuning().bww_gen == 2;
+  return {vec, gen2};
+}
 
-static BwwPlan plan_bww(int N, int Cin, int Cout, int D, int H, int W) {
-  BwwPlan p{};
-  p.gx = pick_gx(W);
-  const int tz = p.gx == 8 ? 4 : 2, ty = p.gx == 32 ? 4 : 8;
-  p.tz_tiles = (int)ceil_div(D, tz);
-  p.ty_tiles = (int)ceil_div(H, ty);
-  p.tx_tiles = (int)ceil_div(W, p.gx);
-  p.otiles = (int)ceil_div(Cout, 32);
-  p.ctiles = (int)ceil_div(Cin, 32);
-  const int64_t ntiles = (int64_t)N * p.tz_tiles * p.ty_tiles * p.tx_tiles;
-  const int64_t pairs = (int64_t)p.otiles * p.ctiles;
-  const auto rem16 = [](int c) { return c % 32 >= 1 && c % 32 <= 16 ? 1 : 0; };
-  p.k.orem = tuning().tile16 ? rem16(Cout) : 0;
-  p.k.crem = tuning().tile16 ? rem16(Cin) : 0;
-  p.k.of = p.otiles - p.k.orem;
-  p.k.cf = p.ctiles - p.k.crem;
-  p.classes = (p.k.orem || p.k.crem) && Cin > 4 && Cout > 4;
-  // One workgroup per CU; workgroups have equal work, so time ~ rounds x (tiles per split + fixed
-  // cost of a workgroup: pipeline fill + the 110 KB slab write, ~half a tile).  Pick the split that
-  // minimises it (a power of two up to the tile count) instead of just filling 256 CUs once.
-  int64_t nsplit = 1;
-  const int cus = num_cus();
-  {
-    int64_t cand[24];
-    int nc = 0;
-    for (int64_t ns = 1; ns < ntiles; ns *= 2) cand[nc++] = ns;
-    for (int r = 1; r <= 8; ++r) cand[nc++] = std::max<int64_t>(1, (int64_t)cus * r / pairs);  // exactly r rounds
-    cand[nc++] = std::max<int64_t>(1, ntiles);
-    std::sort(cand, cand + nc);
-    double best = 1e30;
-    for (int i = 0; i < nc; ++i) {
-      const int64_t ns = std::min<int64_t>(cand[i], std::max<int64_t>(1, ntiles));
-      const double rounds = (double)ceil_div(pairs * ns, cus);
-      const double cost = rounds * ((double)ceil_div(ntiles, ns) + 0.5);
-      if (cost < best * 0.97) {  // prefer fewer splits (less slab traffic) unless clearly better
-        best = cost;
-        nsplit = ns;
-      }
+int launch_f32_bww(const BwwRoute& r, const m355_conv3d_desc* d, const float* x, const float* dy, float* dw, float* slab,
+                   int64_t xbs, int64_t ybs, hipStream_t st) {
+  const BwwPlan& p = r.plan;
+  switch (r.kind) {
+    case BwwKind::Direct: {
+      const int OD = out_dim(d->D, d->k, d->stride, d->pad), OH = out_dim(d->H, d->k, d->stride, d->pad),
+                OW = out_dim(d->W, d->k, d->stride, d->pad);
+      const int k3 = d->k * d->k * d->k;
+      const int64_t nblk = (int64_t)d->Cout * d->Cin * k3;
+      M355_REQUIRE(nblk < (1ll << 31), M355_EUNSUPPORTED, "conv3d_bwd_weight: grid too large");
+      hipLaunchKernelGGL(conv3d_direct_bwd_weight_kernel, dim3((unsigned)nblk), dim3(256), 0, st, x,
+                         dy, dw, d->N, d->Cin, d->Cout, d->D, d->H, d->W, OD, OH, OW, d->k,
+                         d->stride, d->pad, xbs, ybs);
+      return M355_OK;
     }
-  }
-  // Queue-driven: the plan above fills the chip in ONE residency (one workgroup per CU), so a CU that another
-  // kernel still holds when this one starts -- an RCCL gradient bucket overlapping the backward pass -- delays
-  // exactly the workgroup mapped there, and the launch takes up to twice as long.  Splitting the voxel range 2-3x
-  // finer makes 2-3 units per CU that the hardware dispatcher hands to whichever CU is free (a held CU simply
-  // takes fewer); every unit still sums a FIXED tile set into its own slab, so the result does not depend on who
-  // ran what and stays bit-reproducible.  Each unit pays a pipeline fill and a slab write (and the reduce reads
-  // one more slab), so this is only done where a unit keeps >= 32 tiles: measured +0.8 % on 96->32 @128^3 at 3
-  // units per CU, but +9 % / +18 % on 32->32 @128^3 / 64->64 @64^3 (11 / 5 tiles per unit), which stay static.
-  if (tuning().bww_queue && Cin > 4 && Cout > 4 && pairs * nsplit <= cus) {
-    const int64_t per_unit = ceil_div(ntiles, nsplit);
-    const int m = per_unit >= 96 ? 3 : (per_unit >= 64 ? 2 : 1);
-    if (m * nsplit * (int64_t)Cout * Cin * 27 * 4 <= (96ll << 20)) nsplit *= m;
-  }
-  if (const int force = tuning().bww_nsplit) nsplit = std::min<int64_t>(force, std::max<int64_t>(1, ntiles));
-  if (Cin <= 4 || Cout <= 4)  // tap-on-lane kernel: small LDS footprint, ~3 workgroups per CU
-    nsplit = std::max<int64_t>(1, 768 / std::max<int64_t>(1, ceil_div(Cin <= 4 ? Cout : Cin, 32)));
-  nsplit = std::min<int64_t>(nsplit, ntiles);
-  p.nsplit = (int)nsplit;
-  int64_t max_ns = nsplit;
-  for (int c = 0; c < 4; ++c) p.k.ns[c] = p.nsplit;
-  if (p.classes) {
-    // pair classes of the remainder kernel: MFMA cost of a pair in units of a full 32 x 32 pair; the split count of
-    // a class is proportional to it, scaled so that the whole launch is `rounds` residencies of equal workgroups
-    const double cost[4] = {1.0, 0.5, 0.5, 0.25};
-    const int64_t npairs[4] = {(int64_t)p.k.of * p.k.cf, (int64_t)p.k.of * p.k.crem, (int64_t)p.k.orem * p.k.cf,
-                               (int64_t)p.k.orem * p.k.crem};
-    double units = 0;
-    for (int c = 0; c < 4; ++c) units += cost[c] * (double)npairs[c];
-    // splits of a full pair: one residency of the chip (one workgroup per CU), never more splits than tiles; the
-    // rounding of the per-class counts must not spill a workgroup into a second residency
-    double base = std::min((double)ntiles, (double)cus / units);
-    if (const int force = tuning().bww_nsplit) base = (double)std::min<int64_t>(force, std::max<int64_t>(1, ntiles));
-    int wg = 0;
-    for (;;) {
-      wg = 0;
-      max_ns = 1;
-      for (int c = 0; c < 4; ++c) {
-        const int64_t ns = std::max<int64_t>(1, std::min<int64_t>(ntiles, (int64_t)(base * cost[c] + 0.5)));
-        p.k.ns[c] = npairs[c] ? (int)ns : 1;
-        p.k.start[c] = wg;
-        wg += (int)(npairs[c] * p.k.ns[c]);
-        if (npairs[c]) max_ns = std::max<int64_t>(max_ns, ns);
-      }
-      if (wg <= cus || base <= 1.0 || tuning().bww_nsplit) break;
-      base *= 0.99;
-    }
-    p.class_wgs = wg;
-    max_ns = std::max<int64_t>(max_ns, nsplit);   // the uniform plan stays usable (generic kernel when W % 4 != 0)
-  }
-  p.slab_bytes = (size_t)round_up(max_ns * Cout * Cin * 27 * 4, 256);
-  return p;
-}
-
-}  // namespace m355
-
-using namespace m355;
-
-// ---------------------------------------------------------------------- ABI
-extern "C" size_t m355_conv3d_fwd_workspace(const m355_conv3d_desc* d) {
-  if (!d || !is_k3s1p1(d)) return 0;
-  if (small_cout_fwd(d)) return small_cout_ws(d);
-  const FwdPlan p = plan_mfma(d->N, d->Cin, d->Cout, d->D, d->H, d->W, d->compute);
-  return p.wp_bytes + p.slab_bytes +
-         (is16(d->compute) ? act16_staging_bytes(d->N, d->Cin, d->D, d->H, d->W) : 0);
-}
-
-static int validate_conv(const m355_conv3d_desc* d, const char* who) {
-  M355_REQUIRE(d != nullptr, M355_EINVALID_ARG, "%s: null descriptor", who);
-  M355_REQUIRE(d->N > 0 && d->Cin > 0 && d->Cout > 0 && d->D > 0 && d->H > 0 && d->W > 0,
-               M355_EINVALID_ARG, "%s: non-positive dimension", who);
-  M355_REQUIRE(d->k >= 1 && d->k <= 7 && d->stride >= 1 && d->pad >= 0, M355_EINVALID_ARG,
-               "%s: bad k/stride/pad (%d/%d/%d)", who, d->k, d->stride, d->pad);
-  M355_REQUIRE(d->compute == M355_COMPUTE_F32 || d->compute == M355_COMPUTE_BF16 || d->compute == M355_COMPUTE_F16 ||
-                   d->compute == M355_COMPUTE_F32X3,
-               M355_EINVALID_ARG,
-               "%s: unknown compute mode %d", who, d->compute);
-  return M355_OK;
-}
-
-// Per (sample, output channel): how many (sum, sum of squares) partials the forward kernel writes
-// when statistics are fused (4 waves x spatial tiles); 0 = this descriptor has no fused statistics
-// (not 3x3x3 s1 p1, small-Cout kernel, bf16 operand mode, or a split-K plan).
-static int64_t conv_stats_slots(const m355_conv3d_desc* d) {
-  if (!is_k3s1p1(d) || small_cout_fwd(d)) return 0;
-  const FwdPlan p = plan_mfma(d->N, d->Cin, d->Cout, d->D, d->H, d->W, d->compute);
-  if (p.ksplit != 1)   // split-K: the fp32 reduction pass emits the partials (one slot per block of it); the 16-bit
-    return !is16(d->compute) && d->N <= 65535 && d->Cout <= 65535   // kernels only with a c8 output
-               ? splitk_c8_slots((int64_t)d->D * d->H * d->W) : 0;
-  return (int64_t)p.tz_tiles * p.ty_tiles * p.tx_tiles * p.nw;
-}
-extern "C" int64_t m355_conv3d_stats_slots(const m355_conv3d_desc* d) { return d ? conv_stats_slots(d) : 0; }
-// c8-output forward of the 16-bit modes: split-K plans emit the partials from their reduction pass
-static int64_t conv_stats_slots_c8(const m355_conv3d_desc* d) {
-  if (!is_k3s1p1(d) || !is16(d->compute)) return 0;
-  FwdPlan p = plan_mfma(d->N, d->Cin, d->Cout, d->D, d->H, d->W, d->compute);
-  if (p.ksplit != 1) return splitk_c8_slots((int64_t)d->D * d->H * d->W);
-  return (int64_t)p.tz_tiles * p.ty_tiles * p.tx_tiles * p.nw;
-}
-extern "C" int64_t m355_conv3d_stats_slots_c8(const m355_conv3d_desc* d) { return d ? conv_stats_slots_c8(d) : 0; }
-
-static void launch_pack_smallcout(const m355_conv3d_desc* d, const float* w, float* wpz, hipStream_t st) {
-  if (tuning().smallcout_valu && (int64_t)d->D * d->H * d->W < (1ll << 27)) {
-    hipLaunchKernelGGL(pack_w3_valu_kernel, dim3((unsigned)ceil_div(d->Cin * 27 * 4, 256)), dim3(256), 0, st, w, wpz,
-                       d->Cout, d->Cin);
-  } else {
-    const int kin_pad = (int)round_up(d->Cin, 2);
-    const int64_t total = (int64_t)kin_pad * TZ_K * 32;
-    hipLaunchKernelGGL(pack_w3_toeplitz_kernel, dim3((unsigned)std::min<int64_t>(ceil_div(total, 256), 2048)), dim3(256),
-                       0, st, w, wpz, d->Cout, d->Cin, kin_pad);
-  }
-}
-
-// softmax over the output channels in the epilogue: the fp32 packed-FMA kernel for Cout <= 4
-static bool fuses_softmax(const m355_conv3d_desc* d) {
-  if (!is_k3s1p1(d) || !tuning().fuse_softmax) return false;
-  if (is16(d->compute))   // 16-bit kernels (c8 input, m355_conv3d_fwd_h16): in-register epilogue, unsplit plans
-    return d->Cout <= 4 && plan_mfma(d->N, d->Cin, d->Cout, d->D, d->H, d->W, d->compute).ksplit == 1;
-  return small_cout_fwd(d) && tuning().smallcout_valu && (int64_t)d->D * d->H * d->W < (1ll << 27);
-}
-extern "C" int32_t m355_conv3d_fuses_softmax(const m355_conv3d_desc* d) { return d && fuses_softmax(d) ? 1 : 0; }
-
-static int conv3d_fwd_impl(const m355_conv3d_desc* d, const float* x, const float* w, const float* bias,
-                           const float* add, float* y, float* stat, void* workspace, size_t workspace_bytes,
-                           void* stream) {
-  if (int rc = validate_conv(d, "conv3d_fwd")) return rc;
-  M355_REQUIRE(!(d->flags & M355_CONV_SOFTMAX) || fuses_softmax(d), M355_EUNSUPPORTED,
-               "conv3d_fwd: M355_CONV_SOFTMAX needs m355_conv3d_fuses_softmax(desc) != 0");
-  M355_REQUIRE(!stat || conv_stats_slots(d) > 0, M355_EINVALID_ARG,
-               "conv3d_fwd_stats: this descriptor has no fused statistics (m355_conv3d_stats_slots() == 0)");
-  M355_REQUIRE(x && w && y, M355_EINVALID_ARG, "conv3d_fwd: null pointer");
-  hipStream_t st = (hipStream_t)stream;
-  const int OD = out_dim(d->D, d->k, d->stride, d->pad), OH = out_dim(d->H, d->k, d->stride, d->pad),
-            OW = out_dim(d->W, d->k, d->stride, d->pad);
-  M355_REQUIRE(OD > 0 && OH > 0 && OW > 0, M355_EINVALID_ARG, "conv3d_fwd: empty output");
-  const int64_t xbs = dense_or(d->x_batch_stride, (int64_t)d->Cin * d->D * d->H * d->W);
-  const int64_t ybs = dense_or(d->y_batch_stride, (int64_t)d->Cout * OD * OH * OW);
-  if (is_k3s1p1(d) && small_cout_fwd(d)) {
-    M355_REQUIRE(workspace && workspace_bytes >= small_cout_ws(d), M355_EWORKSPACE,
-                 "conv3d_fwd: workspace too small (%zu < %zu)", workspace_bytes, small_cout_ws(d));
-    M355_REQUIRE(((uintptr_t)workspace & 15) == 0, M355_EINVALID_ARG, "conv3d: workspace not 16B aligned");
-    const bool packed = (d->flags & M355_CONV_W_PACKED) != 0;
-    float* wpz = packed ? (float*)w : (float*)workspace;
-    if (tuning().smallcout_valu && (int64_t)d->D * d->H * d->W < (1ll << 27)) {
-      // packed-FMA kernel (see conv3_valu_smallcout_kernel); the workspace of the MFMA variant is larger
-      if (!packed) launch_pack_smallcout(d, w, wpz, st);
-      const int tyv = (int)ceil_div(d->H, VS_TY), txv = (int)ceil_div(d->W, VS_TX);
-      dim3 gv((unsigned)(ceil_div(d->D, VS_TZ) * tyv * txv), (unsigned)d->N);
-      hipLaunchKernelGGL(conv3_valu_smallcout_kernel, gv, dim3(256), 0, st, x, wpz, bias, add, y, d->Cin, d->Cout,
-                         d->D, d->H, d->W, tyv, txv, xbs, ybs, (d->flags & M355_CONV_SOFTMAX) ? 1 : 0);
-      return check_launch("conv3_valu_smallcout");
-    }
-    const int kin_pad = (int)round_up(d->Cin, 2);
-    if (!packed) launch_pack_smallcout(d, w, wpz, st);
-    const int tyt = (int)ceil_div(d->H, 8), txt = (int)ceil_div(d->W, 32);
-    dim3 grid((unsigned)(ceil_div(d->D, 8) * tyt * txt), (unsigned)d->N);
-    hipLaunchKernelGGL(conv3_mfma_fwd_smallcout_kernel, grid, dim3(256), 0, st, x, wpz, bias, add, y, d->Cin,
-                       d->Cout, d->D, d->H, d->W, tyt, txt, kin_pad / 2, xbs, ybs);
-    return check_launch("conv3_mfma_fwd_smallcout");
-  }
-  if (is_k3s1p1(d)) {
-    const bool packed = (d->flags & M355_CONV_W_PACKED) != 0;
-    return run_mfma_conv(x, packed ? nullptr : w, false, d->Cout, d->Cin, bias, add, y, d->N, d->Cin, d->Cout, d->D,
-                         d->H, d->W, xbs, ybs, workspace, workspace_bytes, st, d->compute, stat, nullptr, 0,
-                         packed ? w : nullptr, false, (d->flags & M355_CONV_SOFTMAX) != 0);
-  }
-  M355_REQUIRE(!(d->flags & M355_CONV_W_PACKED), M355_EINVALID_ARG, "conv3d_fwd: this descriptor has no packed weights");
-  const int64_t total = (int64_t)d->N * d->Cout * OD * OH * OW;
-  const int blocks = (int)std::min<int64_t>(ceil_div(total, 256), 65535);
-  hipLaunchKernelGGL(conv3d_direct_fwd_kernel, dim3(blocks), dim3(256), 0, st, x, w, bias, add, y,
-                     d->N, d->Cin, d->Cout, d->D, d->H, d->W, OD, OH, OW, d->k, d->stride, d->pad,
-                     xbs, ybs);
-  return check_launch("conv3d_direct_fwd");
-}
-
-extern "C" int m355_conv3d_fwd(const m355_conv3d_desc* d, const float* x, const float* w,
-                               const float* bias, const float* add, float* y, void* workspace,
-                               size_t workspace_bytes, void* stream) {
-  return conv3d_fwd_impl(d, x, w, bias, add, y, nullptr, workspace, workspace_bytes, stream);
-}
-
-extern "C" int m355_conv3d_fwd_stats(const m355_conv3d_desc* d, const float* x, const float* w,
-                                     const float* bias, const float* add, float* y, float* stat_partials,
-                                     void* workspace, size_t workspace_bytes, void* stream) {
-  M355_REQUIRE(stat_partials, M355_EINVALID_ARG, "conv3d_fwd_stats: null statistics buffer");
-  return conv3d_fwd_impl(d, x, w, bias, add, y, stat_partials, workspace, workspace_bytes, stream);
-}
-
-// ---- packed weights (M355_CONV_W_PACKED) ----
-extern "C" size_t m355_conv3d_packed_bytes(const m355_conv3d_desc* d, int32_t which) {
-  if (!d || !is_k3s1p1(d) || d->N <= 0 || d->Cin <= 0 || d->Cout <= 0) return 0;
-  if (which == 0 && small_cout_fwd(d)) return small_cout_ws(d);
-  const FwdPlan p = which == 0 ? plan_mfma(d->N, d->Cin, d->Cout, d->D, d->H, d->W, d->compute)
-                               : plan_mfma(d->N, d->Cout, d->Cin, d->D, d->H, d->W, d->compute);
-  return p.wp_bytes;
-}
-
-extern "C" int m355_conv3d_pack(const m355_conv3d_desc* d, int32_t which, const float* w, void* packed, void* stream) {
-  if (int rc = validate_conv(d, "conv3d_pack")) return rc;
-  M355_REQUIRE(w && packed && ((uintptr_t)packed & 15) == 0, M355_EINVALID_ARG, "conv3d_pack: null / unaligned pointer");
-  M355_REQUIRE(is_k3s1p1(d) && (which == 0 || which == 1), M355_EUNSUPPORTED,
-               "conv3d_pack: only the 3x3x3 / stride 1 / pad 1 kernels have packed weights");
-  hipStream_t st = (hipStream_t)stream;
-  if (which == 0 && small_cout_fwd(d)) {
-    launch_pack_smallcout(d, w, (float*)packed, st);
-    return check_launch("conv3d_pack");
-  }
-  const FwdPlan p = which == 0 ? plan_mfma(d->N, d->Cin, d->Cout, d->D, d->H, d->W, d->compute)
-                               : plan_mfma(d->N, d->Cout, d->Cin, d->D, d->H, d->W, d->compute);
-  if (p.x3)
-    launch_pack_w3_x3(p, w, packed, d->Cout, d->Cin, which == 1, st);
-  else if (!is16(d->compute))
-    launch_pack_w3(p, w, (float*)packed, d->Cout, d->Cin, which == 1, st);
-  else
-    launch_pack_w3_h16(p, d->compute, w, packed, d->Cout, d->Cin, which == 1, st);
-  return check_launch("conv3d_pack");
-}
-
-extern "C" int m355_conv3d_pack_batch(const m355_pack_item* items, int32_t n, void* stream) {
-  M355_REQUIRE(items || n == 0, M355_EINVALID_ARG, "conv3d_pack_batch: null items");
-  hipStream_t st = (hipStream_t)stream;
-  PackBatch b;
-  X3PackBatch b3;
-  int nb = 0, nb3 = 0;
-  for (int i = 0; i < n; ++i) {
-    const m355_pack_item& it = items[i];
-    const m355_conv3d_desc* d = &it.desc;
-    if (int rc = validate_conv(d, "conv3d_pack_batch")) return rc;
-    M355_REQUIRE(it.w && it.packed && ((uintptr_t)it.packed & 15) == 0, M355_EINVALID_ARG,
-                 "conv3d_pack_batch: item %d: null / unaligned pointer", i);
-    M355_REQUIRE(is_k3s1p1(d) && (it.which == 0 || it.which == 1), M355_EUNSUPPORTED,
-                 "conv3d_pack_batch: item %d: only the 3x3x3 / stride 1 / pad 1 kernels have packed weights", i);
-    if (it.which == 0 && small_cout_fwd(d)) {   // (the Cout <= 4 forward layouts: one per model, launched on its own)
-      launch_pack_smallcout(d, it.w, (float*)it.packed, st);
-      continue;
-    }
-    const FwdPlan p = it.which == 0 ? plan_mfma(d->N, d->Cin, d->Cout, d->D, d->H, d->W, d->compute)
-                                    : plan_mfma(d->N, d->Cout, d->Cin, d->D, d->H, d->W, d->compute);
-    if (p.x3) {   // split + fragment-ordered weights: a batch of their own
-      X3PackEntry& e = b3.e[nb3++];
-      e.w = it.w;
-      e.wq = it.packed;
-      e.Cout = d->Cout;
-      e.Cin = d->Cin;
-      e.nchunks = p.nchunks;
-      e.otiles = p.otiles;
-      e.tile16 = p.tile16;
-      e.transpose = it.which == 1;
-      if (nb3 == PACK_BATCH) {
-        launch_pack_x3_batch(b3, nb3, st);
-        nb3 = 0;
-      }
-      continue;
-    }
-    const int kind = !is16(d->compute) ? 0 : (d->compute == M355_COMPUTE_BF16 ? 1 : 2);
-    if (nb && (kind == 0) != (b.e[0].kind == 0)) {   // a launch holds fp32 entries or 16-bit entries, not both
-      launch_pack_batch(b, nb, st);
-      nb = 0;
-    }
-    PackEntry& e = b.e[nb++];
-    e.w = it.w;
-    e.wp = it.packed;
-    e.counter = (int*)((char*)it.packed + p.wp_bytes - 256);
-    e.Cout = d->Cout;
-    e.Cin = d->Cin;
-    e.kdim = !is16(d->compute) ? p.kin_pad : p.nchunks;
-    e.mout_pad = p.mout_pad;
-    e.transpose = it.which == 1;
-    e.kind = kind;
-    if (nb == PACK_BATCH) {
-      launch_pack_batch(b, nb, st);
-      nb = 0;
-    }
-  }
-  if (nb) launch_pack_batch(b, nb, st);
-  if (nb3) launch_pack_x3_batch(b3, nb3, st);
-  return check_launch("conv3d_pack_batch");
-}
-
-// ---- 16-bit operand modes with c8 tensors handed over by the caller (h16.hpp) ----
-extern "C" size_t m355_act16_bytes(int32_t N, int32_t C, int64_t S) {
-  if (N <= 0 || C <= 0 || S <= 0) return 0;
-  return (size_t)N * (size_t)c8_blocks(C) * (size_t)S * 16;
-}
-
-static int validate_act16(const char* who, const void* a, const void* b, int N, int C, int64_t S, int compute) {
-  M355_REQUIRE(a && b, M355_EINVALID_ARG, "%s: null pointer", who);
-  M355_REQUIRE(N > 0 && C > 0 && S > 0 && N <= 65535 && c8_blocks(C) <= 65535, M355_EINVALID_ARG, "%s: bad shape", who);
-  M355_REQUIRE(compute == M355_COMPUTE_BF16 || compute == M355_COMPUTE_F16, M355_EINVALID_ARG,
-               "%s: compute must be M355_COMPUTE_BF16 or M355_COMPUTE_F16", who);
-  return M355_OK;
-}
-
-extern "C" int m355_act16_pack(const float* x, void* x16, int32_t N, int32_t C, int64_t S, int64_t x_batch_stride,
-                               int64_t x16_batch_stride, int32_t compute, void* stream) {
-  if (int rc = validate_act16("act16_pack", x, x16, N, C, S, compute)) return rc;
-  M355_REQUIRE(((uintptr_t)x16 & 15) == 0 && x16_batch_stride % 8 == 0, M355_EINVALID_ARG, "act16_pack: c8 tensor not 16B aligned");
-  return launch_pack_act16(x, x16, N, C, S, dense_or(x_batch_stride, (int64_t)C * S),
-                           dense_or(x16_batch_stride, c8_blocks(C) * S * 8), compute, (hipStream_t)stream);
-}
-
-extern "C" int m355_act16_unpack(const void* x16, float* x, int32_t N, int32_t C, int64_t S, int64_t x16_batch_stride,
-                                 int64_t x_batch_stride, int32_t compute, void* stream) {
-  if (int rc = validate_act16("act16_unpack", x16, x, N, C, S, compute)) return rc;
-  M355_REQUIRE(((uintptr_t)x16 & 15) == 0 && x16_batch_stride % 8 == 0, M355_EINVALID_ARG, "act16_unpack: c8 tensor not 16B aligned");
-  return launch_unpack_act16(x16, x, N, C, S, dense_or(x16_batch_stride, c8_blocks(C) * S * 8),
-                             dense_or(x_batch_stride, (int64_t)C * S), compute, (hipStream_t)stream);
-}
-
-extern "C" size_t m355_conv3d_h16_workspace(const m355_conv3d_desc* d, int32_t which) {
-  if (!d || !is_k3s1p1(d) || !is16(d->compute)) return 0;
-  const FwdPlan p = which == 0 ? plan_mfma(d->N, d->Cin, d->Cout, d->D, d->H, d->W, d->compute)
-                               : plan_mfma(d->N, d->Cout, d->Cin, d->D, d->H, d->W, d->compute);
-  return p.wp_bytes + p.slab_bytes;
-}
-
-static int validate_h16(const m355_conv3d_desc* d, const char* who) {
-  if (int rc = validate_conv(d, who)) return rc;
-  M355_REQUIRE(is_k3s1p1(d) && is16(d->compute), M355_EUNSUPPORTED,
-               "%s: c8 input is only defined for the 3x3x3 / stride 1 / pad 1 kernels in a 16-bit compute mode", who);
-  return M355_OK;
-}
-
-extern "C" int m355_conv3d_fwd_h16(const m355_conv3d_desc* d, const void* x16, int64_t x16_batch_stride, const float* w,
-                                   const float* bias, const float* add, float* y, float* stat_partials, void* workspace,
-                                   size_t workspace_bytes, void* stream) {
-  if (int rc = validate_h16(d, "conv3d_fwd_h16")) return rc;
-  M355_REQUIRE(x16 && w && y && workspace, M355_EINVALID_ARG, "conv3d_fwd_h16: null pointer");
-  M355_REQUIRE(!stat_partials || conv_stats_slots(d) > 0, M355_EINVALID_ARG,
-               "conv3d_fwd_h16: this descriptor has no fused statistics (m355_conv3d_stats_slots() == 0)");
-  const bool softmax = (d->flags & M355_CONV_SOFTMAX) != 0;
-  M355_REQUIRE(!softmax || fuses_softmax(d), M355_EUNSUPPORTED,
-               "conv3d_fwd_h16: M355_CONV_SOFTMAX needs m355_conv3d_fuses_softmax(desc) != 0");
-  const int64_t S = (int64_t)d->D * d->H * d->W;
-  const bool packed = (d->flags & M355_CONV_W_PACKED) != 0;
-  return run_mfma_conv(nullptr, packed ? nullptr : w, false, d->Cout, d->Cin, bias, add, y, d->N, d->Cin, d->Cout, d->D,
-                       d->H, d->W, 0, dense_or(d->y_batch_stride, (int64_t)d->Cout * S), workspace, workspace_bytes,
-                       (hipStream_t)stream, d->compute, stat_partials, x16,
-                       dense_or(x16_batch_stride, c8_blocks(d->Cin) * S * 8), packed ? w : nullptr, false, softmax);
-}
-
-extern "C" int m355_conv3d_fwd_h16_c8(const m355_conv3d_desc* d, const void* x16, int64_t x16_batch_stride,
-                                      const float* w, const float* bias, void* y16, int64_t y16_batch_stride,
-                                      float* stat_partials, void* workspace, size_t workspace_bytes, void* stream) {
-  if (int rc = validate_h16(d, "conv3d_fwd_h16_c8")) return rc;
-  M355_REQUIRE(x16 && w && y16 && workspace, M355_EINVALID_ARG, "conv3d_fwd_h16_c8: null pointer");
-  M355_REQUIRE(!stat_partials || conv_stats_slots_c8(d) > 0, M355_EINVALID_ARG,
-               "conv3d_fwd_h16_c8: this descriptor has no fused statistics (m355_conv3d_stats_slots_c8() == 0)");
-  const int64_t S = (int64_t)d->D * d->H * d->W;
-  const bool packed = (d->flags & M355_CONV_W_PACKED) != 0;
-  return run_mfma_conv(nullptr, packed ? nullptr : w, false, d->Cout, d->Cin, bias, nullptr, (float*)y16, d->N, d->Cin,
-                       d->Cout, d->D, d->H, d->W, 0, dense_or(y16_batch_stride, c8_blocks(d->Cout) * S * 8), workspace,
-                       workspace_bytes, (hipStream_t)stream, d->compute, stat_partials, x16,
-                       dense_or(x16_batch_stride, c8_blocks(d->Cin) * S * 8), packed ? w : nullptr, true);
-}
-
-extern "C" int m355_conv3d_bwd_data_h16(const m355_conv3d_desc* d, const void* dy16, int64_t dy16_batch_stride,
-                                        const float* w, float* dx, void* workspace, size_t workspace_bytes,
-                                        void* stream) {
-  if (int rc = validate_h16(d, "conv3d_bwd_data_h16")) return rc;
-  M355_REQUIRE(dy16 && w && dx && workspace, M355_EINVALID_ARG, "conv3d_bwd_data_h16: null pointer");
-  const int64_t S = (int64_t)d->D * d->H * d->W;
-  const bool packed = (d->flags & M355_CONV_W_PACKED) != 0;
-  return run_mfma_conv(nullptr, packed ? nullptr : w, true, d->Cout, d->Cin, nullptr, nullptr, dx, d->N, d->Cout, d->Cin,
-                       d->D, d->H, d->W, 0, dense_or(d->x_batch_stride, (int64_t)d->Cin * S), workspace, workspace_bytes,
-                       (hipStream_t)stream, d->compute, nullptr, dy16,
-                       dense_or(dy16_batch_stride, c8_blocks(d->Cout) * S * 8), packed ? w : nullptr);
-}
-
-// ---- weight gradient with both operands in c8 (the 16-bit training flow keeps the packed conv input of the forward
-// pass and packs dy once for the data and the weight gradient) ----
-static size_t dbias_ws_bytes(int Cout, int64_t S);
-int launch_dbias(const float* dy, float* dbias, int N, int Cout, int64_t S, int64_t ybs, void* ws, hipStream_t st);
-static int bww_c8_nsplit(const m355_conv3d_desc* d) {
-  const int64_t ntiles = (int64_t)d->N * ceil_div(d->D, 2) * ceil_div(d->H, 4) * ceil_div(d->W, 32);
-  const int64_t pairs = ceil_div(d->Cin, 32) * ceil_div(d->Cout, 32);
-  const int64_t slots = 2 * (int64_t)num_cus();
-  if (const int force = tuning().bww_nsplit) return (int)std::min<int64_t>(force, ntiles);
-  // time ~ residencies x (tiles per split x tile time + ~4 us pipeline fill and slab write) + the slab traffic (written
-  // by the kernel, read by the reduction).  Tile time ~1.8 us with two workgroups sharing a CU, ~1.1 us alone: for few
-  // pairs one workgroup per CU with half the slabs wins (32->32 @128^3: 256 splits 170 us, 512 splits 184 us), for many
-  // tiles per pair two per CU do (tools/plan_sweep_bww_c8.py).
-  const double slab_us = 2.0 * (double)d->Cout * d->Cin * 27 * 4 / 4.0e6;
-  double best = 1e30;
-  int64_t best_ns = 1;
-  for (int h = pairs <= 2 ? 1 : 2; h <= 8; ++h) {   // h half-residencies: 256, 512, 768, ... workgroups (one per CU
-                                                    // only pays for one or two pairs: more pairs share tiles in L2)
-    const int64_t ns = std::max<int64_t>(1, std::min<int64_t>(ntiles, slots * h / (2 * pairs)));
-    const int64_t wgs = pairs * ns;
-    const double rounds = (double)ceil_div(wgs, slots);
-    const double tile_us = wgs * 2 <= slots ? 1.1 : (wgs >= slots ? 1.8 : 1.1 + 0.7 * (double)(wgs * 2 - slots) / (double)slots);
-    const double cost = rounds * ((double)ceil_div(ntiles, ns) * tile_us + 4.0) + (double)ns * slab_us;
-    if (cost < best * 0.97) {
-      best = cost;
-      best_ns = ns;
-    }
-  }
-  return (int)best_ns;
-}
-
-static bool bww_c8_ok(const m355_conv3d_desc* d) {
-  return is_k3s1p1(d) && is16(d->compute) && (int64_t)d->D * d->H * d->W * 64 < (1ll << 31);
-}
-
-extern "C" size_t m355_conv3d_bwd_weight_h16_workspace(const m355_conv3d_desc* d) {
-  if (!d || !bww_c8_ok(d)) return 0;
-  return (size_t)round_up((int64_t)bww_c8_nsplit(d) * d->Cout * d->Cin * 27 * 4, 256) +
-         dbias_ws_bytes(d->Cout, (int64_t)d->D * d->H * d->W);
-}
-
-extern "C" int m355_conv3d_bwd_weight_h16(const m355_conv3d_desc* d, const void* x16, int64_t x16_batch_stride,
-                                          const void* dy16, int64_t dy16_batch_stride, const float* dy, float* dw,
-                                          float* dbias, void* workspace, size_t workspace_bytes, void* stream) {
-  if (int rc = validate_h16(d, "conv3d_bwd_weight_h16")) return rc;
-  M355_REQUIRE(x16 && dy16 && dw && workspace, M355_EINVALID_ARG, "conv3d_bwd_weight_h16: null pointer");
-  M355_REQUIRE(bww_c8_ok(d), M355_EUNSUPPORTED, "conv3d_bwd_weight_h16: volume too large for the c8 kernel (>= 2^25 voxels)");
-  M355_REQUIRE(!dbias || dy, M355_EINVALID_ARG, "conv3d_bwd_weight_h16: the bias gradient needs the fp32 dy");
-  M355_REQUIRE(workspace_bytes >= m355_conv3d_bwd_weight_h16_workspace(d), M355_EWORKSPACE,
-               "conv3d_bwd_weight_h16: workspace too small (%zu < %zu)", workspace_bytes,
-               m355_conv3d_bwd_weight_h16_workspace(d));
-  const int64_t S = (int64_t)d->D * d->H * d->W;
-  const int64_t xbs = dense_or(x16_batch_stride, c8_blocks(d->Cin) * S * 8);
-  const int64_t ybs = dense_or(dy16_batch_stride, c8_blocks(d->Cout) * S * 8);
-  M355_REQUIRE((((uintptr_t)x16 | (uintptr_t)dy16) & 15) == 0 && xbs % 8 == 0 && ybs % 8 == 0, M355_EINVALID_ARG,
-               "conv3d_bwd_weight_h16: c8 tensor not 16B aligned");
-  hipStream_t st = (hipStream_t)stream;
-  const int nsplit = bww_c8_nsplit(d);
-  float* slab = (float*)workspace;
-  if (int rc = launch_bww_c8(d->compute, x16, dy16, slab, d->N, d->Cin, d->Cout, d->D, d->H, d->W, nsplit, xbs, ybs, st))
-    return rc;
-  BwwClasses kred{};
-  kred.of = (int)ceil_div(d->Cout, 32);
-  kred.cf = (int)ceil_div(d->Cin, 32);
-  for (int c = 0; c < 4; ++c) kred.ns[c] = nsplit;
-  launch_slab_reduce_t(slab, dw, d->Cin, d->Cout, kred.cf, kred, 1.f, st);
-  if (dbias) {
-    const size_t slab_b = (size_t)round_up((int64_t)nsplit * d->Cout * d->Cin * 27 * 4, 256);
-    launch_dbias(dy, dbias, d->N, d->Cout, S, dense_or(d->y_batch_stride, (int64_t)d->Cout * S), (char*)workspace + slab_b, st);
-  }
-  return check_launch("conv3d_bwd_weight_h16");
-}
-
-// ---- the c8-only training flow: data gradient written as c8, weight gradient with the bias gradient reduced from
-// the c8 dy and the loss scale of the fp16 mode removed in the fp32 epilogue ----
-extern "C" int m355_conv3d_bwd_data_h16_c8(const m355_conv3d_desc* d, const void* dy16, int64_t dy16_batch_stride,
-                                           const float* w, void* dx16, int64_t dx16_batch_stride, void* workspace,
-                                           size_t workspace_bytes, void* stream) {
-  if (int rc = validate_h16(d, "conv3d_bwd_data_h16_c8")) return rc;
-  M355_REQUIRE(dy16 && w && dx16 && workspace, M355_EINVALID_ARG, "conv3d_bwd_data_h16_c8: null pointer");
-  const int64_t S = (int64_t)d->D * d->H * d->W;
-  const bool packed = (d->flags & M355_CONV_W_PACKED) != 0;
-  return run_mfma_conv(nullptr, packed ? nullptr : w, true, d->Cout, d->Cin, nullptr, nullptr, (float*)dx16, d->N, d->Cout,
-                       d->Cin, d->D, d->H, d->W, 0, dense_or(dx16_batch_stride, c8_blocks(d->Cin) * S * 8), workspace,
-                       workspace_bytes, (hipStream_t)stream, d->compute, nullptr, dy16,
-                       dense_or(dy16_batch_stride, c8_blocks(d->Cout) * S * 8), packed ? w : nullptr, true, false,
-                       d->compute == M355_COMPUTE_F16 ? overflow_flag() : nullptr);
-}
-
-extern "C" size_t m355_conv3d_bwd_weight_c8_workspace(const m355_conv3d_desc* d) {
-  if (!d || !bww_c8_ok(d)) return 0;
-  return (size_t)round_up((int64_t)bww_c8_nsplit(d) * d->Cout * d->Cin * 27 * 4, 256) +
-         dbias_c8_ws_bytes(d->N, d->Cout, (int64_t)d->D * d->H * d->W);
-}
-
-extern "C" int m355_conv3d_bwd_weight_c8(const m355_conv3d_desc* d, const void* x16, int64_t x16_batch_stride,
-                                         const void* dy16, int64_t dy16_batch_stride, float* dw, float* dbias,
-                                         float grad_unscale, void* workspace, size_t workspace_bytes, void* stream) {
-  if (int rc = validate_h16(d, "conv3d_bwd_weight_c8")) return rc;
-  M355_REQUIRE(x16 && dy16 && dw && workspace, M355_EINVALID_ARG, "conv3d_bwd_weight_c8: null pointer");
-  M355_REQUIRE(bww_c8_ok(d), M355_EUNSUPPORTED, "conv3d_bwd_weight_c8: volume too large for the c8 kernel (>= 2^25 voxels)");
-  M355_REQUIRE(workspace_bytes >= m355_conv3d_bwd_weight_c8_workspace(d), M355_EWORKSPACE,
-               "conv3d_bwd_weight_c8: workspace too small (%zu < %zu)", workspace_bytes, m355_conv3d_bwd_weight_c8_workspace(d));
-  const int64_t S = (int64_t)d->D * d->H * d->W;
-  const int64_t xbs = dense_or(x16_batch_stride, c8_blocks(d->Cin) * S * 8);
-  const int64_t ybs = dense_or(dy16_batch_stride, c8_blocks(d->Cout) * S * 8);
-  M355_REQUIRE((((uintptr_t)x16 | (uintptr_t)dy16) & 15) == 0 && xbs % 8 == 0 && ybs % 8 == 0, M355_EINVALID_ARG,
-               "conv3d_bwd_weight_c8: c8 tensor not 16B aligned");
-  hipStream_t st = (hipStream_t)stream;
-  const int nsplit = bww_c8_nsplit(d);
-  float* slab = (float*)workspace;
-  // edge layers (first conv: Cin <= 4; output conv: Cout <= 4): tap and narrow channel share the MFMA column
-  const bool edge = (d->Cin <= 4 || d->Cout <= 4) && !tuning().no_small;
-  if (int rc = edge ? launch_bww_c8_small(d->compute, x16, dy16, slab, d->N, d->Cin, d->Cout, d->D, d->H, d->W, nsplit, xbs, ybs, st)
-                    : launch_bww_c8(d->compute, x16, dy16, slab, d->N, d->Cin, d->Cout, d->D, d->H, d->W, nsplit, xbs, ybs, st))
-    return rc;
-  BwwClasses kred{};
-  kred.of = (int)ceil_div(d->Cout, 32);
-  kred.cf = (int)ceil_div(d->Cin, 32);
-  for (int c = 0; c < 4; ++c) kred.ns[c] = nsplit;
-  launch_slab_reduce_t(slab, dw, d->Cin, d->Cout, kred.cf, kred, grad_unscale, st);
-  if (dbias) {
-    const size_t slab_b = (size_t)round_up((int64_t)nsplit * d->Cout * d->Cin * 27 * 4, 256);
-    if (int rc = launch_dbias_c8(dy16, ybs, dbias, d->N, d->Cout, S, d->compute, grad_unscale, (char*)workspace + slab_b, st))
-      return rc;
-  }
-  return check_launch("conv3d_bwd_weight_c8");
-}
-
-static bool bww_plain_h16(const m355_conv3d_desc* d);
-static bool bww_x3(const m355_conv3d_desc* d);
-extern "C" int m355_conv3d_plan(const m355_conv3d_desc* d, int32_t which, int32_t* out4) {
-  M355_REQUIRE(d && out4, M355_EINVALID_ARG, "conv3d_plan: null pointer");
-  out4[0] = out4[1] = out4[2] = out4[3] = 0;
-  if (!is_k3s1p1(d)) return M355_OK;
-  if (which == 2) {   // weight gradient of the plain entry point: 8 = conv3_bww_x3_kernel, 9 = conv3_mfma_bww2(c)_kernel,
-                      // 10 = conv3_mfma_bww_small_kernel, 11 = the c8 kernel behind an operand pack (16-bit modes)
-    if (bww_x3(d)) {
-      const BwwX3Plan p = plan_bww_x3(d->N, d->Cin, d->Cout, d->D, d->H, d->W);
-      out4[0] = 8; out4[2] = p.tx; out4[3] = p.nsplit;
-    } else {
-      const BwwPlan p = plan_bww(d->N, d->Cin, d->Cout, d->D, d->H, d->W);
-      out4[0] = bww_plain_h16(d) ? 11 : (small_bww(d) ? 10 : 9); out4[2] = p.gx; out4[3] = p.nsplit;
-    }
-    return M355_OK;
-  }
-  if (which == 0 && small_cout_fwd(d)) { out4[0] = 2; return M355_OK; }  // z-Toeplitz small-Cout kernel
-  const FwdPlan p = which == 0 ? plan_mfma(d->N, d->Cin, d->Cout, d->D, d->H, d->W, d->compute)
-                               : plan_mfma(d->N, d->Cout, d->Cin, d->D, d->H, d->W, d->compute);
-  out4[0] = is16(d->compute) ? (p.oneshot ? 6 : (p.nw == 8 ? 5 : 4)) : (p.x3 ? 7 : (p.persistent ? 3 : 1)); out4[1] = p.ntw; out4[2] = p.gx; out4[3] = p.ksplit;
-  return M355_OK;
-}
-
-extern "C" size_t m355_conv3d_bwd_data_workspace(const m355_conv3d_desc* d) {
-  if (!d || !is_k3s1p1(d)) return 0;
-  const FwdPlan p = plan_mfma(d->N, d->Cout, d->Cin, d->D, d->H, d->W, d->compute);
-  return p.wp_bytes + p.slab_bytes +
-         (is16(d->compute) ? act16_staging_bytes(d->N, d->Cout, d->D, d->H, d->W) : 0);
-}
-
-extern "C" int m355_conv3d_bwd_data(const m355_conv3d_desc* d, const float* dy, const float* w,
-                                    float* dx, void* workspace, size_t workspace_bytes,
-                                    void* stream) {
-  if (int rc = validate_conv(d, "conv3d_bwd_data")) return rc;
-  M355_REQUIRE(dy && w && dx, M355_EINVALID_ARG, "conv3d_bwd_data: null pointer");
-  hipStream_t st = (hipStream_t)stream;
-  const int OD = out_dim(d->D, d->k, d->stride, d->pad), OH = out_dim(d->H, d->k, d->stride, d->pad),
-            OW = out_dim(d->W, d->k, d->stride, d->pad);
-  const int64_t xbs = dense_or(d->x_batch_stride, (int64_t)d->Cin * d->D * d->H * d->W);
-  const int64_t ybs = dense_or(d->y_batch_stride, (int64_t)d->Cout * OD * OH * OW);
-  if (is_k3s1p1(d)) {
-    // dx = conv(dy, flipped/transposed w): K-channels = Cout, M-channels = Cin
-    const bool packed = (d->flags & M355_CONV_W_PACKED) != 0;
-    return run_mfma_conv(dy, packed ? nullptr : w, true, d->Cout, d->Cin, nullptr, nullptr, dx, d->N, d->Cout, d->Cin,
-                         d->D, d->H, d->W, ybs, xbs, workspace, workspace_bytes, st, d->compute, nullptr, nullptr, 0,
-                         packed ? w : nullptr);
-  }
-  M355_REQUIRE(!(d->flags & M355_CONV_W_PACKED), M355_EINVALID_ARG, "conv3d_bwd_data: this descriptor has no packed weights");
-  const int64_t total = (int64_t)d->N * d->Cin * d->D * d->H * d->W;
-  const int blocks = (int)std::min<int64_t>(ceil_div(total, 256), 65535);
-  hipLaunchKernelGGL(conv3d_direct_bwd_data_kernel, dim3(blocks), dim3(256), 0, st, dy, w, dx,
-                     d->N, d->Cin, d->Cout, d->D, d->H, d->W, OD, OH, OW, d->k, d->stride, d->pad,
-                     xbs, ybs);
-  return check_launch("conv3d_direct_bwd_data");
-}
-
-static size_t dbias_ws_bytes(int Cout, int64_t S) {
-  return (size_t)round_up((int64_t)Cout * ceil_div(S, DBIAS_CHUNK) * 8, 256);
-}
-
-// dbias through the shared two-stage reduction; `ws` must hold dbias_ws_bytes()
-int launch_dbias(const float* dy, float* dbias, int N, int Cout, int64_t S, int64_t ybs, void* ws,
-                 hipStream_t st) {
-  const int nblk = (int)ceil_div(S, DBIAS_CHUNK);
-  if (S % 4 == 0 && ybs % 4 == 0 && ((uintptr_t)dy & 15) == 0)
-    hipLaunchKernelGGL(dbias_partial_kernel<true>, dim3((unsigned)nblk, (unsigned)Cout), dim3(256), 0, st, dy,
-                       (double*)ws, N, S, ybs, nblk);
-  else
-    hipLaunchKernelGGL(dbias_partial_kernel<false>, dim3((unsigned)nblk, (unsigned)Cout), dim3(256), 0, st, dy,
-                       (double*)ws, N, S, ybs, nblk);
-  hipLaunchKernelGGL(dbias_finalize_kernel, dim3((unsigned)ceil_div(Cout, 64)), dim3(64), 0, st,
-                     (const double*)ws, dbias, Cout, nblk);
-  return M355_OK;
-}
-
-// fp32 NCDHW operands in a 16-bit compute mode (the plain entry point; the model path hands over c8 tensors through
-// m355_conv3d_bwd_weight_h16 / _c8): both operands are rounded into c8 copies and the c8 kernel runs (round 1 had a kernel
-// of its own for this case, conv3_mfma_bww_h16_kernel, three dx-shifted LDS copies at a third of the c8 kernel's rate)
-static bool bww_c8_ok(const m355_conv3d_desc* d);
-static bool bww_plain_h16(const m355_conv3d_desc* d) {
-  return is16(d->compute) && is_k3s1p1(d) && !small_bww(d) && bww_c8_ok(d) && d->N <= 65535;
-}
-
-// M355_COMPUTE_F32X3: the weight gradient on the split kernels too (conv3_bww_x3_kernel; M355_F32X3=2 forces every
-// fp32 layer there, M355_F32X3_BWW=0 keeps the weight gradient on the fp32 MFMA kernels)
-static bool bww_x3(const m355_conv3d_desc* d) {
-  const bool mode = d->compute == M355_COMPUTE_F32X3 || (d->compute == M355_COMPUTE_F32 && tuning().f32x3 == 2);
-  return mode && tuning().f32x3 && tuning().f32x3_bww && is_k3s1p1(d) && d->Cin > 4 && d->Cout > 4 && d->D >= 2 &&
-         (int64_t)d->D * d->H * d->W < (1ll << 24);
-}
-
-extern "C" size_t m355_conv3d_bwd_weight_workspace(const m355_conv3d_desc* d) {
-  if (!d) return 0;
-  const int OD = out_dim(d->D, d->k, d->stride, d->pad), OH = out_dim(d->H, d->k, d->stride, d->pad),
-            OW = out_dim(d->W, d->k, d->stride, d->pad);
-  const size_t db = dbias_ws_bytes(d->Cout, (int64_t)OD * OH * OW);
-  if (!is_k3s1p1(d)) return db;
-  if (bww_x3(d)) return plan_bww_x3(d->N, d->Cin, d->Cout, d->D, d->H, d->W).slab_bytes + db;
-  const size_t f32 = plan_bww(d->N, d->Cin, d->Cout, d->D, d->H, d->W).slab_bytes + db;
-  if (bww_plain_h16(d)) {   // 16-bit operand mode: both operands are rounded into c8 copies behind the c8 kernel's own workspace
-    const int64_t S = (int64_t)d->D * d->H * d->W;
-    return std::max(f32, m355_conv3d_bwd_weight_h16_workspace(d) + (size_t)round_up(d->N * c8_blocks(d->Cin) * S * 16, 256) +
-                             (size_t)round_up(d->N * c8_blocks(d->Cout) * S * 16, 256));
-  }
-  return f32;
-}
-
-extern "C" int m355_conv3d_bwd_weight(const m355_conv3d_desc* d, const float* x, const float* dy,
-                                      float* dw, float* dbias, void* workspace,
-                                      size_t workspace_bytes, void* stream) {
-  if (int rc = validate_conv(d, "conv3d_bwd_weight")) return rc;
-  M355_REQUIRE(x && dy && dw, M355_EINVALID_ARG, "conv3d_bwd_weight: null pointer");
-  hipStream_t st = (hipStream_t)stream;
-  const int OD = out_dim(d->D, d->k, d->stride, d->pad), OH = out_dim(d->H, d->k, d->stride, d->pad),
-            OW = out_dim(d->W, d->k, d->stride, d->pad);
-  const int64_t xbs = dense_or(d->x_batch_stride, (int64_t)d->Cin * d->D * d->H * d->W);
-  const int64_t ybs = dense_or(d->y_batch_stride, (int64_t)d->Cout * OD * OH * OW);
-  size_t slab_used = 0;   // the bias gradient's scratch follows the slabs
-  if (bww_x3(d)) {
-    const BwwX3Plan p = plan_bww_x3(d->N, d->Cin, d->Cout, d->D, d->H, d->W);
-    M355_REQUIRE(workspace && workspace_bytes >= p.slab_bytes, M355_EWORKSPACE,
-                 "conv3d_bwd_weight: workspace too small (%zu < %zu)", workspace_bytes, p.slab_bytes);
-    M355_REQUIRE((((uintptr_t)x | (uintptr_t)dy) & 3) == 0, M355_EINVALID_ARG, "conv3d_bwd_weight: misaligned tensor");
-    float* slab = (float*)workspace;
-    if (int rc = launch_bww_x3(p, x, dy, slab, d->N, d->Cin, d->Cout, d->D, d->H, d->W, xbs, ybs, st)) return rc;
-    launch_slab_reduce_t(slab, dw, d->Cin, d->Cout, p.ctiles, p.k, 1.f, st);   // p.k.ns: splits of each pair class
-    slab_used = p.slab_bytes;
-  } else if (is_k3s1p1(d)) {
-    const BwwPlan p = plan_bww(d->N, d->Cin, d->Cout, d->D, d->H, d->W);
-    slab_used = p.slab_bytes;
-    M355_REQUIRE(workspace_bytes >= p.slab_bytes, M355_EWORKSPACE,
-                 "conv3d_bwd_weight: workspace too small (%zu < %zu)", workspace_bytes,
-                 p.slab_bytes);
-    float* slab = (float*)workspace;
-    M355_REQUIRE((int64_t)d->Cin * d->D * d->H * d->W < (1ll << 31) &&
-                     (int64_t)d->Cout * d->D * d->H * d->W < (1ll << 31),
-                 M355_EUNSUPPORTED, "conv3d_bwd_weight: tensor exceeds 2^31 elements per sample");
-    if (bww_plain_h16(d)) {
-      const int64_t S = (int64_t)d->D * d->H * d->W;
-      const size_t hws = m355_conv3d_bwd_weight_h16_workspace(d);
-      const size_t xb = (size_t)round_up(d->N * c8_blocks(d->Cin) * S * 16, 256), yb = (size_t)round_up(d->N * c8_blocks(d->Cout) * S * 16, 256);
-      M355_REQUIRE(workspace && workspace_bytes >= hws + xb + yb, M355_EWORKSPACE,
-                   "conv3d_bwd_weight: workspace too small (%zu < %zu)", workspace_bytes, hws + xb + yb);
-      char* x16 = (char*)workspace + hws;
-      char* dy16 = x16 + xb;
-      if (int rc = launch_pack_act16(x, x16, d->N, d->Cin, S, xbs, c8_blocks(d->Cin) * S * 8, d->compute, st)) return rc;
-      if (int rc = launch_pack_act16(dy, dy16, d->N, d->Cout, S, ybs, c8_blocks(d->Cout) * S * 8, d->compute, st)) return rc;
-      m355_conv3d_desc dd = *d;
-      dd.y_batch_stride = ybs;
-      return m355_conv3d_bwd_weight_h16(&dd, x16, 0, dy16, 0, dbias ? dy : nullptr, dw, dbias, workspace, hws, stream);
-    } else if (small_bww(d)) {
+    case BwwKind::X3:
+      M355_REQUIRE((((uintptr_t)x | (uintptr_t)dy) & 3) == 0, M355_EINVALID_ARG, "conv3d_bwd_weight: misaligned tensor");
+      if (int rc = launch_bww_x3(r.x3, x, dy, slab, d->N, d->Cin, d->Cout, d->D, d->H, d->W, xbs, ybs, st)) return rc;
+      launch_slab_reduce_t(slab, dw, d->Cin, d->Cout, r.x3.ctiles, r.x3.k, 1.f, st);   // k.ns: splits of each pair class
+      return M355_OK;
+    case BwwKind::Small: {
       // narrow side (<= 4 channels) shares the lane index with the taps
       const int swap = d->Cin <= 4 ? 0 : 1;
       const float* P = swap ? x : dy;
@@ -2939,10 +2052,12 @@ extern "C" int m355_conv3d_bwd_weight(const m355_conv3d_desc* d, const float* x,
       const int64_t total = (int64_t)d->Cout * d->Cin * 27;
       const int blocks = (int)std::min<int64_t>(ceil_div(total, 256), 2048);
       hipLaunchKernelGGL(slab_reduce_kernel, dim3(blocks), dim3(256), 0, st, slab, dw, total, p.nsplit);
-    } else {
-    dim3 grid((unsigned)p.ctiles, (unsigned)p.otiles, (unsigned)p.nsplit);
-    // float4 interior rows need 16-byte aligned rows; per-sample extents must fit int32 offsets
-    const bool vec = (d->W % 4 == 0) && (xbs % 4 == 0) && (((uintptr_t)x) & 15) == 0;
+      return M355_OK;
+    }
+    case BwwKind::Mfma2: {
+      dim3 grid((unsigned)p.ctiles, (unsigned)p.otiles, (unsigned)p.nsplit);
+      const BwwVariant v = bww_variant(d, x, dy, xbs);
+      const bool vec = v.vec, gen2 = v.gen2;
 #define M355_BWW_LAUNCH(GXV)                                                                      \
   {                                                                                               \
     if (vec)                                                                                      \
@@ -2954,14 +2069,6 @@ extern "C" int m355_conv3d_bwd_weight(const m355_conv3d_desc* d, const float* x,
                          slab, d->N, d->Cin, d->Cout, d->D, d->H, d->W, p.tz_tiles, p.ty_tiles, \
                          p.tx_tiles, p.nsplit, xbs, ybs);                                        \
   }
-    M355_REQUIRE((int64_t)d->Cin * d->D * d->H * d->W < (1ll << 31) &&
-                     (int64_t)d->Cout * d->D * d->H * d->W < (1ll << 31),
-                 M355_EUNSUPPORTED, "conv3d_bwd_weight: tensor exceeds 2^31 elements per sample");
-    // second-generation kernel: float4 rows, and a sample must fit the 32-bit byte offsets of a
-    // buffer descriptor (the hardware zero-fills what lies past it)
-    const int64_t spatial = (int64_t)d->D * d->H * d->W;
-    const bool gen2 = vec && ((uintptr_t)dy & 3) == 0 && (int64_t)d->Cin * spatial < (1ll << 29) &&
-                      (int64_t)d->Cout * spatial < (1ll << 29) && tuning().bww_gen == 2;
 #define M355_BWW2_LAUNCH(GXV)                                                                     \
   hipLaunchKernelGGL((conv3_mfma_bww2_kernel<GXV>), dim3((unsigned)(p.ctiles * p.otiles * p.nsplit)),  \
                      dim3(256), 0, st, x, dy, slab, d->N, d->Cin, d->Cout, d->D, d->H, d->W, p.tz_tiles, \
@@ -2969,40 +2076,45 @@ extern "C" int m355_conv3d_bwd_weight(const m355_conv3d_desc* d, const float* x,
 #define M355_BWW2C_LAUNCH(GXV)                                                                    \
   hipLaunchKernelGGL((conv3_mfma_bww2c_kernel<GXV>), dim3((unsigned)p.class_wgs), dim3(256), 0, st, x, dy, slab, d->N, \
                      d->Cin, d->Cout, d->D, d->H, d->W, p.tz_tiles, p.ty_tiles, p.tx_tiles, p.k, xbs, ybs);
-    BwwClasses kred = p.k;   // what the reduction sums: the class splits, or the uniform count
-    if (gen2 && p.classes) {
-      if (p.gx == 32) { M355_BWW2C_LAUNCH(32) } else if (p.gx == 16) { M355_BWW2C_LAUNCH(16) } else { M355_BWW2C_LAUNCH(8) }
-    } else if (gen2) {
-      for (int c = 0; c < 4; ++c) kred.ns[c] = p.nsplit;
-      if (p.gx == 32) { M355_BWW2_LAUNCH(32) } else if (p.gx == 16) { M355_BWW2_LAUNCH(16) } else { M355_BWW2_LAUNCH(8) }
-    } else if (p.gx == 32)
-      M355_BWW_LAUNCH(32)
-    else if (p.gx == 16)
-      M355_BWW_LAUNCH(16)
-    else
-      M355_BWW_LAUNCH(8)
-    if (gen2) {
-      launch_slab_reduce_t(slab, dw, d->Cin, d->Cout, p.ctiles, kred, 1.f, st);
-    } else {
-      const int64_t total = (int64_t)d->Cout * d->Cin * 27;
-      const int blocks = (int)std::min<int64_t>(ceil_div(total, 64), 4096);
-      hipLaunchKernelGGL(slab_reduce_kernel, dim3(blocks), dim3(64), 0, st, slab, dw, total, p.nsplit);
+      BwwClasses kred = p.k;   // what the reduction sums: the class splits, or the uniform count
+      if (gen2 && p.classes) {
+        if (p.gx == 32) { M355_BWW2C_LAUNCH(32) } else if (p.gx == 16) { M355_BWW2C_LAUNCH(16) } else { M355_BWW2C_LAUNCH(8) }
+      } else if (gen2) {
+        for (int c = 0; c < 4; ++c) kred.ns[c] = p.nsplit;
+        if (p.gx == 32) { M355_BWW2_LAUNCH(32) } else if (p.gx == 16) { M355_BWW2_LAUNCH(16) } else { M355_BWW2_LAUNCH(8) }
+      } else if (p.gx == 32)
+        M355_BWW_LAUNCH(32)
+      else if (p.gx == 16)
+        M355_BWW_LAUNCH(16)
+      else
+        M355_BWW_LAUNCH(8)
+      if (gen2) {
+        launch_slab_reduce_t(slab, dw, d->Cin, d->Cout, p.ctiles, kred, 1.f, st);
+      } else {
+        const int64_t total = (int64_t)d->Cout * d->Cin * 27;
+        const int blocks = (int)std::min<int64_t>(ceil_div(total, 64), 4096);
+        hipLaunchKernelGGL(slab_reduce_kernel, dim3(blocks), dim3(64), 0, st, slab, dw, total, p.nsplit);
+      }
+      return M355_OK;
     }
-    }
-  } else {
-    const int k3 = d->k * d->k * d->k;
-    const int64_t nblk = (int64_t)d->Cout * d->Cin * k3;
-    M355_REQUIRE(nblk < (1ll << 31), M355_EUNSUPPORTED, "conv3d_bwd_weight: grid too large");
-    hipLaunchKernelGGL(conv3d_direct_bwd_weight_kernel, dim3((unsigned)nblk), dim3(256), 0, st, x,
-                       dy, dw, d->N, d->Cin, d->Cout, d->D, d->H, d->W, OD, OH, OW, d->k,
-                       d->stride, d->pad, xbs, ybs);
+    default:
+      set_error("conv3d_bwd_weight: no fp32 kernel for this route");
+      return M355_EUNSUPPORTED;
   }
-  if (dbias) {
-    const int64_t OS = (int64_t)OD * OH * OW;
-    const size_t slab_b = slab_used;
-    M355_REQUIRE(workspace && workspace_bytes >= slab_b + dbias_ws_bytes(d->Cout, OS), M355_EWORKSPACE,
-                 "conv3d_bwd_weight: workspace too small for the bias gradient");
-    launch_dbias(dy, dbias, d->N, d->Cout, OS, ybs, (char*)workspace + slab_b, st);
-  }
-  return check_launch("conv3d_bwd_weight");
+}
+
+}  // namespace m355
+
+// (global namespace: convt.hip shares it)  dbias through the shared two-stage reduction; `ws` holds Cout * ceil(S / DBIAS_CHUNK) doubles
+int launch_dbias(const float* dy, float* dbias, int N, int Cout, int64_t S, int64_t ybs, void* ws, hipStream_t st) {
+  const int nblk = (int)m355::ceil_div(S, m355::DBIAS_CHUNK);
+  if (S % 4 == 0 && ybs % 4 == 0 && ((uintptr_t)dy & 15) == 0)
+    hipLaunchKernelGGL(m355::dbias_partial_kernel<true>, dim3((unsigned)nblk, (unsigned)Cout), dim3(256), 0, st, dy,
+                       (double*)ws, N, S, ybs, nblk);
+  else
+    hipLaunchKernelGGL(m355::dbias_partial_kernel<false>, dim3((unsigned)nblk, (unsigned)Cout), dim3(256), 0, st, dy,
+                       (double*)ws, N, S, ybs, nblk);
+  hipLaunchKernelGGL(m355::dbias_finalize_kernel, dim3((unsigned)m355::ceil_div(Cout, 64)), dim3(64), 0, st,
+                     (const double*)ws, dbias, Cout, nblk);
+  return M355_OK;
 }

@@ -1,5 +1,6 @@
-// Shared pieces of the 3x3x3 convolution kernels (conv3d.hip: fp32 MFMA path, planning, ABI;
-// conv3d_h16.hip: bf16 / fp16 operand kernels).
+// Shared pieces of the 3x3x3 convolution code: device helpers of the kernels (conv3d.hip: fp32 kernels and their launcher;
+// conv3d_f32x3.hip: split kernels; conv3d_h16.hip: bf16 / fp16 operand kernels), the plans, and the routes that the host
+// layer (conv3d_host.hip: resolver, planners, every extern "C" entry point) resolves a descriptor to.
 #pragma once
 #include "common.hpp"
 #include "h16.hpp"
@@ -216,7 +217,6 @@ __device__ __forceinline__ void store_conv_tile16(const f32x4v (&acc)[NTW][2], f
   }
 }
 
-int pick_gx(int W);
 inline bool is16(int compute) { return compute == M355_COMPUTE_BF16 || compute == M355_COMPUTE_F16; }
 // M355_COMPUTE_F32X3 (conv3d_f32x3.hip): split + fragment-ordered weights, and the kernel launch of a plan with x3 != 0
 void launch_pack_w3_x3(const FwdPlan& p, const float* w, void* wp, int Cout_w, int Cin_w, bool transpose, hipStream_t st);
@@ -246,7 +246,90 @@ int launch_bww_x3(const BwwX3Plan& p, const float* x, const float* dy, float* sl
 int convt_fwd_x3_nvt(int Cin);
 void launch_convt_fwd_x3(int nvt, dim3 grid, const float* x, const float* w, const float* bias, float* y, int Cin, int Cout,
                          int D, int H, int W, int64_t xbs, int64_t ybs, int mt_per_wg, hipStream_t st);
-FwdPlan plan_mfma(int N, int kin, int mout, int D, int H, int W, int compute = M355_COMPUTE_F32);
+
+// ------------------------------------------------------------------ routes (conv3d_host.hip)
+// What a descriptor runs and what it needs, resolved ONCE per call on the host.  The queries return a route's numbers, the
+// launching entry points check their arguments against the same numbers and switch on `kind`: nothing else decides.
+enum class ConvKind {
+  Direct,             // not 3x3x3 / s1 / p1 (or >= 2^27 voxels): conv3d_direct_*_kernel
+  SmallCoutValu,      // Cout <= 4 forward: conv3_valu_smallcout_kernel (optional softmax epilogue)
+  SmallCoutToeplitz,  //   ... conv3_mfma_fwd_smallcout_kernel (M355_SMALLCOUT_VALU=0)
+  MfmaF32,            // conv3_mfma_fwd_kernel, one tile per workgroup
+  MfmaF32Queue,       // conv3_mfma_fwd_p_kernel
+  X3,                 // conv3_f32x3_kernel
+  H16Queue, H16Queue8, H16OneShot   // conv3_h16_kernel: queue-driven, its 8-wave variant, one item per workgroup
+};
+inline bool is_h16(ConvKind k) { return k == ConvKind::H16Queue || k == ConvKind::H16Queue8 || k == ConvKind::H16OneShot; }
+struct ConvRoute {            // forward (which = 0) or data gradient (which = 1) of one descriptor
+  ConvKind kind;
+  FwdPlan plan;               // the MFMA kinds (MfmaF32 .. H16OneShot)
+  size_t packed_bytes;        // m355_conv3d_packed_bytes
+  size_t workspace_bytes;     // fp32 NCDHW input (16-bit modes: + the c8 staging copy)
+  size_t h16_workspace_bytes; // c8 input handed over by the caller
+  int64_t stats_slots, stats_slots_c8;   // fused statistics partials per (sample, channel): fp32 / c8 output; 0 = none
+  bool fuses_softmax;
+  int32_t plan_code[4];       // m355_conv3d_plan
+};
+ConvRoute route_conv(const m355_conv3d_desc* d, int which);
+
+struct BwwPlan {
+  int gx, tz_tiles, ty_tiles, tx_tiles, otiles, ctiles, nsplit;
+  size_t slab_bytes;
+  bool classes;     // a 1..16 channel remainder on either side: conv3_mfma_bww2c_kernel (needs the gen-2 conditions)
+  BwwClasses k;     // always filled: without remainders one class with ns[*] = nsplit
+  int class_wgs;    // grid of the class kernel
+};
+enum class BwwKind {
+  Direct,       // conv3d_direct_bwd_weight_kernel
+  X3,           // conv3_bww_x3(c)_kernel
+  Mfma2,        // conv3_mfma_bww2(c)_kernel, or conv3_mfma_bww_kernel where the pointers rule them out (bww_gen2)
+  Small,        // conv3_mfma_bww_small_kernel (<= 4 channels on one side)
+  H16ViaPack    // 16-bit modes: both operands packed to c8, then the c8 kernel
+};
+struct BwwRoute {             // weight gradient of the plain entry point
+  BwwKind kind;
+  BwwPlan plan;               // Mfma2, Small
+  BwwX3Plan x3;               // X3
+  size_t slab_bytes;          // fp32 kinds: the slabs; the bias gradient's scratch follows them
+  size_t workspace_bytes;
+  int32_t plan_code[4];
+};
+BwwRoute route_bww(const m355_conv3d_desc* d);
+
+// ------------------------------------------------------------------ fp32 launcher (conv3d.hip)
+// One forward / data-gradient call.  The logical conv has K-channels kin = transpose ? Cout : Cin of `in`, M-channels mout.
+struct ConvCall {
+  const m355_conv3d_desc* d;
+  bool transpose;             // data gradient: flipped / transposed filter
+  const float* in;            // fp32 NCDHW, `in_bs` elements between samples ...
+  int64_t in_bs;
+  const void* in16;           // ... or c8 (16-bit kinds only), `in16_bs` elements between samples
+  int64_t in16_bs;
+  const float* w;             // weight tensor, or with `prepacked` the buffer m355_conv3d_pack filled for this route
+  bool prepacked;
+  const float* bias;
+  const float* add;
+  float* out;                 // fp32 NCDHW, or with `out16` a c8 tensor; `out_bs` elements between samples
+  int64_t out_bs;
+  bool out16, softmax;
+  float* stat;                // fused statistics partials (null: none)
+  int* oflag;                 // overflow word of a c8 data gradient (fp16: the stores saturate and report there)
+  void* ws;
+  size_t ws_bytes;
+  hipStream_t st;
+};
+// every kind but the 16-bit ones: weight pack unless prepacked, the kernel, the split-K reduction
+int launch_f32_conv(const ConvRoute& r, const ConvCall& c);
+// packed weights of every kind with a packed form (m355_conv3d_pack)
+void launch_pack_weights(const ConvRoute& r, const m355_conv3d_desc* d, bool transpose, const float* w, void* packed,
+                         hipStream_t st);
+size_t smallcout_packed_bytes(int Cin);
+// weight gradient of every kind but H16ViaPack into dw, slabs in `slab`
+int launch_f32_bww(const BwwRoute& r, const m355_conv3d_desc* d, const float* x, const float* dy, float* dw, float* slab,
+                   int64_t xbs, int64_t ybs, hipStream_t st);
+void launch_slab_reduce_t(const float* slab, float* dw, int Cin, int Cout, int ctiles, const BwwClasses& k, float scale,
+                          hipStream_t st);
+inline int out_dim(int in, int k, int s, int p) { return (in + 2 * p - k) / s + 1; }
 
 // 16-bit operand convolution (conv3d_h16.hip).  in16: c8 layout (h16.hpp) with `in16_bs` ELEMENTS between
 // samples; out: fp32 NCDHW.  Workspace: p.wp_bytes (packed weights + work queue) + p.slab_bytes.
@@ -325,3 +408,6 @@ __global__ void splitk_reduce_kernel(const float* __restrict__ slab, const float
                                      int64_t ybs);
 
 }  // namespace m355
+
+// dbias through the shared two-stage reduction; `ws` holds Cout * ceil(S / DBIAS_CHUNK) doubles
+int launch_dbias(const float* dy, float* dbias, int N, int Cout, int64_t S, int64_t ybs, void* ws, hipStream_t st);

@@ -86,7 +86,7 @@ def test_conv3d_f32x3_fwd_bwd(hip, oracle, case, tuning):
     products are below 2^-24 of each product; the split kernels add six partial products per 16 k-values to the accumulator
     where the fp32 MFMA adds eight)."""
     N, Ci, Co, D, H, W = case
-    tuning(M355_F32X3_EDGE=1)   # (3..7 K-channels on the split kernel too: opt-in, see x3_layer in conv3d.hip)
+    tuning(M355_F32X3_EDGE=1)   # (3..7 K-channels on the split kernel too: opt-in, see x3_layer in conv3d_host.hip)
     plan = hip.conv_plan((N, Ci, D, H, W), Co, compute=X3)
     assert plan[0] == 7, f"expected conv3_f32x3_kernel for {case}, got family {plan}"
     # (a single z plane has no ring to walk: the weight gradient stays on the fp32 MFMA kernel)
@@ -1479,3 +1479,61 @@ def test_c8_training_flow_architectures_with_fallback_ops(golden, mode, name):
     # points; BatchNorm over a batch of 2 x 16^3 amplifies the rounding noise of both)
     c8, twin = all_cosine(grads, True), all_cosine(grads_twin, False)
     assert c8 >= min(0.995 if mode == "bf16" else 0.9995, twin - (0.01 if mode == "bf16" else 0.001)), (c8, twin)
+
+
+SHORT_WS_CASES = [   # (Cin, Cout, compute, tuning): one descriptor per route kind the defaults reach, and a split-K plan
+    *[(ci, co, comp, {}) for comp in (0, X3) for ci, co in ((4, 32), (32, 3), (32, 32), (24, 40))],
+    (32, 32, 1, {}), (32, 3, 1, {}), (32, 32, 0, {"M355_CONV_KSPLIT": 2})]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("case", SHORT_WS_CASES, ids=lambda c: f"{c[0]}-{c[1]}-c{c[2]}" + ("-ks2" if c[3] else ""))
+def test_conv3d_short_workspace_is_refused_and_writes_nothing(hip, tuning, case):
+    """Every launching conv entry point, handed the full-size workspace buffer but a byte count one below what its
+    query returned, answers M355_EWORKSPACE and leaves its outputs (canary slots) unwritten: the launch checks the very
+    number the query reports.  (The buffer really is full-size, so a broken check cannot write out of bounds.)"""
+    from raw_ops import Slot, _p
+    EWORKSPACE = -4
+    Cin, Cout, compute, env = case
+    tuning(**env)
+    N, D, H, W = 1, 8, 8, 32
+    S = D * H * W
+    L, dev, st = hip.lib, hip.device, hip._stream()
+    x, dy, w = hip.to(rnd(N, Cin, D, H, W, seed=1)), hip.to(rnd(N, Cout, D, H, W, seed=2)), hip.to(rnd(Cout, Cin, 3, 3, 3, seed=3))
+    bias = hip.to(rnd(Cout, seed=4))
+    d = hip.conv_desc(x.shape, Cout, 3, 1, 1, compute=compute)
+    ref = C.byref(d)
+    y, dx = (lambda: Slot(dev, (N, Cout, D, H, W))), (lambda: Slot(dev, (N, Cin, D, H, W)))
+    dw, db = (lambda: Slot(dev, (1, Cout * Cin * 27))), (lambda: Slot(dev, (1, Cout)))
+    calls = [   # (entry point, workspace query result, outputs, arguments around (workspace, bytes, stream))
+        ("conv3d_fwd", L.m355_conv3d_fwd_workspace(ref), lambda o: (ref, _p(x), _p(w), _p(bias), None, _p(o[0])), (y,)),
+        ("conv3d_bwd_data", L.m355_conv3d_bwd_data_workspace(ref), lambda o: (ref, _p(dy), _p(w), _p(o[0])), (dx,)),
+        ("conv3d_bwd_weight", L.m355_conv3d_bwd_weight_workspace(ref), lambda o: (ref, _p(x), _p(dy), _p(o[0]), _p(o[1])), (dw, db)),
+    ]
+    if compute in (1, 2):
+        x16, dy16 = hip.act16_pack(x, compute), hip.act16_pack(dy, compute)
+        y16 = lambda: Slot(dev, (N, (Cout + 7) // 8, S, 8), dtype=hip.dt16(compute))
+        calls += [
+            ("conv3d_fwd_h16", L.m355_conv3d_h16_workspace(ref, 0),
+             lambda o: (ref, _p(x16), 0, _p(w), _p(bias), None, _p(o[0]), None), (y,)),
+            ("conv3d_fwd_h16_c8", L.m355_conv3d_h16_workspace(ref, 0),
+             lambda o: (ref, _p(x16), 0, _p(w), _p(bias), _p(o[0]), o[0].bs_arg, None), (y16,)),
+            ("conv3d_bwd_data_h16", L.m355_conv3d_h16_workspace(ref, 1), lambda o: (ref, _p(dy16), 0, _p(w), _p(o[0])), (dx,)),
+            ("conv3d_bwd_weight_h16", L.m355_conv3d_bwd_weight_h16_workspace(ref),
+             lambda o: (ref, _p(x16), 0, _p(dy16), 0, _p(dy), _p(o[0]), _p(o[1])), (dw, db)),
+            ("conv3d_bwd_weight_c8", L.m355_conv3d_bwd_weight_c8_workspace(ref),
+             lambda o: (ref, _p(x16), 0, _p(dy16), 0, _p(o[0]), _p(o[1]), 1.0), (dw, db)),
+        ]
+    ran = 0
+    for name, need, args, outs in calls:
+        if need == 0:
+            continue      # (no workspace to be short of: the c8 entry points in an fp32 mode)
+        ws = torch.empty(int(need), dtype=torch.uint8, device=dev)
+        o = [mk() for mk in outs]
+        rc = hip.fn(name)(*args(o), _p(ws), int(need) - 1, st)
+        torch.cuda.synchronize()
+        assert rc == EWORKSPACE, f"{name}: {need - 1} of {need} workspace bytes -> {rc} {L.m355_last_error().decode()}"
+        for s in o:
+            s.assert_untouched(name)
+        ran += 1
+    assert ran >= (8 if compute in (1, 2) else 3)

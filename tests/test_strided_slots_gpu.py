@@ -24,11 +24,11 @@ channel blocks of 16-byte items in a 256-byte aligned allocation.
 Host / kernel branches on a stride or a pointer (file:line, condition, who takes the fast | the slow side):
   conv3d.hip:792    per sample: row vector stores need yn, an 16-B aligned, W % 4 == 0   test_conv3d_small_cout[aligned W=40 | odd, offset*, W=33]
   conv3d.hip:1711   dbias VEC: S % 4, ybs % 4, dy 16-B aligned                           test_conv3d_bwd_weight[aligned S%4==0 cases | odd, offset*]
-  conv3d.hip:2840   (the host side of the same choice)                                  as above
-  conv3d.hip:2898   split weight gradient requires 4-byte aligned x / dy                every fp32 tensor is (no other side to take)
-  conv3d.hip:2945   bww float4 rows: W % 4, xbs % 4, x 16-B aligned (gen2 | gen1)        test_conv3d_bwd_weight[aligned W=36 family 9 | odd, offset* family 9]
-  conv3d.hip:2963   gen2 needs dy 4-byte aligned                                        always true for fp32 tensors
-  conv3d.hip:2573/2581/2700/2752, conv3d_h16.hip:1084/1090   c8 REQUIREs (16 B, % 8): act16_pack / _unpack, conv3d_bwd_weight_h16 / _c8,
+  conv3d.hip:2111   (the host side of the same choice)                                  as above
+  conv3d.hip:2035   split weight gradient requires 4-byte aligned x / dy                every fp32 tensor is (no other side to take)
+  conv3d.hip:2013   bww float4 rows: W % 4, xbs % 4, x 16-B aligned (gen2 | gen1)        test_conv3d_bwd_weight[aligned W=36 family 9 | odd, offset* family 9]
+  conv3d.hip:2014   gen2 needs dy 4-byte aligned                                        always true for fp32 tensors
+  conv3d_host.hip:691/699/800, conv3d_h16.hip:1084/1090   c8 REQUIREs (16 B, % 8): act16_pack / _unpack, conv3d_bwd_weight_h16 / _c8,
                     the conv3d h16 forward / data gradient                               test_c8_conv3d, test_act16_pack_unpack | test_c8_rejects_misaligned_slots (each by name)
   convt.hip:1195    k2 s2 forward MFMA kernel: ybs % 2 == 0, y 8-B aligned               test_conv_transpose3d[aligned, offset2 | odd (ybs odd), offset1, n1]
   convt.hip:1293    k2 s2 data gradient, same condition on dy                           test_conv_transpose3d (same ids)

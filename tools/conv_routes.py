@@ -1,0 +1,129 @@
+#!/usr/bin/env python3
+"""Every host answer of the conv3d route resolver (csrc/conv3d_host.hip) for a fixed descriptor list under a fixed list of
+tuning sets: one line per (tuning set, descriptor) with m355_conv3d_plan for which = 0, 1, 2, the workspace queries, the
+packed-weight sizes, the statistics slots and the softmax answer; then the line count and a SHA-256 of the lines.
+
+Pure host code: runs without a GPU (num_cus() is then 256, the MI355X's count).  A change that must not move any descriptor
+to another route, workspace size or plan code gives the same hash before and after; M355_LIB_PATH points the run at
+another build of the library.
+
+usage: python tools/conv_routes.py [--hash-only] [--jobs N] > routes.txt"""
+import argparse
+import ctypes as C
+import hashlib
+import itertools
+import multiprocessing
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+CHANNELS = [1, 3, 4, 5, 8, 13, 16, 24, 32, 33, 40, 48, 64, 80, 96, 120, 128, 192, 256, 320, 384]
+VOLUMES = [(8, 8, 8), (1, 5, 7), (8, 2, 32), (12, 9, 8), (6, 21, 16), (9, 10, 36), (17, 4, 62), (16, 16, 16), (32, 32, 32),
+           (64, 64, 64), (96, 96, 96), (128, 128, 128), (32, 256, 256), (160, 160, 160)]
+# each side of the 2^24, 2^26 and 2^27 voxel guards (channel counts <= 8 only)
+GUARD_VOLUMES = [(256, 256, 255), (256, 256, 256), (256, 256, 1023), (256, 256, 1024), (512, 512, 511), (512, 512, 512)]
+NON_K3 = [(1, 1, 0), (3, 2, 1), (2, 2, 0)]   # (k, stride, pad) of the direct kernels, on VOLUMES[:3]
+
+
+def descriptors():
+    """(N, Cin, Cout, D, H, W, k, stride, pad, compute)"""
+    for vol, ci, co, n, comp in itertools.product(VOLUMES, CHANNELS, CHANNELS, (1, 2), range(4)):
+        yield (n, ci, co) + vol + (3, 1, 1, comp)
+    small = [c for c in CHANNELS if c <= 8]
+    for vol, ci, co, n, comp in itertools.product(GUARD_VOLUMES, small, small, (1, 2), range(4)):
+        yield (n, ci, co) + vol + (3, 1, 1, comp)
+    for ksp, vol, ci, co, n, comp in itertools.product(NON_K3, VOLUMES[:3], CHANNELS, CHANNELS, (1, 2), range(4)):
+        yield (n, ci, co) + vol + ksp + (comp,)
+
+
+def _e(**kw):
+    return {k: str(v) for k, v in kw.items()}
+
+
+# the default, every distinct dict that tests/*_gpu.py hands to the `tuning` fixture, and single knobs
+TUNING_SETS = [
+    {},
+    # tests/test_fp16_overflow_gpu.py, tests/test_model_gpu.py
+    _e(M355_CONV_SLOTS=5, M355_H16_ONESHOT=3), _e(M355_H16_ONESHOT=2, M355_CONV_KSPLIT=1),
+    _e(M355_CONV_KSPLIT=2, M355_CONV_SLOTS=5, M355_H16_ONESHOT=3), _e(M355_CONV_NTW=1),
+    _e(M355_CONV_PERSISTENT=2, M355_CONV_SLOTS=6, M355_H16_ONESHOT=3),
+    # tests/test_strided_slots_gpu.py
+    _e(M355_CONV_SLOTS=5), _e(M355_CONV_KSPLIT=2, M355_CONV_NTW=2), _e(M355_TILE16=1), _e(M355_F32X3_EDGE=1),
+    _e(M355_F32X3_EDGE=1, M355_TILE16=1), _e(M355_CONV_KSPLIT=1), _e(M355_CONV_KSPLIT=1, M355_CONV_SLOTS=5),
+    _e(M355_BWW_NSPLIT=3), _e(M355_BWW_NSPLIT=3, M355_TILE16=0), _e(M355_BWW_NSPLIT=1),
+    # tests/test_kernels_gpu.py
+    _e(M355_TILE16=0), _e(M355_CONV_SLOTS=7), _e(M355_CONV_SLOTS=5, M355_CONV_KSPLIT=2), _e(M355_CONV_SLOTS=3, M355_CONV_NTW=8),
+    *[_e(M355_TILE16=t, **env) for t in (1, 0) for env in (
+        _e(M355_CONV_SLOTS=5), _e(M355_CONV_NTW=1), _e(M355_CONV_NTW=2, M355_CONV_KSPLIT=3),
+        _e(M355_CONV_NTW=4, M355_CONV_KSPLIT=1), _e(M355_BWW_NSPLIT=3), _e(M355_BWW_NSPLIT=1))],
+    _e(M355_CONV_KSPLIT=2), _e(M355_CONV_KSPLIT=0),
+    *[_e(M355_H16_W8=w8, M355_H16_ONESHOT=one, M355_CONV_KSPLIT=1) for w8, one in ((0, 3), (2, 3), (0, 1))],
+    _e(M355_NO_SMALL=0, M355_CONV_KSPLIT=1, M355_CONV_NTW=4), _e(M355_NO_SMALL=1, M355_CONV_KSPLIT=1, M355_CONV_NTW=4),
+    _e(M355_NO_SMALL=0),
+    _e(M355_CONV_KSPLIT=1, M355_CONV_SLOTS=5, M355_H16_ONESHOT=3), _e(M355_CONV_SLOTS=3, M355_CONV_KSPLIT=2, M355_H16_ONESHOT=3),
+    _e(M355_CONV_KSPLIT=1, M355_CONV_NTW=1), _e(M355_CONV_NTW=2, M355_CONV_SLOTS=7, M355_H16_ONESHOT=3, M355_CONV_KSPLIT=1),
+    _e(M355_CONV_KSPLIT=3),
+    *[_e(M355_H16_W8=w8, M355_H16_ONESHOT=3, **env) for w8 in (2, 0) for env in (
+        _e(M355_CONV_KSPLIT=1), _e(M355_CONV_KSPLIT=1, M355_CONV_SLOTS=3), _e(M355_CONV_KSPLIT=2, M355_CONV_SLOTS=5))],
+    _e(M355_CONVT_H16=1), _e(M355_CONVT_H16=0), _e(M355_BWW_NSPLIT=5),
+    # single knobs
+    _e(M355_SMALLCOUT_VALU=0), _e(M355_NO_SMALL=1), _e(M355_BWW_GEN=1), _e(M355_BWW_QUEUE=0), _e(M355_F32X3=0), _e(M355_F32X3=2),
+    _e(M355_F32X3_BWW=0), _e(M355_FUSE_SOFTMAX=0), _e(M355_CONV_PERSISTENT=0), _e(M355_CONV_PERSISTENT=2),
+    _e(M355_H16_ONESHOT=0), _e(M355_H16_W8=2),
+]
+TUNING_SETS = [dict(t) for t in dict.fromkeys(tuple(sorted(t.items())) for t in TUNING_SETS)]   # distinct, in order
+
+
+def run_set(args):
+    """All lines of one tuning set (a process of its own: the library reads the environment)."""
+    idx = args
+    env = TUNING_SETS[idx]
+    for k in [k for k in os.environ if k.startswith("M355_") and k != "M355_LIB_PATH"]:
+        del os.environ[k]
+    os.environ.update(env)
+    from segmentation_pipeline_amd import _lib
+    L = _lib.lib()
+    _lib.reload_tuning()
+    tag = ",".join(f"{k[5:]}={v}" for k, v in sorted(env.items())) or "default"
+    d = _lib.ConvDesc()
+    ref = C.byref(d)
+    out4 = (C.c_int32 * 4)()
+    sizes = [L.m355_conv3d_fwd_workspace, L.m355_conv3d_bwd_data_workspace, L.m355_conv3d_bwd_weight_workspace]
+    sizes_which = [L.m355_conv3d_h16_workspace, L.m355_conv3d_packed_bytes]
+    tail = [L.m355_conv3d_bwd_weight_h16_workspace, L.m355_conv3d_bwd_weight_c8_workspace, L.m355_conv3d_stats_slots,
+            L.m355_conv3d_stats_slots_c8, L.m355_conv3d_fuses_softmax]
+    lines = []
+    for (d.N, d.Cin, d.Cout, d.D, d.H, d.W, d.k, d.stride, d.pad, d.compute) in descriptors():
+        f = [tag, f"N{d.N} {d.Cin}->{d.Cout} {d.D}x{d.H}x{d.W} k{d.k}s{d.stride}p{d.pad} c{d.compute}"]
+        for which in (0, 1, 2):
+            rc = L.m355_conv3d_plan(ref, which, out4)
+            f.append(f"plan{which}={rc}:" + "/".join(str(v) for v in out4))
+        f.append("ws=" + "/".join(str(q(ref)) for q in sizes))
+        f += [name + "=" + "/".join(str(q(ref, w)) for w in (0, 1)) for name, q in zip(("h16ws", "packed"), sizes_which)]
+        f.append("bww16/c8/slots/slots_c8/softmax=" + "/".join(str(q(ref)) for q in tail))
+        lines.append(" ".join(f))
+    text = "\n".join(lines) + "\n"
+    return idx, len(lines), text
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    ap.add_argument("--hash-only", action="store_true", help="print no lines, only one hash per tuning set and the total")
+    ap.add_argument("--jobs", type=int, default=min(8, os.cpu_count() or 1))
+    a = ap.parse_args()
+    total, n = hashlib.sha256(), 0
+    with multiprocessing.get_context("spawn").Pool(a.jobs, maxtasksperchild=1) as pool:
+        for idx, count, text in pool.imap(run_set, range(len(TUNING_SETS))):
+            if a.hash_only:
+                print(f"set {idx:2d} {count} {hashlib.sha256(text.encode()).hexdigest()}", flush=True)
+            else:
+                sys.stdout.write(text)
+            total.update(text.encode())
+            n += count
+    print(f"lines {n} sha256 {total.hexdigest()}")
+
+
+if __name__ == "__main__":
+    main()
