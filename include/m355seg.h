@@ -885,6 +885,61 @@ int m355_eval_scores(const m355_eval_scores_desc* descs, int32_t n, void* dev_de
                      const int32_t* table, int32_t mask_kind, int32_t mask_axis, int32_t mask_upper,
                      const int32_t* labels, int32_t L, int32_t nokey, uint64_t* counts, void* stream);
 
+/* ------------------------------------------ contour images
+ * The device half of the reference's FindInterestingSlice and ContourImageEvaluator (evaluators.py).
+ * Volumes are [W, H, D], contiguous with D fastest, fewer than 2^31 voxels, every dimension at most
+ * M355_SLICE_MAX_DIM.  Planes are named by the axis they fix: SAGGITAL (the reference's spelling) fixes W, CORONAL H,
+ * AXIAL D.  Host descriptors are copied to `dev_descs` (device, room for all of them) on the stream; one launch per
+ * call whatever the sizes; nothing synchronises.
+ *   m355_slice_counts  counts[counts_offset + {0 .. W, W .. W+H, W+H .. W+H+D}) (device int32, zeroed here) = the
+ *                      foreground voxels of every sagittal, coronal and axial slice of subject i.  channels == 0: a
+ *                      label map of any M355_EV_* type up to float32, foreground = `data != 0` (a NaN is foreground).
+ *                      channels >= 1 (at most M355_EV_MAX_CHANNELS): a one-hot or score map [channels, W, H, D] in
+ *                      float32, bfloat16 or float16, foreground = argmax over the channels != 0 with the rule of
+ *                      m355_eval_scores (first maximum, a NaN is the maximum).  counts_offset of subject i must be the
+ *                      sum of W + H + D over the subjects before it.
+ *   m355_slice_rank    for every segment (offset, len) of `counts`: ids[offset ..) = the slices with a non-zero count,
+ *                      by count descending, ties by ascending slice id; ranked[offset ..) their counts in that order;
+ *                      nums[segment] their number.  Entries past nums[segment] are id -1 and count 0.
+ *   m355_slice_mosaic  up to 3 mosaics (torchvision make_grid with padding 1, row 0 of its channels) of 2-D slices:
+ *                      AXIAL x[:, :, k] ([W, H]), CORONAL rot90(x[:, k, :]) ([D, W]), SAGGITAL rot90(x[k, :, :])
+ *                      ([D, H]), rot90(m)[i, j] = m[j, B - 1 - i].  Mosaic m holds tiles [first_tile, first_tile +
+ *                      ntiles), all tile_h x tile_w, xmaps = min(ncol, ntiles) per row; rows x cols is
+ *                      (ymaps * (tile_h + 1) + 1) x (xmaps * (tile_w + 1) + 1) filled with `pad`, tile k at row0 =
+ *                      (k / xmaps) * (tile_h + 1) + 1, col0 = (k % xmaps) * (tile_w + 1) + 1; a single tile is the
+ *                      bare tile_h x tile_w (row0 = col0 = 0).  A tile without a source is zeros.  The mosaic has the
+ *                      element type of its tiles (a pure gather); a float32 mosaic also takes bfloat16 / float16
+ *                      tiles.  Everything is checked on the host (M355_EINVALID_ARG) before the launch. */
+#define M355_SLICE_MAX_DIM 2048
+enum { M355_PLANE_SAGGITAL = 0, M355_PLANE_CORONAL = 1, M355_PLANE_AXIAL = 2 };
+typedef struct {
+  const void* data;            /* [W, H, D] or [channels, W, H, D] */
+  int64_t counts_offset;
+  int32_t size3[3];
+  int32_t dtype, channels;
+} m355_slice_counts_desc;
+typedef struct {
+  int64_t offset;
+  int32_t len, reserved;
+} m355_slice_seg;
+typedef struct {
+  const void* src;             /* channel 0 of the volume; NULL: a tile of zeros */
+  int32_t dtype;
+  int32_t size3[3];
+  int32_t plane, slice;
+  int32_t row0, col0;
+} m355_slice_tile_desc;
+typedef struct {
+  void* out;                   /* [rows, cols] of element type dtype */
+  int32_t dtype, rows, cols, tile_h, tile_w, ncol, ntiles, first_tile;
+  float pad;
+} m355_slice_mosaic_desc;
+int m355_slice_counts(const m355_slice_counts_desc* descs, int32_t n, void* dev_descs, int32_t* counts, void* stream);
+int m355_slice_rank(const int32_t* counts, const m355_slice_seg* segs, int32_t nseg, void* dev_descs, int32_t* ids,
+                    int32_t* ranked, int32_t* nums, void* stream);
+int m355_slice_mosaic(const m355_slice_mosaic_desc* mosaics, int32_t nmosaics, const m355_slice_tile_desc* tiles,
+                      int32_t ntiles, void* dev_descs, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

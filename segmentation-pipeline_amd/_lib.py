@@ -95,6 +95,34 @@ class EvalScoresDesc(C.Structure):
                 ("target_dtype", C.c_int32), ("mask_dtype", C.c_int32)]
 
 
+SLICE_MAX_DIM = 2048
+PLANE_SAGGITAL, PLANE_CORONAL, PLANE_AXIAL = 0, 1, 2
+
+
+class SliceCountsDesc(C.Structure):
+    """m355_slice_counts_desc"""
+    _fields_ = [("data", C.c_void_p), ("counts_offset", C.c_int64), ("size3", C.c_int32 * 3), ("dtype", C.c_int32),
+                ("channels", C.c_int32)]
+
+
+class SliceSeg(C.Structure):
+    """m355_slice_seg"""
+    _fields_ = [("offset", C.c_int64), ("len", C.c_int32), ("reserved", C.c_int32)]
+
+
+class SliceTileDesc(C.Structure):
+    """m355_slice_tile_desc"""
+    _fields_ = [("src", C.c_void_p), ("dtype", C.c_int32), ("size3", C.c_int32 * 3), ("plane", C.c_int32),
+                ("slice", C.c_int32), ("row0", C.c_int32), ("col0", C.c_int32)]
+
+
+class SliceMosaicDesc(C.Structure):
+    """m355_slice_mosaic_desc"""
+    _fields_ = [("out", C.c_void_p), ("dtype", C.c_int32), ("rows", C.c_int32), ("cols", C.c_int32),
+                ("tile_h", C.c_int32), ("tile_w", C.c_int32), ("ncol", C.c_int32), ("ntiles", C.c_int32),
+                ("first_tile", C.c_int32), ("pad", C.c_float)]
+
+
 _P = C.c_void_p
 ABI_VERSION = 3   # M355_ABI_VERSION of include/m355seg.h this binding was written against
 _i32, _i64, _f32, _sz = C.c_int32, C.c_int64, C.c_float, C.c_size_t
@@ -234,6 +262,9 @@ SIGNATURES = {
     "m355_eval_confusion": (C.c_int, [C.POINTER(EvalMapDesc), _i32, _P, _I3, _i32, _i32, _P, _P]),
     "m355_eval_scores": (C.c_int, [C.POINTER(EvalScoresDesc), _i32, _P, _i32, _i32, _I3, _i32, _i32, _i32, _I3, _i32,
                                    _i32, _P, _P]),
+    "m355_slice_counts": (C.c_int, [C.POINTER(SliceCountsDesc), _i32, _P, _P, _P]),
+    "m355_slice_rank": (C.c_int, [_P, C.POINTER(SliceSeg), _i32, _P, _P, _P, _P, _P]),
+    "m355_slice_mosaic": (C.c_int, [C.POINTER(SliceMosaicDesc), _i32, C.POINTER(SliceTileDesc), _i32, _P, _P]),
 }
 
 

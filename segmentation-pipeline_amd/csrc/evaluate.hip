@@ -13,14 +13,16 @@
 // LDS histogram; the block's totals go out with one 64-bit atomic per (block, subject, label, stat) that is not zero.
 // Integer counts: exact and independent of the order of the atomics.
 #include "common.hpp"
-#include <hip/hip_fp16.h>
+#include "ev_load.hpp"
 
 namespace {
+
+using namespace m355::ev;
 
 constexpr int EV_NT = 256;
 constexpr int EV_REG_L = 8;
 constexpr int EV_E = 16;      // label-map elements per lane and step (one 16-byte load of a byte map)
-constexpr int EV_V = 8;       // voxels per lane and step of the score kernel (8 scores per channel load)
+constexpr int EV_V = m355::ev::SCORE_V;   // voxels per lane and step of the score kernel (8 scores per channel load)
 
 __device__ __forceinline__ int32_t fkey(float f, int32_t nokey) {
   return (f == truncf(f) && fabsf(f) < 2147483520.f) ? (int32_t)f : nokey;
@@ -224,33 +226,6 @@ struct ScoreArgs {
   int32_t table[2][M355_EV_MAX_CHANNELS];   // label value of channel c: [0] outside the mask, [1] inside
   int32_t C, scores_dtype, mask_kind, mask_axis, mask_upper;
 };
-
-template <int SD>
-__device__ __forceinline__ void load_scores8(const void* p, int64_t i, float s[EV_V]) {
-  if (SD == M355_EV_F32) {
-    const float4 a = *(const float4*)((const float*)p + i), b = *(const float4*)((const float*)p + i + 4);
-    s[0] = a.x; s[1] = a.y; s[2] = a.z; s[3] = a.w; s[4] = b.x; s[5] = b.y; s[6] = b.z; s[7] = b.w;
-  } else {
-    const uint4 r = *(const uint4*)((const uint16_t*)p + i);
-    const uint32_t w[4] = {r.x, r.y, r.z, r.w};
-#pragma unroll
-    for (int j = 0; j < EV_V; ++j) {
-      const uint16_t h = (uint16_t)(w[j >> 1] >> (16 * (j & 1)));
-      if (SD == M355_EV_BF16) s[j] = __uint_as_float((uint32_t)h << 16);
-      else s[j] = __half2float(__ushort_as_half(h));
-    }
-  }
-}
-template <int SD>
-__device__ __forceinline__ float load_score1(const void* p, int64_t i) {
-  if (SD == M355_EV_F32) return ((const float*)p)[i];
-  const uint16_t h = ((const uint16_t*)p)[i];
-  if (SD == M355_EV_BF16) return __uint_as_float((uint32_t)h << 16);
-  return __half2float(__ushort_as_half(h));
-}
-
-// torch.argmax: the first maximum; a NaN is larger than everything and the first NaN wins
-__device__ __forceinline__ bool takes(double best, double v) { return !(best != best) && (v != v || v > best); }
 
 // one-hot target values as doubles (exact for every integer type and for float32)
 __device__ __forceinline__ double load_t1(const void* p, int dt, int64_t i) {

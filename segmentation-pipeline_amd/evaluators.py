@@ -1,14 +1,20 @@
 """The reference's evaluators (evaluators/segmentation_evaluator.py, label_map_evaluator.py,
 instance_segmentation_evaluator.py, labeled_tensor.py) with their counts taken on the device, and lesion-wise detection
 statistics (the per-subject numbers of the reference's InstanceSegmentationEvaluator,
-evaluators/instance_segmentation_evaluator.py) with the labelling and the overlap table on the device.
+evaluators/instance_segmentation_evaluator.py) with the labelling and the overlap table on the device.  ContourImageEvaluator
+(evaluators/contour_image_evaluator.py) and FindInterestingSlice (transforms/find_interesting_slice.py) take their
+per-slice counts, ranks and slice mosaics on the device and draw on the host.
 
 The overlap table of N target and M predicted components is a dense int64 [N + 1, M + 1] histogram (component 0 is
 the background of either map), built by one pass of m355_label_histogram over the two label maps.  It is refused
 above MAX_OVERLAP_ENTRIES entries.  The detection test and every statistic derived from the table run on the host in
 float32, the dtype of the reference's table (so N == 0 or M == 0 gives the same nan results).
 """
+import io
 import itertools
+import random
+import warnings
+from collections.abc import Mapping
 from typing import Callable, Dict, Optional, Sequence
 
 import numpy as np
@@ -20,7 +26,8 @@ from .post_processing import _OP_COPY, _OP_POSITIVE, _ccl, _connectivity, _devic
 
 __all__ = ["overlap_histogram", "msseg_detection_test", "instance_segmentation_stats", "MAX_OVERLAP_ENTRIES", "STAT_NAMES",
            "LabeledTensor", "LabelMap", "Evaluator", "SegmentationEvaluator", "LabelMapEvaluator",
-           "InstanceSegmentationEvaluator", "label_counts"]
+           "InstanceSegmentationEvaluator", "label_counts", "ScalarImage", "find_interesting_slices",
+           "FindInterestingSlice", "ContourImageEvaluator", "render_contours"]
 
 MAX_OVERLAP_ENTRIES = 1 << 26   # (N + 1) * (M + 1): 512 MiB of int64 counts
 
@@ -440,3 +447,320 @@ class InstanceSegmentationEvaluator(Evaluator):
             for stat_name in self.stats_to_output:
                 table[subject['name'], stat_name] = stats[stat_name]
         return _finish(table, self.summary_stats_to_output)
+
+
+# ---------------------------------------------------------------------------------------------- contour images
+class ScalarImage(dict):
+    """The part of a torchio ScalarImage ContourImageEvaluator reads: `.data` ([C, W, H, D])."""
+
+    def __init__(self, data=None, **attributes):
+        super().__init__(attributes)
+        if data is not None:
+            self['data'] = data
+
+    @property
+    def data(self):
+        return self['data']
+
+
+PLANES = ops.PLANES
+
+
+class _RankCall:
+    """The device results of one find_interesting_slices call (ops.slice_rank) shared by its holders: ids and ranked
+    counts laid out as the count table, and the number of non-empty slices per (holder, plane) segment."""
+
+    def __init__(self, ids, ranked, nums, segments):
+        self.ids, self.ranked, self.nums, self.segments = ids, ranked, nums, segments
+        dev = ids.device
+        self._offsets = torch.tensor([o for o, _ in segments], dtype=torch.int64, device=dev)
+        self._lens = torch.tensor([n for _, n in segments], dtype=torch.int64, device=dev)
+        self._host_nums = None
+        self._picks = {}
+
+    def host_nums(self):
+        if self._host_nums is None:
+            self._host_nums = self.nums.cpu().tolist()
+        return self._host_nums
+
+    def pick(self, slice_id):
+        """int64 device [segments, 2]: get_slice_property of the ids and of the counts at rank `slice_id`, for every
+        segment at once (no synchronisation)"""
+        if slice_id not in self._picks:
+            num = self.nums.to(torch.int64)
+            at = self._offsets + torch.clamp(torch.clamp(num - 1, max=slice_id), min=0)
+            middle = self._lens // 2
+            empty = num == 0
+            self._picks[slice_id] = torch.stack([torch.where(empty, middle, self.ids[at].to(torch.int64)),
+                                                 torch.where(empty, middle, self.ranked[at].to(torch.int64))], dim=1)
+        return self._picks[slice_id]
+
+
+class _RankedPlanes(Mapping):
+    """{'Saggital' | 'Coronal' | 'Axial': ranked device tensor} as the reference's FindInterestingSlice stores it: a
+    read-only mapping, so copies, `dict(x)` and iteration all go through `__getitem__`.  The tensors' lengths (the
+    slices with foreground) are known on the device only: the first item access copies the lengths of the whole call
+    to the host, once.  ContourImageEvaluator reads the padded tables instead."""
+
+    def __init__(self, call, table, first_segment):
+        self.call, self.table, self.first_segment = call, table, first_segment
+
+    def __getitem__(self, plane):
+        if plane not in PLANES:
+            raise KeyError(plane)
+        seg = self.first_segment + PLANES.index(plane)
+        off, _ = self.call.segments[seg]
+        return self.table[off:off + self.call.host_nums()[seg]]
+
+    def __iter__(self):
+        return iter(PLANES)
+
+    def __len__(self):
+        return len(PLANES)
+
+
+def _is_one_hot(image):
+    return "one_hot" in image and bool(image['one_hot'])
+
+
+def find_interesting_slices(label_maps):
+    """FindInterestingSlice for every holder of `label_maps` (anything with `.data` [C, W, H, D] and item access) in one
+    ops.slice_counts and one ops.slice_rank launch: sets image['interesting_slice_ids'] and
+    image['interesting_slice_counts'], dicts keyed 'Saggital', 'Coronal', 'Axial' of int32 device tensors -- the
+    slices holding foreground (`data[0] != 0`, or argmax over the channels != 0 when image['one_hot']) by voxel
+    count descending, and those counts.  Equal counts are ordered by ascending slice id (the reference leaves their
+    order to an unstable sort).  Returns the holders."""
+    label_maps = list(label_maps)
+    if not label_maps:
+        return label_maps
+    datas = [image.data for image in label_maps]
+    dev = next((t.device for t in datas if t.is_cuda), None) or torch.device("cuda", torch.cuda.current_device())
+    one_hot = [_is_one_hot(image) for image in label_maps]
+    volumes = []
+    for i, (t, oh) in enumerate(zip(datas, one_hot)):
+        if t.dim() != 4:
+            raise ValueError(f"label map {i}: data of shape {tuple(t.shape)}; expected [C, W, H, D]")
+        volumes.append((t if oh else t[0]).to(dev))
+    counts, layout = ops.slice_counts(volumes, one_hot)
+    segments = []
+    for off, size3 in layout:
+        for dim in size3:
+            segments.append((off, dim))
+            off += dim
+    call = _RankCall(*ops.slice_rank(counts, segments), segments)
+    for i, image in enumerate(label_maps):
+        image['interesting_slice_ids'] = _RankedPlanes(call, call.ids, 3 * i)
+        image['interesting_slice_counts'] = _RankedPlanes(call, call.ranked, 3 * i)
+    return label_maps
+
+
+class FindInterestingSlice:
+    """transforms/find_interesting_slice.py of the reference as a callable: FindInterestingSlice()(image) annotates a
+    label map holder, FindInterestingSlice()(subject) every label map of a subject dict.  The reference takes the
+    subject's `tio.LabelMap`s; here a label map is an evaluators.LabelMap, or any other holder with a tensor `.data`
+    and item access that is not a scalar image: not an evaluators.ScalarImage, and when it has a 'type' (every torchio
+    image does) that type is 'label'."""
+
+    def __init__(self, **kwargs):
+        self.kwargs = kwargs
+
+    @staticmethod
+    def _is_label_map(value):
+        if isinstance(value, LabelMap):
+            return True
+        if isinstance(value, ScalarImage) or not isinstance(value, Mapping) or not hasattr(value, "__setitem__"):
+            return False
+        if not torch.is_tensor(getattr(value, "data", None)):
+            return False
+        return value.get("type", "label") == "label"
+
+    def __call__(self, image_or_subject):
+        if torch.is_tensor(getattr(image_or_subject, "data", None)):
+            find_interesting_slices([image_or_subject])
+        else:
+            find_interesting_slices([v for v in image_or_subject.values() if self._is_label_map(v)])
+        return image_or_subject
+
+
+def render_contours(img, y, y_pred, label_values, scale=0.1, line_width=1.5, legend=False):
+    """The drawing of contour_image_evaluator.py:136-172 (reference), call for call: `img` a 2-D array, `y` / `y_pred`
+    {label name: bool mask} or None.  Targets are contoured at level 0.5, solid; predictions at 0.95, dashed; colours
+    by label id.  Returns a PIL.Image.  matplotlib's backend is whatever the process has chosen."""
+    import matplotlib
+    import matplotlib.pyplot as plt
+    from PIL import Image
+
+    H, W = img.shape
+    fig = plt.figure(figsize=tuple(np.array((W, H)) * scale))
+    plt.imshow(img, cmap="gray",)
+    X_grid, Y_grid = np.meshgrid(np.linspace(0, W - 1, W), np.linspace(0, H - 1, H))
+    options = dict(linewidths=line_width, alpha=1.)
+    cmap = [None, "r", "g", "b", "y", "c", "m"]
+    for name in ("Accent", "Dark2", "Set1", "Set2", "tab20"):
+        cmap += list(matplotlib.colormaps[name].colors)
+    contours = []
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")
+        if y is not None:
+            for label_name, label_id in label_values.items():
+                contour = plt.contour(X_grid, Y_grid, y[label_name], levels=[0.5], colors=cmap[label_id:label_id + 1],
+                                      **options)
+                contours.append(contour)
+                if legend:
+                    plt.legend([contour.legend_elements()[0][0] for contour in contours], label_values.items(), ncol=3,
+                               bbox_to_anchor=(0.5, 0), loc='upper center', fancybox=True)
+        if y_pred is not None:
+            for label_name, label_id in label_values.items():
+                plt.contour(X_grid, Y_grid, y_pred[label_name], levels=[0.95], linestyles="dashed",
+                            colors=cmap[label_id:label_id + 1], **options)
+    plt.tick_params(which='both', bottom=False, top=False, left=False, labelbottom=False, labelleft=False)
+    buf = io.BytesIO()
+    fig.savefig(buf, bbox_inches="tight", pad_inches=0.0, facecolor="black")
+    buf.seek(0)
+    pil_image = Image.open(buf)
+    plt.close(fig)
+    return pil_image
+
+
+class ContourImageEvaluator(Evaluator):
+    """A slice of every subject's image tiled into one picture, the target's labels contoured solid and the
+    prediction's dashed (contour_image_evaluator.py, reference); a PIL.Image, or {subject name: PIL.Image} with
+    `split_subjects`.  `plane`: 'Axial', 'Coronal', 'Saggital', 'random' (random.randint per call) or 'interesting'
+    (with `interesting_slice`: the plane whose slice at rank `slice_id` holds most foreground in the first subject).
+    With `interesting_slice`, `slice_id` is a rank among the slices by foreground voxels (find_interesting_slices).
+
+    The volumes stay on the device: per call the chosen ranks come back in one copy (with `interesting_slice` only)
+    and the finished mosaics -- image, target labels, prediction labels -- in another (ops.slice_mosaic)."""
+
+    def __init__(self, plane: str, image_name: str, prediction_label_map_name: str, target_label_map_name: str,
+                 slice_id: int, legend: bool, ncol: int, scale: float = 0.1, line_width: float = 1.5,
+                 interesting_slice: bool = False, split_subjects: bool = False):
+        self.plane = plane
+        self.image_name = image_name
+        self.prediction_label_map_name = prediction_label_map_name
+        self.target_label_map_name = target_label_map_name
+        self.slice_id = slice_id
+        self.legend = legend
+        self.ncol = ncol
+        self.scale = scale
+        self.line_width = line_width
+        self.interesting_slice = interesting_slice
+        self.split_subjects = split_subjects
+
+    def _ranked_image(self, subject):
+        if self.target_label_map_name in subject:
+            return subject[self.target_label_map_name]
+        return subject[self.prediction_label_map_name]
+
+    def get_slice_id(self, subject, plane):
+        if not self.interesting_slice:
+            return self.slice_id, plane
+        image = self._ranked_image(subject)
+        if 'interesting_slice_ids' not in image:
+            image = FindInterestingSlice()(image)
+        interesting_slice_ids = image['interesting_slice_ids']
+        interesting_slice_counts = image['interesting_slice_counts']
+        if plane.lower() == 'interesting':
+            count = -1
+            for check_plane in ("Axial", "Coronal", "Saggital"):
+                new_count = self.get_slice_property(image, interesting_slice_counts, self.slice_id, check_plane)
+                if new_count > count:
+                    plane = check_plane
+                    count = new_count
+        return self.get_slice_property(image, interesting_slice_ids, self.slice_id, plane), plane
+
+    def get_slice_property(self, image, slice_property, slice_id, plane):
+        _, W, H, D = image.data.shape
+        dim = {'Axial': D, 'Coronal': H, 'Saggital': W}[plane]
+
+        if slice_property[plane].shape[0] == 0:
+            return dim // 2
+        if slice_id >= slice_property[plane].shape[0]:
+            return slice_property[plane][-1]
+        return slice_property[plane][slice_id]
+
+    def _resolve(self, subjects, plane):
+        """[(slice id, plane)] per subject, as get_slice_id gives them subject by subject (the first subject settles
+        an 'interesting' plane for all), with one copy from the device for all of them"""
+        if not self.interesting_slice:
+            return [(self.slice_id, plane)] * len(subjects)
+        images = [self._ranked_image(subject) for subject in subjects]
+        find_interesting_slices([image for image in images if 'interesting_slice_ids' not in image])
+        ours = [isinstance(image['interesting_slice_ids'], _RankedPlanes) for image in images]
+        calls = list({id(image['interesting_slice_ids'].call): image['interesting_slice_ids'].call
+                      for image, own in zip(images, ours) if own}.values())
+        rows, base = {}, 0
+        if calls:
+            picked = torch.cat([call.pick(self.slice_id) for call in calls]).cpu().tolist()
+            for call in calls:
+                rows[id(call)] = picked[base:base + len(call.segments)]
+                base += len(call.segments)
+        out = []
+        for subject, image, own in zip(subjects, images, ours):
+            if not own:   # ranks another FindInterestingSlice stored: the reference's own path
+                slice_id, plane = self.get_slice_id(subject, plane)
+                out.append((int(slice_id), plane))
+                continue
+            ranked = image['interesting_slice_ids']
+            by_plane = dict(zip(PLANES, rows[id(ranked.call)][ranked.first_segment:ranked.first_segment + 3]))
+            if plane.lower() == 'interesting':
+                count = -1
+                for check_plane in ("Axial", "Coronal", "Saggital"):
+                    if by_plane[check_plane][1] > count:
+                        plane, count = check_plane, by_plane[check_plane][1]
+            out.append((by_plane[plane][0], plane))
+        return out
+
+    def _mosaics(self, subjects, resolved, names, impute_shape):
+        """the make_grid mosaics of `names` [(image name, pad value)] as host arrays: one launch, one copy"""
+        datas = [subject[name].data for name, _ in names for subject in subjects if name in subject]
+        dev = next((t.device for t in datas if t.is_cuda), None) or torch.device("cuda", torch.cuda.current_device())
+        specs = []
+        for name, pad in names:
+            tiles = [(subject[name].data[0].to(dev) if name in subject else None, plane, slice_id)
+                     for subject, (slice_id, plane) in zip(subjects, resolved)]
+            specs.append((tiles, self.ncol, pad, impute_shape))
+        outs, buf = ops.slice_mosaic(specs)
+        host = buf.cpu()
+        arrays = []
+        for out in outs:
+            start = out.data_ptr() - buf.data_ptr()
+            arrays.append(host[start:start + out.numel() * out.element_size()].view(out.dtype).view(out.shape))
+        return arrays
+
+    def __call__(self, subjects):
+        if not self.split_subjects:
+            return self.get_image(subjects)
+        return {subject['name']: self.get_image([subject]) for subject in subjects}
+
+    def get_image(self, subjects):
+        out_pred = self.prediction_label_map_name is not None and self.prediction_label_map_name in subjects[0]
+        out_target = self.target_label_map_name is not None and self.target_label_map_name in subjects[0]
+        if out_pred:
+            label_values = subjects[0][self.prediction_label_map_name]['label_values']
+        if out_target:
+            label_values = subjects[0][self.target_label_map_name]['label_values']
+
+        if self.plane.lower() == 'random':
+            plane = ("Axial", "Coronal", "Saggital")[random.randint(0, 2)]
+        else:
+            plane = self.plane
+
+        resolved = self._resolve(subjects, plane)
+        plane = resolved[0][1]
+        resolved = [(slice_id, plane) for slice_id, _ in resolved]
+        impute_shape = ops.slice_shape(subjects[0][self.image_name].data.shape[1:], plane)
+
+        names = [(self.image_name, -1)]
+        if out_target:
+            names.append((self.target_label_map_name, 0))
+        if out_pred:
+            names.append((self.prediction_label_map_name, 0))
+        arrays = self._mosaics(subjects, resolved, names, impute_shape)
+        img, y, y_pred = arrays[0].numpy(), None, None
+        if out_target:
+            y = {label_name: (arrays[1] == label_value).numpy() for label_name, label_value in label_values.items()}
+        if out_pred:
+            y_pred = {label_name: (arrays[-1] == label_value).numpy() for label_name, label_value in label_values.items()}
+        return render_contours(img, y, y_pred, label_values if (out_target or out_pred) else {}, self.scale,
+                               self.line_width, self.legend)

@@ -2534,3 +2534,155 @@ def eval_scores(scores, table, labels, targets=None, masks=None, half=None, writ
         check(_lib.lib().m355_eval_scores(descs, n, _p(dev_descs), sd, Cc, tab, mask_kind, axis, upper, arr, L, nokey,
                                           _p(counts), _stream()), "eval_scores")
     return counts, (pred_outs if write_pred else None), (target_outs if write_target else None)
+
+
+# ----------------------------------------------------------------- contour images (csrc/contour.hip)
+PLANES = ("Saggital", "Coronal", "Axial")   # by the axis of [W, H, D] a plane fixes; the reference's spelling
+_SLICE_DTYPE = {**_EV_MAP_DTYPE, **_EV_SCORE_DTYPE}
+
+
+def slice_counts(volumes, one_hot=None):
+    """Foreground voxels per slice.  volumes[i]: a device label map [W, H, D] (any evaluation element type,
+    foreground = `!= 0`), or where one_hot[i] a one-hot / score map [C, W, H, D] (float32 / bfloat16 / float16,
+    foreground = argmax over C != 0).  -> (int32 device tensor, [(offset, (W, H, D))]): subject i's table at
+    [offset, offset + W + H + D) holds its sagittal, coronal and axial counts.  One launch, no synchronisation."""
+    n = len(volumes)
+    if n == 0:
+        raise _lib.M355Error("slice_counts: no volume")
+    one_hot = [False] * n if one_hot is None else [bool(o) for o in one_hot]
+    descs = (_lib.SliceCountsDesc * n)()
+    keep, layout, total = [], [], 0
+    dev = volumes[0].device
+    for i, (v, oh) in enumerate(zip(volumes, one_hot)):
+        if v.dim() != (4 if oh else 3) or v.device != dev:
+            raise _lib.M355Error(f"slice_counts: subject {i}: {'one-hot' if oh else 'label'} map {tuple(v.shape)} on "
+                                 f"{v.device}; expected {'[C, W, H, D]' if oh else '[W, H, D]'} on {dev}")
+        v = v.contiguous()
+        keep.append(v)
+        d = descs[i]
+        d.data, d.counts_offset = v.data_ptr(), total
+        d.size3[:] = tuple(v.shape[-3:])
+        d.dtype = _ev_code(v, _EV_SCORE_DTYPE if oh else _EV_MAP_DTYPE, f"slice_counts: subject {i}")
+        d.channels = v.shape[0] if oh else 0
+        layout.append((total, tuple(v.shape[-3:])))
+        total += sum(v.shape[-3:])
+    with torch.cuda.device(dev):
+        dev_descs = torch.empty(C.sizeof(descs), dtype=torch.uint8, device=dev)
+        counts = torch.empty(total, dtype=torch.int32, device=dev)
+        check(_lib.lib().m355_slice_counts(descs, n, _p(dev_descs), _p(counts), _stream()), "slice_counts")
+    return counts, layout
+
+
+def slice_rank(counts, segments):
+    """For every segment (offset, length) of the int32 device table `counts`: the slices with a non-zero count by count
+    descending, ties by ascending slice id.  -> (ids, ranked counts, nums): int32 device tensors, ids / ranked laid out
+    as `counts` (the first nums[s] entries of a segment are valid, the rest id -1 / count 0), nums one per segment.
+    One launch, no synchronisation."""
+    _require(counts, dtype=torch.int32)
+    nseg = len(segments)
+    if nseg == 0:
+        raise _lib.M355Error("slice_rank: no segment")
+    segs = (_lib.SliceSeg * nseg)()
+    for s, (off, ln) in enumerate(segments):
+        if off < 0 or ln < 1 or off + ln > counts.numel():
+            raise _lib.M355Error(f"slice_rank: segment {s} [{off}, {off} + {ln}) of a table of {counts.numel()}")
+        segs[s].offset, segs[s].len = off, ln
+    counts = counts.contiguous()
+    with torch.cuda.device(counts.device):
+        dev_descs = torch.empty(C.sizeof(segs), dtype=torch.uint8, device=counts.device)
+        ids = torch.full_like(counts, -1)
+        ranked = torch.zeros_like(counts)
+        nums = torch.empty(nseg, dtype=torch.int32, device=counts.device)
+        check(_lib.lib().m355_slice_rank(_p(counts), segs, nseg, _p(dev_descs), _p(ids), _p(ranked), _p(nums), _stream()),
+              "slice_rank")
+    return ids, ranked, nums
+
+
+def slice_shape(size3, plane):
+    """shape of slice_volume(x, 0, plane, k) for x [1, W, H, D] (utils/utils.py:64-72, reference): Axial x[:, :, k],
+    Coronal rot90(x[:, k, :]), Saggital rot90(x[k, :, :])"""
+    if plane not in PLANES:
+        raise ValueError(f'plane must be one of "Axial", "Coronal", or "Saggital" not {plane}')
+    W, H, D = size3
+    return {"Axial": (W, H), "Coronal": (D, W), "Saggital": (D, H)}[plane]
+
+
+def grid_geometry(n, h, w, ncol):
+    """torchvision.utils.make_grid(n tiles of h x w, nrow=ncol, padding=1): -> (rows, cols, [(row0, col0) per tile]).
+    A single tile is returned bare."""
+    if n < 1 or ncol < 1:
+        raise ValueError(f"a grid of {n} tiles in rows of {ncol}")
+    if n == 1:
+        return h, w, [(0, 0)]
+    xmaps = min(ncol, n)
+    ymaps = -(-n // xmaps)
+    return (ymaps * (h + 1) + 1, xmaps * (w + 1) + 1,
+            [((k // xmaps) * (h + 1) + 1, (k % xmaps) * (w + 1) + 1) for k in range(n)])
+
+
+def slice_mosaic(mosaics):
+    """Up to three make_grid mosaics in one launch.  mosaics: [(tiles, ncol, pad_value, tile_shape)], tiles a list of
+    (volume [W, H, D] device tensor or None, plane name, slice index); None is a tile of zeros of `tile_shape` (h, w)
+    (None: the shape of the other tiles).  A mosaic has the element type of its tiles (bfloat16 / float16 tiles give a
+    float32 mosaic; all tiles None: float32).  Tiles of differing shape or element type in one mosaic: ValueError,
+    before anything is launched.  -> (2-D device tensors, the uint8 device buffer they are views of): one copy of the
+    buffer brings every mosaic to the host.  No synchronisation."""
+    if not 1 <= len(mosaics) <= 3:
+        raise _lib.M355Error(f"slice_mosaic: {len(mosaics)} mosaics (1 .. 3)")
+    plans, ntiles, nbytes = [], 0, 0
+    for q, (tiles, ncol, pad, tile_shape) in enumerate(mosaics):
+        shape = tuple(tile_shape) if tile_shape is not None else None
+        dtype = None
+        for k, (vol, plane, _) in enumerate(tiles):
+            if vol is None:
+                continue
+            if vol.dim() != 3:
+                raise ValueError(f"mosaic {q}, tile {k}: a volume of shape {tuple(vol.shape)}; expected [W, H, D]")
+            got = slice_shape(vol.shape, plane)
+            if shape is not None and got != shape:
+                raise ValueError(f"mosaic {q}, tile {k}: a slice of {got[0]} x {got[1]} among tiles of {shape[0]} x {shape[1]}")
+            if dtype is not None and vol.dtype != dtype:
+                raise ValueError(f"mosaic {q}, tile {k}: element type {vol.dtype} among tiles of {dtype}")
+            shape, dtype = got, vol.dtype
+        if shape is None:
+            raise ValueError(f"mosaic {q}: no tile has a source and no tile shape is given")
+        out_dtype = torch.float32 if dtype in (None, torch.bfloat16, torch.float16) else dtype
+        if out_dtype not in _SLICE_DTYPE:
+            raise ValueError(f"mosaic {q}: element type {out_dtype}")
+        rows, cols, at = grid_geometry(len(tiles), shape[0], shape[1], int(ncol))
+        nbytes = -(-nbytes // 16) * 16
+        plans.append((tiles, int(ncol), float(pad), shape, out_dtype, rows, cols, at, ntiles, nbytes))
+        ntiles += len(tiles)
+        nbytes += rows * cols * torch.empty((), dtype=out_dtype).element_size()
+    sources = [vol for tiles, *_ in plans for vol, _, _ in tiles if vol is not None]
+    if not sources:
+        raise _lib.M355Error("slice_mosaic: no tile has a source (nothing says which device)")
+    dev = sources[0].device
+    if dev.type != "cuda":
+        raise _lib.M355Error(f"slice_mosaic: expected device tensors, the first source is on {dev}")
+    md = (_lib.SliceMosaicDesc * len(plans))()
+    td = (_lib.SliceTileDesc * ntiles)()
+    keep, outs = [], []
+    with torch.cuda.device(dev):
+        buf = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        for q, (tiles, ncol, pad, shape, out_dtype, rows, cols, at, first, byte0) in enumerate(plans):
+            out = buf[byte0:byte0 + rows * cols * torch.empty((), dtype=out_dtype).element_size()].view(out_dtype).view(rows, cols)
+            outs.append(out)
+            m = md[q]
+            m.out, m.dtype, m.rows, m.cols = out.data_ptr(), _SLICE_DTYPE[out_dtype], rows, cols
+            m.tile_h, m.tile_w, m.ncol, m.ntiles, m.first_tile, m.pad = shape[0], shape[1], ncol, len(tiles), first, pad
+            for k, (vol, plane, slice_id) in enumerate(tiles):
+                t = td[first + k]
+                t.row0, t.col0 = at[k]
+                if vol is None:
+                    continue
+                if vol.device != dev:
+                    raise _lib.M355Error(f"slice_mosaic: mosaic {q}, tile {k} is on {vol.device}, the first source on {dev}")
+                vol = vol.contiguous()
+                keep.append(vol)
+                t.src, t.dtype = vol.data_ptr(), _ev_code(vol, _SLICE_DTYPE, f"slice_mosaic: mosaic {q}, tile {k}")
+                t.size3[:] = tuple(vol.shape)
+                t.plane, t.slice = PLANES.index(plane), int(slice_id)
+        dev_descs = torch.empty(C.sizeof(td), dtype=torch.uint8, device=dev)
+        check(_lib.lib().m355_slice_mosaic(md, len(plans), td, ntiles, _p(dev_descs), _stream()), "slice_mosaic")
+    return outs, buf

@@ -356,7 +356,16 @@ class TrainLoop:
             D.all_reduce_mean_scalars(vals)           # flags: mean > 0 <=> some rank raised it
         return bool(vals[0] > 0), bool(vals[1] > 0), float(vals[2])
 
-    def _training_evaluations(self, due, batch, label_transform, label_values):
+    @staticmethod
+    def _attach_images(subject, source, evaluation_images, index=None):
+        """subject[name] = a [C, W, H, D] (or, with a channel, [1, W, H, D]) device view of source[key]"""
+        from .evaluators import ScalarImage
+        for name, spec in (evaluation_images or {}).items():
+            key, channel = spec if isinstance(spec, (tuple, list)) else (spec, None)
+            data = source[key] if index is None else source[key][index]
+            subject[name] = ScalarImage(data.detach() if channel is None else data.detach()[channel:channel + 1])
+
+    def _training_evaluations(self, due, batch, label_transform, label_values, evaluation_images=None):
         from .prediction import add_evaluation_labels
         if not due:
             return {}
@@ -364,10 +373,12 @@ class TrainLoop:
         names = batch.get("name") or [str(i) for i in range(n)]
         subjects = add_evaluation_labels({"y_pred": batch["y_pred"].detach(), "y": batch["y"], "name": list(names)},
                                          label_transform, label_values)
+        for i, subject in enumerate(subjects):
+            self._attach_images(subject, batch, evaluation_images, i)
         return {s.log_name: s.evaluator(subjects) for s in due}
 
     def _validation_evaluations(self, due, model, device, validation_predictor, validation_subjects, label_transform,
-                                label_values):
+                                label_values, evaluation_images=None):
         """segmentation_trainer.py:193-241: predict every subject a due evaluator needs, then run the evaluators"""
         from .prediction import add_evaluation_labels
         if not due:
@@ -391,6 +402,8 @@ class TrainLoop:
                     out["y_pred"] = batch["y_pred"][0]
                     if torch.is_tensor(out.get("y")):
                         out["y"] = out["y"].to(device)
+                    source = dict(out, X=batch["X"][0]) if torch.is_tensor(batch.get("X")) else out   # (the device copy)
+                    self._attach_images(out, source, evaluation_images)
                     evaluated[id(subject)] = out
         add_evaluation_labels(list(evaluated.values()), label_transform, label_values)
         by_name = {s["name"]: s for s in evaluated.values()}
@@ -408,7 +421,7 @@ class TrainLoop:
             timer: Optional[PhaseTimer] = None, training_evaluators: Sequence[ScheduledEvaluation] = (),
             validation_evaluators: Sequence[ScheduledEvaluation] = (), validation_predictor=None,
             validation_subjects: Optional[Dict[str, list]] = None, label_transform=None,
-            label_values: Optional[Dict[str, int]] = None):
+            label_values: Optional[Dict[str, int]] = None, evaluation_images: Optional[Dict] = None):
         """`batches`: iterator of dicts with stacked "X" / "y" tensors (the collate_subjects output,
         utils/utils.py:75-85).  `max_training_time` in seconds.  Returns the last loss dict.
 
@@ -418,7 +431,12 @@ class TrainLoop:
         `validation_predictor` (default: `predictor`) under no_grad.  Both get 'y_pred_eval' / 'y_eval' from
         prediction.add_evaluation_labels(label_transform, label_values): `label_transform` is the preprocessing
         Compose that produced 'y', `label_values` the training target's label_values after it.  Outputs go into the
-        log dict (and so to `scoring_function`) under each evaluator's log_name."""
+        log dict (and so to `scoring_function`) under each evaluator's log_name.
+
+        `evaluation_images`: {image name: key or (key, channel)} -- every evaluated subject gets subject[image name], an
+        evaluators.ScalarImage whose `.data` is a view (no copy) of the batch's or validation subject's tensor under
+        `key`, or of its one channel as [1, W, H, D]; e.g. {'mean_dwi': ('X', 0)} for ContourImageEvaluator(image_name=
+        'mean_dwi').  None: nothing is attached."""
         if max_training_time is not None:
             save_buffer = min(int(max_training_time * 0.1), 5 * 60)
             stop_time = time.time() + max_training_time - save_buffer
@@ -433,10 +451,10 @@ class TrainLoop:
             log_dict = dict(loss_dict)
             if training_evaluators or validation_evaluators:
                 log_dict.update(self._training_evaluations(_due(training_evaluators, self.iteration), _batch,
-                                                           label_transform, label_values))
+                                                           label_transform, label_values, evaluation_images))
                 log_dict.update(self._validation_evaluations(
                     _due(validation_evaluators, self.iteration), model, device, validation_predictor or predictor,
-                    validation_subjects or {}, label_transform, label_values))
+                    validation_subjects or {}, label_transform, label_values, evaluation_images))
             score = None
             scoring = self.scoring_function is not None and self.iteration % self.scoring_interval == 0
             if scoring:
