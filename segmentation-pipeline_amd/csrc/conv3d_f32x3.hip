@@ -21,9 +21,14 @@
 // value in registers (5.5 vector-ALU ops per element, once per staged element) and writes three bf16 planes to LDS in
 // the c8 form [plane][voxel][8 channels] -- one 16-byte item per voxel and plane, which IS the B fragment of the MFMA
 // for a lane (voxel, k-half).  K = 16 of one MFMA = 8 channels x 2 TAPS: the lower lane half reads tap t0, the upper
-// half tap t1 of a pair (27 taps = 14 pairs, the last one half empty), so a chunk is 8 channels and its three planes
-// fit LDS twice per CU (58.8 KB per workgroup at NTW = 4).  The weights are split and laid out in fragment order once
-// per optimizer step (pack_w3_x3_kernel: [channel tile][chunk][pair][plane][lane] x 16 B) and stream from L2 straight
+// half tap t1 of a pair (27 taps = 13 pairs + tap 26 alone), so a chunk is 8 channels and its three planes fit LDS
+// twice per CU (58.8 KB per workgroup at NTW = 4).  The lone tap fills its second K-half with a second plane product
+// of ITSELF: both lane halves read its voxel, and its six products run as three MFMAs
+//     weights lo | hi  x  activations hi | lo,     hi | mid  x  mid | mid,     hi | mid  x  hi | hi      (lower | upper K-half)
+// -- a chunk is 13 x 6 + 3 = 81 MFMAs per voxel group, exactly six per tap pair of real work (a partner from the next
+// chunk would need that chunk's planes, or a copy of the tap's window, in LDS: neither fits next to a second workgroup).
+// The same six products enter the accumulator; only their grouping inside the K-sum differs from the other pairs'.
+// The weights are split and laid out in fragment order once per optimizer step (pack_w3_x3_kernel: [channel tile][chunk][pair][plane][lane] x 16 B) and stream from L2 straight
 // into registers, two (NTW = 4) or six (NTW <= 2) pairs ahead of their use -- their three planes would not fit LDS next
 // to the activations.
 #include "conv3d_common.hpp"
@@ -35,13 +40,13 @@ typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int X3_PAIRS = 14;
 constexpr int X3_QUADS = 7;   // 16-row tile (conv3_f32x3_m16_kernel): K = 32 = 8 channels x 4 taps, tap 4 q + (lane >> 4)
-// tap (dz*9 + dy*3 + dx) of lane half `half` of pair `pair`; -1 = no tap (zero weights)
+// tap (dz*9 + dy*3 + dx) of lane half `half` of pair `pair`
 //   pairs 0..8   (dz, dy) = (pair / 3, pair % 3): dx = 0 | 1         -> the halves are one voxel apart along x
 //   pairs 9..11  dz = pair - 9, dx = 2: dy = 0 | 1                   -> one tile row apart
 //   pair 12      dy = 2, dx = 2: dz = 0 | 1                          -> one tile plane apart
-//   pair 13      (2, 2, 2) | none
+//   pair 13      (2, 2, 2) in BOTH halves: the same voxel, the halves differ in the PLANES they multiply (see the pack)
 __host__ __device__ constexpr int x3_pair_tap(int pair, int half) {
-  return pair < 9 ? pair * 3 + half : (pair < 12 ? (pair - 9) * 9 + half * 3 + 2 : (pair == 12 ? half * 9 + 8 : (half ? -1 : 26)));
+  return pair < 9 ? pair * 3 + half : (pair < 12 ? (pair - 9) * 9 + half * 3 + 2 : (pair == 12 ? half * 9 + 8 : 26));
 }
 
 // x = hi + mid + lo, the three as the HIGH halves of the returned words (lo: the word of the exact remainder, whose low
@@ -60,6 +65,8 @@ __device__ __forceinline__ unsigned x3_pack(unsigned a, unsigned b) { return __b
 // ---- weights: split + fragment order ----
 // wq[((((ot * nchunks + ch) * 14 + pair) * 3 + plane) * 64 + lane] = 8 bf16: the channels 8 ch .. 8 ch + 7 of output
 // channel 32 ot + (lane & 31) at tap x3_pair_tap(pair, lane >> 5); plane 0 / 1 / 2 = hi / mid / lo.
+// Pair 13 (tap 26 in both halves) keeps its three items, but they are the A fragments of its three MFMAs: items 0 and 1 =
+// hi (lanes 0..31) | mid (lanes 32..63), item 2 = lo | hi.
 // transpose (data gradient): the logical filter is W'[m][k][t] = w[k][m][26 - t] (m over Cin_w, k over Cout_w).
 __device__ __forceinline__ void pack_w3_x3_item(const float* __restrict__ w, u32x4* __restrict__ wq, int64_t i, int Cout_w,
                                                 int Cin_w, int kin, int mout, int nchunks, int transpose) {
@@ -78,9 +85,18 @@ __device__ __forceinline__ void pack_w3_x3_item(const float* __restrict__ w, u32
     x3_split(v, h[j], m[j], l[j]);
   }
   u32x4* dst = wq + f * 3 * 64 + lane;
-  dst[0] = (u32x4){x3_pack(h[0], h[1]), x3_pack(h[2], h[3]), x3_pack(h[4], h[5]), x3_pack(h[6], h[7])};
-  dst[64] = (u32x4){x3_pack(m[0], m[1]), x3_pack(m[2], m[3]), x3_pack(m[4], m[5]), x3_pack(m[6], m[7])};
-  dst[128] = (u32x4){x3_pack(l[0], l[1]), x3_pack(l[2], l[3]), x3_pack(l[4], l[5]), x3_pack(l[6], l[7])};
+  const u32x4 qh = {x3_pack(h[0], h[1]), x3_pack(h[2], h[3]), x3_pack(h[4], h[5]), x3_pack(h[6], h[7])};
+  const u32x4 qm = {x3_pack(m[0], m[1]), x3_pack(m[2], m[3]), x3_pack(m[4], m[5]), x3_pack(m[6], m[7])};
+  const u32x4 ql = {x3_pack(l[0], l[1]), x3_pack(l[2], l[3]), x3_pack(l[4], l[5]), x3_pack(l[6], l[7])};
+  if (pair == X3_PAIRS - 1) {   // the lone tap: hi | mid, hi | mid, lo | hi
+    const bool up = lane >= 32;
+    dst[0] = dst[64] = up ? qm : qh;
+    dst[128] = up ? qh : ql;
+  } else {
+    dst[0] = qh;
+    dst[64] = qm;
+    dst[128] = ql;
+  }
 }
 
 // the 16-row remainder tile (conv3_f32x3_m16_kernel), behind the 32-row tiles' region:
@@ -262,7 +278,10 @@ __global__ __launch_bounds__(256, 2) void conv3_f32x3_kernel(
   const unsigned lane16 = (unsigned)lane * 16u;
   // Weight fragments in flight: a pair step is 6 * NTW MFMAs, so at NTW = 4 two pairs of distance (~1500 cycles) cover
   // the L2 latency; at NTW <= 2 (the 32^3 .. 8^3 levels: 6 or 12 MFMAs per pair) they did not -- six pairs ahead there
-  // (a ring of 7 slots divides the 14 pairs of a chunk: no rotation at the chunk boundary).
+  // (a ring of 7 slots divides the 14 pairs of a chunk: no rotation at the chunk boundary).  Pair 13 is half a step (3 or 6
+  // MFMAs there): the loads issued in pairs 8 .. 13 for the next chunk's pairs 0 .. 5 have 5.5 pair steps instead of 6 in
+  // front of their use, plus the barriers and the commit of the next chunk's planes (~50 vector-ALU instructions per staged
+  // voxel: longer than the half step that went); the loads for pairs 6 .. 13 keep six whole steps.
   constexpr int AR = NTW >= 4 ? 3 : 7, AD = AR - 1;
   u32x4 afr[AR][3];   // [slot][plane]; pair p of a chunk sits in slot p % AR
   auto aload = [&](int slot, int pg) {
@@ -300,10 +319,13 @@ __global__ __launch_bounds__(256, 2) void conv3_f32x3_kernel(
         const int t0 = x3_pair_tap(p, 0);
         const int off = (t0 / 9) * PS + ((t0 / 3) % 3) * RS + t0 % 3;
         const int vb = (p < 9 ? vbx : (p < 12 ? vby : (p == 12 ? vbz : vb0))) + off;
+        // pair 13: both lane halves read the voxel of tap 26; fragment 2 is hi | lo (the upper half reads the lo plane)
+        const int vb2 = p == X3_PAIRS - 1 ? vb + half * 2 * NV : vb + 2 * NV;
 #pragma unroll
         for (int pl = 0; pl < 3; ++pl)
 #pragma unroll
-          for (int gi = 0; gi < GH; ++gi) bq[buf][gi][pl] = __builtin_bit_cast(bf16x8, xs[pl][vb + (h * GH + gi) * GY * RS]);
+          for (int gi = 0; gi < GH; ++gi)
+            bq[buf][gi][pl] = __builtin_bit_cast(bf16x8, xs[0][(pl == 2 ? vb2 : vb + pl * NV) + (h * GH + gi) * GY * RS]);
       };
       bload(0, 0, 0);
 #pragma unroll
@@ -315,28 +337,44 @@ __global__ __launch_bounds__(256, 2) void conv3_f32x3_kernel(
         const bf16x8 a_hi = __builtin_bit_cast(bf16x8, afr[p % AR][0]), a_mid = __builtin_bit_cast(bf16x8, afr[p % AR][1]),
                      a_lo = __builtin_bit_cast(bf16x8, afr[p % AR][2]);
         // (the small terms of a product group first; consecutive MFMAs write different accumulators)
+        const bool lone = p == X3_PAIRS - 1;   // tap 26: two plane products per MFMA, one in each K-half
+        if (!lone) {
 #pragma unroll
-        for (int pr = 0; pr < 6; ++pr) {
-          constexpr int PB[6] = {0, 0, 0, 1, 1, 2};
-          const bf16x8 a = pr == 0 ? a_lo : (pr == 1 || pr == 3 ? a_mid : a_hi);   // (lo,hi) (mid,hi) (hi,hi) (mid,mid) (hi,mid) (hi,lo)
+          for (int pr = 0; pr < 6; ++pr) {
+            constexpr int PB[6] = {0, 0, 0, 1, 1, 2};
+            const bf16x8 a = pr == 0 ? a_lo : (pr == 1 || pr == 3 ? a_mid : a_hi);   // (lo,hi) (mid,hi) (hi,hi) (mid,mid) (hi,mid) (hi,lo)
 #pragma unroll
-          for (int gi = 0; gi < GH; ++gi)
-            acc[h * GH + gi] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, bq[sb & 1][gi][PB[pr]], acc[h * GH + gi], 0, 0, 0);
+            for (int gi = 0; gi < GH; ++gi)
+              acc[h * GH + gi] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, bq[sb & 1][gi][PB[pr]], acc[h * GH + gi], 0, 0, 0);
+          }
+        } else {
+#pragma unroll
+          for (int pr = 0; pr < 3; ++pr) {
+            // weights lo | hi, hi | mid, hi | mid against activations hi | lo, mid | mid, hi | hi:
+            // (lo,hi) + (hi,lo),  (hi,mid) + (mid,mid),  (hi,hi) + (mid,hi)
+            const bf16x8 a = pr == 0 ? a_lo : (pr == 1 ? a_mid : a_hi);
+#pragma unroll
+            for (int gi = 0; gi < GH; ++gi)
+              acc[h * GH + gi] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, bq[sb & 1][gi][2 - pr], acc[h * GH + gi], 0, 0, 0);
+          }
         }
         if (last) {
 #pragma unroll
           for (int k = 0; k < LPS; ++k) fetch(p * LPS + k);
         }
-        constexpr int NM = 6 * GH, NR = 3 * GH;
+        // the lone pair's sub-step is half as long: every MFMA has a fragment read behind it, and the global loads follow
+        // their MFMA from the first one on
+        constexpr int NR = 3 * GH;
+        const int NM = lone ? 3 * GH : 6 * GH, L0 = lone ? 0 : NR;
         const int nv = (first ? 3 : 0) + (last ? LPS : 0);   // global loads of this sub-step
 #pragma unroll
         for (int i = 0; i < NM; ++i) {
           __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);                        // MFMA
           if (nb && i < NR) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);      // a B fragment of the next sub-step
-          if (i >= NR && i - NR < nv) __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);   // a global load
+          if (i >= L0 && i - L0 < nv) __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);   // a global load
         }
 #pragma unroll
-        for (int i = NM - NR; i < 3 + LPS; ++i)
+        for (int i = NM - L0; i < 3 + LPS; ++i)
           if (i < nv) __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
         __builtin_amdgcn_sched_barrier(0);
       }
