@@ -264,6 +264,21 @@ int m355_conv_transpose3d_bwd_weight(const m355_conv3d_desc* d, const float* x, 
                                      float* dw, float* dbias,
                                      void* workspace, size_t workspace_bytes, void* stream);
 
+/* Introspection, as m355_conv3d_plan: the route a conv-transpose call takes.  which: 0 / 1 / 2 = forward / data gradient /
+ * weight gradient of the fp32 entry points above, 3 / 4 / 5 = the same of the c8 entry points (*_h16).  y_side (fp32
+ * entry points only): the y / dy pointer the call would get; the MFMA kernels need it 8-byte aligned and an even
+ * y_batch_stride.  NULL = aligned, which is what m355_conv_transpose3d_workspace assumes.  out[0] = kernel family:
+ * 0 the generic direct kernels, 1 the fp32-MFMA k2s2 kernels, 2 the split forward of M355_COMPUTE_F32X3
+ * (convt_k2s2_fwd_x3_kernel), 3 convt_k2s2_fwd_c8_kernel / convt_k2s2_bww_c8_kernel, 4 convt_k2s2_fwd_h16_kernel /
+ * convt_k2s2_bwd_data_h16_kernel, 5 none: the c8 entry point returns M355_EUNSUPPORTED.  out[1..3] by which and family
+ * (all 0 for families 0 and 5):
+ *   0: voxel tile NVT, m-tiles per workgroup, 0          1: voxel tile NVT, channel tiles MT, splits of K = 8 * Cout
+ *   2: channel tiles MT, voxel-range splits, 0           3, family 3: voxel tile NVT, m-tile pairs per workgroup, 0
+ *   3, family 4: K steps KS (4 | 8), voxel groups NG, m-tiles staged per workgroup
+ *   4: m-tiles staged per workgroup MTW, grid.x, 0       5: channel tiles CT, voxel-range splits, 0
+ * Pure host function. */
+int m355_conv_transpose3d_plan(const m355_conv3d_desc* d, int32_t which, const void* y_side, int32_t* out4);
+
 /* nn.ConvTranspose3d(kernel_size=2, stride=2) c8 -> c8 for the 16-bit modes (fp32 weights and arithmetic: the op
  * is HBM-bound): the output lands directly in its slot of the decoder's c8 concat buffer
  * (models/modular_unet.py:96-97).  Other geometries: M355_EUNSUPPORTED (unpack / fp32 / pack instead). */

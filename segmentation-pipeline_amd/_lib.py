@@ -187,6 +187,7 @@ SIGNATURES = {
     "m355_conv3d_bwd_weight_workspace": (_sz, [_CD]),
     "m355_conv3d_bwd_weight": (C.c_int, [_CD, _P, _P, _P, _P, _P, _sz, _P]),
     "m355_conv_transpose3d_workspace": (_sz, [_CD]),
+    "m355_conv_transpose3d_plan": (C.c_int, [_CD, _i32, _P, C.POINTER(C.c_int32)]),
     "m355_conv_transpose3d_fwd": (C.c_int, [_CD, _P, _P, _P, _P, _P, _sz, _P]),
     "m355_conv_transpose3d_bwd_data": (C.c_int, [_CD, _P, _P, _P, _P, _sz, _P]),
     "m355_conv_transpose3d_bwd_weight": (C.c_int, [_CD, _P, _P, _P, _P, _P, _sz, _P]),

@@ -296,6 +296,35 @@ struct BwwRoute {             // weight gradient of the plain entry point
 };
 BwwRoute route_bww(const m355_conv3d_desc* d);
 
+// ConvTranspose3d (convt.hip): the same contract.  `kind` names the kernel family of the call, the numbers are that
+// family's launch; the byte counts hold for every kind, so one workspace serves whichever side the pointers pick.
+enum class ConvtKind {
+  Direct,       // convt_direct_*_kernel: not k2 s2 p0, >= 2^31 elements per sample, or a y side the MFMA kernels cannot take
+  MfmaF32,      // convt_k2s2_{fwd,bwd_data,bwd_weight}_mfma_kernel
+  X3,           // convt_k2s2_fwd_x3_kernel (M355_COMPUTE_F32X3 forward)
+  C8,           // convt_k2s2_fwd_c8_kernel, convt_k2s2_bww_c8_kernel
+  H16,          // convt_k2s2_fwd_h16_kernel, convt_k2s2_bwd_data_h16_kernel
+  Unsupported   // c8 entry points only: M355_EUNSUPPORTED
+};
+struct ConvtRoute {
+  ConvtKind kind;
+  int nvt;                    // voxels per workgroup tile (forward, fp32 data gradient)
+  int mt;                     // 32-channel tiles per workgroup: fp32 gradients (2 | 4), c8 weight gradient (ct: 1 | 2 | 4)
+  int mt_per_wg;              // m-tiles a workgroup walks (C8 forward: m-tile pairs) or stages (H16)
+  int ks_n, ng;               // H16 forward: 16-channel K steps, 128-voxel groups per tile
+  dim3 grid;
+  size_t lds;
+  int split, o_per_split;     // data gradient: splits of K = 8 * Cout and output channels of each; weight gradient: voxel-range splits
+  size_t slab_bytes;          // split partials, at the head of the workspace
+  size_t dbias_offset, dbias_bytes;   // the bias gradient's scratch (weight gradient)
+  size_t workspace_bytes;
+  int32_t plan_code[4];       // m355_conv_transpose3d_plan
+};
+// which: 0 forward, 1 data gradient, 2 weight gradient.  y_side_ok: even y batch stride and 8-byte aligned y / dy -- the
+// one fact that is neither in the descriptor nor in the tuning (the queries pass true: the upper bound)
+ConvtRoute route_convt(const m355_conv3d_desc* d, int which, bool y_side_ok);
+ConvtRoute route_convt_c8(const m355_conv3d_desc* d, int which);   // the c8 entry points (*_h16)
+
 // ------------------------------------------------------------------ fp32 launcher (conv3d.hip)
 // One forward / data-gradient call.  The logical conv has K-channels kin = transpose ? Cout : Cin of `in`, M-channels mout.
 struct ConvCall {

@@ -11,16 +11,14 @@
 // fp32-MFMA GEMMs with the voxel on the lane (coalesced x reads, float2-coalesced
 // y / dy accesses); any other geometry takes the generic direct kernels below.  (M355_COMPUTE_F32X3: the forward runs
 // on the bf16 matrix pipe through the exact three-way operand split -- convt_k2s2_fwd_x3_kernel, conv3d_f32x3.hip.)
-#include "h16.hpp"
+//
+// The device half comes first; the host half at the foot resolves each descriptor to one ConvtRoute
+// (conv3d_common.hpp) that the queries, the entry points and m355_conv_transpose3d_plan all read.
+#include "conv3d_common.hpp"
 
 namespace m355 {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-// the k2s2 forward of M355_COMPUTE_F32X3 (conv3d_f32x3.hip)
-int convt_fwd_x3_nvt(int Cin);
-void launch_convt_fwd_x3(int nvt, dim3 grid, const float* x, const float* w, const float* bias, float* y, int Cin, int Cout,
-                         int D, int H, int W, int64_t xbs, int64_t ybs, int mt_per_wg, hipStream_t st);
 
 // =============================== k2s2 as fp32-MFMA GEMMs ===============================
 // Every input voxel owns its 2x2x2 output block, so with t = a*4 + b*2 + c (the position
@@ -1095,28 +1093,23 @@ __global__ __launch_bounds__(256) void convt_direct_bwd_weight_kernel(
   if (threadIdx.x == 0) dw[((int64_t)c * Cout + o) * k3 + tap] = (float)tot;
 }
 
+// =============================== host: routes, queries, entry points ===============================
 static bool is_k2s2(const m355_conv3d_desc* d) {
   return d->k == 2 && d->stride == 2 && d->pad == 0 && d->out_pad == 0;
 }
 static int convt_out(int in, const m355_conv3d_desc* d) {
   return (in - 1) * d->stride - 2 * d->pad + d->k + d->out_pad;
 }
-static int convt_bww_mt(const m355_conv3d_desc* d) { return d->Cin > 64 ? 4 : 2; }
-static int convt_nsplit(const m355_conv3d_desc* d) {
-  const int64_t tiles = ceil_div(d->Cin, 32 * convt_bww_mt(d)) * ceil_div(d->Cout, 16);
-  const int64_t nsteps = ceil_div((int64_t)d->N * d->D * d->H * d->W, 64);
-  int64_t ns = std::max<int64_t>(1, 2 * num_cus() / tiles);  // persistent: 2 workgroups per CU, one round
-  ns = std::min<int64_t>(ns, nsteps);
-  return (int)ns;
-}
 static bool convt_fits_i32(const m355_conv3d_desc* d) {
   return (int64_t)d->D * d->H * d->W * 8 * std::max(d->Cin, d->Cout) < (1ll << 31);
+}
+static bool convt_dims_ok(const m355_conv3d_desc* d) {
+  return d->N > 0 && d->Cin > 0 && d->Cout > 0 && d->D > 0 && d->H > 0 && d->W > 0;
 }
 
 static int validate_convt(const m355_conv3d_desc* d, const char* who) {
   M355_REQUIRE(d != nullptr, M355_EINVALID_ARG, "%s: null descriptor", who);
-  M355_REQUIRE(d->N > 0 && d->Cin > 0 && d->Cout > 0 && d->D > 0 && d->H > 0 && d->W > 0,
-               M355_EINVALID_ARG, "%s: non-positive dimension", who);
+  M355_REQUIRE(convt_dims_ok(d), M355_EINVALID_ARG, "%s: non-positive dimension", who);
   M355_REQUIRE(d->k >= 1 && d->k <= 7 && d->stride >= 1 && d->pad >= 0 && d->out_pad >= 0 &&
                    d->out_pad < d->stride,
                M355_EINVALID_ARG, "%s: bad k/stride/pad/out_pad", who);
@@ -1125,22 +1118,19 @@ static int validate_convt(const m355_conv3d_desc* d, const char* who) {
   return M355_OK;
 }
 
-}  // namespace m355
-
-using namespace m355;
-
-// shared with conv3d.hip
-int launch_dbias(const float* dy, float* dbias, int N, int Cout, int64_t S, int64_t ybs, void* ws,
-                 hipStream_t st);
-static size_t convt_slab_bytes(const m355_conv3d_desc* d) {
-  return is_k2s2(d) ? (size_t)round_up((int64_t)convt_nsplit(d) * d->Cin * d->Cout * 8 * 4, 256) : 0;
+// output extent and batch strides (elements) of the fp32 entry points
+struct ConvtGeom {
+  int OD, OH, OW;
+  int64_t xbs, ybs;
+};
+static ConvtGeom convt_geom(const m355_conv3d_desc* d) {
+  ConvtGeom g{convt_out(d->D, d), convt_out(d->H, d), convt_out(d->W, d), 0, 0};
+  g.xbs = dense_or(d->x_batch_stride, (int64_t)d->Cin * d->D * d->H * d->W);
+  g.ybs = dense_or(d->y_batch_stride, (int64_t)d->Cout * g.OD * g.OH * g.OW);
+  return g;
 }
-static size_t convt_dbias_bytes(const m355_conv3d_desc* d) {
-  const int64_t OS = (int64_t)convt_out(d->D, d) * convt_out(d->H, d) * convt_out(d->W, d);
-  const int64_t generic = (int64_t)d->Cout * ceil_div(OS, DBIAS_CHUNK) * 8;              // launch_dbias partials
-  const int64_t fused = is_k2s2(d) ? (int64_t)convt_nsplit(d) * d->Cout * 8 : 0;        // bslab[split][Cout]
-  return (size_t)round_up(std::max(generic, fused), 256);
-}
+// the MFMA kernels move y / dy as float2
+static bool convt_y_side_ok(const ConvtGeom& g, const void* y) { return g.ybs % 2 == 0 && ((uintptr_t)y & 7) == 0; }
 
 // forward tile: the largest voxel tile whose [Cin][NVT] x slab fits 64 KB of LDS (0: none does)
 static int convt_fwd_nvt(const m355_conv3d_desc* d) {
@@ -1149,35 +1139,260 @@ static int convt_fwd_nvt(const m355_conv3d_desc* d) {
     if (cin2 * nvt * 4 <= 65536) return nvt;
   return 0;
 }
-
-// data-gradient plan: voxel tile, channel tile, and a split of the K = 8*Cout contraction when the level has
-// too few voxels to fill the chip (deep levels: few, long, latency-bound workgroups otherwise)
-struct ConvtBwdPlan {
-  int mt, nvt, ksplit, o_per_split;
-  size_t slab_bytes;
-};
-static ConvtBwdPlan plan_convt_bwd(const m355_conv3d_desc* d) {
-  ConvtBwdPlan p{};
+// forward grid over `rows` m-tiles (c8: m-tile pairs) with the x tile of r.nvt voxels resident in LDS.  x is re-read
+// once per m-tile group: split M only as far as needed to fill the chip
+static void convt_fwd_tiles(ConvtRoute& r, const m355_conv3d_desc* d, int rows) {
   const int64_t S = (int64_t)d->D * d->H * d->W;
-  p.mt = d->Cin > 64 ? 4 : 2;  // all input channels of a standard level in one pass over dY
-  const int64_t cblocks = ceil_div(d->Cin, 32 * p.mt);
-  p.nvt = 256;
-  while (p.nvt > 64 && ceil_div(S, p.nvt) * cblocks * d->N < 512) p.nvt >>= 1;
-  const int64_t wgs = ceil_div(S, p.nvt) * cblocks * d->N;
-  int64_t ks = 1;
-  if (wgs < 256) ks = std::min<int64_t>(std::min<int64_t>(8, ceil_div(512, wgs)), std::max(1, d->Cout / 16));
-  p.o_per_split = (int)round_up(ceil_div(d->Cout, ks), 4);
-  p.ksplit = (int)ceil_div(d->Cout, p.o_per_split);
-  p.slab_bytes = p.ksplit > 1 ? (size_t)round_up((int64_t)p.ksplit * d->N * d->Cin * S * 4, 256) : 0;
-  return p;
+  const int64_t vox_tiles = ceil_div(S, r.nvt) * d->N;
+  const int64_t groups = std::max<int64_t>(1, std::min<int64_t>(ceil_div(768, vox_tiles), ceil_div(rows, 4)));
+  r.mt_per_wg = (int)round_up(ceil_div(rows, groups), 4);
+  r.grid = dim3((unsigned)ceil_div(S, r.nvt), (unsigned)ceil_div(rows, r.mt_per_wg), (unsigned)d->N);
+  r.lds = (size_t)round_up(d->Cin, 16) * r.nvt * 4;
+}
+static void convt_plan_code(ConvtRoute& r, int a, int b, int c) {
+  const int32_t code[4] = {(int32_t)r.kind, a, b, c};
+  std::copy_n(code, 4, r.plan_code);
 }
 
+ConvtRoute route_convt(const m355_conv3d_desc* d, int which, bool y_side_ok) {
+  ConvtRoute r{};
+  r.kind = ConvtKind::Direct;
+  const int64_t S = (int64_t)d->D * d->H * d->W;
+  const bool k2s2 = is_k2s2(d);
+  bool mfma = k2s2 && y_side_ok && convt_fits_i32(d);
+  if (which == 0) {
+    // M355_COMPUTE_F32X3: the same GEMM on the bf16 matrix pipe through the exact three-way operand split (conv3d_f32x3.hip)
+    const bool x3 = d->compute == M355_COMPUTE_F32X3 && tuning().f32x3 && tuning().f32x3_convt && convt_fwd_x3_nvt(d->Cin) != 0;
+    r.nvt = x3 ? convt_fwd_x3_nvt(d->Cin) : convt_fwd_nvt(d);
+    if (mfma && r.nvt) {
+      r.kind = x3 ? ConvtKind::X3 : ConvtKind::MfmaF32;
+      convt_fwd_tiles(r, d, (int)ceil_div(d->Cout, 4));
+      if (x3) r.lds = 0;   // launch_convt_fwd_x3 sizes its own
+    }
+    convt_plan_code(r, r.kind == ConvtKind::Direct ? 0 : r.nvt, r.mt_per_wg, 0);
+  } else if (which == 1) {
+    // data gradient: voxel tile, channel tile, and a split of the K = 8*Cout contraction when the level has too few
+    // voxels to fill the chip (deep levels: few, long, latency-bound workgroups otherwise)
+    if (k2s2) {
+      r.mt = d->Cin > 64 ? 4 : 2;  // all input channels of a standard level in one pass over dY
+      const int64_t cblocks = ceil_div(d->Cin, 32 * r.mt);
+      r.nvt = 256;
+      while (r.nvt > 64 && ceil_div(S, r.nvt) * cblocks * d->N < 512) r.nvt >>= 1;
+      const int64_t wgs = ceil_div(S, r.nvt) * cblocks * d->N;
+      int64_t ks = 1;
+      if (wgs < 256) ks = std::min<int64_t>(std::min<int64_t>(8, ceil_div(512, wgs)), std::max(1, d->Cout / 16));
+      r.o_per_split = (int)round_up(ceil_div(d->Cout, ks), 4);
+      r.split = (int)ceil_div(d->Cout, r.o_per_split);
+      r.slab_bytes = r.split > 1 ? (size_t)round_up((int64_t)r.split * d->N * d->Cin * S * 4, 256) : 0;
+      r.grid = dim3((unsigned)ceil_div(S, r.nvt), (unsigned)cblocks, (unsigned)(d->N * r.split));
+    }
+    if (mfma) r.kind = ConvtKind::MfmaF32;
+    r.workspace_bytes = r.slab_bytes;
+    if (mfma) convt_plan_code(r, r.nvt, r.mt, r.split); else convt_plan_code(r, 0, 0, 0);
+  } else {
+    const int64_t OS = (int64_t)convt_out(d->D, d) * convt_out(d->H, d) * convt_out(d->W, d);
+    int64_t dbias = (int64_t)d->Cout * ceil_div(OS, DBIAS_CHUNK) * 8;   // launch_dbias partials (Direct)
+    if (k2s2) {
+      r.mt = d->Cin > 64 ? 4 : 2;
+      const int64_t otiles = ceil_div(d->Cout, 16), ctiles = ceil_div(d->Cin, 32 * r.mt);
+      // persistent: 2 workgroups per CU, one round
+      r.split = (int)std::min(std::max<int64_t>(1, 2 * num_cus() / (ctiles * otiles)), ceil_div(d->N * S, 64));
+      r.slab_bytes = (size_t)round_up((int64_t)r.split * d->Cin * d->Cout * 8 * 4, 256);
+      dbias = std::max(dbias, (int64_t)r.split * d->Cout * 8);          // bslab[split][Cout] (MfmaF32)
+      r.grid = dim3((unsigned)r.split, (unsigned)otiles, (unsigned)ctiles);
+    }
+    if (mfma) r.kind = ConvtKind::MfmaF32;
+    r.dbias_offset = r.slab_bytes;
+    r.dbias_bytes = (size_t)round_up(dbias, 256);
+    r.workspace_bytes = r.slab_bytes + r.dbias_bytes;
+    if (mfma) convt_plan_code(r, r.mt, r.split, 0); else convt_plan_code(r, 0, 0, 0);
+  }
+  return r;
+}
+
+ConvtRoute route_convt_c8(const m355_conv3d_desc* d, int which) {
+  ConvtRoute r{};
+  r.kind = ConvtKind::Unsupported;
+  convt_plan_code(r, 0, 0, 0);
+  if (!convt_dims_ok(d) || !is_k2s2(d)) return r;
+  const int64_t S = (int64_t)d->D * d->H * d->W;
+  if (which == 0) {
+    r.nvt = std::min(convt_fwd_nvt(d), 64);  // two m-tiles per wave: 64 voxels keep two workgroups per CU
+    if (!r.nvt || !convt_fits_i32(d)) return r;
+    // large levels: 16-bit MFMA kernel (weights staged once per workgroup; worth it from ~16k voxels per sample)
+    r.ks_n = (int)ceil_div(d->Cin, 16);
+    const int mtiles = 2 * (int)c8_blocks(d->Cout);
+    if (S >= 16384 && r.ks_n <= 8 && tuning().convt_h16) {
+      r.kind = ConvtKind::H16;
+      r.mt_per_wg = std::max(1, std::min(mtiles, 64 / r.ks_n));          // <= 64 KB of A fragments
+      const int groups = (int)ceil_div(mtiles, r.mt_per_wg);
+      r.ng = (S / 256) * groups * d->N >= 512 ? 2 : 1;
+      const int64_t vox_tiles = ceil_div(S, 128 * r.ng);
+      const int gx = (int)std::max<int64_t>(1, std::min<int64_t>(vox_tiles, ceil_div(512, (int64_t)groups * d->N)));
+      r.grid = dim3((unsigned)gx, (unsigned)groups, (unsigned)d->N);
+      r.lds = (size_t)r.mt_per_wg * r.ks_n * 1024;
+      convt_plan_code(r, r.ks_n <= 4 ? 4 : 8, r.ng, r.mt_per_wg);
+    } else {
+      r.kind = ConvtKind::C8;
+      convt_fwd_tiles(r, d, (int)ceil_div(ceil_div(d->Cout, 4), 2));
+      convt_plan_code(r, r.nvt, r.mt_per_wg, 0);
+    }
+    return r;
+  }
+  // the gradients: all weights of an m-tile group within 64 KB of A fragments, 32-bit buffer offsets
+  const int nks = 8 * (int)ceil_div(c8_blocks(d->Cout), 2);
+  if (nks > 64 || S * 8 * 16 * 4 >= (1ll << 31) || S * 16 * std::min<int64_t>(16, c8_blocks(d->Cin)) >= (1ll << 31)) return r;
+  const int mtiles = (int)ceil_div(d->Cin, 32);
+  if (which == 1) {
+    r.kind = ConvtKind::H16;
+    r.mt_per_wg = std::max(1, std::min(std::min(mtiles, 64 / nks), 4));
+    if (r.mt_per_wg == 3) r.mt_per_wg = 2;
+    const int groups = (int)ceil_div(mtiles, r.mt_per_wg);
+    const int64_t vox_tiles = ceil_div(S, 128);
+    // one residency of workgroups (2 per CU), each walking its share of the voxel tiles: the weights are staged once
+    const int64_t wgs = (int64_t)(tuning().convt_wgs ? tuning().convt_wgs : 2) * num_cus();
+    // (weights are staged per workgroup: at least four voxel tiles each on the small levels)
+    const int gx = (int)std::max<int64_t>(1, std::min<int64_t>(ceil_div(vox_tiles, 4), ceil_div(wgs, (int64_t)groups * d->N)));
+    r.grid = dim3((unsigned)gx, (unsigned)groups, (unsigned)d->N);
+    r.lds = (size_t)r.mt_per_wg * nks * 1024;
+    convt_plan_code(r, r.mt_per_wg, gx, 0);
+  } else {
+    r.kind = ConvtKind::C8;
+    r.mt = mtiles >= 4 ? 4 : (mtiles >= 2 ? 2 : 1);
+    const int64_t ntiles = (int64_t)d->N * d->D * ceil_div(d->H, 2) * ceil_div(d->W, 32);
+    const int64_t cgroups = ceil_div(mtiles, r.mt);
+    // (every split writes a slab of 8 * Cin * Cout floats that the reduction reads again: one workgroup per CU)
+    const int64_t wgs = (int64_t)(tuning().convt_wgs ? tuning().convt_wgs : 1) * num_cus();
+    r.split = (int)std::max<int64_t>(1, std::min<int64_t>(ntiles, wgs / (ceil_div(d->Cout, 32) * cgroups)));
+    r.grid = dim3((unsigned)r.split, (unsigned)ceil_div(d->Cout, 32), (unsigned)cgroups);
+    r.slab_bytes = (size_t)round_up((int64_t)r.split * 8 * d->Cin * d->Cout * 4, 256);
+    r.dbias_offset = r.slab_bytes;
+    r.dbias_bytes = dbias_c8_ws_bytes(d->N, d->Cout, S * 8);
+    r.workspace_bytes = r.slab_bytes + r.dbias_bytes;
+    convt_plan_code(r, r.mt, r.split, 0);
+  }
+  return r;
+}
+
+// ---- launchers: one per kernel family, the template switch over the route's numbers ----
+static void launch_convt_fwd_mfma(const ConvtRoute& r, const m355_conv3d_desc* d, const ConvtGeom& g, const float* x,
+                                  const float* w, const float* bias, float* y, hipStream_t st) {
+#define M355_CONVT_FWD(NVT)                                                                                          \
+  hipLaunchKernelGGL(convt_k2s2_fwd_mfma_kernel<NVT>, r.grid, dim3(256), r.lds, st, x, w, bias, y, d->Cin, d->Cout, \
+                     d->D, d->H, d->W, g.xbs, g.ybs, r.mt_per_wg)
+  switch (r.nvt) {
+    case 128: M355_CONVT_FWD(128); break;
+    case 64: M355_CONVT_FWD(64); break;
+    default: M355_CONVT_FWD(32); break;
+  }
+#undef M355_CONVT_FWD
+}
+
+static void launch_convt_bwd_data_mfma(const ConvtRoute& r, const m355_conv3d_desc* d, const ConvtGeom& g, const float* dy,
+                                       const float* w, float* dx, float* slab, hipStream_t st) {
+#define M355_CONVT_BWD(NVT, MT)                                                                                   \
+  hipLaunchKernelGGL((convt_k2s2_bwd_data_mfma_kernel<NVT, MT>), r.grid, dim3(256), 0, st, dy, w, dx, d->Cin,     \
+                     d->Cout, d->D, d->H, d->W, g.xbs, g.ybs, r.split, r.o_per_split, slab)
+  if (r.mt == 2) {
+    if (r.nvt == 256) M355_CONVT_BWD(256, 2); else if (r.nvt == 128) M355_CONVT_BWD(128, 2); else M355_CONVT_BWD(64, 2);
+  } else {
+    if (r.nvt == 256) M355_CONVT_BWD(256, 4); else if (r.nvt == 128) M355_CONVT_BWD(128, 4); else M355_CONVT_BWD(64, 4);
+  }
+#undef M355_CONVT_BWD
+  if (r.split > 1) {
+    const int64_t S = (int64_t)d->D * d->H * d->W, total = (int64_t)d->N * d->Cin * S;
+    hipLaunchKernelGGL(convt_dx_reduce_kernel, dim3((unsigned)std::min<int64_t>(ceil_div(total, 256), 2048)), dim3(256),
+                       0, st, slab, dx, d->N, (int64_t)d->Cin * S, g.xbs, r.split);
+  }
+}
+
+// slabs, then their reduction into dw (and, from bslab, into dbias)
+static void launch_convt_bww_mfma(const ConvtRoute& r, const m355_conv3d_desc* d, const ConvtGeom& g, const float* x,
+                                  const float* dy, float* dw, float* dbias, float* slab, double* bslab, hipStream_t st) {
+  if (r.mt == 2)
+    hipLaunchKernelGGL(convt_k2s2_bwd_weight_mfma_kernel<2>, r.grid, dim3(256), 0, st, x, dy, slab, bslab, d->N,
+                       d->Cin, d->Cout, d->D, d->H, d->W, g.xbs, g.ybs, r.split);
+  else
+    hipLaunchKernelGGL(convt_k2s2_bwd_weight_mfma_kernel<4>, r.grid, dim3(256), 0, st, x, dy, slab, bslab, d->N,
+                       d->Cin, d->Cout, d->D, d->H, d->W, g.xbs, g.ybs, r.split);
+  const int64_t total = (int64_t)d->Cin * d->Cout * 8;
+  hipLaunchKernelGGL(convt_slab_reduce_kernel, dim3((unsigned)std::min<int64_t>(ceil_div(total, 256), 1024)),
+                     dim3(256), 0, st, slab, dw, total, r.split, bslab, dbias, d->Cout);
+}
+
+// the c8 forward of either kind
+static void launch_convt_fwd_c8(const ConvtRoute& r, const m355_conv3d_desc* d, const void* x16, int64_t xbs, const float* w,
+                                const float* bias, void* y16, int64_t ybs, int compute, hipStream_t st) {
+  const int ks_n = r.ks_n, ng = r.ng, nvt = r.nvt;
+#define M355_CONVT_H16(HT, KS, NG)                                                                                      \
+  hipLaunchKernelGGL((convt_k2s2_fwd_h16_kernel<HT, KS, NG>), r.grid, dim3(256), r.lds, st, (const HT*)x16, w, bias,     \
+                     (HT*)y16, d->Cin, d->Cout, d->D, d->H, d->W, xbs, ybs, r.mt_per_wg)
+#define M355_CONVT_C8(NVT, HT)                                                                                             \
+  hipLaunchKernelGGL((convt_k2s2_fwd_c8_kernel<NVT, HT>), r.grid, dim3(256), r.lds, st, (const HT*)x16, w, bias, (HT*)y16, \
+                     d->Cin, d->Cout, d->D, d->H, d->W, xbs, ybs, r.mt_per_wg)
+#define M355_CONVT_FWD_T(HT)                                                                 \
+  if (r.kind == ConvtKind::C8) { if (nvt == 64) M355_CONVT_C8(64, HT); else M355_CONVT_C8(32, HT); } \
+  else if (ks_n <= 4) { if (ng == 2) M355_CONVT_H16(HT, 4, 2); else M355_CONVT_H16(HT, 4, 1); }       \
+  else { if (ng == 2) M355_CONVT_H16(HT, 8, 2); else M355_CONVT_H16(HT, 8, 1); }
+  if (compute == M355_COMPUTE_BF16) { M355_CONVT_FWD_T(__bf16) } else { M355_CONVT_FWD_T(_Float16) }
+#undef M355_CONVT_FWD_T
+#undef M355_CONVT_C8
+#undef M355_CONVT_H16
+}
+
+static void launch_convt_bwd_data_h16(const ConvtRoute& r, const m355_conv3d_desc* d, const void* dy16, int64_t ybs,
+                                      const float* w, void* dx16, int64_t xbs, int compute, hipStream_t st) {
+  // fp16 rounds a loss-scaled gradient: its stores saturate and report; bf16 neither clamps nor reports
+  int* oflag = compute == M355_COMPUTE_F16 ? overflow_flag() : nullptr;
+#define M355_CTBD(HT, MTW)                                                                                               \
+  hipLaunchKernelGGL((convt_k2s2_bwd_data_h16_kernel<HT, MTW>), r.grid, dim3(256), r.lds, st, (const HT*)dy16, w,        \
+                     (HT*)dx16, d->Cin, d->Cout, d->D, d->H, d->W, ybs, xbs, r.mt_per_wg, oflag)
+#define M355_CTBD_T(HT)                                                  \
+  if (r.mt_per_wg == 1) M355_CTBD(HT, 1); else if (r.mt_per_wg == 2) M355_CTBD(HT, 2); else M355_CTBD(HT, 4);
+  if (compute == M355_COMPUTE_BF16) { M355_CTBD_T(__bf16) } else { M355_CTBD_T(_Float16) }
+#undef M355_CTBD_T
+#undef M355_CTBD
+}
+
+// slabs, then their reduction (times grad_unscale) into dw
+static void launch_convt_bww_c8(const ConvtRoute& r, const m355_conv3d_desc* d, const void* x16, int64_t xbs, const void* dy16,
+                                int64_t ybs, float* dw, float grad_unscale, int compute, float* slab, hipStream_t st) {
+#define M355_CTBW(HT, CT)                                                                                                 \
+  hipLaunchKernelGGL((convt_k2s2_bww_c8_kernel<HT, CT>), r.grid, dim3(256), 0, st, (const HT*)x16, (const HT*)dy16, slab,  \
+                     d->N, d->Cin, d->Cout, d->D, d->H, d->W, xbs, ybs, r.split, (int)r.grid.z)
+#define M355_CTBW_T(HT) if (r.mt == 1) M355_CTBW(HT, 1); else if (r.mt == 2) M355_CTBW(HT, 2); else M355_CTBW(HT, 4);
+  if (compute == M355_COMPUTE_BF16) { M355_CTBW_T(__bf16) } else { M355_CTBW_T(_Float16) }
+#undef M355_CTBW_T
+#undef M355_CTBW
+  const int64_t total = (int64_t)d->Cin * d->Cout * 8;
+  hipLaunchKernelGGL(convt_slab_reduce_t_kernel, dim3((unsigned)ceil_div(total, 64)), dim3(256), 0, st, slab, dw, d->Cin,
+                     d->Cout, r.split, grad_unscale, overflow_flag());
+}
+
+}  // namespace m355
+
+using namespace m355;
+
+// ---- queries: a number of the route ----
 extern "C" size_t m355_conv_transpose3d_workspace(const m355_conv3d_desc* d) {
-  if (!d) return 0;
-  const size_t bwd = is_k2s2(d) ? plan_convt_bwd(d).slab_bytes : 0;
-  return std::max(convt_slab_bytes(d) + convt_dbias_bytes(d), bwd);
+  return d ? std::max(route_convt(d, 2, true).workspace_bytes, route_convt(d, 1, true).workspace_bytes) : 0;
+}
+extern "C" int32_t m355_conv_transpose3d_h16_bwd_supported(const m355_conv3d_desc* d) {
+  return d && route_convt_c8(d, 1).kind != ConvtKind::Unsupported ? 1 : 0;
+}
+extern "C" size_t m355_conv_transpose3d_h16_bwd_workspace(const m355_conv3d_desc* d) {
+  return d ? route_convt_c8(d, 2).workspace_bytes : 0;
+}
+// (the codes: include/m355seg.h)
+extern "C" int m355_conv_transpose3d_plan(const m355_conv3d_desc* d, int32_t which, const void* y_side, int32_t* out4) {
+  if (int rc = validate_convt(d, "conv_transpose3d_plan")) return rc;
+  M355_REQUIRE(out4 && which >= 0 && which <= 5, M355_EINVALID_ARG, "conv_transpose3d_plan: null pointer or which not in 0..5");
+  const ConvtRoute r = which < 3 ? route_convt(d, which, convt_y_side_ok(convt_geom(d), y_side)) : route_convt_c8(d, which - 3);
+  std::copy_n(r.plan_code, 4, out4);
+  return M355_OK;
 }
 
+// ---- fp32 entry points: validate, route, check the workspace against the route's own number, launch on `kind` ----
 extern "C" int m355_conv_transpose3d_fwd(const m355_conv3d_desc* d, const float* x, const float* w,
                                          const float* bias, float* y, void* workspace,
                                          size_t workspace_bytes, void* stream) {
@@ -1185,100 +1400,23 @@ extern "C" int m355_conv_transpose3d_fwd(const m355_conv3d_desc* d, const float*
   M355_REQUIRE(x && w && y, M355_EINVALID_ARG, "conv_transpose3d_fwd: null pointer");
   (void)workspace; (void)workspace_bytes;
   hipStream_t st = (hipStream_t)stream;
-  const int OD = convt_out(d->D, d), OH = convt_out(d->H, d), OW = convt_out(d->W, d);
-  M355_REQUIRE(OD > 0 && OH > 0 && OW > 0, M355_EINVALID_ARG, "conv_transpose3d_fwd: empty output");
-  const int64_t xbs = dense_or(d->x_batch_stride, (int64_t)d->Cin * d->D * d->H * d->W);
-  const int64_t ybs = dense_or(d->y_batch_stride, (int64_t)d->Cout * OD * OH * OW);
-  // M355_COMPUTE_F32X3: the same GEMM on the bf16 matrix pipe through the exact three-way operand split (conv3d_f32x3.hip)
-  const bool x3 = d->compute == M355_COMPUTE_F32X3 && tuning().f32x3 && tuning().f32x3_convt && convt_fwd_x3_nvt(d->Cin) != 0;
-  const int nvt = x3 ? convt_fwd_x3_nvt(d->Cin) : convt_fwd_nvt(d);
-  if (is_k2s2(d) && nvt && (ybs % 2 == 0) && ((uintptr_t)y & 7) == 0 && convt_fits_i32(d)) {
-    const int64_t S = (int64_t)d->D * d->H * d->W;
-    const int64_t vox_tiles = ceil_div(S, nvt) * d->N;
-    const int mtiles = (int)ceil_div(d->Cout, 4);
-    // x is re-read once per m-tile group: split M only as far as needed to fill the chip
-    const int64_t groups = std::max<int64_t>(1, std::min<int64_t>(ceil_div(768, vox_tiles), ceil_div(mtiles, 4)));
-    const int mt_per_wg = (int)round_up(ceil_div(mtiles, groups), 4);
-    dim3 grid((unsigned)ceil_div(S, nvt), (unsigned)ceil_div(mtiles, mt_per_wg), (unsigned)d->N);
-    if (x3) {
-      launch_convt_fwd_x3(nvt, grid, x, w, bias, y, d->Cin, d->Cout, d->D, d->H, d->W, xbs, ybs, mt_per_wg, st);
+  const ConvtGeom g = convt_geom(d);
+  M355_REQUIRE(g.OD > 0 && g.OH > 0 && g.OW > 0, M355_EINVALID_ARG, "conv_transpose3d_fwd: empty output");
+  const ConvtRoute r = route_convt(d, 0, convt_y_side_ok(g, y));
+  switch (r.kind) {
+    case ConvtKind::X3:
+      launch_convt_fwd_x3(r.nvt, r.grid, x, w, bias, y, d->Cin, d->Cout, d->D, d->H, d->W, g.xbs, g.ybs, r.mt_per_wg, st);
       return check_launch("convt_k2s2_fwd_x3");
-    }
-    const size_t lds = (size_t)round_up(d->Cin, 16) * nvt * 4;
-#define M355_CONVT_FWD(NVT)                                                                                   \
-  hipLaunchKernelGGL(convt_k2s2_fwd_mfma_kernel<NVT>, grid, dim3(256), lds, st, x, w, bias, y, d->Cin, d->Cout, \
-                     d->D, d->H, d->W, xbs, ybs, mt_per_wg)
-    switch (nvt) {
-      case 128: M355_CONVT_FWD(128); break;
-      case 64: M355_CONVT_FWD(64); break;
-      default: M355_CONVT_FWD(32); break;
-    }
-#undef M355_CONVT_FWD
-    return check_launch("convt_k2s2_fwd");
+    case ConvtKind::MfmaF32:
+      launch_convt_fwd_mfma(r, d, g, x, w, bias, y, st);
+      return check_launch("convt_k2s2_fwd");
+    default: break;
   }
-  const int64_t total = (int64_t)d->N * d->Cout * OD * OH * OW;
+  const int64_t total = (int64_t)d->N * d->Cout * g.OD * g.OH * g.OW;
   const int blocks = (int)std::min<int64_t>(ceil_div(total, 256), 65535);
-  hipLaunchKernelGGL(convt_direct_fwd_kernel, dim3(blocks), dim3(256), 0, st, x, w, bias, y, d->N,
-                     d->Cin, d->Cout, d->D, d->H, d->W, OD, OH, OW, d->k, d->stride, d->pad, xbs, ybs);
+  hipLaunchKernelGGL(convt_direct_fwd_kernel, dim3(blocks), dim3(256), 0, st, x, w, bias, y, d->N, d->Cin, d->Cout,
+                     d->D, d->H, d->W, g.OD, g.OH, g.OW, d->k, d->stride, d->pad, g.xbs, g.ybs);
   return check_launch("convt_direct_fwd");
-}
-
-extern "C" int m355_conv_transpose3d_fwd_h16(const m355_conv3d_desc* d, const void* x16, int64_t x16_batch_stride,
-                                             const float* w, const float* bias, void* y16, int64_t y16_batch_stride,
-                                             int32_t compute, void* stream) {
-  if (int rc = validate_convt(d, "conv_transpose3d_fwd_h16")) return rc;
-  M355_REQUIRE(x16 && w && y16, M355_EINVALID_ARG, "conv_transpose3d_fwd_h16: null pointer");
-  M355_REQUIRE(compute == M355_COMPUTE_BF16 || compute == M355_COMPUTE_F16, M355_EINVALID_ARG,
-               "conv_transpose3d_fwd_h16: compute must be M355_COMPUTE_BF16 or M355_COMPUTE_F16");
-  const int nvt = std::min(convt_fwd_nvt(d), 64);  // two m-tiles per wave: 64 voxels keep two workgroups per CU
-  M355_REQUIRE(is_k2s2(d) && nvt && convt_fits_i32(d), M355_EUNSUPPORTED,
-               "conv_transpose3d_fwd_h16: only kernel_size 2 / stride 2 / padding 0 has a c8 kernel");
-  const int64_t S = (int64_t)d->D * d->H * d->W;
-  const int64_t xbs = dense_or(x16_batch_stride, c8_blocks(d->Cin) * S * 8);
-  const int64_t ybs = dense_or(y16_batch_stride, c8_blocks(d->Cout) * S * 8 * 8);
-  M355_REQUIRE((((uintptr_t)x16 | (uintptr_t)y16) & 15) == 0 && xbs % 8 == 0 && ybs % 8 == 0, M355_EINVALID_ARG,
-               "conv_transpose3d_fwd_h16: c8 tensor not 16B aligned");
-  hipStream_t st = (hipStream_t)stream;
-  {
-    // large levels: 16-bit MFMA kernel (weights staged once per workgroup; worth it from ~16k voxels per sample)
-    const int ks_n = (int)ceil_div(d->Cin, 16);
-    const int mtiles = 2 * (int)c8_blocks(d->Cout);
-    if (S >= 16384 && ks_n <= 8 && tuning().convt_h16) {
-      const int mt_per_wg = std::max(1, std::min(mtiles, 64 / ks_n));          // <= 64 KB of A fragments
-      const int groups = (int)ceil_div(mtiles, mt_per_wg);
-      const int ng = (S / 256) * groups * d->N >= 512 ? 2 : 1;
-      const int64_t vox_tiles = ceil_div(S, 128 * ng);
-      const int gx = (int)std::max<int64_t>(1, std::min<int64_t>(vox_tiles, ceil_div(512, (int64_t)groups * d->N)));
-      dim3 grid((unsigned)gx, (unsigned)groups, (unsigned)d->N);
-      const size_t lds = (size_t)mt_per_wg * ks_n * 1024;
-#define M355_CONVT_H16(HT, KS, NG)                                                                                  \
-  hipLaunchKernelGGL((convt_k2s2_fwd_h16_kernel<HT, KS, NG>), grid, dim3(256), lds, st, (const HT*)x16, w, bias,     \
-                     (HT*)y16, d->Cin, d->Cout, d->D, d->H, d->W, xbs, ybs, mt_per_wg)
-#define M355_CONVT_H16_T(HT)                                                         \
-  if (ks_n <= 4) { if (ng == 2) M355_CONVT_H16(HT, 4, 2); else M355_CONVT_H16(HT, 4, 1); } \
-  else { if (ng == 2) M355_CONVT_H16(HT, 8, 2); else M355_CONVT_H16(HT, 8, 1); }
-      if (compute == M355_COMPUTE_BF16) { M355_CONVT_H16_T(__bf16) } else { M355_CONVT_H16_T(_Float16) }
-#undef M355_CONVT_H16_T
-#undef M355_CONVT_H16
-      return check_launch("convt_k2s2_fwd_h16");
-    }
-  }
-  const int64_t vox_tiles = ceil_div(S, nvt) * d->N;
-  const int mpairs = (int)ceil_div(ceil_div(d->Cout, 4), 2);
-  const int64_t groups = std::max<int64_t>(1, std::min<int64_t>(ceil_div(768, vox_tiles), ceil_div(mpairs, 4)));
-  const int mp_per_wg = (int)round_up(ceil_div(mpairs, groups), 4);
-  dim3 grid((unsigned)ceil_div(S, nvt), (unsigned)ceil_div(mpairs, mp_per_wg), (unsigned)d->N);
-  const size_t lds = (size_t)round_up(d->Cin, 16) * nvt * 4;
-#define M355_CONVT_C8(NVT, HT)                                                                                       \
-  hipLaunchKernelGGL((convt_k2s2_fwd_c8_kernel<NVT, HT>), grid, dim3(256), lds, st, (const HT*)x16, w, bias, (HT*)y16, \
-                     d->Cin, d->Cout, d->D, d->H, d->W, xbs, ybs, mp_per_wg)
-  if (compute == M355_COMPUTE_BF16) {
-    if (nvt == 64) M355_CONVT_C8(64, __bf16); else M355_CONVT_C8(32, __bf16);
-  } else {
-    if (nvt == 64) M355_CONVT_C8(64, _Float16); else M355_CONVT_C8(32, _Float16);
-  }
-#undef M355_CONVT_C8
-  return check_launch("convt_k2s2_fwd_c8");
 }
 
 extern "C" int m355_conv_transpose3d_bwd_data(const m355_conv3d_desc* d, const float* dy,
@@ -1287,40 +1425,18 @@ extern "C" int m355_conv_transpose3d_bwd_data(const m355_conv3d_desc* d, const f
   if (int rc = validate_convt(d, "conv_transpose3d_bwd_data")) return rc;
   M355_REQUIRE(dy && w && dx, M355_EINVALID_ARG, "conv_transpose3d_bwd_data: null pointer");
   hipStream_t st = (hipStream_t)stream;
-  const int OD = convt_out(d->D, d), OH = convt_out(d->H, d), OW = convt_out(d->W, d);
-  const int64_t xbs = dense_or(d->x_batch_stride, (int64_t)d->Cin * d->D * d->H * d->W);
-  const int64_t ybs = dense_or(d->y_batch_stride, (int64_t)d->Cout * OD * OH * OW);
-  if (is_k2s2(d) && (ybs % 2 == 0) && ((uintptr_t)dy & 7) == 0 && convt_fits_i32(d)) {
-    const int64_t S = (int64_t)d->D * d->H * d->W;
-    const ConvtBwdPlan bp = plan_convt_bwd(d);
-    const int mt = bp.mt, nvt = bp.nvt, ksplit = bp.ksplit;
-    float* slab = nullptr;
-    if (ksplit > 1) {
-      M355_REQUIRE(workspace && workspace_bytes >= bp.slab_bytes, M355_EWORKSPACE,
-                   "conv_transpose3d_bwd_data: workspace too small (%zu < %zu)", workspace_bytes, bp.slab_bytes);
-      slab = (float*)workspace;
-    }
-    dim3 grid((unsigned)ceil_div(S, nvt), (unsigned)ceil_div(d->Cin, 32 * mt), (unsigned)(d->N * ksplit));
-#define M355_CONVT_BWD(NVT, MT)                                                                                \
-  hipLaunchKernelGGL((convt_k2s2_bwd_data_mfma_kernel<NVT, MT>), grid, dim3(256), 0, st, dy, w, dx, d->Cin,    \
-                     d->Cout, d->D, d->H, d->W, xbs, ybs, ksplit, bp.o_per_split, slab)
-    if (mt == 2) {
-      if (nvt == 256) M355_CONVT_BWD(256, 2); else if (nvt == 128) M355_CONVT_BWD(128, 2); else M355_CONVT_BWD(64, 2);
-    } else {
-      if (nvt == 256) M355_CONVT_BWD(256, 4); else if (nvt == 128) M355_CONVT_BWD(128, 4); else M355_CONVT_BWD(64, 4);
-    }
-#undef M355_CONVT_BWD
-    if (ksplit > 1) {
-      const int64_t total = (int64_t)d->N * d->Cin * S;
-      hipLaunchKernelGGL(convt_dx_reduce_kernel, dim3((unsigned)std::min<int64_t>(ceil_div(total, 256), 2048)), dim3(256),
-                         0, st, slab, dx, d->N, (int64_t)d->Cin * S, xbs, ksplit);
-    }
+  const ConvtGeom g = convt_geom(d);
+  const ConvtRoute r = route_convt(d, 1, convt_y_side_ok(g, dy));
+  if (r.kind == ConvtKind::MfmaF32) {
+    M355_REQUIRE(r.split == 1 || (workspace && workspace_bytes >= r.slab_bytes), M355_EWORKSPACE,
+                 "conv_transpose3d_bwd_data: workspace too small (%zu < %zu)", workspace_bytes, r.slab_bytes);
+    launch_convt_bwd_data_mfma(r, d, g, dy, w, dx, r.split > 1 ? (float*)workspace : nullptr, st);
     return check_launch("convt_k2s2_bwd_data");
   }
   const int64_t total = (int64_t)d->N * d->Cin * d->D * d->H * d->W;
   const int blocks = (int)std::min<int64_t>(ceil_div(total, 256), 65535);
-  hipLaunchKernelGGL(convt_direct_bwd_data_kernel, dim3(blocks), dim3(256), 0, st, dy, w, dx, d->N,
-                     d->Cin, d->Cout, d->D, d->H, d->W, OD, OH, OW, d->k, d->stride, d->pad, xbs, ybs);
+  hipLaunchKernelGGL(convt_direct_bwd_data_kernel, dim3(blocks), dim3(256), 0, st, dy, w, dx, d->N, d->Cin, d->Cout,
+                     d->D, d->H, d->W, g.OD, g.OH, g.OW, d->k, d->stride, d->pad, g.xbs, g.ybs);
   return check_launch("convt_direct_bwd_data");
 }
 
@@ -1331,113 +1447,73 @@ extern "C" int m355_conv_transpose3d_bwd_weight(const m355_conv3d_desc* d, const
   if (int rc = validate_convt(d, "conv_transpose3d_bwd_weight")) return rc;
   M355_REQUIRE(x && dy && dw, M355_EINVALID_ARG, "conv_transpose3d_bwd_weight: null pointer");
   hipStream_t st = (hipStream_t)stream;
-  const int OD = convt_out(d->D, d), OH = convt_out(d->H, d), OW = convt_out(d->W, d);
-  const int64_t xbs = dense_or(d->x_batch_stride, (int64_t)d->Cin * d->D * d->H * d->W);
-  const int64_t ybs = dense_or(d->y_batch_stride, (int64_t)d->Cout * OD * OH * OW);
-  if (is_k2s2(d) && (ybs % 2 == 0) && ((uintptr_t)dy & 7) == 0 && convt_fits_i32(d)) {
-    const int nsplit = convt_nsplit(d);
-    const size_t need = convt_slab_bytes(d);
-    M355_REQUIRE(workspace && workspace_bytes >= need, M355_EWORKSPACE,
-                 "conv_transpose3d_bwd_weight: workspace too small (%zu < %zu)", workspace_bytes,
-                 need);
-    float* slab = (float*)workspace;
-    double* bslab = nullptr;
-    if (dbias) {
-      M355_REQUIRE(workspace_bytes >= need + convt_dbias_bytes(d), M355_EWORKSPACE,
-                   "conv_transpose3d_bwd_weight: workspace too small for the bias gradient");
-      bslab = (double*)((char*)workspace + need);
-    }
-    const int mt = convt_bww_mt(d);
-    dim3 grid((unsigned)nsplit, (unsigned)ceil_div(d->Cout, 16), (unsigned)ceil_div(d->Cin, 32 * mt));
-    if (mt == 2)
-      hipLaunchKernelGGL(convt_k2s2_bwd_weight_mfma_kernel<2>, grid, dim3(256), 0, st, x, dy, slab, bslab, d->N,
-                         d->Cin, d->Cout, d->D, d->H, d->W, xbs, ybs, nsplit);
-    else
-      hipLaunchKernelGGL(convt_k2s2_bwd_weight_mfma_kernel<4>, grid, dim3(256), 0, st, x, dy, slab, bslab, d->N,
-                         d->Cin, d->Cout, d->D, d->H, d->W, xbs, ybs, nsplit);
-    const int64_t total = (int64_t)d->Cin * d->Cout * 8;
-    hipLaunchKernelGGL(convt_slab_reduce_kernel, dim3((unsigned)std::min<int64_t>(ceil_div(total, 256), 1024)),
-                       dim3(256), 0, st, slab, dw, total, nsplit, bslab, dbias, d->Cout);
-    return check_launch("conv_transpose3d_bwd_weight");
+  const ConvtGeom g = convt_geom(d);
+  const ConvtRoute r = route_convt(d, 2, convt_y_side_ok(g, dy));
+  const bool mfma = r.kind == ConvtKind::MfmaF32;
+  const int64_t nblk = (int64_t)d->Cin * d->Cout * d->k * d->k * d->k;   // Direct: one block per (c, o, tap)
+  M355_REQUIRE(mfma || nblk < (1ll << 31), M355_EUNSUPPORTED, "conv_transpose3d_bwd_weight: grid too large");
+  M355_REQUIRE(!mfma || (workspace && workspace_bytes >= r.slab_bytes), M355_EWORKSPACE,
+               "conv_transpose3d_bwd_weight: workspace too small (%zu < %zu)", workspace_bytes, r.slab_bytes);
+  M355_REQUIRE(!dbias || (workspace && workspace_bytes >= r.workspace_bytes), M355_EWORKSPACE,
+               "conv_transpose3d_bwd_weight: workspace too small for the bias gradient");
+  void* bias_ws = dbias ? (char*)workspace + r.dbias_offset : nullptr;
+  if (mfma) {
+    launch_convt_bww_mfma(r, d, g, x, dy, dw, dbias, (float*)workspace, (double*)bias_ws, st);
   } else {
-    const int k3 = d->k * d->k * d->k;
-    const int64_t nblk = (int64_t)d->Cin * d->Cout * k3;
-    M355_REQUIRE(nblk < (1ll << 31), M355_EUNSUPPORTED, "conv_transpose3d_bwd_weight: grid too large");
-    hipLaunchKernelGGL(convt_direct_bwd_weight_kernel, dim3((unsigned)nblk), dim3(256), 0, st, x, dy,
-                       dw, d->N, d->Cin, d->Cout, d->D, d->H, d->W, OD, OH, OW, d->k, d->stride,
-                       d->pad, xbs, ybs);
-  }
-  if (dbias) {
-    M355_REQUIRE(workspace && workspace_bytes >= convt_slab_bytes(d) + convt_dbias_bytes(d), M355_EWORKSPACE,
-                 "conv_transpose3d_bwd_weight: workspace too small for the bias gradient");
-    launch_dbias(dy, dbias, d->N, d->Cout, (int64_t)OD * OH * OW, ybs, (char*)workspace + convt_slab_bytes(d), st);
+    hipLaunchKernelGGL(convt_direct_bwd_weight_kernel, dim3((unsigned)nblk), dim3(256), 0, st, x, dy, dw, d->N, d->Cin,
+                       d->Cout, d->D, d->H, d->W, g.OD, g.OH, g.OW, d->k, d->stride, d->pad, g.xbs, g.ybs);
+    if (dbias) launch_dbias(dy, dbias, d->N, d->Cout, (int64_t)g.OD * g.OH * g.OW, g.ybs, bias_ws, st);
   }
   return check_launch("conv_transpose3d_bwd_weight");
 }
 
-// ---------------------------------------------------------------- c8 backward entry points (16-bit training flow)
-static bool convt_c8_bwd_ok(const m355_conv3d_desc* d) {
-  // the MFMA kernels: k2 s2, all weights of an m-tile group within 64 KB of A fragments, 32-bit buffer offsets
+// ---- c8 entry points (16-bit training flow) ----
+// What the three share: descriptor, pointers, compute mode, route, workspace, and the x-side / y-side c8 tensors with
+// their batch strides (0 = dense; resolved in place), in the order the error codes have always had.
+static int validate_convt_c8(const char* who, const m355_conv3d_desc* d, const ConvtRoute& r, bool pointers, const void* xs,
+                             int64_t* xbs, const void* ys, int64_t* ybs, int32_t compute, size_t workspace_bytes,
+                             const char* unsupported) {
+  M355_REQUIRE(pointers, M355_EINVALID_ARG, "%s: null pointer", who);
+  M355_REQUIRE(compute == M355_COMPUTE_BF16 || compute == M355_COMPUTE_F16, M355_EINVALID_ARG,
+               "%s: compute must be M355_COMPUTE_BF16 or M355_COMPUTE_F16", who);
+  M355_REQUIRE(r.kind != ConvtKind::Unsupported, M355_EUNSUPPORTED, "%s: %s", who, unsupported);
+  M355_REQUIRE(workspace_bytes >= r.workspace_bytes, M355_EWORKSPACE, "%s: workspace too small (%zu < %zu)", who,
+               workspace_bytes, r.workspace_bytes);
   const int64_t S = (int64_t)d->D * d->H * d->W;
-  return is_k2s2(d) && 8 * ceil_div(c8_blocks(d->Cout), 2) <= 64 && S * 8 * 16 * 4 < (1ll << 31) &&
-         S * 16 * std::min<int64_t>(16, c8_blocks(d->Cin)) < (1ll << 31);
+  *xbs = dense_or(*xbs, c8_blocks(d->Cin) * S * 8);
+  *ybs = dense_or(*ybs, c8_blocks(d->Cout) * S * 8 * 8);
+  M355_REQUIRE((((uintptr_t)xs | (uintptr_t)ys) & 15) == 0 && *xbs % 8 == 0 && *ybs % 8 == 0, M355_EINVALID_ARG,
+               "%s: c8 tensor not 16B aligned", who);
+  return M355_OK;
 }
-static int convt_c8_ct(const m355_conv3d_desc* d) { const int ct = (int)ceil_div(d->Cin, 32); return ct >= 4 ? 4 : (ct >= 2 ? 2 : 1); }
-static int convt_c8_nsplit(const m355_conv3d_desc* d) {
-  const int64_t ntiles = (int64_t)d->N * d->D * ceil_div(d->H, 2) * ceil_div(d->W, 32);
-  const int64_t groups = ceil_div(d->Cout, 32) * ceil_div(ceil_div(d->Cin, 32), convt_c8_ct(d));
-  // (every split writes a slab of 8 * Cin * Cout floats that the reduction reads again: one workgroup per CU)
-  const int64_t wgs = (int64_t)(tuning().convt_wgs ? tuning().convt_wgs : 1) * num_cus();
-  return (int)std::max<int64_t>(1, std::min<int64_t>(ntiles, wgs / groups));
-}
+static const char* const CONVT_C8_BWD_UNSUPPORTED =
+    "only kernel_size 2 / stride 2 / padding 0 with Cout <= 128 and below 2^22 voxels per sample has a c8 kernel "
+    "(m355_conv_transpose3d_h16_bwd_supported)";
 
-extern "C" int32_t m355_conv_transpose3d_h16_bwd_supported(const m355_conv3d_desc* d) {
-  return d && d->N > 0 && d->Cin > 0 && d->Cout > 0 && d->D > 0 && d->H > 0 && d->W > 0 && convt_c8_bwd_ok(d) ? 1 : 0;
-}
-
-extern "C" size_t m355_conv_transpose3d_h16_bwd_workspace(const m355_conv3d_desc* d) {
-  if (!d || !m355_conv_transpose3d_h16_bwd_supported(d)) return 0;
-  const int64_t OS = (int64_t)d->D * d->H * d->W * 8;
-  return (size_t)round_up((int64_t)convt_c8_nsplit(d) * 8 * d->Cin * d->Cout * 4, 256) + dbias_c8_ws_bytes(d->N, d->Cout, OS);
+extern "C" int m355_conv_transpose3d_fwd_h16(const m355_conv3d_desc* d, const void* x16, int64_t x16_batch_stride,
+                                             const float* w, const float* bias, void* y16, int64_t y16_batch_stride,
+                                             int32_t compute, void* stream) {
+  const char* who = "conv_transpose3d_fwd_h16";
+  if (int rc = validate_convt(d, who)) return rc;
+  const ConvtRoute r = route_convt_c8(d, 0);
+  if (int rc = validate_convt_c8(who, d, r, x16 && w && y16, x16, &x16_batch_stride, y16, &y16_batch_stride, compute, 0,
+                                 "only kernel_size 2 / stride 2 / padding 0 with Cin <= 512 and below 2^31 output elements "
+                                 "per sample has a c8 kernel"))
+    return rc;
+  launch_convt_fwd_c8(r, d, x16, x16_batch_stride, w, bias, y16, y16_batch_stride, compute, (hipStream_t)stream);
+  return check_launch(r.kind == ConvtKind::H16 ? "convt_k2s2_fwd_h16" : "convt_k2s2_fwd_c8");
 }
 
 extern "C" int m355_conv_transpose3d_bwd_data_h16(const m355_conv3d_desc* d, const void* dy16, int64_t dy16_batch_stride,
                                                   const float* w, void* dx16, int64_t dx16_batch_stride, int32_t compute,
                                                   void* stream) {
-  if (int rc = validate_convt(d, "conv_transpose3d_bwd_data_h16")) return rc;
-  M355_REQUIRE(dy16 && w && dx16, M355_EINVALID_ARG, "conv_transpose3d_bwd_data_h16: null pointer");
-  M355_REQUIRE(compute == M355_COMPUTE_BF16 || compute == M355_COMPUTE_F16, M355_EINVALID_ARG,
-               "conv_transpose3d_bwd_data_h16: compute must be M355_COMPUTE_BF16 or M355_COMPUTE_F16");
-  M355_REQUIRE(convt_c8_bwd_ok(d), M355_EUNSUPPORTED,
-               "conv_transpose3d_bwd_data_h16: only kernel_size 2 / stride 2 / padding 0 with Cout <= 128 has a c8 kernel "
-               "(m355_conv_transpose3d_h16_bwd_supported)");
-  const int64_t S = (int64_t)d->D * d->H * d->W;
-  const int64_t ybs = dense_or(dy16_batch_stride, c8_blocks(d->Cout) * S * 8 * 8);
-  const int64_t xbs = dense_or(dx16_batch_stride, c8_blocks(d->Cin) * S * 8);
-  M355_REQUIRE((((uintptr_t)dy16 | (uintptr_t)dx16) & 15) == 0 && xbs % 8 == 0 && ybs % 8 == 0, M355_EINVALID_ARG,
-               "conv_transpose3d_bwd_data_h16: c8 tensor not 16B aligned");
-  hipStream_t st = (hipStream_t)stream;
-  const int nks = 8 * (int)ceil_div(c8_blocks(d->Cout), 2);
-  const int mtiles = (int)ceil_div(d->Cin, 32);
-  int mt_per_wg = std::max(1, std::min(std::min(mtiles, 64 / nks), 4));
-  if (mt_per_wg == 3) mt_per_wg = 2;
-  const int groups = (int)ceil_div(mtiles, mt_per_wg);
-  const int64_t vox_tiles = ceil_div(S, 128);
-  // one residency of workgroups (2 per CU), each walking its share of the voxel tiles: the weights are staged once
-  const int64_t wgs = (int64_t)(tuning().convt_wgs ? tuning().convt_wgs : 2) * num_cus();
-  // (weights are staged per workgroup: at least four voxel tiles each on the small levels)
-  const int gx = (int)std::max<int64_t>(1, std::min<int64_t>(ceil_div(vox_tiles, 4), ceil_div(wgs, (int64_t)groups * d->N)));
-  dim3 grid((unsigned)gx, (unsigned)groups, (unsigned)d->N);
-  const size_t lds = (size_t)mt_per_wg * nks * 1024;
-#define M355_CTBD(HT, MTW)                                                                                            \
-  hipLaunchKernelGGL((convt_k2s2_bwd_data_h16_kernel<HT, MTW>), grid, dim3(256), lds, st, (const HT*)dy16, w, (HT*)dx16, \
-                     d->Cin, d->Cout, d->D, d->H, d->W, ybs, xbs, mt_per_wg,                                      \
-                     compute == M355_COMPUTE_F16 ? overflow_flag() : nullptr)
-#define M355_CTBD_T(HT)                                                  \
-  if (mt_per_wg == 1) M355_CTBD(HT, 1); else if (mt_per_wg == 2) M355_CTBD(HT, 2); else M355_CTBD(HT, 4);
-  if (compute == M355_COMPUTE_BF16) { M355_CTBD_T(__bf16) } else { M355_CTBD_T(_Float16) }
-#undef M355_CTBD_T
-#undef M355_CTBD
+  const char* who = "conv_transpose3d_bwd_data_h16";
+  if (int rc = validate_convt(d, who)) return rc;
+  const ConvtRoute r = route_convt_c8(d, 1);
+  if (int rc = validate_convt_c8(who, d, r, dy16 && w && dx16, dx16, &dx16_batch_stride, dy16, &dy16_batch_stride, compute,
+                                 0, CONVT_C8_BWD_UNSUPPORTED))
+    return rc;
+  launch_convt_bwd_data_h16(r, d, dy16, dy16_batch_stride, w, dx16, dx16_batch_stride, compute, (hipStream_t)stream);
   return check_launch("convt_k2s2_bwd_data_h16");
 }
 
@@ -1445,38 +1521,18 @@ extern "C" int m355_conv_transpose3d_bwd_weight_h16(const m355_conv3d_desc* d, c
                                                     const void* dy16, int64_t dy16_batch_stride, float* dw, float* dbias,
                                                     float grad_unscale, int32_t compute, void* workspace,
                                                     size_t workspace_bytes, void* stream) {
-  if (int rc = validate_convt(d, "conv_transpose3d_bwd_weight_h16")) return rc;
-  M355_REQUIRE(x16 && dy16 && dw && workspace, M355_EINVALID_ARG, "conv_transpose3d_bwd_weight_h16: null pointer");
-  M355_REQUIRE(compute == M355_COMPUTE_BF16 || compute == M355_COMPUTE_F16, M355_EINVALID_ARG,
-               "conv_transpose3d_bwd_weight_h16: compute must be M355_COMPUTE_BF16 or M355_COMPUTE_F16");
-  M355_REQUIRE(convt_c8_bwd_ok(d), M355_EUNSUPPORTED,
-               "conv_transpose3d_bwd_weight_h16: unsupported geometry (m355_conv_transpose3d_h16_bwd_supported)");
-  M355_REQUIRE(workspace_bytes >= m355_conv_transpose3d_h16_bwd_workspace(d), M355_EWORKSPACE,
-               "conv_transpose3d_bwd_weight_h16: workspace too small (%zu < %zu)", workspace_bytes,
-               m355_conv_transpose3d_h16_bwd_workspace(d));
-  const int64_t S = (int64_t)d->D * d->H * d->W;
-  const int64_t xbs = dense_or(x16_batch_stride, c8_blocks(d->Cin) * S * 8);
-  const int64_t ybs = dense_or(dy16_batch_stride, c8_blocks(d->Cout) * S * 8 * 8);
-  M355_REQUIRE((((uintptr_t)x16 | (uintptr_t)dy16) & 15) == 0 && xbs % 8 == 0 && ybs % 8 == 0, M355_EINVALID_ARG,
-               "conv_transpose3d_bwd_weight_h16: c8 tensor not 16B aligned");
+  const char* who = "conv_transpose3d_bwd_weight_h16";
+  if (int rc = validate_convt(d, who)) return rc;
+  const ConvtRoute r = route_convt_c8(d, 2);
+  if (int rc = validate_convt_c8(who, d, r, x16 && dy16 && dw && workspace, x16, &x16_batch_stride, dy16, &dy16_batch_stride,
+                                 compute, workspace_bytes, CONVT_C8_BWD_UNSUPPORTED))
+    return rc;
   hipStream_t st = (hipStream_t)stream;
-  const int ct = convt_c8_ct(d), nsplit = convt_c8_nsplit(d);
-  const int cgroups = (int)ceil_div(ceil_div(d->Cin, 32), ct);
-  float* slab = (float*)workspace;
-  dim3 grid((unsigned)nsplit, (unsigned)ceil_div(d->Cout, 32), (unsigned)cgroups);
-#define M355_CTBW(HT, CT)                                                                                               \
-  hipLaunchKernelGGL((convt_k2s2_bww_c8_kernel<HT, CT>), grid, dim3(256), 0, st, (const HT*)x16, (const HT*)dy16, slab,  \
-                     d->N, d->Cin, d->Cout, d->D, d->H, d->W, xbs, ybs, nsplit, cgroups)
-#define M355_CTBW_T(HT) if (ct == 1) M355_CTBW(HT, 1); else if (ct == 2) M355_CTBW(HT, 2); else M355_CTBW(HT, 4);
-  if (compute == M355_COMPUTE_BF16) { M355_CTBW_T(__bf16) } else { M355_CTBW_T(_Float16) }
-#undef M355_CTBW_T
-#undef M355_CTBW
-  const int64_t total = (int64_t)d->Cin * d->Cout * 8;
-  hipLaunchKernelGGL(convt_slab_reduce_t_kernel, dim3((unsigned)ceil_div(total, 64)), dim3(256), 0, st, slab, dw, d->Cin,
-                     d->Cout, nsplit, grad_unscale, overflow_flag());
+  launch_convt_bww_c8(r, d, x16, x16_batch_stride, dy16, dy16_batch_stride, dw, grad_unscale, compute, (float*)workspace, st);
   if (dbias) {
-    const size_t slab_b = (size_t)round_up((int64_t)nsplit * 8 * d->Cin * d->Cout * 4, 256);
-    if (int rc = launch_dbias_c8(dy16, ybs, dbias, d->N, d->Cout, S * 8, compute, grad_unscale, (char*)workspace + slab_b, st))
+    const int64_t OS = (int64_t)d->D * d->H * d->W * 8;
+    if (int rc = launch_dbias_c8(dy16, dy16_batch_stride, dbias, d->N, d->Cout, OS, compute, grad_unscale,
+                                 (char*)workspace + r.dbias_offset, st))
       return rc;
   }
   return check_launch("conv_transpose3d_bwd_weight_h16");

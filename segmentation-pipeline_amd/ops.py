@@ -1066,6 +1066,16 @@ class _PoolC8Fn(torch.autograd.Function):
         return dx16, None, None, None
 
 
+def _convt_c8_fwd(x: Act16, weight, bias, y16: Act16):
+    """The c8 -> c8 launch of nn.ConvTranspose3d(kernel_size=2, stride=2) into y16; returns the descriptor."""
+    _require(weight, bias)
+    N, Cin, D, H, W = x.shape
+    d = _conv_desc(N, Cin, weight.shape[1], D, H, W, 2, 2, 0, 0, 0)
+    check(_lib.lib().m355_conv_transpose3d_fwd_h16(C.byref(d), x.ptr(), x.batch_stride(), _p(weight), _p(bias), y16.ptr(),
+                                                   y16.batch_stride(), x.compute, _stream()), "conv_transpose3d_fwd_h16")
+    return d
+
+
 class _ConvTC8Fn(torch.autograd.Function):
     """nn.ConvTranspose3d(kernel_size=2, stride=2) of the c8 training flow: c8 -> c8 straight into its concat slot;
     backward on the 16-bit MFMA from c8 operands where the library has the kernels (Cout <= 128), else through the
@@ -1073,17 +1083,12 @@ class _ConvTC8Fn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x_t, weight, bias, x: Act16, y16: Act16):
-        L = _lib.lib()
-        _require(weight, bias)
         weight = weight.contiguous()
         N, Cin, D, H, W = x.shape
         Cout = weight.shape[1]
         if y16.shape != (N, Cout, 2 * D, 2 * H, 2 * W):
             raise _lib.M355Error(f"c8 slot shape {y16.shape} != op output shape {(N, Cout, 2 * D, 2 * H, 2 * W)}")
-        d = _conv_desc(N, Cin, Cout, D, H, W, 2, 2, 0, 0, 0)
-        check(L.m355_conv_transpose3d_fwd_h16(C.byref(d), x.ptr(), x.batch_stride(), _p(weight), _p(bias), y16.ptr(),
-                                              y16.batch_stride(), x.compute, _stream()), "conv_transpose3d_fwd_h16")
-        ctx.desc, ctx.compute, ctx.has_bias = d, x.compute, bias is not None
+        ctx.desc, ctx.compute, ctx.has_bias = _convt_c8_fwd(x, weight, bias, y16), x.compute, bias is not None
         ctx.gs = _gs()
         ctx.save_for_backward(x.alias(), weight)
         return y16.alias()
@@ -1424,16 +1429,11 @@ def conv_transpose3d(x, weight, bias=None, stride=2, padding=0, output_padding=0
                     y16 = Act16.empty(N, weight.shape[1], (2 * D, 2 * H, 2 * W), x.compute, x.device)
                 t = _ConvTC8Fn.apply(x.t, weight, bias, x, y16)
                 return Act16(y16.data, y16.C, y16.spatial, y16.compute, y16.cb0, t)
-            _require(weight, bias)
-            N, Cin, D, H, W = x.shape
-            Cout = weight.shape[1]
             y16 = out.act16() if (out is not None and out.buf16 is not None) else None
             if y16 is None:
-                y16 = Act16.empty(N, Cout, (2 * D, 2 * H, 2 * W), x.compute, x.device)
-            d = _conv_desc(N, Cin, Cout, D, H, W, 2, 2, 0, 0, 0)
-            check(_lib.lib().m355_conv_transpose3d_fwd_h16(C.byref(d), x.ptr(), x.batch_stride(), _p(weight.contiguous()),
-                                                           _p(bias), y16.ptr(), y16.batch_stride(), x.compute, _stream()),
-                  "conv_transpose3d_fwd_h16")
+                N, Cin, D, H, W = x.shape
+                y16 = Act16.empty(N, weight.shape[1], (2 * D, 2 * H, 2 * W), x.compute, x.device)
+            _convt_c8_fwd(x, weight.contiguous(), bias, y16)
             return y16
         y = _ConvT3dFn.apply(x.to_f32(), weight, bias, (k, stride, padding, output_padding, None))
         return _into_c8_slot(y, out, x.compute)

@@ -300,6 +300,14 @@ class RawOps:
         self._chk(self.lib.m355_conv3d_plan(C.byref(d), which, out), "conv3d_plan")
         return tuple(out)
 
+    def convt_plan(self, x_shape, Cout, k=2, stride=2, pad=0, out_pad=0, compute=0, which=0, xbs=0, ybs=0, y_side=None):
+        """(kernel family, three numbers of its launch) of a conv-transpose call (m355_conv_transpose3d_plan; which 0..2 the
+        fp32 entry points, 3..5 the c8 ones).  y_side: the y / dy tensor or Slot the call would get (None: aligned)"""
+        d = self.conv_desc(x_shape, Cout, k, stride, pad, out_pad, xbs=xbs, ybs=ybs, compute=compute)
+        out = (C.c_int32 * 4)()
+        self._chk(self.lib.m355_conv_transpose3d_plan(C.byref(d), which, _p(y_side), out), "conv_transpose3d_plan")
+        return tuple(out)
+
     def conv3d_fwd_h16(self, x16, Cin, spatial, w, bias=None, add=None, compute=1, groups=None, eps=1e-5, softmax=False,
                        out=None):
         """forward on a c8 input; groups != None also returns the fused statistics (mean, rstd); softmax: the

@@ -448,15 +448,21 @@ CONVT = [
     # N, Cin, Cout, D, H, W, k, s, p, out_pad
     (1, 64, 64, 4, 4, 8, 2, 2, 0, 0),
     (2, 5, 7, 3, 5, 6, 2, 2, 0, 0),     # ragged channel tiles
-    (1, 320, 48, 2, 2, 2, 2, 2, 0, 0),
+    (1, 320, 48, 2, 2, 2, 2, 2, 0, 0),  # 8 voxels: the data gradient splits K = 8 * Cout
     (1, 8, 8, 4, 4, 4, 4, 2, 1, 0),     # BlurConvTranspose3d geometry
     (1, 3, 4, 3, 3, 3, 3, 2, 1, 1),
+    (1, 520, 8, 2, 2, 2, 2, 2, 0, 0),   # Cin > 512: no forward x tile fits 64 KB of LDS; the gradients keep none there
 ]
+# kernel family of fwd / bwd_data / bwd_weight (m355_conv_transpose3d_plan: 1 fp32 MFMA, 0 direct), in the order of CONVT
+CONVT_FAMILIES = [(1, 1, 1), (1, 1, 1), (1, 1, 1), (0, 0, 0), (0, 0, 0), (0, 1, 1)]
 
 
 @pytest.mark.parametrize("case", CONVT)
 def test_conv_transpose3d_fwd_bwd(hip, oracle, case):
     N, Ci, Co, D, H, W, k, s, p, op = case
+    plans = [hip.convt_plan((N, Ci, D, H, W), Co, k, s, p, op, which=which) for which in (0, 1, 2)]
+    assert tuple(pl[0] for pl in plans) == CONVT_FAMILIES[CONVT.index(case)], plans
+    assert Ci != 320 or plans[1][3] > 1, f"splits of the data gradient's K: {plans[1]}"
     x, w, b = rnd(N, Ci, D, H, W, seed=1), rnd(Ci, Co, k, k, k, seed=2) * (1.0 / Ci ** 0.5), rnd(Co, seed=3)
     yo = oracle.convt_fwd(x, w, b, s, p, op)
     close(hip.convt_fwd(x, w, b, s, p, op), yo, what="fwd")

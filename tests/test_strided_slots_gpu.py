@@ -30,10 +30,11 @@ Host / kernel branches on a stride or a pointer (file:line, condition, who takes
   conv3d.hip:2014   gen2 needs dy 4-byte aligned                                        always true for fp32 tensors
   conv3d_host.hip:691/699/800, conv3d_h16.hip:1084/1090   c8 REQUIREs (16 B, % 8): act16_pack / _unpack, conv3d_bwd_weight_h16 / _c8,
                     the conv3d h16 forward / data gradient                               test_c8_conv3d, test_act16_pack_unpack | test_c8_rejects_misaligned_slots (each by name)
-  convt.hip:1195    k2 s2 forward MFMA kernel: ybs % 2 == 0, y 8-B aligned               test_conv_transpose3d[aligned, offset2 | odd (ybs odd), offset1, n1]
-  convt.hip:1293    k2 s2 data gradient, same condition on dy                           test_conv_transpose3d (same ids)
-  convt.hip:1337    k2 s2 weight gradient, same condition on dy                         test_conv_transpose3d (same ids)
-  convt.hip:1239/1417/1460   c8 REQUIREs: conv-transpose fwd / bwd_data / bwd_weight h16 test_c8_conv_transpose | test_c8_rejects_misaligned_slots (each by name)
+  convt.hip convt_y_side_ok -> route_convt   k2 s2 forward: ConvtKind MfmaF32 / X3 needs ybs % 2 == 0, y 8-B aligned, else Direct
+                                                                                        test_conv_transpose3d[aligned, offset2 | odd (ybs odd), offset1, n1]
+                    ... data gradient (MfmaF32 | Direct), same condition on dy          test_conv_transpose3d (same ids)
+                    ... weight gradient (MfmaF32 | Direct), same condition on dy        test_conv_transpose3d (same ids)
+  convt.hip validate_convt_c8   c8 REQUIREs: conv-transpose fwd / bwd_data / bwd_weight h16  test_c8_conv_transpose | test_c8_rejects_misaligned_slots (each by name)
   norm.hip:470-474  vec_ok: S % 4, xbs / ybs / abs % 4, x / y / add 16-B aligned         test_norm[aligned S%4==0 | odd, offset*, S odd]
   norm.hip:511,737  statistics: len % 4, S % 4, xbs % 4, x aligned                      test_norm (same ids); 737 (m355_norm_sums, synchronised BN) launches the same two kernels from the same condition
                     and has no raw_ops wrapper: untested here, test_distributed_gpu.py runs it dense
@@ -303,9 +304,11 @@ CONVT = [
 @pytest.mark.parametrize("case", CONVT, ids=["k2s2-ragged", "k2s2-64", "k4s2p1", "k3s2p1op1"])
 def test_conv_transpose3d(hip, oracle, case, cls):
     """m355_conv_transpose3d_fwd (F32 and, k2 s2, F32X3) / _bwd_data / _bwd_weight.  k2 s2 runs on the MFMA kernels when
-    ybs % 2 == 0 and the y-side pointer is 8-byte aligned (convt.hip:1195, 1293, 1337): classes aligned, offset2; an odd
-    ybs ("odd": the output's S is a multiple of 8, so the stride is made odd with `extra` elements) and a 4-byte
-    aligned pointer ("offset1", "n1") push the same shapes onto the direct kernels -- same tolerance either way."""
+    ybs % 2 == 0 and the y-side pointer is 8-byte aligned (convt_y_side_ok, the one fact route_convt takes from the
+    call): classes aligned, offset2; an odd ybs ("odd": the output's S is a multiple of 8, so the stride is made odd with
+    `extra` elements) and a 4-byte aligned pointer ("offset1", "n1") push the same shapes onto the direct kernels -- same
+    tolerance either way.  m355_conv_transpose3d_plan, given each call's own y / dy slot, must name that side for all
+    three entry points: family 1 (MfmaF32) or 2 (X3) against 0 (Direct)."""
     ci, co, D, H, W, k, s, p, op = case
     N = nb(cls)
     xsh = (N, ci, D, H, W)
@@ -317,15 +320,28 @@ def test_conv_transpose3d(hip, oracle, case, cls):
         ly = layout(cls, co, unit_of(ysh), 1)
         ybs = (ly["c_pre"] + co + ly["c_post"]) * unit_of(ysh) + ly["extra"]
         mfma = ybs % 2 == 0 and (4 * (ly["lead"] + ly["c_pre"] * unit_of(ysh))) % 8 == 0
-        assert mfma == (cls in ("aligned", "offset2")), "which side of convt.hip:1195 this class takes"
+        assert mfma == (cls in ("aligned", "offset2")), "which side of convt_y_side_ok this class takes"
+    families = []
+
+    def planned(o, which, y_side, compute=0):
+        """notes the family the library plans for the call that gets the slot `y_side` (the dense repeat has none)"""
+        if isinstance(y_side, Slot):
+            families.append((which, compute, o.convt_plan(xsh, co, k, s, p, op, compute, which, ybs=y_side.bs, y_side=y_side)[0]))
+
     for compute in ((0, X3) if k == 2 else (0,)):
-        (y,) = run(hip, cls, lambda o, i, out: o.convt_fwd(i[0], w, b, s, p, op, compute=compute, out=out[0]), [(x, 0)],
-                   [(ysh, 1)], f"convt_fwd compute {compute}")
+        (y,) = run(hip, cls, lambda o, i, out: (planned(o, 0, out[0], compute),
+                                                o.convt_fwd(i[0], w, b, s, p, op, compute=compute, out=out[0]))[1],
+                   [(x, 0)], [(ysh, 1)], f"convt_fwd compute {compute}")
         close(y, yo, what="fwd")
-    (dx,) = run(hip, cls, lambda o, i, out: o.convt_bwd_data(i[0], w, xsh, s, p, op, out=out[0]), [(dy, 1)], [(xsh, 0)],
-                "convt_bwd_data")
+    (dx,) = run(hip, cls, lambda o, i, out: (planned(o, 1, i[0]), o.convt_bwd_data(i[0], w, xsh, s, p, op, out=out[0]))[1],
+                [(dy, 1)], [(xsh, 0)], "convt_bwd_data")
     close(dx, oracle.convt_bwd_data(dy, w, xsh, s, p, op), what="bwd_data")
-    dw, db = run(hip, cls, lambda o, i, out: o.convt_bwd_weight(i[0], i[1], k, s, p, op), [(x, 0), (dy, 1)], [], "convt_bwd_weight")
+    dw, db = run(hip, cls, lambda o, i, out: (planned(o, 2, i[1]), o.convt_bwd_weight(i[0], i[1], k, s, p, op))[1],
+                 [(x, 0), (dy, 1)], [], "convt_bwd_weight")
+    assert sorted(f[:2] for f in families) == [(0, 0)] + [(0, X3)] * (k == 2) + [(1, 0), (2, 0)]
+    for which, compute, family in families:
+        assert (family in (1, 2)) == (k == 2 and mfma) and (family == 0) != (k == 2 and mfma), (which, compute, family)
+        assert family != 2 or (which == 0 and compute == X3), (which, compute, family)
     dwo, dbo = oracle.convt_bwd_weight(x, dy, k, s, p, op)
     close(dw, dwo, 3e-5, 1e-4, what="bwd_weight")
     close(db, dbo, 3e-5, 1e-4, what="dbias")

@@ -7,7 +7,12 @@ Pure host code: runs without a GPU (num_cus() is then 256, the MI355X's count). 
 to another route, workspace size or plan code gives the same hash before and after; M355_LIB_PATH points the run at
 another build of the library.
 
-usage: python tools/conv_routes.py [--hash-only] [--jobs N] > routes.txt"""
+--convt: the same for the conv-transpose routes (csrc/convt.hip): per line the three queries (workspace, h16_bwd_supported,
+h16_bwd_workspace), m355_conv_transpose3d_plan for which = 0..5 with an aligned y side, and for which = 0..2 with a y side
+at a 4-byte offset.  Two hashes: "queries" covers the three queries alone, so it can be compared with a library that
+predates the plan query (it then is the only one printed), "routes" covers the whole lines.
+
+usage: python tools/conv_routes.py [--convt] [--hash-only] [--jobs N] > routes.txt"""
 import argparse
 import ctypes as C
 import hashlib
@@ -36,6 +41,73 @@ def descriptors():
         yield (n, ci, co) + vol + (3, 1, 1, comp)
     for ksp, vol, ci, co, n, comp in itertools.product(NON_K3, VOLUMES[:3], CHANNELS, CHANNELS, (1, 2), range(4)):
         yield (n, ci, co) + vol + ksp + (comp,)
+
+
+# ---- --convt ----
+CONVT_GEOMS = [(2, 2, 0, 0), (2, 2, 0, 1), (2, 1, 0, 0), (4, 2, 1, 0), (3, 2, 1, 1)]   # (k, stride, pad, out_pad)
+# (Cin, Cout, volume): each side of convt_fits_i32, of the c8 gradients' 32-bit offsets and channel limit, and of the
+# h16 forward's 16384 voxels and 128 input channels
+CONVT_GUARDS = [(8, 8, (256, 256, 511)), (8, 8, (256, 256, 512)), (8, 8, (128, 128, 255)), (8, 8, (128, 128, 256)),
+                (256, 8, (128, 128, 255)), (256, 8, (128, 128, 256)),
+                *[(32, co, (16, 16, 16)) for co in (128, 129, 136, 137)],
+                *[(ci, 32, vol) for ci in (128, 129) for vol in ((16, 32, 31), (16, 32, 32), (16, 32, 33))]]
+
+
+def convt_descriptors():
+    """(N, Cin, Cout, D, H, W, k, stride, pad, out_pad, compute)"""
+    for geom, vol, ci, co, n, comp in itertools.product(CONVT_GEOMS, VOLUMES, CHANNELS, CHANNELS, (1, 2), range(4)):
+        yield (n, ci, co) + vol + geom + (comp,)
+    for geom, (ci, co, vol), n, comp in itertools.product(CONVT_GEOMS[:2], CONVT_GUARDS, (1, 2), range(4)):
+        yield (n, ci, co) + vol + geom + (comp,)
+
+
+CONVT_TUNING_SETS = [{}, {"M355_CONVT_H16": "0"}, {"M355_CONVT_WGS": "1"}, {"M355_CONVT_WGS": "2"}, {"M355_F32X3": "0"},
+                     {"M355_F32X3_CONVT": "0"}]
+
+
+def run_convt_set(idx):
+    """(index, line count, query-only text, whole text) of one conv-transpose tuning set."""
+    env = CONVT_TUNING_SETS[idx]
+    for k in [k for k in os.environ if k.startswith("M355_") and k != "M355_LIB_PATH"]:
+        del os.environ[k]
+    os.environ.update(env)
+    from segmentation_pipeline_amd import _lib
+    L = _lib.lib()
+    _lib.reload_tuning()
+    plan = getattr(L, "m355_conv_transpose3d_plan", None)   # None: a library from before the plan query
+    tag = ",".join(f"{k[5:]}={v}" for k, v in sorted(env.items())) or "default"
+    d = _lib.ConvDesc()
+    ref = C.byref(d)
+    out4 = (C.c_int32 * 4)()
+    queries = [L.m355_conv_transpose3d_workspace, L.m355_conv_transpose3d_h16_bwd_supported,
+               L.m355_conv_transpose3d_h16_bwd_workspace]
+    qlines, lines = [], []
+    for (d.N, d.Cin, d.Cout, d.D, d.H, d.W, d.k, d.stride, d.pad, d.out_pad, d.compute) in convt_descriptors():
+        f = [tag, f"N{d.N} {d.Cin}->{d.Cout} {d.D}x{d.H}x{d.W} k{d.k}s{d.stride}p{d.pad}o{d.out_pad} c{d.compute}",
+             "ws/h16_bwd/h16_bwd_ws=" + "/".join(str(q(ref)) for q in queries)]
+        qlines.append(" ".join(f))
+        if plan:
+            for which, y_side in [(w, None) for w in range(6)] + [(w, 4) for w in range(3)]:
+                rc = plan(ref, which, y_side, out4)
+                f.append(f"plan{which}{'+4' if y_side else ''}={rc}:" + "/".join(str(v) for v in out4))
+            lines.append(" ".join(f))
+    return idx, len(qlines), "\n".join(qlines) + "\n", "\n".join(lines) + "\n" if plan else None
+
+
+def convt_main(a):
+    queries, routes, n, have_plan = hashlib.sha256(), hashlib.sha256(), 0, True
+    with multiprocessing.get_context("spawn").Pool(a.jobs, maxtasksperchild=1) as pool:
+        for idx, count, qtext, text in pool.imap(run_convt_set, range(len(CONVT_TUNING_SETS))):
+            have_plan = have_plan and text is not None
+            if a.hash_only:
+                print(f"set {idx:2d} {count} queries {hashlib.sha256(qtext.encode()).hexdigest()}"
+                      + (f" routes {hashlib.sha256(text.encode()).hexdigest()}" if text else ""), flush=True)
+            else:
+                sys.stdout.write(text or qtext)
+            queries.update(qtext.encode())
+            routes.update((text or "").encode())
+            n += count
+    print(f"lines {n} queries sha256 {queries.hexdigest()}" + (f" routes sha256 {routes.hexdigest()}" if have_plan else ""))
 
 
 def _e(**kw):
@@ -112,7 +184,10 @@ def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--hash-only", action="store_true", help="print no lines, only one hash per tuning set and the total")
     ap.add_argument("--jobs", type=int, default=min(8, os.cpu_count() or 1))
+    ap.add_argument("--convt", action="store_true", help="the conv-transpose routes (two hashes: queries, routes)")
     a = ap.parse_args()
+    if a.convt:
+        return convt_main(a)
     total, n = hashlib.sha256(), 0
     with multiprocessing.get_context("spawn").Pool(a.jobs, maxtasksperchild=1) as pool:
         for idx, count, text in pool.imap(run_set, range(len(TUNING_SETS))):
