@@ -511,6 +511,31 @@ int m355_avgpool3d_2x_bwd_add(const float* dy, const float* add, float* dx, int3
                               int64_t dy_batch_stride, int64_t add_batch_stride, int64_t dx_batch_stride,
                               void* stream);
 
+/* nn.MaxPool3d(kernel_size=2, stride=2) (downsample_class of ModularUNet): D, H, W even (M355_EUNSUPPORTED otherwise,
+ * as m355_avgpool3d_2x_fwd).  torch's semantics: the 2x2x2 window is scanned in (d, h, w) order from max = -inf,
+ * index = first, updating on `v > max || isnan(v)` -- ties go to the first maximum, a NaN window returns NaN and
+ * routes to its last NaN; y holds the selected element's bits.
+ * idx: the route, uint8 [N, C, D/2, H/2, W/2] dense, window position 0..7 = (dd * 2 + dh) * 2 + dw; may be NULL
+ * (inference).  Batch strides in elements, 0 = dense.  Wide accesses only where pointers and strides prove the
+ * alignment; any 4-byte aligned channel slice is accepted. */
+int m355_maxpool3d_2x_fwd(const float* x, float* y, uint8_t* idx, int32_t N, int32_t C, int32_t D, int32_t H, int32_t W,
+                          int64_t x_batch_stride, int64_t y_batch_stride, void* stream);
+/* dx[v] = (idx[v/2] == position of v in its window ? dy[v/2] : 0) + (add ? add[v] : 0); D, H, W: the UN-pooled size.
+ * A pure gather: x is not read, every dx element is written exactly once, no atomics (deterministic).  `add` (may be
+ * NULL): the skip gradient, as in m355_avgpool3d_2x_bwd_add. */
+int m355_maxpool3d_2x_bwd(const float* dy, const uint8_t* idx, const float* add, float* dx, int32_t N, int32_t C,
+                          int32_t D, int32_t H, int32_t W, int64_t dy_batch_stride, int64_t add_batch_stride,
+                          int64_t dx_batch_stride, void* stream);
+/* c8 -> c8; idx8: uint8 [N, ceil(C/8), S/8, 8] dense (8-byte aligned), may be NULL.  The comparison runs on the 16-bit
+ * values; lanes past C are written as zero. */
+int m355_maxpool3d_2x_fwd_h16(const void* x16, void* y16, uint8_t* idx8, int32_t N, int32_t C, int32_t D, int32_t H,
+                              int32_t W, int64_t x16_batch_stride, int64_t y16_batch_stride, int32_t compute, void* stream);
+/* dx16[v] = dskip16[v] (may be NULL) + routed dpool16, rounded once; fp16 saturates into the overflow word (bit 0) as
+ * m355_avgpool3d_2x_bwd_h16 does.  D, H, W: the UN-pooled size. */
+int m355_maxpool3d_2x_bwd_h16(const void* dpool16, const uint8_t* idx8, const void* dskip16, void* dx16, int32_t N,
+                              int32_t C, int32_t D, int32_t H, int32_t W, int64_t dpool16_batch_stride,
+                              int64_t dskip16_batch_stride, int64_t dx16_batch_stride, int32_t compute, void* stream);
+
 /* ------------------------------------------------------------- upsampling
  * nn.Upsample(scale_factor=2, mode='trilinear', align_corners=True)
  * (models/modular_unet.py:20,39,80,96).  D,H,W = input size; output = 2x.

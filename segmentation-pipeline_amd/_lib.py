@@ -208,6 +208,10 @@ SIGNATURES = {
     "m355_avgpool3d_2x_fwd": (C.c_int, [_P, _P, _i32, _i32, _i32, _i32, _i32, _i64, _i64, _P]),
     "m355_avgpool3d_2x_bwd": (C.c_int, [_P, _P, _i32, _i32, _i32, _i32, _i32, _i64, _i64, _P]),
     "m355_avgpool3d_2x_bwd_add": (C.c_int, [_P, _P, _P, _i32, _i32, _i32, _i32, _i32, _i64, _i64, _i64, _P]),
+    "m355_maxpool3d_2x_fwd": (C.c_int, [_P, _P, _P, _i32, _i32, _i32, _i32, _i32, _i64, _i64, _P]),
+    "m355_maxpool3d_2x_bwd": (C.c_int, [_P, _P, _P, _P, _i32, _i32, _i32, _i32, _i32, _i64, _i64, _i64, _P]),
+    "m355_maxpool3d_2x_fwd_h16": (C.c_int, [_P, _P, _P, _i32, _i32, _i32, _i32, _i32, _i64, _i64, _i32, _P]),
+    "m355_maxpool3d_2x_bwd_h16": (C.c_int, [_P, _P, _P, _P, _i32, _i32, _i32, _i32, _i32, _i64, _i64, _i64, _i32, _P]),
     "m355_upsample_trilinear2x_fwd": (C.c_int, [_P, _P, _i32, _i32, _i32, _i32, _i32, _i64, _i64, _P]),
     "m355_upsample_trilinear2x_bwd": (C.c_int, [_P, _P, _i32, _i32, _i32, _i32, _i32, _i64, _i64, _P]),
     "m355_softmax_fwd": (C.c_int, [_P, _P, _i32, _i32, _i32, _i64, _f32, _P]),

@@ -24,6 +24,17 @@ def _run_downsample(m, x):
         if k != 2 or s != 2 or _uniform_int(m.padding, "padding") != 0 or m.ceil_mode:
             raise NotImplementedError("only AvgPool3d(kernel_size=2, stride=2) has a HIP kernel")
         return None if x is None else ops.avgpool3d_2x(x)
+    if isinstance(m, nn.MaxPool3d):
+        try:
+            ok = (_uniform_int(m.kernel_size, "kernel_size") == 2
+                  and _uniform_int(m.kernel_size if m.stride is None else m.stride, "stride") == 2
+                  and _uniform_int(m.padding, "padding") == 0 and _uniform_int(m.dilation, "dilation") == 1
+                  and not m.ceil_mode and not m.return_indices)
+        except (NotImplementedError, ValueError, TypeError):
+            ok = False
+        if not ok:
+            raise NotImplementedError("only MaxPool3d(kernel_size=2, stride=2) has a HIP kernel")
+        return None if x is None else ops.maxpool3d_2x(x)
     if isinstance(m, BlurConv3d):
         return m(x)      # (a c8 activation of the 16-bit flows stays c8: space-to-depth and the conv run on c8)
     if isinstance(m, nn.Conv3d):  # WSConv3d / strided nn.Conv3d
@@ -180,10 +191,13 @@ class ModularUNet(nn.Module):
                 x = self.down_blocks[i](x, out=slot, pool=True) if fuse_pool else self.down_blocks[i](x, out=slot)
                 if isinstance(x, tuple):
                     x_skip, x = x      # AvgPool3d(2, 2) came out of the block's last norm + activation pass
-                elif (isinstance(self.downsampling[i], nn.AvgPool3d) and isinstance(x, (torch.Tensor, ops.Act16))
-                        and x.requires_grad and torch.is_grad_enabled()):
+                elif (isinstance(self.downsampling[i], (nn.AvgPool3d, nn.MaxPool3d))
+                        and isinstance(x, (torch.Tensor, ops.Act16)) and x.requires_grad and torch.is_grad_enabled()):
                     _run_downsample(self.downsampling[i], None)          # validates the module's geometry
-                    x_skip, x = ops.avgpool3d_2x_with_skip(x)            # one fused gradient for both uses
+                    if isinstance(self.downsampling[i], nn.MaxPool3d):   # (fuse_pool above stays average-only)
+                        x_skip, x = ops.maxpool3d_2x_with_skip(x)
+                    else:
+                        x_skip, x = ops.avgpool3d_2x_with_skip(x)        # one fused gradient for both uses
                 else:
                     x_skip = x
                     x = _run_downsample(self.downsampling[i], x)

@@ -1820,6 +1820,142 @@ def avgpool3d_2x(x, out: Optional[OutSlot] = None):
     return _AvgPoolFn.apply(x, out)
 
 
+# nn.MaxPool3d(2, 2) (csrc/maxpool.hip): the forward leaves a route byte per pooled element (window position 0..7 of
+# torch's argmax, ties / NaN included), the backward is a gather through it.  The route tensor comes from the caching
+# allocator and lives on ctx; it is not allocated when nothing will run backward (no_grad, the c8 no-grad flow).
+def _maxpool_fwd(x, y, ybs, route):
+    xd, xbs = _dense_channels(x)
+    N, Cc, D, H, W = xd.shape
+    idx = torch.empty((N, Cc, D // 2, H // 2, W // 2), dtype=torch.uint8, device=x.device) if route else None
+    check(_lib.lib().m355_maxpool3d_2x_fwd(_p(xd), _p(y), _p(idx), N, Cc, D, H, W, xbs, ybs, _stream()), "maxpool3d_2x_fwd")
+    return idx
+
+
+def _tracks(x):
+    return torch.is_grad_enabled() and x.requires_grad
+
+
+def _maxpool_bwd(ctx, g_pool, g_skip):
+    N, Cc, D, H, W = ctx.shape
+    g_pool, gpbs = _dense_channels(g_pool)
+    gsbs = 0
+    if g_skip is not None:
+        g_skip, gsbs = _dense_channels(g_skip)
+    dx = torch.empty(ctx.shape, dtype=g_pool.dtype, device=g_pool.device)
+    check(_lib.lib().m355_maxpool3d_2x_bwd(_p(g_pool), _p(ctx.idx), _p(g_skip), _p(dx), N, Cc, D, H, W, gpbs, gsbs, 0,
+                                           _stream()), "maxpool3d_2x_bwd")
+    return dx
+
+
+class _MaxPoolFn(torch.autograd.Function):
+    # route: autograd was recording at .apply and x carries a gradient (inside forward grad mode is always off, and
+    # ctx.needs_input_grad stays True under no_grad for a tensor that requires grad)
+    @staticmethod
+    def forward(ctx, x, out, route):
+        _require(x)
+        N, Cc, D, H, W = x.shape
+        y = _alloc_out(out, (N, Cc, D // 2, H // 2, W // 2), x)
+        y, ybs = _dense_channels(y)
+        ctx.idx = _maxpool_fwd(x, y, ybs, route)
+        ctx.shape = (N, Cc, D, H, W)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        return _maxpool_bwd(ctx, dy, None), None, None
+
+
+class _MaxPoolSkipFn(torch.autograd.Function):
+    """MaxPool3d(2, 2) of a tensor that ALSO continues as a skip connection: (skip alias, pooled), and one backward pass
+    for the sum of both gradients (m355_maxpool3d_2x_bwd with `add`), as _PoolSkipFn does for the average pool."""
+
+    @staticmethod
+    def forward(ctx, x, route):
+        _require(x)
+        N, Cc, D, H, W = x.shape
+        y = torch.empty((N, Cc, D // 2, H // 2, W // 2), dtype=x.dtype, device=x.device)
+        ctx.idx = _maxpool_fwd(x, y, 0, route)
+        ctx.shape = (N, Cc, D, H, W)
+        return x.view_as(x), y
+
+    @staticmethod
+    def backward(ctx, g_skip, g_pool):
+        if g_pool is None:
+            return g_skip, None
+        return _maxpool_bwd(ctx, g_pool, g_skip), None
+
+
+class _MaxPoolC8Fn(torch.autograd.Function):
+    """nn.MaxPool3d(2, 2) c8 -> c8 of the c8 training flow, modelled on _PoolC8Fn (skip=True: also returns the input as
+    it continues into the skip connection); the route is one byte per lane of the pooled items"""
+
+    @staticmethod
+    def forward(ctx, x_t, x: Act16, y16: Act16, skip: bool):
+        N, Cc, D, H, W = x.shape
+        idx8 = torch.empty((N, x.CB, y16.S, 8), dtype=torch.uint8, device=x.device)
+        check(_lib.lib().m355_maxpool3d_2x_fwd_h16(x.ptr(), y16.ptr(), _p(idx8), N, Cc, D, H, W, x.batch_stride(),
+                                                   y16.batch_stride(), x.compute, _stream()), "maxpool3d_2x_fwd_h16")
+        ctx.info = (N, Cc, D, H, W, x.compute)
+        ctx.idx8 = idx8
+        if x.compute == _lib.COMPUTE_F16:
+            # the backward's sum with the skip gradient reports its saturation in the overflow word.  _PoolC8Fn leaves
+            # installing it to a neighbouring node (_UnpackFn, the c8 conv); this op is also used on its own
+            # (pack -> pool -> backward), where no other node would
+            _overflow_word(x.device)
+        return (x_t.view_as(x_t), y16.alias()) if skip else y16.alias()
+
+    @staticmethod
+    def backward(ctx, *grads):
+        N, Cc, D, H, W, compute = ctx.info
+        g_skip, g_pool = (grads if len(grads) == 2 else (None, grads[0]))
+        if g_pool is None:
+            return g_skip, None, None, None
+        g_pool, pbs = _c8t(g_pool)
+        sbs = 0
+        if g_skip is not None:
+            g_skip, sbs = _c8t(g_skip)
+        dx16 = torch.empty((N, (Cc + 7) // 8, D * H * W, 8), dtype=_DT16[compute], device=g_pool.device)
+        check(_lib.lib().m355_maxpool3d_2x_bwd_h16(_p(g_pool), _p(ctx.idx8), _p(g_skip), _p(dx16), N, Cc, D, H, W, pbs, sbs, 0,
+                                                   compute, _stream()), "maxpool3d_2x_bwd_h16")
+        return dx16, None, None, None
+
+
+def _maxpool_c8_slot(x: Act16, out: Optional[OutSlot]) -> Act16:
+    N, Cc, D, H, W = x.shape
+    y16 = out.act16() if out is not None else None
+    if y16 is None:
+        return Act16.empty(N, Cc, (D // 2, H // 2, W // 2), x.compute, x.device)
+    if y16.shape != (N, Cc, D // 2, H // 2, W // 2):
+        raise _lib.M355Error(f"c8 slot shape {y16.shape} != op output shape {(N, Cc, D // 2, H // 2, W // 2)}")
+    return y16
+
+
+def maxpool3d_2x_with_skip(x, out: Optional[OutSlot] = None):
+    """-> (x as it continues into the skip connection, MaxPool3d(2, 2)(x)); see _MaxPoolSkipFn.  `out` (c8 flow): the
+    pooled tensor is written into this concat slot."""
+    if isinstance(x, Act16):
+        if not _act16_tracks(x):
+            return x, maxpool3d_2x(x, out)
+        y16 = _maxpool_c8_slot(x, out)
+        skip_t, pooled_t = _MaxPoolC8Fn.apply(x.t, x, y16, True)
+        return (Act16(x.data, x.C, x.spatial, x.compute, x.cb0, skip_t),
+                Act16(y16.data, y16.C, y16.spatial, y16.compute, y16.cb0, pooled_t))
+    return _MaxPoolSkipFn.apply(x, _tracks(x))
+
+
+def maxpool3d_2x(x, out: Optional[OutSlot] = None):
+    """nn.MaxPool3d(kernel_size=2, stride=2), torch's tie / NaN routing; c8 -> c8 in the 16-bit flows."""
+    if isinstance(x, Act16):
+        N, Cc, D, H, W = x.shape
+        y16 = _maxpool_c8_slot(x, out)
+        if _act16_tracks(x):
+            return Act16(y16.data, y16.C, y16.spatial, y16.compute, y16.cb0, _MaxPoolC8Fn.apply(x.t, x, y16, False))
+        check(_lib.lib().m355_maxpool3d_2x_fwd_h16(x.ptr(), y16.ptr(), None, N, Cc, D, H, W, x.batch_stride(),
+                                                   y16.batch_stride(), x.compute, _stream()), "maxpool3d_2x_fwd_h16")
+        return y16
+    return _MaxPoolFn.apply(x, out, _tracks(x))
+
+
 class _UpsampleFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, out):
