@@ -310,6 +310,21 @@ typedef struct m355_norm_desc {
 int64_t m355_norm_num_stats(const m355_norm_desc* d);
 size_t m355_norm_workspace(const m355_norm_desc* d);
 
+/* Introspection, as m355_conv3d_plan: how a normalisation pass of this descriptor is launched.  which = the pass:
+ *   0 statistics (m355_norm_stats, m355_norm_sums)    1 forward fp32      2 forward fp32 -> c8 (m355_norm_act_fwd_h16)
+ *   3 forward c8 -> c8     4 forward with pooled second output     5 / 6 backward pass 1 / pass 2, fp32
+ *   7 backward pass 2 with a c8 twin of dx (m355_norm_act_bwd_h16)        8 / 9 backward pass 1 / pass 2, c8
+ * out[0] = 1 when the pass takes its vector kernel (float4 rows; which = 2: four voxels per thread in flight; 0 where the
+ * pass has one kernel only), judged with every pointer 16-byte aligned -- a call on a pointer that is not takes the scalar
+ * kernel; out[1] = chunks per statistic (which = 0) or per channel (5, 8) of the first-stage partial sums, else 0;
+ * out[2] = grid.x; out[3] = byte offset of stat_m[num_stats][2] (float) behind the backward's partials in the workspace
+ * (which >= 5, else 0; saturates at INT32_MAX): m355_norm_workspace(desc) covers the largest such offset + 8 * num_stats.
+ * Returns M355_EINVALID_ARG for a null desc / out4, an unknown pass or a descriptor the pass's entry point rejects with that
+ * code, M355_EUNSUPPORTED where that entry point would (N or C > 65535 on the fp32 passes).  The descriptor carries no
+ * D, H, W, so which = 4 answers for any S, although m355_norm_act_pool_fwd itself needs D * H * W == S, all even.
+ * Pure host function. */
+int m355_norm_plan(const m355_norm_desc* d, int32_t which, int32_t* out4);
+
 /* Pass 1: mean[s], rstd[s] (biased variance, 1/sqrt(var+eps)).  For BN in
  * training mode running_mean/running_var (may be NULL) are updated in place
  * with `momentum` and the UNBIASED variance, as torch does. */

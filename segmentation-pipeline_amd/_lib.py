@@ -194,6 +194,7 @@ SIGNATURES = {
     "m355_conv_transpose3d_fwd_h16": (C.c_int, [_CD, _P, _i64, _P, _P, _P, _i64, _i32, _P]),
     "m355_norm_num_stats": (_i64, [_ND]),
     "m355_norm_workspace": (_sz, [_ND]),
+    "m355_norm_plan": (C.c_int, [_ND, _i32, C.POINTER(C.c_int32)]),
     "m355_norm_stats": (C.c_int, [_ND, _P, _P, _P, _P, _P, _f32, _P, _sz, _P]),
     "m355_norm_stats_from_partials": (C.c_int, [_ND, _P, _i64, _P, _P, _P, _P, _f32, _P, _sz, _P]),
     "m355_norm_stats_from_running": (C.c_int, [_ND, _P, _P, _P, _P, _P]),

@@ -5,7 +5,7 @@
 // Reference ops replaced: normalization_class + activation_class inside Block3d
 // (models/components.py:52-55, + the residual sum :67-68) and nn.AvgPool3d(2, 2)
 // (models/modular_unet.py:22,41,64,92), for the data flow conv -> norm/act -> conv under BASELINE cfg3 / cfg5.
-#include "h16.hpp"
+#include "norm_host.hpp"
 
 namespace m355 {
 
@@ -162,18 +162,15 @@ __global__ __launch_bounds__(256) void norm_bwd_apply_c8_kernel(
   report_saturation(sat, oflag);
 }
 
-int launch_norm_bwd_apply_c8(const float* x, const float* dy, const float* mean, const float* rstd, const float* gamma,
-                             const float* beta, const float* stat_m, float* dx, void* dx16, int N, int C, int64_t S,
-                             int groups, int act, float slope, int64_t xbs, int64_t ybs, int64_t dx16bs, int compute,
-                             hipStream_t st) {
-  const unsigned bx = (unsigned)std::max<int64_t>(1, std::min<int64_t>(ceil_div(S, 256 * 2), 1024));
-  dim3 grid(bx, (unsigned)c8_blocks(C), (unsigned)N);
-  if (compute == M355_COMPUTE_BF16)
-    hipLaunchKernelGGL(norm_bwd_apply_c8_kernel<__bf16>, grid, dim3(256), 0, st, x, dy, mean, rstd, gamma, beta, stat_m, dx,
-                       (__bf16*)dx16, C, S, groups, act, slope, xbs, ybs, dx16bs, nullptr);
-  else
-    hipLaunchKernelGGL(norm_bwd_apply_c8_kernel<_Float16>, grid, dim3(256), 0, st, x, dy, mean, rstd, gamma, beta, stat_m,
-                       dx, (_Float16*)dx16, C, S, groups, act, slope, xbs, ybs, dx16bs, overflow_flag());
+int launch_norm_bwd_apply_c8(const m355_norm_desc* d, const NormPlan& p, const float* x, const float* dy, const float* mean,
+                             const float* rstd, const float* gamma, const float* beta, const float* stat_m, float* dx,
+                             void* dx16, int64_t dx16bs, int compute, hipStream_t st) {
+  with_h16(compute, [&](auto T) {
+    typedef typename decltype(T)::type HT;   // (bf16 has fp32's range: nothing to clamp, no overflow word)
+    hipLaunchKernelGGL(norm_bwd_apply_c8_kernel<HT>, norm_pass(d, p, NORM_BWD2_H16).grid, dim3(256), 0, st, x, dy, mean, rstd,
+                       gamma, beta, stat_m, dx, (HT*)dx16, d->C, d->S, d->groups, d->act, d->act_slope, p.xbs, p.ybs, dx16bs,
+                       std::is_same<HT, __bf16>::value ? nullptr : overflow_flag());
+  });
   return check_launch("norm_bwd_apply_c8");
 }
 
@@ -314,31 +311,20 @@ extern "C" int m355_norm_act_fwd_h16(const m355_norm_desc* d, const float* x, co
                                      const float* gamma, const float* beta, const float* add, float* y,
                                      void* y16, int64_t y16_batch_stride, int32_t compute, void* stream) {
   M355_REQUIRE(d && x && mean && rstd && y16, M355_EINVALID_ARG, "norm_act_fwd_h16: null pointer");
-  M355_REQUIRE(d->N > 0 && d->C > 0 && d->S > 0 && d->N <= 65535 && c8_blocks(d->C) <= 65535, M355_EINVALID_ARG,
-               "norm_act_fwd_h16: bad shape");
-  M355_REQUIRE(d->groups >= 0 && (d->groups == 0 || d->C % d->groups == 0), M355_EINVALID_ARG,
-               "norm_act_fwd_h16: C=%d not divisible by groups=%d", d->C, d->groups);
-  M355_REQUIRE(compute == M355_COMPUTE_BF16 || compute == M355_COMPUTE_F16, M355_EINVALID_ARG,
-               "norm_act_fwd_h16: compute must be M355_COMPUTE_BF16 or M355_COMPUTE_F16");
-  const int64_t CS = (int64_t)d->C * d->S;
-  const int64_t xbs = dense_or(d->x_batch_stride, CS), ybs = dense_or(d->y_batch_stride, CS);
-  const int64_t abs_ = dense_or(d->add_batch_stride, CS);
-  const int64_t y16bs = dense_or(y16_batch_stride, c8_blocks(d->C) * d->S * 8);
+  if (int rc = validate_norm(d, "norm_act_fwd_h16", NORM_F32_C8)) return rc;
+  if (int rc = check_h16("norm_act_fwd_h16", compute)) return rc;
+  const NormPlan p = plan_norm(d, NORM_F32_C8);
+  const int64_t y16bs = p.bs16(y16_batch_stride);
   M355_REQUIRE(((uintptr_t)y16 & 15) == 0 && y16bs % 8 == 0, M355_EINVALID_ARG, "norm_act_fwd_h16: c8 tensor not 16B aligned");
-  auto al16 = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
-  (void)al16;
-  const bool vec = d->S >= 4096;   // large tensors: four voxels per thread in flight
-  dim3 grid((unsigned)std::max<int64_t>(1, std::min<int64_t>(ceil_div(d->S, 256 * (vec ? 4 : 1)), 2048)),
-            (unsigned)c8_blocks(d->C), (unsigned)d->N);
-#define M355_NA16(HT, V)                                                                                             \
-  hipLaunchKernelGGL((norm_act_fwd_c8_kernel<HT, V>), grid, dim3(256), 0, (hipStream_t)stream, x, mean, rstd, gamma, \
-                     beta, add, y, (HT*)y16, d->C, d->S, d->groups, d->act, d->act_slope, xbs, ybs, abs_, y16bs)
-  if (compute == M355_COMPUTE_BF16) {
-    if (vec) M355_NA16(__bf16, true); else M355_NA16(__bf16, false);
-  } else {
-    if (vec) M355_NA16(_Float16, true); else M355_NA16(_Float16, false);
-  }
-#undef M355_NA16
+  const NormLaunch L = norm_pass(d, p, NORM_FWD_H16);
+  with_h16(compute, [&](auto T) {
+    typedef typename decltype(T)::type HT;
+    with_bool(L.vec, [&](auto V) {
+      hipLaunchKernelGGL((norm_act_fwd_c8_kernel<HT, decltype(V)::value>), L.grid, dim3(256), 0, (hipStream_t)stream, x, mean,
+                         rstd, gamma, beta, add, y, (HT*)y16, d->C, d->S, d->groups, d->act, d->act_slope, p.xbs, p.ybs, p.abs_,
+                         y16bs);
+    });
+  });
   return check_launch("norm_act_fwd_h16");
 }
 
@@ -367,38 +353,23 @@ extern "C" int m355_avgpool3d_2x_fwd_h16(const void* x16, void* y16, int32_t N, 
   return check_launch("avgpool3d_2x_fwd_h16");
 }
 
-static int check_c8_args(const char* who, const m355_norm_desc* d, int32_t compute) {
-  M355_REQUIRE(d, M355_EINVALID_ARG, "%s: null descriptor", who);
-  M355_REQUIRE(d->N > 0 && d->C > 0 && d->S > 0 && d->N <= 65535 && c8_blocks(d->C) <= 65535, M355_EINVALID_ARG,
-               "%s: bad shape", who);
-  M355_REQUIRE(d->groups >= 0 && (d->groups == 0 || d->C % d->groups == 0), M355_EINVALID_ARG,
-               "%s: C=%d not divisible by groups=%d", who, d->C, d->groups);
-  M355_REQUIRE(compute == M355_COMPUTE_BF16 || compute == M355_COMPUTE_F16, M355_EINVALID_ARG,
-               "%s: compute must be M355_COMPUTE_BF16 or M355_COMPUTE_F16", who);
-  return M355_OK;
-}
-
 extern "C" int m355_norm_act_fwd_c8(const m355_norm_desc* d, const void* x16, int64_t x16_batch_stride,
                                     const float* mean, const float* rstd, const float* gamma, const float* beta,
                                     const void* add16, int64_t add16_batch_stride, void* y16,
                                     int64_t y16_batch_stride, int32_t compute, void* stream) {
-  if (int rc = check_c8_args("norm_act_fwd_c8", d, compute)) return rc;
+  if (int rc = validate_norm(d, "norm_act_fwd_c8", NORM_C8)) return rc;
+  if (int rc = check_h16("norm_act_fwd_c8", compute)) return rc;
   M355_REQUIRE(x16 && mean && rstd && y16, M355_EINVALID_ARG, "norm_act_fwd_c8: null pointer");
-  const int64_t dense = c8_blocks(d->C) * d->S * 8;
-  const int64_t xbs = dense_or(x16_batch_stride, dense), abs_ = dense_or(add16_batch_stride, dense);
-  const int64_t ybs = dense_or(y16_batch_stride, dense);
+  const NormPlan p = plan_norm(d, NORM_C8);
+  const int64_t xbs = p.bs16(x16_batch_stride), abs_ = p.bs16(add16_batch_stride), ybs = p.bs16(y16_batch_stride);
   M355_REQUIRE((((uintptr_t)x16 | (uintptr_t)y16 | (uintptr_t)add16) & 15) == 0 && xbs % 8 == 0 && ybs % 8 == 0 &&
                    abs_ % 8 == 0, M355_EINVALID_ARG, "norm_act_fwd_c8: c8 tensor not 16B aligned");
-  dim3 grid((unsigned)std::max<int64_t>(1, std::min<int64_t>(ceil_div(d->S, 256 * 4), 2048)), (unsigned)c8_blocks(d->C),
-            (unsigned)d->N);
-  if (compute == M355_COMPUTE_BF16)
-    hipLaunchKernelGGL(norm_act_c8c8_kernel<__bf16>, grid, dim3(256), 0, (hipStream_t)stream, (const __bf16*)x16, mean,
-                       rstd, gamma, beta, (const __bf16*)add16, (__bf16*)y16, d->C, d->S, d->groups, d->act,
+  with_h16(compute, [&](auto T) {
+    typedef typename decltype(T)::type HT;
+    hipLaunchKernelGGL(norm_act_c8c8_kernel<HT>, norm_pass(d, p, NORM_FWD_C8).grid, dim3(256), 0, (hipStream_t)stream,
+                       (const HT*)x16, mean, rstd, gamma, beta, (const HT*)add16, (HT*)y16, d->C, d->S, d->groups, d->act,
                        d->act_slope, xbs, abs_, ybs);
-  else
-    hipLaunchKernelGGL(norm_act_c8c8_kernel<_Float16>, grid, dim3(256), 0, (hipStream_t)stream, (const _Float16*)x16,
-                       mean, rstd, gamma, beta, (const _Float16*)add16, (_Float16*)y16, d->C, d->S, d->groups, d->act,
-                       d->act_slope, xbs, abs_, ybs);
+  });
   return check_launch("norm_act_fwd_c8");
 }
 

@@ -72,17 +72,9 @@ int launch_pack_act16(const float* x, void* x16, int N, int C, int64_t S, int64_
 int launch_unpack_act16(const void* x16, float* x, int N, int C, int64_t S, int64_t x16bs, int64_t xbs, int compute,
                         hipStream_t st);
 
-// second pass of the normalisation backward that also emits dx as c8 (act16.hip; used by m355_norm_act_bwd_h16)
-int launch_norm_bwd_apply_c8(const float* x, const float* dy, const float* mean, const float* rstd, const float* gamma,
-                             const float* beta, const float* stat_m, float* dx, void* dx16, int N, int C, int64_t S,
-                             int groups, int act, float slope, int64_t xbs, int64_t ybs, int64_t dx16bs, int compute,
-                             hipStream_t st);
+// (the launchers the normalisation passes share across files: norm_host.hpp)
 
-// c8-only training flow (train16.hip / norm.hip): finalize stage of the normalisation backward shared by the fp32 and c8
-// first passes; bias gradient of a conv from its c8 output gradient
-int launch_norm_bwd_reduce(const double* partial, const float* gamma, float* dgamma, float* dbeta, float* stat_m, int N,
-                           int C, int groups, int64_t S, int training, float grad_unscale, hipStream_t st,
-                           const double* count_ptr = nullptr);
+// c8-only training flow (train16.hip): bias gradient of a conv from its c8 output gradient
 size_t dbias_c8_ws_bytes(int N, int C, int64_t S);
 int launch_dbias_c8(const void* dy16, int64_t dybs16, float* dbias, int N, int C, int64_t S, int compute, float unscale,
                     void* ws, hipStream_t st);

@@ -11,34 +11,9 @@
 // short runs, combined in double -> partial[s][blk][2]; a finalize kernel sums
 // the partials in fixed order.  Pass 2 (apply): float4 streaming, one (n,c)
 // channel chunk per block so gamma/beta/mean/rstd are block-uniform.
-#include "common.hpp"
-#include "h16.hpp"
+#include "norm_host.hpp"
 
 namespace m355 {
-
-struct NormGeom {
-  int64_t nstats;  // number of statistics
-  int64_t runs;    // runs per statistic
-  int64_t len;     // elements per run
-  int64_t count;   // runs * len
-  int nblk;        // blocks per statistic
-};
-
-static NormGeom geom(const m355_norm_desc* d) {
-  NormGeom g;
-  if (d->groups == 0) {
-    g.nstats = d->C;
-    g.runs = d->N;
-    g.len = d->S;
-  } else {
-    g.nstats = (int64_t)d->N * d->groups;
-    g.runs = 1;
-    g.len = (int64_t)(d->C / d->groups) * d->S;
-  }
-  g.count = g.runs * g.len;
-  g.nblk = (int)ceil_div(g.count, NORM_CHUNK);
-  return g;
-}
 
 __device__ __forceinline__ int64_t stat_base(int64_t s, int64_t run, int groups, int C, int64_t S,
                                              int64_t xbs, int64_t len) {
@@ -455,23 +430,109 @@ __global__ __launch_bounds__(256) void norm_bwd_apply_kernel(
   }
 }
 
-static int validate_norm(const m355_norm_desc* d, const char* who) {
-  M355_REQUIRE(d != nullptr, M355_EINVALID_ARG, "%s: null descriptor", who);
-  M355_REQUIRE(d->N > 0 && d->C > 0 && d->S > 0, M355_EINVALID_ARG, "%s: non-positive size", who);
-  M355_REQUIRE(d->groups >= 0 && (d->groups == 0 || d->C % d->groups == 0), M355_EINVALID_ARG,
-               "%s: C=%d not divisible by groups=%d", who, d->C, d->groups);
-  M355_REQUIRE(d->act >= M355_ACT_NONE && d->act <= M355_ACT_LEAKY_RELU, M355_EINVALID_ARG,
-               "%s: bad activation %d", who, d->act);
-  M355_REQUIRE(d->N <= 65535 && d->C <= 65535, M355_EUNSUPPORTED, "%s: N or C > 65535", who);
+// ---------------------------------------------------------------- host half
+// Every entry point: validate, plan (norm_host.hpp), check the workspace against the plan, launch.  Each kernel of this
+// file is launched from exactly one function.
+
+static void launch_partial(const m355_norm_desc* d, const NormPlan& p, const float* x, double* partial, hipStream_t st) {
+  const NormLaunch L = norm_pass(d, p, NORM_STATS, (uintptr_t)x);
+  with_bool(L.vec, [&](auto V) {
+    hipLaunchKernelGGL(norm_partial_kernel<decltype(V)::value>, L.grid, dim3(256), 0, st, x, partial, d->groups, d->C, d->S,
+                       p.xbs, p.runs, p.len, L.nblk);
+  });
+}
+
+// statistics from the conv epilogue partials [N][slots][C][2]: items per statistic, and the blocks that share them in
+// the two-launch reduction (~2048 items each, never more than the statistics partials of the plan hold)
+static int64_t partials_items(const m355_norm_desc* d, int64_t slots) {
+  return (d->groups == 0 ? (int64_t)d->N : 1) * slots * (d->groups == 0 ? 1 : d->C / d->groups);
+}
+static int launch_from_partials(const m355_norm_desc* d, const NormPlan& p, const float* part, int64_t slots, double* partial,
+                                hipStream_t st) {
+  const int nblk = (int)std::max<int64_t>(1, std::min<int64_t>(p.nblk, ceil_div(partials_items(d, slots), 2048)));
+  hipLaunchKernelGGL(norm_from_partials_kernel, dim3((unsigned)nblk, (unsigned)p.nstats), dim3(256), 0, st, part, partial,
+                     d->groups, d->N, d->C, slots, nblk);
+  return nblk;
+}
+
+// mean / rstd (+ running statistics) from nblk partials per statistic; count_ptr: see norm_finalize_kernel
+static void launch_finalize(const m355_norm_desc* d, const NormPlan& p, const double* partial, int nblk, float* mean,
+                            float* rstd, float* running_mean, float* running_var, float momentum, const double* count_ptr,
+                            hipStream_t st) {
+  hipLaunchKernelGGL(norm_finalize_kernel, dim3((unsigned)p.nstats), dim3(64), 0, st, partial, mean, rstd, running_mean,
+                     running_var, momentum, d->eps, p.nstats, nblk, p.count, count_ptr);
+}
+
+// what the statistics entry points check after their pointers, in this order
+static int check_stats(const m355_norm_desc* d, const NormPlan& p, const char* who, size_t workspace_bytes, bool running) {
+  M355_REQUIRE(workspace_bytes >= p.workspace_bytes, M355_EWORKSPACE, "%s: workspace too small", who);
+  M355_REQUIRE(d->groups == 0 || !running, M355_EINVALID_ARG, "%s: running statistics are only defined for batch norm", who);
+  M355_REQUIRE(p.nstats <= 65535, M355_EUNSUPPORTED, "%s: too many statistics", who);
   return M355_OK;
 }
 
-static bool vec_ok(const m355_norm_desc* d, const void* a, const void* b, const void* c) {
-  auto al = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
-  const int64_t xbs = dense_or(d->x_batch_stride, (int64_t)d->C * d->S);
-  const int64_t ybs = dense_or(d->y_batch_stride, (int64_t)d->C * d->S);
-  const int64_t abs_ = dense_or(d->add_batch_stride, (int64_t)d->C * d->S);
-  return (d->S % 4 == 0) && (xbs % 4 == 0) && (ybs % 4 == 0) && (abs_ % 4 == 0) && al(a) && al(b) && (!c || al(c));
+int launch_norm_bwd_reduce(const m355_norm_desc* d, const NormPlan& p, const double* partial, const float* gamma, float* dgamma,
+                           float* dbeta, float* stat_m, int training, const double* count_ptr, float grad_unscale, int* oflag,
+                           hipStream_t st) {
+  hipLaunchKernelGGL(norm_bwd_reduce_kernel, dim3((unsigned)std::max<int64_t>(p.nstats, d->C)), dim3(64), 0, st, partial,
+                     gamma, dgamma, dbeta, stat_m, d->N, d->C, d->groups, p.bwd().nblk, p.count, training, count_ptr,
+                     grad_unscale, oflag);
+  return check_launch("norm_bwd_reduce");
+}
+
+// first half of the fp32 backward: partial sums + reduction -> stat_m[s][2] (means of dxhat and dxhat*xhat), dgamma,
+// dbeta.  stat_m may be the caller's buffer (synchronised batch norm: all-reduced before the second half).
+static int bwd_reduce_half(const m355_norm_desc* d, const NormPlan& p, const float* x, const float* dy, const float* mean,
+                           const float* rstd, const float* gamma, const float* beta, float* dgamma, float* dbeta, int training,
+                           const double* count_ptr, float* stat_m, void* workspace, size_t workspace_bytes, hipStream_t st,
+                           const char* who) {
+  M355_REQUIRE(x && dy && mean && rstd && workspace && stat_m, M355_EINVALID_ARG, "%s: null pointer", who);
+  M355_REQUIRE(workspace_bytes >= p.workspace_bytes, M355_EWORKSPACE, "%s: workspace too small", who);
+  const NormLaunch L = norm_pass(d, p, NORM_BWD1, (uintptr_t)x | (uintptr_t)dy);
+  with_bool(L.vec, [&](auto V) {
+    hipLaunchKernelGGL(norm_bwd_partial_kernel<decltype(V)::value>, L.grid, dim3(256), 0, st, x, dy, mean, rstd, gamma, beta,
+                       p.partial(workspace), d->C, d->S, d->groups, d->act, d->act_slope, p.xbs, p.ybs, L.nblk);
+  });
+  return launch_norm_bwd_reduce(d, p, p.partial(workspace), gamma, dgamma, dbeta, stat_m, training, count_ptr, 1.f, nullptr, st);
+}
+
+// second half: dx (and, dx16 != null, its c8 twin in the same pass) from x, dy and the per-statistic means
+static int bwd_apply_half(const m355_norm_desc* d, const NormPlan& p, const float* x, const float* dy, const float* mean,
+                          const float* rstd, const float* gamma, const float* beta, const float* stat_m, float* dx, void* dx16,
+                          int64_t dx16_batch_stride, int compute, hipStream_t st, const char* who) {
+  M355_REQUIRE(x && dy && mean && rstd && dx && stat_m, M355_EINVALID_ARG, "%s: null pointer", who);
+  if (dx16)
+    return launch_norm_bwd_apply_c8(d, p, x, dy, mean, rstd, gamma, beta, stat_m, dx, dx16, p.bs16(dx16_batch_stride), compute,
+                                    st);
+  const NormLaunch L = norm_pass(d, p, NORM_BWD2, (uintptr_t)x | (uintptr_t)dy | (uintptr_t)dx);
+  with_bool(L.vec, [&](auto V) {
+    hipLaunchKernelGGL(norm_bwd_apply_kernel<decltype(V)::value>, L.grid, dim3(256), 0, st, x, dy, mean, rstd, gamma, beta,
+                       stat_m, dx, d->C, d->S, d->groups, d->act, d->act_slope, p.xbs, p.ybs);
+  });
+  return check_launch(who);
+}
+
+// what m355_norm_act_bwd_h16 / _bwd_apply ask of a c8 twin of dx
+static bool dx16_ok(const void* dx16, int64_t dx16_batch_stride, int32_t compute) {
+  return (compute == M355_COMPUTE_BF16 || compute == M355_COMPUTE_F16) && ((uintptr_t)dx16 & 15) == 0 &&
+         dx16_batch_stride % 8 == 0;
+}
+
+// the fused backward: both halves on one plan, stat_m inside the workspace.  (The twin's first pass is the fp32 kernel
+// with grid.y = C, so the descriptor is validated for the fp32 layout either way.)
+static int norm_act_bwd_impl(const m355_norm_desc* d, const float* x, const float* dy, const float* mean, const float* rstd,
+                             const float* gamma, const float* beta, float* dx, float* dgamma, float* dbeta, int training,
+                             void* workspace, size_t workspace_bytes, void* stream, void* dx16, int64_t dx16_batch_stride,
+                             int compute) {
+  M355_REQUIRE(d && workspace && dx, M355_EINVALID_ARG, "norm_act_bwd: null pointer");
+  if (int rc = validate_norm(d, "norm_act_bwd", NORM_F32)) return rc;
+  const NormPlan p = plan_norm(d, dx16 ? NORM_F32_C8 : NORM_F32);
+  float* stat_m = p.stat_m(workspace);
+  if (int rc = bwd_reduce_half(d, p, x, dy, mean, rstd, gamma, beta, dgamma, dbeta, training, nullptr, stat_m, workspace,
+                               workspace_bytes, (hipStream_t)stream, "norm_act_bwd"))
+    return rc;
+  return bwd_apply_half(d, p, x, dy, mean, rstd, gamma, beta, stat_m, dx, dx16, dx16_batch_stride, compute,
+                        (hipStream_t)stream, "norm_act_bwd");
 }
 
 }  // namespace m355
@@ -485,40 +546,34 @@ extern "C" int64_t m355_norm_num_stats(const m355_norm_desc* d) {
 
 extern "C" size_t m355_norm_workspace(const m355_norm_desc* d) {
   if (!d || d->N <= 0 || d->C <= 0 || d->S <= 0) return 0;
-  const NormGeom g = geom(d);
-  const size_t fwd = (size_t)g.nstats * g.nblk * 2 * sizeof(double);
-  const int nblk_c = (int)ceil_div(d->S, NORM_CHUNK_C8);   // (the c8 backward's chunks: the larger of the two layouts)
-  const size_t bwd = (size_t)round_up((int64_t)d->N * d->C * nblk_c * 2 * sizeof(double), 256) +
-                     (size_t)round_up((int64_t)d->N * d->C * 2 * sizeof(double), 256) +
-                     (size_t)g.nstats * 2 * sizeof(float) + 256;
-  return std::max(fwd, bwd) + 256;
+  return plan_norm(d, NORM_F32).workspace_bytes;
+}
+
+extern "C" int m355_norm_plan(const m355_norm_desc* d, int32_t which, int32_t* out4) {
+  M355_REQUIRE(d && out4, M355_EINVALID_ARG, "norm_plan: null pointer");
+  M355_REQUIRE(which >= 0 && which < NORM_PASS_COUNT, M355_EINVALID_ARG, "norm_plan: no pass %d", which);
+  const NormPass pass = (NormPass)which;
+  const NormLayout layout = (pass == NORM_FWD_C8 || pass >= NORM_BWD1_C8) ? NORM_C8 : pass == NORM_FWD_H16 ? NORM_F32_C8 : NORM_F32;
+  if (int rc = validate_norm(d, "norm_plan", layout)) return rc;
+  const NormPlan p = plan_norm(d, layout);
+  const NormLaunch L = norm_pass(d, p, pass);
+  out4[0] = L.vec;
+  out4[1] = L.nblk;
+  out4[2] = (int32_t)L.grid.x;
+  out4[3] = pass < NORM_BWD1 ? 0 : (int32_t)std::min<size_t>(p.bwd().stat_m_off, INT32_MAX);
+  return M355_OK;
 }
 
 extern "C" int m355_norm_stats(const m355_norm_desc* d, const float* x, float* mean, float* rstd,
                                float* running_mean, float* running_var, float momentum,
                                void* workspace, size_t workspace_bytes, void* stream) {
-  if (int rc = validate_norm(d, "norm_stats")) return rc;
+  if (int rc = validate_norm(d, "norm_stats", NORM_F32)) return rc;
   M355_REQUIRE(x && mean && rstd && workspace, M355_EINVALID_ARG, "norm_stats: null pointer");
-  M355_REQUIRE(workspace_bytes >= m355_norm_workspace(d), M355_EWORKSPACE,
-               "norm_stats: workspace too small");
-  M355_REQUIRE(d->groups == 0 || (!running_mean && !running_var), M355_EINVALID_ARG,
-               "norm_stats: running statistics are only defined for batch norm");
+  const NormPlan p = plan_norm(d, NORM_F32);
+  if (int rc = check_stats(d, p, "norm_stats", workspace_bytes, running_mean || running_var)) return rc;
   hipStream_t st = (hipStream_t)stream;
-  const NormGeom g = geom(d);
-  M355_REQUIRE(g.nstats <= 65535, M355_EUNSUPPORTED, "norm_stats: too many statistics");
-  const int64_t xbs = dense_or(d->x_batch_stride, (int64_t)d->C * d->S);
-  double* partial = (double*)workspace;
-  const bool vec = (g.len % 4 == 0) && (d->S % 4 == 0) && (xbs % 4 == 0) && ((uintptr_t)x & 15) == 0;
-  if (vec)
-    hipLaunchKernelGGL(norm_partial_kernel<true>, dim3((unsigned)g.nblk, (unsigned)g.nstats),
-                       dim3(256), 0, st, x, partial, d->groups, d->C, d->S, xbs, g.runs, g.len,
-                       g.nblk);
-  else
-    hipLaunchKernelGGL(norm_partial_kernel<false>, dim3((unsigned)g.nblk, (unsigned)g.nstats),
-                       dim3(256), 0, st, x, partial, d->groups, d->C, d->S, xbs, g.runs, g.len,
-                       g.nblk);
-  hipLaunchKernelGGL(norm_finalize_kernel, dim3((unsigned)g.nstats), dim3(64), 0, st, partial, mean,
-                     rstd, running_mean, running_var, momentum, d->eps, g.nstats, g.nblk, g.count, nullptr);
+  launch_partial(d, p, x, p.partial(workspace), st);
+  launch_finalize(d, p, p.partial(workspace), p.nblk, mean, rstd, running_mean, running_var, momentum, nullptr, st);
   return check_launch("norm_stats");
 }
 
@@ -526,36 +581,26 @@ extern "C" int m355_norm_stats_from_partials(const m355_norm_desc* d, const floa
                                              float* mean, float* rstd, float* running_mean,
                                              float* running_var, float momentum, void* workspace,
                                              size_t workspace_bytes, void* stream) {
-  if (int rc = validate_norm(d, "norm_stats_from_partials")) return rc;
+  if (int rc = validate_norm(d, "norm_stats_from_partials", NORM_F32)) return rc;
   M355_REQUIRE(stat_partials && mean && rstd && workspace && slots > 0, M355_EINVALID_ARG,
                "norm_stats_from_partials: null pointer / no slots");
-  M355_REQUIRE(workspace_bytes >= m355_norm_workspace(d), M355_EWORKSPACE,
-               "norm_stats_from_partials: workspace too small");
-  M355_REQUIRE(d->groups == 0 || (!running_mean && !running_var), M355_EINVALID_ARG,
-               "norm_stats_from_partials: running statistics are only defined for batch norm");
-  const NormGeom g = geom(d);
-  M355_REQUIRE(g.nstats <= 65535, M355_EUNSUPPORTED, "norm_stats_from_partials: too many statistics");
+  const NormPlan p = plan_norm(d, NORM_F32);
+  if (int rc = check_stats(d, p, "norm_stats_from_partials", workspace_bytes, running_mean || running_var)) return rc;
   hipStream_t st = (hipStream_t)stream;
-  // blocks per statistic: ~2048 partial items each, never more than the workspace of norm_stats holds
-  const int64_t items = (d->groups == 0 ? (int64_t)d->N : 1) * slots * (d->groups == 0 ? 1 : d->C / d->groups);
-  if (items <= 8192) {
-    hipLaunchKernelGGL(norm_from_partials_final_kernel, dim3((unsigned)g.nstats), dim3(1024), 0, st, stat_partials, mean,
-                       rstd, running_mean, running_var, momentum, d->eps, d->groups, d->N, d->C, slots, g.count);
+  if (partials_items(d, slots) <= 8192) {   // one launch, finalize included (norm_from_partials_final_kernel)
+    hipLaunchKernelGGL(norm_from_partials_final_kernel, dim3((unsigned)p.nstats), dim3(1024), 0, st, stat_partials, mean,
+                       rstd, running_mean, running_var, momentum, d->eps, d->groups, d->N, d->C, slots, p.count);
     return check_launch("norm_stats_from_partials");
   }
-  const int nblk = (int)std::max<int64_t>(1, std::min<int64_t>(g.nblk, ceil_div(items, 2048)));
-  double* partial = (double*)workspace;
-  hipLaunchKernelGGL(norm_from_partials_kernel, dim3((unsigned)nblk, (unsigned)g.nstats), dim3(256), 0, st,
-                     stat_partials, partial, d->groups, d->N, d->C, slots, nblk);
-  hipLaunchKernelGGL(norm_finalize_kernel, dim3((unsigned)g.nstats), dim3(64), 0, st, partial, mean, rstd,
-                     running_mean, running_var, momentum, d->eps, g.nstats, nblk, g.count, nullptr);
+  const int nblk = launch_from_partials(d, p, stat_partials, slots, p.partial(workspace), st);
+  launch_finalize(d, p, p.partial(workspace), nblk, mean, rstd, running_mean, running_var, momentum, nullptr, st);
   return check_launch("norm_stats_from_partials");
 }
 
 extern "C" int m355_norm_stats_from_running(const m355_norm_desc* d, const float* running_mean,
                                             const float* running_var, float* mean, float* rstd,
                                             void* stream) {
-  if (int rc = validate_norm(d, "norm_stats_from_running")) return rc;
+  if (int rc = validate_norm(d, "norm_stats_from_running", NORM_F32)) return rc;
   M355_REQUIRE(d->groups == 0, M355_EINVALID_ARG, "norm_stats_from_running: batch norm only");
   M355_REQUIRE(running_mean && running_var && mean && rstd, M355_EINVALID_ARG,
                "norm_stats_from_running: null pointer");
@@ -567,129 +612,32 @@ extern "C" int m355_norm_stats_from_running(const m355_norm_desc* d, const float
 extern "C" int m355_norm_act_fwd(const m355_norm_desc* d, const float* x, const float* mean,
                                  const float* rstd, const float* gamma, const float* beta,
                                  const float* add, float* y, void* stream) {
-  if (int rc = validate_norm(d, "norm_act_fwd")) return rc;
+  if (int rc = validate_norm(d, "norm_act_fwd", NORM_F32)) return rc;
   M355_REQUIRE(x && mean && rstd && y, M355_EINVALID_ARG, "norm_act_fwd: null pointer");
-  hipStream_t st = (hipStream_t)stream;
-  const int64_t xbs = dense_or(d->x_batch_stride, (int64_t)d->C * d->S);
-  const int64_t ybs = dense_or(d->y_batch_stride, (int64_t)d->C * d->S);
-  const int64_t abs_ = dense_or(d->add_batch_stride, (int64_t)d->C * d->S);
-  const bool vec = vec_ok(d, x, y, add);
-  const int64_t work = vec ? d->S / 4 : d->S;
-  const unsigned bx = (unsigned)std::max<int64_t>(1, std::min<int64_t>(ceil_div(work, 256 * 4), 1024));
-  dim3 grid(bx, (unsigned)d->C, (unsigned)d->N);
-  if (vec)
-    hipLaunchKernelGGL(norm_act_fwd_kernel<true>, grid, dim3(256), 0, st, x, mean, rstd, gamma,
-                       beta, add, y, d->C, d->S, d->groups, d->act, d->act_slope, xbs, ybs, abs_);
-  else
-    hipLaunchKernelGGL(norm_act_fwd_kernel<false>, grid, dim3(256), 0, st, x, mean, rstd, gamma,
-                       beta, add, y, d->C, d->S, d->groups, d->act, d->act_slope, xbs, ybs, abs_);
+  const NormPlan p = plan_norm(d, NORM_F32);
+  const NormLaunch L = norm_pass(d, p, NORM_FWD, (uintptr_t)x | (uintptr_t)y | (uintptr_t)add);
+  with_bool(L.vec, [&](auto V) {
+    hipLaunchKernelGGL(norm_act_fwd_kernel<decltype(V)::value>, L.grid, dim3(256), 0, (hipStream_t)stream, x, mean, rstd,
+                       gamma, beta, add, y, d->C, d->S, d->groups, d->act, d->act_slope, p.xbs, p.ybs, p.abs_);
+  });
   return check_launch("norm_act_fwd");
-}
-
-// first half of the normalisation backward: partial sums + reduction -> stat_m[s][2] (means of dxhat and dxhat*xhat),
-// dgamma, dbeta.  stat_m may be the caller's buffer (synchronised batch norm: all-reduced before the second half).
-static int norm_act_bwd_reduce_impl(const m355_norm_desc* d, const float* x, const float* dy, const float* mean,
-                                    const float* rstd, const float* gamma, const float* beta, float* dgamma, float* dbeta,
-                                    int training, const double* count_ptr, float* stat_m, void* workspace,
-                                    size_t workspace_bytes, hipStream_t st, const char* who) {
-  if (int rc = validate_norm(d, who)) return rc;
-  M355_REQUIRE(x && dy && mean && rstd && workspace && stat_m, M355_EINVALID_ARG, "%s: null pointer", who);
-  M355_REQUIRE(workspace_bytes >= m355_norm_workspace(d), M355_EWORKSPACE, "%s: workspace too small", who);
-  const NormGeom g = geom(d);
-  const int64_t xbs = dense_or(d->x_batch_stride, (int64_t)d->C * d->S);
-  const int64_t ybs = dense_or(d->y_batch_stride, (int64_t)d->C * d->S);
-  const int nblk_c = (int)ceil_div(d->S, NORM_CHUNK);
-  double* partial = (double*)workspace;
-  const bool vec = (d->S % 4 == 0) && (xbs % 4 == 0) && (ybs % 4 == 0) && (((uintptr_t)x | (uintptr_t)dy) & 15) == 0;
-  if (vec)
-    hipLaunchKernelGGL(norm_bwd_partial_kernel<true>,
-                       dim3((unsigned)nblk_c, (unsigned)d->C, (unsigned)d->N), dim3(256), 0, st, x,
-                       dy, mean, rstd, gamma, beta, partial, d->C, d->S, d->groups, d->act,
-                       d->act_slope, xbs, ybs, nblk_c);
-  else
-    hipLaunchKernelGGL(norm_bwd_partial_kernel<false>,
-                       dim3((unsigned)nblk_c, (unsigned)d->C, (unsigned)d->N), dim3(256), 0, st, x,
-                       dy, mean, rstd, gamma, beta, partial, d->C, d->S, d->groups, d->act,
-                       d->act_slope, xbs, ybs, nblk_c);
-  const int64_t nthreads = std::max<int64_t>(g.nstats, d->C);
-  hipLaunchKernelGGL(norm_bwd_reduce_kernel, dim3((unsigned)nthreads), dim3(64), 0, st, partial, gamma, dgamma, dbeta,
-                     stat_m, d->N, d->C, d->groups, nblk_c, g.count, training, count_ptr, 1.f, nullptr);
-  return check_launch(who);
-}
-
-// the finalize stage for the c8 backward (train16.hip), whose first pass writes the same partial layout
-int m355::launch_norm_bwd_reduce(const double* partial, const float* gamma, float* dgamma, float* dbeta, float* stat_m, int N,
-                           int C, int groups, int64_t S, int training, float grad_unscale, hipStream_t st,
-                           const double* count_ptr) {
-  const int nblk_c = (int)ceil_div(S, NORM_CHUNK_C8);
-  const int64_t nstats = groups == 0 ? C : (int64_t)N * groups;
-  const int64_t count = groups == 0 ? (int64_t)N * S : (int64_t)(C / groups) * S;
-  hipLaunchKernelGGL(norm_bwd_reduce_kernel, dim3((unsigned)std::max<int64_t>(nstats, C)), dim3(64), 0, st, partial, gamma,
-                     dgamma, dbeta, stat_m, N, C, groups, nblk_c, count, training, count_ptr, grad_unscale,
-                     overflow_flag());
-  return check_launch("norm_bwd_reduce");
-}
-
-// second half: dx (and its c8 twin) from x, dy and the per-statistic means
-static int norm_act_bwd_apply_impl(const m355_norm_desc* d, const float* x, const float* dy, const float* mean,
-                                   const float* rstd, const float* gamma, const float* beta, const float* stat_m, float* dx,
-                                   hipStream_t st, void* dx16, int64_t dx16_batch_stride, int compute, const char* who) {
-  if (int rc = validate_norm(d, who)) return rc;
-  M355_REQUIRE(x && dy && mean && rstd && dx && stat_m, M355_EINVALID_ARG, "%s: null pointer", who);
-  const int64_t xbs = dense_or(d->x_batch_stride, (int64_t)d->C * d->S);
-  const int64_t ybs = dense_or(d->y_batch_stride, (int64_t)d->C * d->S);
-  if (dx16)   // 16-bit training flow: dx as fp32 and as c8 in one pass
-    return launch_norm_bwd_apply_c8(x, dy, mean, rstd, gamma, beta, stat_m, dx, dx16, d->N, d->C, d->S, d->groups, d->act,
-                                    d->act_slope, xbs, ybs, dense_or(dx16_batch_stride, c8_blocks(d->C) * d->S * 8), compute,
-                                    st);
-  const bool vec = (d->S % 4 == 0) && (xbs % 4 == 0) && (ybs % 4 == 0) &&
-                   (((uintptr_t)x | (uintptr_t)dy | (uintptr_t)dx) & 15) == 0;
-  const int64_t work = vec ? d->S / 4 : d->S;
-  const unsigned bx = (unsigned)std::max<int64_t>(1, std::min<int64_t>(ceil_div(work, 256 * 4), 1024));
-  dim3 grid(bx, (unsigned)d->C, (unsigned)d->N);
-  if (vec)
-    hipLaunchKernelGGL(norm_bwd_apply_kernel<true>, grid, dim3(256), 0, st, x, dy, mean, rstd,
-                       gamma, beta, stat_m, dx, d->C, d->S, d->groups, d->act, d->act_slope, xbs,
-                       ybs);
-  else
-    hipLaunchKernelGGL(norm_bwd_apply_kernel<false>, grid, dim3(256), 0, st, x, dy, mean, rstd,
-                       gamma, beta, stat_m, dx, d->C, d->S, d->groups, d->act, d->act_slope, xbs,
-                       ybs);
-  return check_launch(who);
-}
-
-static int norm_act_bwd_impl(const m355_norm_desc* d, const float* x, const float* dy, const float* mean,
-                             const float* rstd, const float* gamma, const float* beta, float* dx, float* dgamma,
-                             float* dbeta, int training, void* workspace, size_t workspace_bytes, void* stream,
-                             void* dx16, int64_t dx16_batch_stride, int compute) {
-  M355_REQUIRE(d && workspace && dx, M355_EINVALID_ARG, "norm_act_bwd: null pointer");
-  const int nblk_c = (int)ceil_div(d->S, NORM_CHUNK);
-  float* stat_m = (float*)((char*)workspace + round_up((int64_t)d->N * d->C * nblk_c * 2 * sizeof(double), 256));
-  if (int rc = norm_act_bwd_reduce_impl(d, x, dy, mean, rstd, gamma, beta, dgamma, dbeta, training, nullptr, stat_m,
-                                        workspace, workspace_bytes, (hipStream_t)stream, "norm_act_bwd"))
-    return rc;
-  return norm_act_bwd_apply_impl(d, x, dy, mean, rstd, gamma, beta, stat_m, dx, (hipStream_t)stream, dx16,
-                                 dx16_batch_stride, compute, "norm_act_bwd");
 }
 
 extern "C" int m355_norm_act_pool_fwd(const m355_norm_desc* d, const float* x, const float* mean, const float* rstd,
                                       const float* gamma, const float* beta, float* y, float* pooled,
                                       int64_t pooled_batch_stride, int32_t D, int32_t H, int32_t W, void* stream) {
-  if (int rc = validate_norm(d, "norm_act_pool_fwd")) return rc;
+  if (int rc = validate_norm(d, "norm_act_pool_fwd", NORM_F32)) return rc;
   M355_REQUIRE(x && mean && rstd && y && pooled, M355_EINVALID_ARG, "norm_act_pool_fwd: null pointer");
   M355_REQUIRE(D > 0 && H > 0 && W > 0 && (int64_t)D * H * W == d->S, M355_EINVALID_ARG,
                "norm_act_pool_fwd: D*H*W != desc->S");
   M355_REQUIRE(D % 2 == 0 && H % 2 == 0 && W % 2 == 0, M355_EUNSUPPORTED, "norm_act_pool_fwd: odd spatial size (%d,%d,%d)",
                D, H, W);
-  const int64_t xbs = dense_or(d->x_batch_stride, (int64_t)d->C * d->S);
-  const int64_t ybs = dense_or(d->y_batch_stride, (int64_t)d->C * d->S);
+  const NormPlan p = plan_norm(d, NORM_F32);
   const int64_t pbs = dense_or(pooled_batch_stride, (int64_t)d->C * (d->S / 8));
-  M355_REQUIRE((((uintptr_t)x | (uintptr_t)y) & 7) == 0 && xbs % 2 == 0 && ybs % 2 == 0, M355_EINVALID_ARG,
+  M355_REQUIRE((((uintptr_t)x | (uintptr_t)y) & 7) == 0 && p.xbs % 2 == 0 && p.ybs % 2 == 0, M355_EINVALID_ARG,
                "norm_act_pool_fwd: x / y not 8B aligned");
-  const unsigned bx = (unsigned)std::max<int64_t>(1, std::min<int64_t>(ceil_div(d->S / 8, 256 * 2), 1024));
-  dim3 grid(bx, (unsigned)d->C, (unsigned)d->N);
-  hipLaunchKernelGGL(norm_act_pool_fwd_kernel, grid, dim3(256), 0, (hipStream_t)stream, x, mean, rstd, gamma, beta, y, pooled,
-                     d->C, D, H, W, d->groups, d->act, d->act_slope, xbs, ybs, pbs);
+  hipLaunchKernelGGL(norm_act_pool_fwd_kernel, norm_pass(d, p, NORM_POOL_FWD).grid, dim3(256), 0, (hipStream_t)stream, x, mean,
+                     rstd, gamma, beta, y, pooled, d->C, D, H, W, d->groups, d->act, d->act_slope, p.xbs, p.ybs, pbs);
   return check_launch("norm_act_pool_fwd");
 }
 
@@ -706,9 +654,8 @@ extern "C" int m355_norm_act_bwd_h16(const m355_norm_desc* d, const float* x, co
                                      const float* rstd, const float* gamma, const float* beta, float* dx,
                                      float* dgamma, float* dbeta, int training, void* dx16, int64_t dx16_batch_stride,
                                      int32_t compute, void* workspace, size_t workspace_bytes, void* stream) {
-  M355_REQUIRE(dx16 && (compute == M355_COMPUTE_BF16 || compute == M355_COMPUTE_F16) && ((uintptr_t)dx16 & 15) == 0 &&
-                   dx16_batch_stride % 8 == 0,
-               M355_EINVALID_ARG, "norm_act_bwd_h16: needs an aligned c8 destination and a 16-bit compute type");
+  M355_REQUIRE(dx16 && dx16_ok(dx16, dx16_batch_stride, compute), M355_EINVALID_ARG,
+               "norm_act_bwd_h16: needs an aligned c8 destination and a 16-bit compute type");
   return norm_act_bwd_impl(d, x, dy, mean, rstd, gamma, beta, dx, dgamma, dbeta, training, workspace, workspace_bytes,
                            stream, dx16, dx16_batch_stride, compute);
 }
@@ -717,43 +664,31 @@ extern "C" int m355_norm_act_bwd_h16(const m355_norm_desc* d, const float* x, co
 
 extern "C" int m355_norm_sums(const m355_norm_desc* d, const float* x, const float* stat_partials, int64_t slots,
                               double* sums, void* workspace, size_t workspace_bytes, void* stream) {
-  if (int rc = validate_norm(d, "norm_sums")) return rc;
+  if (int rc = validate_norm(d, "norm_sums", NORM_F32)) return rc;
   M355_REQUIRE((x || stat_partials) && sums && workspace, M355_EINVALID_ARG, "norm_sums: null pointer");
   M355_REQUIRE(!stat_partials || slots > 0, M355_EINVALID_ARG, "norm_sums: partials without slots");
   M355_REQUIRE(d->groups == 0, M355_EINVALID_ARG, "norm_sums: batch norm only (group statistics never cross samples)");
-  M355_REQUIRE(workspace_bytes >= m355_norm_workspace(d), M355_EWORKSPACE, "norm_sums: workspace too small");
-  const NormGeom g = geom(d);
-  M355_REQUIRE(g.nstats <= 65535, M355_EUNSUPPORTED, "norm_sums: too many statistics");
+  const NormPlan p = plan_norm(d, NORM_F32);
+  if (int rc = check_stats(d, p, "norm_sums", workspace_bytes, false)) return rc;
   hipStream_t st = (hipStream_t)stream;
-  double* partial = (double*)workspace;
-  int nblk = g.nblk;
-  if (stat_partials) {   // the producing conv's epilogue partials [N][slots][C][2]
-    const int64_t items = (int64_t)d->N * slots;
-    nblk = (int)std::max<int64_t>(1, std::min<int64_t>(g.nblk, ceil_div(items, 2048)));
-    hipLaunchKernelGGL(norm_from_partials_kernel, dim3((unsigned)nblk, (unsigned)g.nstats), dim3(256), 0, st,
-                       stat_partials, partial, d->groups, d->N, d->C, slots, nblk);
-  } else {
-    const int64_t xbs = dense_or(d->x_batch_stride, (int64_t)d->C * d->S);
-    const bool vec = (g.len % 4 == 0) && (d->S % 4 == 0) && (xbs % 4 == 0) && ((uintptr_t)x & 15) == 0;
-    if (vec)
-      hipLaunchKernelGGL(norm_partial_kernel<true>, dim3((unsigned)g.nblk, (unsigned)g.nstats), dim3(256), 0, st, x,
-                         partial, d->groups, d->C, d->S, xbs, g.runs, g.len, g.nblk);
-    else
-      hipLaunchKernelGGL(norm_partial_kernel<false>, dim3((unsigned)g.nblk, (unsigned)g.nstats), dim3(256), 0, st, x,
-                         partial, d->groups, d->C, d->S, xbs, g.runs, g.len, g.nblk);
-  }
-  hipLaunchKernelGGL(norm_sums_kernel, dim3((unsigned)g.nstats), dim3(64), 0, st, partial, sums, g.nstats, nblk, g.count);
+  int nblk = p.nblk;
+  if (stat_partials)   // the producing conv's epilogue partials [N][slots][C][2]
+    nblk = launch_from_partials(d, p, stat_partials, slots, p.partial(workspace), st);
+  else
+    launch_partial(d, p, x, p.partial(workspace), st);
+  hipLaunchKernelGGL(norm_sums_kernel, dim3((unsigned)p.nstats), dim3(64), 0, st, p.partial(workspace), sums, p.nstats, nblk,
+                     p.count);
   return check_launch("norm_sums");
 }
 
 extern "C" int m355_norm_stats_from_sums(const m355_norm_desc* d, const double* sums, float* mean, float* rstd,
                                          float* running_mean, float* running_var, float momentum, void* stream) {
-  if (int rc = validate_norm(d, "norm_stats_from_sums")) return rc;
+  if (int rc = validate_norm(d, "norm_stats_from_sums", NORM_F32)) return rc;
   M355_REQUIRE(sums && mean && rstd, M355_EINVALID_ARG, "norm_stats_from_sums: null pointer");
   M355_REQUIRE(d->groups == 0, M355_EINVALID_ARG, "norm_stats_from_sums: batch norm only");
-  const NormGeom g = geom(d);
-  hipLaunchKernelGGL(norm_finalize_kernel, dim3((unsigned)g.nstats), dim3(64), 0, (hipStream_t)stream, sums, mean, rstd,
-                     running_mean, running_var, momentum, d->eps, g.nstats, 1, g.count, sums + g.nstats * 2);
+  const NormPlan p = plan_norm(d, NORM_F32);
+  // the all-reduced sums are one "partial" per statistic, the element count over all ranks sits behind them
+  launch_finalize(d, p, sums, 1, mean, rstd, running_mean, running_var, momentum, sums + p.nstats * 2, (hipStream_t)stream);
   return check_launch("norm_stats_from_sums");
 }
 
@@ -761,16 +696,17 @@ extern "C" int m355_norm_act_bwd_reduce(const m355_norm_desc* d, const float* x,
                                         const float* rstd, const float* gamma, const float* beta, float* dgamma,
                                         float* dbeta, int training, const double* total_count, float* stat_m,
                                         void* workspace, size_t workspace_bytes, void* stream) {
-  return norm_act_bwd_reduce_impl(d, x, dy, mean, rstd, gamma, beta, dgamma, dbeta, training, total_count, stat_m,
-                                  workspace, workspace_bytes, (hipStream_t)stream, "norm_act_bwd_reduce");
+  if (int rc = validate_norm(d, "norm_act_bwd_reduce", NORM_F32)) return rc;
+  return bwd_reduce_half(d, plan_norm(d, NORM_F32), x, dy, mean, rstd, gamma, beta, dgamma, dbeta, training, total_count,
+                         stat_m, workspace, workspace_bytes, (hipStream_t)stream, "norm_act_bwd_reduce");
 }
 
 extern "C" int m355_norm_act_bwd_apply(const m355_norm_desc* d, const float* x, const float* dy, const float* mean,
                                        const float* rstd, const float* gamma, const float* beta, const float* stat_m,
                                        float* dx, void* dx16, int64_t dx16_batch_stride, int32_t compute, void* stream) {
-  M355_REQUIRE(!dx16 || ((compute == M355_COMPUTE_BF16 || compute == M355_COMPUTE_F16) && ((uintptr_t)dx16 & 15) == 0 &&
-                         dx16_batch_stride % 8 == 0),
-               M355_EINVALID_ARG, "norm_act_bwd_apply: the c8 destination needs alignment and a 16-bit compute type");
-  return norm_act_bwd_apply_impl(d, x, dy, mean, rstd, gamma, beta, stat_m, dx, (hipStream_t)stream, dx16,
-                                 dx16_batch_stride, compute, "norm_act_bwd_apply");
+  M355_REQUIRE(!dx16 || dx16_ok(dx16, dx16_batch_stride, compute), M355_EINVALID_ARG,
+               "norm_act_bwd_apply: the c8 destination needs alignment and a 16-bit compute type");
+  if (int rc = validate_norm(d, "norm_act_bwd_apply", NORM_F32)) return rc;
+  return bwd_apply_half(d, plan_norm(d, dx16 ? NORM_F32_C8 : NORM_F32), x, dy, mean, rstd, gamma, beta, stat_m, dx, dx16,
+                        dx16_batch_stride, compute, (hipStream_t)stream, "norm_act_bwd_apply");
 }

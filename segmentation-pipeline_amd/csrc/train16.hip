@@ -19,7 +19,7 @@
 // Reference ops replaced: autograd of normalization_class + activation_class inside Block3d
 // (models/components.py:52-55,62-73) and of nn.AvgPool3d (models/modular_unet.py:64,92) under
 // `torch.cuda.amp.autocast` (segmentation_trainer.py:203-227).
-#include "h16.hpp"
+#include "norm_host.hpp"
 
 namespace m355 {
 
@@ -330,12 +330,6 @@ size_t dbias_c8_ws_bytes(int N, int C, int64_t S) {
 
 using namespace m355;
 
-static int check_h16(const char* who, int32_t compute) {
-  M355_REQUIRE(compute == M355_COMPUTE_BF16 || compute == M355_COMPUTE_F16, M355_EINVALID_ARG,
-               "%s: compute must be M355_COMPUTE_BF16 or M355_COMPUTE_F16", who);
-  return M355_OK;
-}
-
 extern "C" int m355_act16_pack_scaled(const float* x, void* x16, int32_t N, int32_t C, int64_t S, int64_t x_batch_stride,
                                       int64_t x16_batch_stride, int32_t compute, float scale, void* stream) {
   if (int rc = check_h16("act16_pack_scaled", compute)) return rc;
@@ -378,63 +372,64 @@ static int norm_bwd_c8_check(const char* who, const m355_norm_desc* d, const voi
                              const void* dx16_or_ws, int32_t D, int32_t H, int32_t W, int32_t compute) {
   if (int rc = check_h16(who, compute)) return rc;
   M355_REQUIRE(d && x16 && (dy16 || dpool16) && dx16_or_ws, M355_EINVALID_ARG, "%s: null pointer", who);
-  M355_REQUIRE(d->N > 0 && d->C > 0 && d->S > 0 && d->N <= 65535 && c8_blocks(d->C) <= 65535, M355_EINVALID_ARG, "%s: bad shape", who);
-  M355_REQUIRE(d->groups >= 0 && (d->groups == 0 || d->C % d->groups == 0), M355_EINVALID_ARG,
-               "%s: C=%d not divisible by groups=%d", who, d->C, d->groups);
+  if (int rc = validate_norm(d, who, NORM_C8)) return rc;
   M355_REQUIRE(d->act >= M355_ACT_NONE && d->act <= M355_ACT_LEAKY_RELU, M355_EINVALID_ARG, "%s: bad activation", who);
   M355_REQUIRE(!dpool16 || (D > 0 && H > 0 && W > 0 && D % 2 == 0 && H % 2 == 0 && W % 2 == 0 && (int64_t)D * H * W == d->S),
                M355_EINVALID_ARG, "%s: a pooled gradient needs even D, H, W with D*H*W == S", who);
   return M355_OK;
 }
 
-struct NormBwdC8Geom {
-  int64_t xbs, ybs, dxbs, pbs;
-  int nblk;
-  double* partial;
-  float* stat_m;
+// the c8 tensors of one backward call: pointers, dense-resolved batch strides (elements), the pooled gradient's rows
+struct NormBwdC8Args {
+  const void *x16, *dy16, *dpool16;
+  void* dx16;
+  int64_t xbs, ybs, pbs, dxbs;
+  int H, W;
 };
 
-static int norm_bwd_c8_geom(const char* who, const m355_norm_desc* d, const void* x16, int64_t x16_batch_stride, const void* dy16,
-                            int64_t dy16_batch_stride, const void* dpool16, int64_t dpool16_batch_stride, const void* dx16,
-                            int64_t dx16_batch_stride, void* workspace, NormBwdC8Geom* g) {
-  const int64_t dense = c8_blocks(d->C) * d->S * 8;
-  g->xbs = dense_or(x16_batch_stride, dense);
-  g->ybs = dense_or(dy16_batch_stride, dense);
-  g->dxbs = dense_or(dx16_batch_stride, dense);
-  g->pbs = dpool16 ? dense_or(dpool16_batch_stride, c8_blocks(d->C) * (d->S / 8) * 8) : 0;   // (pooled: S / 8 voxels)
-  M355_REQUIRE((((uintptr_t)x16 | (uintptr_t)dy16 | (uintptr_t)dpool16 | (uintptr_t)dx16) & 15) == 0 && g->xbs % 8 == 0 &&
-                   g->ybs % 8 == 0 && g->dxbs % 8 == 0 && g->pbs % 8 == 0, M355_EINVALID_ARG, "%s: c8 tensor not 16B aligned", who);
-  g->nblk = (int)ceil_div(d->S, NORM_CHUNK_C8);
-  g->partial = (double*)workspace;
-  g->stat_m = workspace ? (float*)((char*)workspace + round_up((int64_t)d->N * d->C * g->nblk * 2 * sizeof(double), 256)) : nullptr;
+static int norm_bwd_c8_args(const char* who, const m355_norm_desc* d, const NormPlan& p, const void* x16,
+                            int64_t x16_batch_stride, const void* dy16, int64_t dy16_batch_stride, const void* dpool16,
+                            int64_t dpool16_batch_stride, void* dx16, int64_t dx16_batch_stride, int H, int W, NormBwdC8Args* a) {
+  *a = {x16, dy16, dpool16, dx16, p.bs16(x16_batch_stride), p.bs16(dy16_batch_stride),
+        dpool16 ? dense_or(dpool16_batch_stride, c8_blocks(d->C) * (d->S / 8) * 8) : 0,   // (pooled: S / 8 voxels)
+        p.bs16(dx16_batch_stride), H, W};
+  M355_REQUIRE((((uintptr_t)x16 | (uintptr_t)dy16 | (uintptr_t)dpool16 | (uintptr_t)dx16) & 15) == 0 && a->xbs % 8 == 0 &&
+                   a->ybs % 8 == 0 && a->dxbs % 8 == 0 && a->pbs % 8 == 0, M355_EINVALID_ARG, "%s: c8 tensor not 16B aligned", who);
   return M355_OK;
 }
 
-static void norm_bwd_c8_pass1(const m355_norm_desc* d, const NormBwdC8Geom& g, const void* x16, const void* dy16, const void* dpool16,
-                              const float* mean, const float* rstd, const float* gamma, const float* beta, int H, int W,
-                              int32_t compute, hipStream_t st) {
-  const dim3 g1((unsigned)g.nblk, (unsigned)c8_blocks(d->C), (unsigned)d->N);
-#define M355_NB1(HT, POOL)                                                                                                 \
-  hipLaunchKernelGGL((norm_bwd_partial_c8_kernel<HT, POOL>), g1, dim3(256), 0, st, (const HT*)x16, (const HT*)dy16,        \
-                     (const HT*)dpool16, mean, rstd, gamma, beta, g.partial, d->C, d->S, d->groups, d->act, d->act_slope, g.xbs, \
-                     g.ybs, g.pbs, H, W, g.nblk)
-  if (compute == M355_COMPUTE_BF16) { if (dpool16) M355_NB1(__bf16, true); else M355_NB1(__bf16, false); }
-  else { if (dpool16) M355_NB1(_Float16, true); else M355_NB1(_Float16, false); }
-#undef M355_NB1
+// reduce half: pass 1 into the workspace's partials, then the finalize stage shared with the fp32 backward
+static int norm_bwd_c8_reduce_half(const m355_norm_desc* d, const NormPlan& p, const NormBwdC8Args& a, const float* mean,
+                                   const float* rstd, const float* gamma, const float* beta, float* dgamma, float* dbeta,
+                                   int training, const double* count_ptr, float grad_unscale, float* stat_m, void* workspace,
+                                   int32_t compute, hipStream_t st) {
+  const NormLaunch L = norm_pass(d, p, NORM_BWD1_C8);
+  with_h16(compute, [&](auto T) {
+    typedef typename decltype(T)::type HT;
+    with_bool(a.dpool16 != nullptr, [&](auto POOL) {
+      hipLaunchKernelGGL((norm_bwd_partial_c8_kernel<HT, decltype(POOL)::value>), L.grid, dim3(256), 0, st, (const HT*)a.x16,
+                         (const HT*)a.dy16, (const HT*)a.dpool16, mean, rstd, gamma, beta, p.partial(workspace), d->C, d->S,
+                         d->groups, d->act, d->act_slope, a.xbs, a.ybs, a.pbs, a.H, a.W, L.nblk);
+    });
+  });
+  return launch_norm_bwd_reduce(d, p, p.partial(workspace), gamma, dgamma, dbeta, stat_m, training, count_ptr, grad_unscale,
+                                overflow_flag(), st);
 }
 
-static void norm_bwd_c8_pass2(const m355_norm_desc* d, const NormBwdC8Geom& g, const void* x16, const void* dy16, const void* dpool16,
-                              const float* mean, const float* rstd, const float* gamma, const float* beta, const float* stat_m,
-                              void* dx16, int H, int W, int32_t compute, hipStream_t st) {
-  const dim3 g2((unsigned)std::max<int64_t>(1, std::min<int64_t>(ceil_div(d->S, 256 * 2), 1024)), (unsigned)c8_blocks(d->C),
-                (unsigned)d->N);
-#define M355_NB2(HT, POOL)                                                                                                 \
-  hipLaunchKernelGGL((norm_bwd_apply_c8c8_kernel<HT, POOL>), g2, dim3(256), 0, st, (const HT*)x16, (const HT*)dy16,        \
-                     (const HT*)dpool16, mean, rstd, gamma, beta, stat_m, (HT*)dx16, d->C, d->S, d->groups, d->act,         \
-                     d->act_slope, g.xbs, g.ybs, g.pbs, g.dxbs, H, W, overflow_flag())
-  if (compute == M355_COMPUTE_BF16) { if (dpool16) M355_NB2(__bf16, true); else M355_NB2(__bf16, false); }
-  else { if (dpool16) M355_NB2(_Float16, true); else M355_NB2(_Float16, false); }
-#undef M355_NB2
+// apply half: pass 2
+static int norm_bwd_c8_apply_half(const m355_norm_desc* d, const NormPlan& p, const NormBwdC8Args& a, const float* mean,
+                                  const float* rstd, const float* gamma, const float* beta, const float* stat_m, int32_t compute,
+                                  hipStream_t st, const char* who) {
+  with_h16(compute, [&](auto T) {
+    typedef typename decltype(T)::type HT;
+    with_bool(a.dpool16 != nullptr, [&](auto POOL) {
+      hipLaunchKernelGGL((norm_bwd_apply_c8c8_kernel<HT, decltype(POOL)::value>), norm_pass(d, p, NORM_BWD2_C8).grid, dim3(256),
+                         0, st, (const HT*)a.x16, (const HT*)a.dy16, (const HT*)a.dpool16, mean, rstd, gamma, beta, stat_m,
+                         (HT*)a.dx16, d->C, d->S, d->groups, d->act, d->act_slope, a.xbs, a.ybs, a.pbs, a.dxbs, a.H, a.W,
+                         overflow_flag());
+    });
+  });
+  return check_launch(who);
 }
 
 extern "C" int m355_norm_act_bwd_c8(const m355_norm_desc* d, const void* x16, int64_t x16_batch_stride, const void* dy16,
@@ -445,18 +440,17 @@ extern "C" int m355_norm_act_bwd_c8(const m355_norm_desc* d, const void* x16, in
                                     void* workspace, size_t workspace_bytes, void* stream) {
   if (int rc = norm_bwd_c8_check("norm_act_bwd_c8", d, x16, dy16, dpool16, dx16, D, H, W, compute)) return rc;
   M355_REQUIRE(mean && rstd && workspace, M355_EINVALID_ARG, "norm_act_bwd_c8: null pointer");
-  M355_REQUIRE(workspace_bytes >= m355_norm_workspace(d), M355_EWORKSPACE, "norm_act_bwd_c8: workspace too small");
-  NormBwdC8Geom g;
-  if (int rc = norm_bwd_c8_geom("norm_act_bwd_c8", d, x16, x16_batch_stride, dy16, dy16_batch_stride, dpool16,
-                                dpool16_batch_stride, dx16, dx16_batch_stride, workspace, &g))
+  const NormPlan p = plan_norm(d, NORM_C8);
+  M355_REQUIRE(workspace_bytes >= p.workspace_bytes, M355_EWORKSPACE, "norm_act_bwd_c8: workspace too small");
+  NormBwdC8Args a;
+  if (int rc = norm_bwd_c8_args("norm_act_bwd_c8", d, p, x16, x16_batch_stride, dy16, dy16_batch_stride, dpool16,
+                                dpool16_batch_stride, dx16, dx16_batch_stride, H, W, &a))
     return rc;
-  hipStream_t st = (hipStream_t)stream;
-  norm_bwd_c8_pass1(d, g, x16, dy16, dpool16, mean, rstd, gamma, beta, H, W, compute, st);
-  if (int rc = launch_norm_bwd_reduce(g.partial, gamma, dgamma, dbeta, g.stat_m, d->N, d->C, d->groups, d->S, training,
-                                      grad_unscale, st))
+  float* stat_m = p.stat_m(workspace);
+  if (int rc = norm_bwd_c8_reduce_half(d, p, a, mean, rstd, gamma, beta, dgamma, dbeta, training, nullptr, grad_unscale, stat_m,
+                                       workspace, compute, (hipStream_t)stream))
     return rc;
-  norm_bwd_c8_pass2(d, g, x16, dy16, dpool16, mean, rstd, gamma, beta, g.stat_m, dx16, H, W, compute, st);
-  return check_launch("norm_act_bwd_c8");
+  return norm_bwd_c8_apply_half(d, p, a, mean, rstd, gamma, beta, stat_m, compute, (hipStream_t)stream, "norm_act_bwd_c8");
 }
 
 extern "C" int m355_norm_act_bwd_c8_reduce(const m355_norm_desc* d, const void* x16, int64_t x16_batch_stride, const void* dy16,
@@ -467,15 +461,14 @@ extern "C" int m355_norm_act_bwd_c8_reduce(const m355_norm_desc* d, const void* 
                                            void* workspace, size_t workspace_bytes, void* stream) {
   if (int rc = norm_bwd_c8_check("norm_act_bwd_c8_reduce", d, x16, dy16, dpool16, workspace, D, H, W, compute)) return rc;
   M355_REQUIRE(mean && rstd && stat_m, M355_EINVALID_ARG, "norm_act_bwd_c8_reduce: null pointer");
-  M355_REQUIRE(workspace_bytes >= m355_norm_workspace(d), M355_EWORKSPACE, "norm_act_bwd_c8_reduce: workspace too small");
-  NormBwdC8Geom g;
-  if (int rc = norm_bwd_c8_geom("norm_act_bwd_c8_reduce", d, x16, x16_batch_stride, dy16, dy16_batch_stride, dpool16,
-                                dpool16_batch_stride, nullptr, 0, workspace, &g))
+  const NormPlan p = plan_norm(d, NORM_C8);
+  M355_REQUIRE(workspace_bytes >= p.workspace_bytes, M355_EWORKSPACE, "norm_act_bwd_c8_reduce: workspace too small");
+  NormBwdC8Args a;
+  if (int rc = norm_bwd_c8_args("norm_act_bwd_c8_reduce", d, p, x16, x16_batch_stride, dy16, dy16_batch_stride, dpool16,
+                                dpool16_batch_stride, nullptr, 0, H, W, &a))
     return rc;
-  hipStream_t st = (hipStream_t)stream;
-  norm_bwd_c8_pass1(d, g, x16, dy16, dpool16, mean, rstd, gamma, beta, H, W, compute, st);
-  return launch_norm_bwd_reduce(g.partial, gamma, dgamma, dbeta, stat_m, d->N, d->C, d->groups, d->S, training, grad_unscale, st,
-                                total_count);
+  return norm_bwd_c8_reduce_half(d, p, a, mean, rstd, gamma, beta, dgamma, dbeta, training, total_count, grad_unscale, stat_m,
+                                 workspace, compute, (hipStream_t)stream);
 }
 
 extern "C" int m355_norm_act_bwd_c8_apply(const m355_norm_desc* d, const void* x16, int64_t x16_batch_stride, const void* dy16,
@@ -485,12 +478,13 @@ extern "C" int m355_norm_act_bwd_c8_apply(const m355_norm_desc* d, const void* x
                                           int64_t dx16_batch_stride, int32_t compute, void* stream) {
   if (int rc = norm_bwd_c8_check("norm_act_bwd_c8_apply", d, x16, dy16, dpool16, dx16, D, H, W, compute)) return rc;
   M355_REQUIRE(mean && rstd && stat_m, M355_EINVALID_ARG, "norm_act_bwd_c8_apply: null pointer");
-  NormBwdC8Geom g;
-  if (int rc = norm_bwd_c8_geom("norm_act_bwd_c8_apply", d, x16, x16_batch_stride, dy16, dy16_batch_stride, dpool16,
-                                dpool16_batch_stride, dx16, dx16_batch_stride, nullptr, &g))
+  const NormPlan p = plan_norm(d, NORM_C8);
+  NormBwdC8Args a;
+  if (int rc = norm_bwd_c8_args("norm_act_bwd_c8_apply", d, p, x16, x16_batch_stride, dy16, dy16_batch_stride, dpool16,
+                                dpool16_batch_stride, dx16, dx16_batch_stride, H, W, &a))
     return rc;
-  norm_bwd_c8_pass2(d, g, x16, dy16, dpool16, mean, rstd, gamma, beta, stat_m, dx16, H, W, compute, (hipStream_t)stream);
-  return check_launch("norm_act_bwd_c8_apply");
+  return norm_bwd_c8_apply_half(d, p, a, mean, rstd, gamma, beta, stat_m, compute, (hipStream_t)stream,
+                                "norm_act_bwd_c8_apply");
 }
 
 extern "C" int m355_avgpool3d_2x_bwd_h16(const void* dpool16, const void* dskip16, void* dx16, int32_t N, int32_t C, int32_t D,

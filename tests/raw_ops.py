@@ -716,6 +716,88 @@ class RawOps:
                                               self._stream()), "norm_act_bwd_h16")
         return dx, dg, db, dx16
 
+    # ---- synchronised batch norm: the local halves around the all-reduce (total_count None = this rank's own count)
+    def norm_sums(self, x=None, stat_partials=None, x_shape=None, eps=1e-5):
+        """-> sums [2 C + 1] (double): per channel (sum, sum of squares), then the element count.  From x (tensor or Slot), or
+        from a conv's epilogue partials [N, P, C, 2] of a tensor of shape x_shape"""
+        x, stat_partials = self.to(x), self.to(stat_partials)
+        N, Cc = (x.shape if x is not None else x_shape)[:2]
+        S = (x.numel() if x is not None else torch.Size(x_shape).numel()) // (N * Cc)
+        d = NormDesc(N, Cc, S, 0, 0, eps, 0.01, _bs(x) if x is not None else 0, 0, 0)
+        sums = self.empty(2 * Cc + 1, dtype=torch.float64)
+        ws = self._ws("norm_workspace", d)
+        slots = stat_partials.shape[1] if stat_partials is not None else 0
+        self._chk(self.fn("norm_sums")(C.byref(d), _p(x), _p(stat_partials), slots, _p(sums), _p(ws), ws.numel(), self._stream()),
+                  "norm_sums")
+        return sums
+
+    def norm_stats_from_sums(self, sums, x_shape, eps=1e-5, running=None, momentum=0.1):
+        N, Cc = x_shape[:2]
+        d = NormDesc(N, Cc, torch.Size(x_shape).numel() // (N * Cc), 0, 0, eps, 0.01, 0, 0, 0)
+        mean, rstd = self.empty(Cc), self.empty(Cc)
+        rm = rv = None
+        if running is not None:
+            rm, rv = self.to(running[0]).clone(), self.to(running[1]).clone()
+        self._chk(self.fn("norm_stats_from_sums")(C.byref(d), _p(sums), _p(mean), _p(rstd), _p(rm), _p(rv), momentum,
+                                                  self._stream()), "norm_stats_from_sums")
+        return mean, rstd, rm, rv
+
+    def norm_act_bwd_reduce(self, x, dy, mean, rstd, gamma, beta, groups, act, training=1, total_count=None, eps=1e-5,
+                            slope=0.01):
+        """first half of norm_act_bwd -> (stat_m [num_stats, 2], dgamma, dbeta); total_count: device double, or None"""
+        x, dy, mean, rstd, gamma, beta = map(self.to, (x, dy, mean, rstd, gamma, beta))
+        d = self.norm_desc(x, groups, act, eps, slope, _bs(x), _bs(dy))
+        stat_m = self.empty(self.fn("norm_num_stats")(C.byref(d)), 2)
+        dg = self.empty(x.shape[1]) if gamma is not None else None
+        db = self.empty(x.shape[1]) if gamma is not None else None
+        ws = self._ws("norm_workspace", d)
+        self._chk(self.fn("norm_act_bwd_reduce")(C.byref(d), _p(x), _p(dy), _p(mean), _p(rstd), _p(gamma), _p(beta), _p(dg),
+                                                 _p(db), training, _p(total_count), _p(stat_m), _p(ws), ws.numel(),
+                                                 self._stream()), "norm_act_bwd_reduce")
+        return stat_m, dg, db
+
+    def norm_act_bwd_apply(self, x, dy, mean, rstd, gamma, beta, stat_m, groups, act, compute=None, eps=1e-5, slope=0.01,
+                           out=None, out16=None):
+        """second half -> (dx, dx16); compute 1 / 2: also the c8 twin of dx (None: dx16 is None)"""
+        x, dy, mean, rstd, gamma, beta = map(self.to, (x, dy, mean, rstd, gamma, beta))
+        N, Cc = x.shape[:2]
+        dx = self._out(out, x.shape)
+        assert _bs(dx) == _bs(x) or N == 1
+        d = self.norm_desc(x, groups, act, eps, slope, _bs(x), _bs(dy))
+        dx16 = self._out(out16, (N, (Cc + 7) // 8, x.numel() // (N * Cc), 8), self.dt16(compute)) if compute else None
+        self._chk(self.fn("norm_act_bwd_apply")(C.byref(d), _p(x), _p(dy), _p(mean), _p(rstd), _p(gamma), _p(beta), _p(stat_m),
+                                                _p(dx), _p(dx16), _bs(dx16), compute or 0, self._stream()),
+                  "norm_act_bwd_apply")
+        return dx, dx16
+
+    def norm_act_bwd_c8_reduce(self, x16, dy16, dpool16, Cc, spatial, mean, rstd, gamma, beta, groups, act, compute, training=1,
+                               total_count=None, unscale=1.0, eps=1e-5, slope=0.01):
+        """first half of norm_act_bwd_c8 -> (stat_m, dgamma, dbeta)"""
+        mean, rstd, gamma, beta = map(self.to, (mean, rstd, gamma, beta))
+        D, H, W = spatial
+        d = NormDesc(x16.shape[0], Cc, x16.shape[2], groups, act, eps, slope, 0, 0, 0)
+        stat_m = self.empty(self.fn("norm_num_stats")(C.byref(d)), 2)
+        dg = self.empty(Cc) if gamma is not None else None
+        db = self.empty(Cc) if gamma is not None else None
+        ws = self._ws("norm_workspace", d)
+        self._chk(self.fn("norm_act_bwd_c8_reduce")(C.byref(d), _p(x16), _bs(x16), _p(dy16), _bs(dy16), _p(dpool16), _bs(dpool16),
+                                                    D, H, W, _p(mean), _p(rstd), _p(gamma), _p(beta), _p(dg), _p(db), training,
+                                                    _p(total_count), float(unscale), _p(stat_m), compute, _p(ws), ws.numel(),
+                                                    self._stream()), "norm_act_bwd_c8_reduce")
+        return stat_m, dg, db
+
+    def norm_act_bwd_c8_apply(self, x16, dy16, dpool16, Cc, spatial, mean, rstd, gamma, beta, stat_m, groups, act, compute,
+                              eps=1e-5, slope=0.01, out=None):
+        """second half -> dx16"""
+        mean, rstd, gamma, beta = map(self.to, (mean, rstd, gamma, beta))
+        D, H, W = spatial
+        d = NormDesc(x16.shape[0], Cc, x16.shape[2], groups, act, eps, slope, 0, 0, 0)
+        dx16 = self._out(out, x16.shape, x16.dtype, fill=7.0)
+        self._chk(self.fn("norm_act_bwd_c8_apply")(C.byref(d), _p(x16), _bs(x16), _p(dy16), _bs(dy16), _p(dpool16),
+                                                   _bs(dpool16), D, H, W, _p(mean), _p(rstd), _p(gamma), _p(beta), _p(stat_m),
+                                                   _p(dx16), _bs(dx16), compute, self._stream()), "norm_act_bwd_c8_apply")
+        return dx16
+
     # -------------------------------------------------- pool / upsample / softmax
     # (every tensor argument may be a Slot, `out` an output Slot: pointers and batch strides then come from the slots)
     def avgpool_fwd(self, x, out=None):

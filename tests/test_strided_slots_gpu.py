@@ -35,14 +35,16 @@ Host / kernel branches on a stride or a pointer (file:line, condition, who takes
                     ... data gradient (MfmaF32 | Direct), same condition on dy          test_conv_transpose3d (same ids)
                     ... weight gradient (MfmaF32 | Direct), same condition on dy        test_conv_transpose3d (same ids)
   convt.hip validate_convt_c8   c8 REQUIREs: conv-transpose fwd / bwd_data / bwd_weight h16  test_c8_conv_transpose | test_c8_rejects_misaligned_slots (each by name)
-  norm.hip:470-474  vec_ok: S % 4, xbs / ybs / abs % 4, x / y / add 16-B aligned         test_norm[aligned S%4==0 | odd, offset*, S odd]
-  norm.hip:511,737  statistics: len % 4, S % 4, xbs % 4, x aligned                      test_norm (same ids); 737 (m355_norm_sums, synchronised BN) launches the same two kernels from the same condition
-                    and has no raw_ops wrapper: untested here, test_distributed_gpu.py runs it dense
-  norm.hip:603,645  backward passes: S % 4, xbs / ybs % 4, x / dy / dx aligned          test_norm (same ids)
-  norm.hip:687      norm_act_pool_fwd REQUIREs x / y 8-B aligned, even strides           test_norm_act_pool[aligned, offset2] | [odd, offset1: status asserted]
-  norm.hip:709      norm_act_bwd_h16: c8 twin of dx 16-B aligned, stride % 8              test_c8_norm (strided twin) | test_c8_rejects_misaligned_slots
-  norm.hip:771      the same REQUIRE in m355_norm_act_bwd_apply (synchronised BN)         untested: no raw_ops wrapper; it guards the call into the
-                    implementation that :709 guards (norm_act_bwd_apply_impl)
+  norm_host.hpp norm_pass   the vector verdict of each pass (one function; keyed by pass, not by line):
+    plan: vector verdict of the forward       S % 4, xbs / ybs / abs % 4, x / y / add 16-B aligned   test_norm[aligned S%4==0 | odd, offset*, S odd]
+    plan: vector verdict of the statistics    len % 4, S % 4, xbs % 4, x aligned                    test_norm (same ids); m355_norm_sums (synchronised BN) launches the same
+                    kernel from the same verdict: test_norm_halves_gpu.py runs it dense and on a batch stride of dense + 1
+    plan: vector verdict of backward pass 1   S % 4, xbs / ybs % 4, x / dy aligned                  test_norm (same ids)
+    plan: vector verdict of backward pass 2   S % 4, xbs / ybs % 4, x / dy / dx aligned             test_norm (same ids)
+  norm.hip m355_norm_act_pool_fwd   REQUIREs x / y 8-B aligned, even strides                test_norm_act_pool[aligned, offset2] | [odd, offset1: status asserted]
+  norm.hip m355_norm_act_bwd_h16    c8 twin of dx 16-B aligned, stride % 8 (dx16_ok)        test_c8_norm (strided twin) | test_c8_rejects_misaligned_slots
+  norm.hip m355_norm_act_bwd_apply  the same REQUIRE (dx16_ok) in the second half alone     test_norm_halves_gpu.py (accepting side: the twin through the half ==
+                    the twin of the fused call); the rejecting side is the one function test_c8_rejects_misaligned_slots reaches through _bwd_h16
   elementwise.hip:625  s2d REQUIREs the full-resolution tensor 8-B aligned, even stride  test_space_to_depth[aligned, offset2] | [odd, offset1: status asserted]
   elementwise.hip:660  avgpool vec: W % 4, xbs % 4, ybs % 2, x 16-B, y 8-B               test_pool[aligned W=8 | odd, offset*, W=6]
   elementwise.hip:712  trilinear quads: W even, ybs % 4, y 16-B                          test_upsample[aligned even W | odd, offset*, odd W]
@@ -50,8 +52,9 @@ Host / kernel branches on a stride or a pointer (file:line, condition, who takes
   elementwise.hip:865  copy_channels vec: C*S % 4, strides % 4, both 16-B               test_copy_channels[aligned | odd, offset*]
   elementwise.hip:890  m355_add: dense, no stride argument                              out of scope (no slot can be passed)
   dwi.hip:79        dwi_mean vec: S % 4, x / y 16-B aligned                              test_dwi_mean_on_an_offset_base[aligned | offset1, offset2, S odd]
-  act16.hip:327 norm_act_fwd_h16, :357 avgpool fwd h16, :390 norm_act_fwd_c8, :417 act16_channel_partials; train16.hip:344 / 361
-                    act16_pack_scaled / _unpack_scaled, :405 norm_act_bwd_c8, :507 avgpool bwd h16
+  c8 REQUIREs (16 B, strides % 8) by entry point: act16.hip m355_norm_act_fwd_h16, m355_avgpool3d_2x_fwd_h16, m355_norm_act_fwd_c8,
+                    m355_act16_channel_partials; train16.hip m355_act16_pack_scaled / _unpack_scaled, norm_bwd_c8_args (m355_norm_act_bwd_c8
+                    and its halves), m355_avgpool3d_2x_bwd_h16
                                                                                         test_c8_*, test_act16_pack_unpack | test_c8_rejects_misaligned_slots (each by name;
                                                                                         act16_channel_partials: the rejecting side only, its accepting side is test_kernels_gpu.py's dense call)
   evaluate.hip:208,349  dense [N, C, S] tensors without a batch stride                   out of scope (test_evaluation_gpu.py covers its alignment fallbacks)

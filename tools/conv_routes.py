@@ -12,7 +12,10 @@ h16_bwd_workspace), m355_conv_transpose3d_plan for which = 0..5 with an aligned 
 at a 4-byte offset.  Two hashes: "queries" covers the three queries alone, so it can be compared with a library that
 predates the plan query (it then is the only one printed), "routes" covers the whole lines.
 
-usage: python tools/conv_routes.py [--convt] [--hash-only] [--jobs N] > routes.txt"""
+--norm: the same for the normalisation plans (csrc/norm_host.hpp): per line m355_norm_num_stats, m355_norm_workspace,
+m355_act16_partials_slots(S) -- the "queries" hash -- and m355_norm_plan for which = 0..9 -- with them the "routes" hash.
+
+usage: python tools/conv_routes.py [--convt | --norm] [--hash-only] [--jobs N] > routes.txt"""
 import argparse
 import ctypes as C
 import hashlib
@@ -110,6 +113,53 @@ def convt_main(a):
     print(f"lines {n} queries sha256 {queries.hexdigest()}" + (f" routes sha256 {routes.hexdigest()}" if have_plan else ""))
 
 
+# ---- --norm ----
+# (C, groups): BatchNorm (0), InstanceNorm (groups = C), GroupNorm with 4 and 5 channels per group
+NORM_CHANNELS = [(8, 0), (20, 0), (32, 0), (8, 8), (8, 2), (32, 8), (20, 4), (40, 8)]
+# S % 4 both ways; each side of the chunk sizes 4096 and 16384; N * S (BN, N = 2: 8191..8193) and (C / groups) * S (GN: 4 * 4096
+# and 4097, 5 * 3276 and 3277) on each side of 16384; the 64^3, 128^3 and 32 x 256 x 256 levels
+NORM_S = [1, 63, 64, 3276, 3277, 4095, 4096, 4097, 4100, 8191, 8192, 8193, 16383, 16384, 16385, 16388, 32768, 64 ** 3, 128 ** 3,
+          32 * 256 * 256]
+NORM_STRIDES = [0, 4, 1]   # batch strides: dense (0), dense + 4 k and dense + k elements for x, y, add (k = 1, 2, 3)
+NORM_PASSES = 10
+
+
+def norm_descriptors():
+    """(N, C, groups, S, stride class)"""
+    return itertools.product((1, 2), NORM_CHANNELS, NORM_S, NORM_STRIDES)
+
+
+def norm_main(a):
+    from segmentation_pipeline_amd import _lib
+    L = C.CDLL(_lib.LIB_PATH)   # (not _lib.lib(): that insists on every symbol, and a parent library has no m355_norm_plan)
+    fns = {}
+    for name in ("m355_norm_num_stats", "m355_norm_workspace", "m355_act16_partials_slots", "m355_norm_plan"):
+        fns[name] = getattr(L, name, None)
+        if fns[name] is not None:
+            fns[name].restype, fns[name].argtypes = _lib.SIGNATURES[name]
+    plan = fns["m355_norm_plan"]
+    d = _lib.NormDesc()
+    ref = C.byref(d)
+    out4 = (C.c_int32 * 4)()
+    qlines, lines = [], []
+    for n, (c, g), s, k in norm_descriptors():
+        d.N, d.C, d.groups, d.S, d.act, d.eps = n, c, g, s, 1, 1e-5
+        d.x_batch_stride, d.y_batch_stride, d.add_batch_stride = [(c * s + k * j) if k else 0 for j in (1, 2, 3)]
+        f = [f"N{n} C{c} g{g} S{s} bs+{k}", f"stats/ws/slots={fns['m355_norm_num_stats'](ref)}/"
+             f"{fns['m355_norm_workspace'](ref)}/{fns['m355_act16_partials_slots'](s)}"]
+        qlines.append(" ".join(f))
+        if plan:
+            for which in range(NORM_PASSES):
+                rc = plan(ref, which, out4)
+                f.append(f"plan{which}={rc}:" + "/".join(str(v) for v in out4))
+            lines.append(" ".join(f))
+    qtext, text = "\n".join(qlines) + "\n", "\n".join(lines) + "\n"
+    if not a.hash_only:
+        sys.stdout.write(text if plan else qtext)
+    print(f"lines {len(qlines)} queries sha256 {hashlib.sha256(qtext.encode()).hexdigest()}"
+          + (f" routes sha256 {hashlib.sha256(text.encode()).hexdigest()}" if plan else ""))
+
+
 def _e(**kw):
     return {k: str(v) for k, v in kw.items()}
 
@@ -185,9 +235,12 @@ def main():
     ap.add_argument("--hash-only", action="store_true", help="print no lines, only one hash per tuning set and the total")
     ap.add_argument("--jobs", type=int, default=min(8, os.cpu_count() or 1))
     ap.add_argument("--convt", action="store_true", help="the conv-transpose routes (two hashes: queries, routes)")
+    ap.add_argument("--norm", action="store_true", help="the normalisation plans (two hashes: queries, routes)")
     a = ap.parse_args()
     if a.convt:
         return convt_main(a)
+    if a.norm:
+        return norm_main(a)
     total, n = hashlib.sha256(), 0
     with multiprocessing.get_context("spawn").Pool(a.jobs, maxtasksperchild=1) as pool:
         for idx, count, text in pool.imap(run_set, range(len(TUNING_SETS))):
