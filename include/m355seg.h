@@ -562,6 +562,22 @@ int m355_upsample_trilinear2x_bwd(const float* dy, float* dx, int32_t N, int32_t
                                   int32_t D, int32_t H, int32_t W,
                                   int64_t dy_batch_stride, int64_t dx_batch_stride, void* stream);
 
+/* Introspection, as m355_norm_plan: how an entry point of the factor-2 resampling family serves a call.  op:
+ *   0 avgpool3d_2x_fwd   1 avgpool3d_2x_bwd   2 avgpool3d_2x_bwd_add   3 upsample_trilinear2x_fwd   4 upsample_trilinear2x_bwd
+ *   5 space_to_depth2    6 depth_to_space2    7 maxpool3d_2x_fwd       8 maxpool3d_2x_bwd
+ *   9 avgpool3d_2x_fwd_h16   10 avgpool3d_2x_bwd_h16   11 upsample_trilinear2x_fwd_h16   12 upsample_trilinear2x_bwd_h16
+ *   13 space_to_depth2_h16   14 depth_to_space2_h16    15 maxpool3d_2x_fwd_h16           16 maxpool3d_2x_bwd_h16
+ * N .. W and compute as that entry point takes them (compute is ignored by the fp32 ones); strides3: its batch strides in
+ * its own argument order; pointers4: the addresses of its tensors in the order of strides3, then the max-pool route
+ * bytes (0 for a NULL); entries the entry point has no argument for are ignored.  The addresses are compared with 0 and
+ * masked, never read.  Runs the entry point's argument checks and returns its code; on M355_OK
+ *   out8[0] = kernel variant: 0 scalar / the only kernel, 1 vector (fp32 pools: 16-byte rows) or quads (trilinear forward),
+ *             2 the LDS-tiled trilinear forward;   out8[1..3] = grid x, y, z;   out8[4] = dynamic LDS bytes;
+ *   out8[5..7] = the batch strides, dense ones resolved (0 for an unused one).
+ * Pure host function, launches nothing. */
+int m355_resample_plan(int32_t op, int32_t N, int32_t C, int32_t D, int32_t H, int32_t W, const int64_t* strides3,
+                       const uint64_t* pointers4, int32_t compute, int64_t* out8);
+
 /* ---------------------------------------------------------------- softmax
  * nn.Softmax(dim=1) (models/modular_unet.py:26,46,84,100) and the softmax of
  * StochasticMatrix (components.py:170-185): x viewed as [N, C, inner, S] with

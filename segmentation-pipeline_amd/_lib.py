@@ -206,6 +206,8 @@ SIGNATURES = {
     "m355_norm_act_bwd_reduce": (C.c_int, [_ND, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int, _P, _P, _P, _sz, _P]),
     "m355_norm_act_bwd_apply": (C.c_int, [_ND, _P, _P, _P, _P, _P, _P, _P, _P, _P, _i64, _i32, _P]),
     "m355_norm_act_bwd_h16": (C.c_int, [_ND, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int, _P, _i64, _i32, _P, _sz, _P]),
+    "m355_resample_plan": (C.c_int, [_i32, _i32, _i32, _i32, _i32, _i32, C.POINTER(_i64), C.POINTER(C.c_uint64), _i32,
+                                     C.POINTER(_i64)]),
     "m355_avgpool3d_2x_fwd": (C.c_int, [_P, _P, _i32, _i32, _i32, _i32, _i32, _i64, _i64, _P]),
     "m355_avgpool3d_2x_bwd": (C.c_int, [_P, _P, _i32, _i32, _i32, _i32, _i32, _i64, _i64, _P]),
     "m355_avgpool3d_2x_bwd_add": (C.c_int, [_P, _P, _P, _i32, _i32, _i32, _i32, _i32, _i64, _i64, _i64, _P]),
@@ -272,6 +274,28 @@ SIGNATURES = {
     "m355_slice_rank": (C.c_int, [_P, C.POINTER(SliceSeg), _i32, _P, _P, _P, _P, _P]),
     "m355_slice_mosaic": (C.c_int, [C.POINTER(SliceMosaicDesc), _i32, C.POINTER(SliceTileDesc), _i32, _P, _P]),
 }
+
+
+# The factor-2 resampling family in the numbering of m355_resample_plan's `op`: (entry point, its pointer arguments as indices
+# into (tensor 0, tensor 1, tensor 2, route bytes) -- the tensors in the order of its batch strides --, number of batch
+# strides, its argument checks first to last: n null, d dimension <= 0, o odd size, c compute mode, a alignment).
+RESAMPLE_OPS = [
+    ("avgpool3d_2x_fwd", (0, 1), 2, "dno"), ("avgpool3d_2x_bwd", (0, 1), 2, "dno"), ("avgpool3d_2x_bwd_add", (0, 1, 2), 3, "dno"),
+    ("upsample_trilinear2x_fwd", (0, 1), 2, "dn"), ("upsample_trilinear2x_bwd", (0, 1), 2, "dn"),
+    ("space_to_depth2", (0, 1), 2, "ndoa"), ("depth_to_space2", (0, 1), 2, "ndoa"),
+    ("maxpool3d_2x_fwd", (0, 1, 3), 2, "ndo"), ("maxpool3d_2x_bwd", (0, 3, 1, 2), 3, "ndo"),
+    ("avgpool3d_2x_fwd_h16", (0, 1), 2, "ndoca"), ("avgpool3d_2x_bwd_h16", (0, 1, 2), 3, "cndoa"),
+    ("upsample_trilinear2x_fwd_h16", (0, 1), 2, "ndca"), ("upsample_trilinear2x_bwd_h16", (0, 1), 2, "ndca"),
+    ("space_to_depth2_h16", (0, 1), 2, "ondca"), ("depth_to_space2_h16", (0, 1), 2, "ondca"),
+    ("maxpool3d_2x_fwd_h16", (0, 1, 3), 2, "ndoca"), ("maxpool3d_2x_bwd_h16", (0, 3, 1, 2), 3, "ndoca"),
+]
+
+
+def resample_args(op, shape, strides, pointers, compute):
+    """the argument tuple of entry point RESAMPLE_OPS[op] for what m355_resample_plan takes (stream: the default one)"""
+    _, order, nstrides, checks = RESAMPLE_OPS[op]
+    return (tuple(C.c_void_p(pointers[i]) for i in order) + tuple(shape) + tuple(strides[:nstrides])
+            + ((compute,) if "c" in checks else ()) + (None,))
 
 
 class M355Error(RuntimeError):

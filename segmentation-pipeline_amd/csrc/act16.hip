@@ -6,6 +6,7 @@
 // (models/components.py:52-55, + the residual sum :67-68) and nn.AvgPool3d(2, 2)
 // (models/modular_unet.py:22,41,64,92), for the data flow conv -> norm/act -> conv under BASELINE cfg3 / cfg5.
 #include "norm_host.hpp"
+#include "resample_host.hpp"
 
 namespace m355 {
 
@@ -331,25 +332,14 @@ extern "C" int m355_norm_act_fwd_h16(const m355_norm_desc* d, const float* x, co
 extern "C" int m355_avgpool3d_2x_fwd_h16(const void* x16, void* y16, int32_t N, int32_t C, int32_t D, int32_t H,
                                          int32_t W, int64_t x16_batch_stride, int64_t y16_batch_stride,
                                          int32_t compute, void* stream) {
-  M355_REQUIRE(x16 && y16, M355_EINVALID_ARG, "avgpool3d_2x_fwd_h16: null pointer");
-  M355_REQUIRE(N > 0 && C > 0 && D > 0 && H > 0 && W > 0, M355_EINVALID_ARG, "avgpool3d_2x_fwd_h16: bad shape");
-  M355_REQUIRE(D % 2 == 0 && H % 2 == 0 && W % 2 == 0, M355_EUNSUPPORTED,
-               "avgpool3d_2x_fwd_h16: odd spatial size (%d,%d,%d)", D, H, W);
-  M355_REQUIRE(compute == M355_COMPUTE_BF16 || compute == M355_COMPUTE_F16, M355_EINVALID_ARG,
-               "avgpool3d_2x_fwd_h16: compute must be M355_COMPUTE_BF16 or M355_COMPUTE_F16");
-  const int CB = (int)c8_blocks(C);
-  const int64_t S = (int64_t)D * H * W;
-  const int64_t xbs = dense_or(x16_batch_stride, CB * S * 8), ybs = dense_or(y16_batch_stride, CB * (S / 8) * 8);
-  M355_REQUIRE((((uintptr_t)x16 | (uintptr_t)y16) & 15) == 0 && xbs % 8 == 0 && ybs % 8 == 0, M355_EINVALID_ARG,
-               "avgpool3d_2x_fwd_h16: c8 tensor not 16B aligned");
-  const int64_t total = (int64_t)N * CB * (S / 8);
-  const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(ceil_div(total, 256), 8192));
-  if (compute == M355_COMPUTE_BF16)
-    hipLaunchKernelGGL(avgpool2_c8_kernel<__bf16>, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const __bf16*)x16,
-                       (__bf16*)y16, CB, D, H, W, xbs, ybs, N);
-  else
-    hipLaunchKernelGGL(avgpool2_c8_kernel<_Float16>, dim3(grid), dim3(256), 0, (hipStream_t)stream,
-                       (const _Float16*)x16, (_Float16*)y16, CB, D, H, W, xbs, ybs, N);
+  const ResampleArgs a = {N, C, D, H, W, compute, {x16_batch_stride, y16_batch_stride, 0}, {(uintptr_t)x16, (uintptr_t)y16, 0, 0}};
+  if (int rc = validate_resample(RS_AVG_FWD_H16, a)) return rc;
+  const ResamplePlan p = plan_resample(RS_AVG_FWD_H16, a);
+  with_h16(compute, [&](auto T) {
+    typedef typename decltype(T)::type HT;
+    hipLaunchKernelGGL(avgpool2_c8_kernel<HT>, p.grid, dim3(256), 0, (hipStream_t)stream, (const HT*)x16, (HT*)y16,
+                       (int)c8_blocks(C), D, H, W, p.bs[0], p.bs[1], N);
+  });
   return check_launch("avgpool3d_2x_fwd_h16");
 }
 

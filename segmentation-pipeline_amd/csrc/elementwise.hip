@@ -6,8 +6,7 @@
 // ModularUNet (models/modular_unet.py:20-26,39-46,92,96,100), torch.cat
 // (modular_unet.py:97), Dropout3d and the residual add of Block3d
 // (models/components.py:58-60,67-71), StochasticMatrix softmax (components.py:170-185).
-#include "common.hpp"
-#include "h16.hpp"
+#include "resample_host.hpp"
 
 namespace m355 {
 
@@ -199,7 +198,6 @@ __global__ __launch_bounds__(256) void trilinear2_fwd_q_kernel(const float* __re
 // <= 4 x 10 input rows they read (coalesced) and takes its eight taps per output from LDS instead of eight scattered
 // global loads -- the quad kernel above is load-instruction-bound (32 L1 loads per thread, 1.9 TB/s of output).
 // Same expressions per output as the other two forward kernels.
-constexpr int TRI_TZ = 4, TRI_TY = 16, TRI_PZ = 4, TRI_PY = 10;
 __global__ __launch_bounds__(256) void trilinear2_fwd_lds_kernel(const float* __restrict__ x,
                                                                  float* __restrict__ y, int C, int D, int H,
                                                                  int W, int64_t xbs, int64_t ybs) {
@@ -612,91 +610,62 @@ __global__ __launch_bounds__(256) void s2d_c8_kernel(const HT* __restrict__ src,
 
 using namespace m355;
 
-static int s2d_common(const float* x, float* y, int32_t N, int32_t C, int32_t D, int32_t H, int32_t W, int64_t xbs_,
-                      int64_t ybs_, void* stream, bool to_depth, const char* who) {
-  M355_REQUIRE(x && y, M355_EINVALID_ARG, "%s: null pointer", who);
-  M355_REQUIRE(N > 0 && C > 0 && D > 0 && H > 0 && W > 0, M355_EINVALID_ARG, "%s: non-positive dimension", who);
-  M355_REQUIRE(D % 2 == 0 && H % 2 == 0 && W % 2 == 0, M355_EUNSUPPORTED, "%s: odd spatial size (%d,%d,%d)", who,
-               D, H, W);
-  const int64_t dense = (int64_t)C * D * H * W;
-  // to_depth: x is the full tensor; otherwise y is
-  const int64_t fbs = dense_or(to_depth ? xbs_ : ybs_, dense), pbs = dense_or(to_depth ? ybs_ : xbs_, dense);
-  const float* full = to_depth ? x : y;
-  M355_REQUIRE(((uintptr_t)full & 7) == 0 && fbs % 2 == 0, M355_EUNSUPPORTED, "%s: full tensor not 8-byte aligned", who);
-  const int64_t total = (int64_t)N * C * D * H * (W / 2);
-  const unsigned blocks = (unsigned)std::max<int64_t>(1, std::min<int64_t>(ceil_div(total, 256), 16384));
-  if (to_depth)
-    hipLaunchKernelGGL(s2d_kernel<true>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, x, y, N, C, D, H, W, fbs, pbs);
-  else
-    hipLaunchKernelGGL(s2d_kernel<false>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, x, y, N, C, D, H, W, fbs,
-                       pbs);
-  return check_launch(who);
+static int s2d_common(ResampleOp op, const float* x, float* y, int32_t N, int32_t C, int32_t D, int32_t H, int32_t W,
+                      int64_t xbs, int64_t ybs, void* stream) {
+  const ResampleArgs a = {N, C, D, H, W, 0, {xbs, ybs, 0}, {(uintptr_t)x, (uintptr_t)y, 0, 0}};
+  if (int rc = validate_resample(op, a)) return rc;
+  const ResamplePlan p = plan_resample(op, a);
+  // the kernel takes the full tensor's stride first
+  with_bool(op == RS_S2D, [&](auto TD) {
+    constexpr bool to_depth = decltype(TD)::value;
+    hipLaunchKernelGGL(s2d_kernel<to_depth>, p.grid, dim3(256), 0, (hipStream_t)stream, x, y, N, C, D, H, W,
+                       p.bs[to_depth ? 0 : 1], p.bs[to_depth ? 1 : 0]);
+  });
+  return check_launch(RESAMPLE_ROWS[op].name);
 }
 
 extern "C" int m355_space_to_depth2(const float* x, float* y, int32_t N, int32_t C, int32_t D, int32_t H, int32_t W,
                                     int64_t x_batch_stride, int64_t y_batch_stride, void* stream) {
-  return s2d_common(x, y, N, C, D, H, W, x_batch_stride, y_batch_stride, stream, true, "space_to_depth2");
+  return s2d_common(RS_S2D, x, y, N, C, D, H, W, x_batch_stride, y_batch_stride, stream);
 }
 extern "C" int m355_depth_to_space2(const float* x, float* y, int32_t N, int32_t C, int32_t D, int32_t H, int32_t W,
                                     int64_t x_batch_stride, int64_t y_batch_stride, void* stream) {
-  return s2d_common(x, y, N, C, D, H, W, x_batch_stride, y_batch_stride, stream, false, "depth_to_space2");
-}
-
-static int check_ncdhw(int N, int C, int D, int H, int W, const char* who) {
-  M355_REQUIRE(N > 0 && C > 0 && D > 0 && H > 0 && W > 0, M355_EINVALID_ARG,
-               "%s: non-positive dimension", who);
-  return M355_OK;
+  return s2d_common(RS_D2S, x, y, N, C, D, H, W, x_batch_stride, y_batch_stride, stream);
 }
 
 extern "C" int m355_avgpool3d_2x_fwd(const float* x, float* y, int32_t N, int32_t C, int32_t D,
                                      int32_t H, int32_t W, int64_t x_batch_stride,
                                      int64_t y_batch_stride, void* stream) {
-  if (int rc = check_ncdhw(N, C, D, H, W, "avgpool3d_2x_fwd")) return rc;
-  M355_REQUIRE(x && y, M355_EINVALID_ARG, "avgpool3d_2x_fwd: null pointer");
-  M355_REQUIRE(D % 2 == 0 && H % 2 == 0 && W % 2 == 0, M355_EUNSUPPORTED,
-               "avgpool3d_2x_fwd: odd spatial size (%d,%d,%d)", D, H, W);
-  const int64_t xbs = dense_or(x_batch_stride, (int64_t)C * D * H * W);
-  const int64_t ybs = dense_or(y_batch_stride, (int64_t)C * (D / 2) * (H / 2) * (W / 2));
-  const bool vec = (W % 4 == 0) && (xbs % 4 == 0) && (ybs % 2 == 0) && ((uintptr_t)x & 15) == 0 &&
-                   ((uintptr_t)y & 7) == 0;
-  const int64_t total = (int64_t)N * C * (D / 2) * (H / 2) * (vec ? W / 4 : W / 2);
-  if (vec)
-    hipLaunchKernelGGL(avgpool2_fwd_kernel<true>, dim3(grid_for(total)), dim3(256), 0,
-                       (hipStream_t)stream, x, y, N, C, D, H, W, xbs, ybs);
-  else
-    hipLaunchKernelGGL(avgpool2_fwd_kernel<false>, dim3(grid_for(total)), dim3(256), 0,
-                       (hipStream_t)stream, x, y, N, C, D, H, W, xbs, ybs);
+  const ResampleArgs a = {N, C, D, H, W, 0, {x_batch_stride, y_batch_stride, 0}, {(uintptr_t)x, (uintptr_t)y, 0, 0}};
+  if (int rc = validate_resample(RS_AVG_FWD, a)) return rc;
+  const ResamplePlan p = plan_resample(RS_AVG_FWD, a);
+  with_bool(p.variant == RS_VECTOR, [&](auto V) {
+    hipLaunchKernelGGL(avgpool2_fwd_kernel<decltype(V)::value>, p.grid, dim3(256), 0, (hipStream_t)stream, x, y, N, C, D, H,
+                       W, p.bs[0], p.bs[1]);
+  });
   return check_launch("avgpool3d_2x_fwd");
 }
 
 extern "C" int m355_avgpool3d_2x_bwd(const float* dy, float* dx, int32_t N, int32_t C, int32_t D,
                                      int32_t H, int32_t W, int64_t dy_batch_stride,
                                      int64_t dx_batch_stride, void* stream) {
-  if (int rc = check_ncdhw(N, C, D, H, W, "avgpool3d_2x_bwd")) return rc;
-  M355_REQUIRE(dy && dx, M355_EINVALID_ARG, "avgpool3d_2x_bwd: null pointer");
-  M355_REQUIRE(D % 2 == 0 && H % 2 == 0 && W % 2 == 0, M355_EUNSUPPORTED,
-               "avgpool3d_2x_bwd: odd spatial size (%d,%d,%d)", D, H, W);
-  const int64_t dxbs = dense_or(dx_batch_stride, (int64_t)C * D * H * W);
-  const int64_t dybs = dense_or(dy_batch_stride, (int64_t)C * (D / 2) * (H / 2) * (W / 2));
-  const int64_t total = (int64_t)N * C * D * H * (W / 2);
-  hipLaunchKernelGGL(avgpool2_bwd_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream,
-                     dy, dx, N, C, D, H, W, dybs, dxbs, (const float*)nullptr, (int64_t)0);
+  const ResampleArgs a = {N, C, D, H, W, 0, {dy_batch_stride, dx_batch_stride, 0}, {(uintptr_t)dy, (uintptr_t)dx, 0, 0}};
+  if (int rc = validate_resample(RS_AVG_BWD, a)) return rc;
+  const ResamplePlan p = plan_resample(RS_AVG_BWD, a);
+  hipLaunchKernelGGL(avgpool2_bwd_kernel, p.grid, dim3(256), 0, (hipStream_t)stream, dy, dx, N, C, D, H, W, p.bs[0], p.bs[1],
+                     (const float*)nullptr, (int64_t)0);
   return check_launch("avgpool3d_2x_bwd");
 }
 
 extern "C" int m355_avgpool3d_2x_bwd_add(const float* dy, const float* add, float* dx, int32_t N, int32_t C, int32_t D,
                                          int32_t H, int32_t W, int64_t dy_batch_stride, int64_t add_batch_stride,
                                          int64_t dx_batch_stride, void* stream) {
-  if (int rc = check_ncdhw(N, C, D, H, W, "avgpool3d_2x_bwd_add")) return rc;
-  M355_REQUIRE(dy && add && dx, M355_EINVALID_ARG, "avgpool3d_2x_bwd_add: null pointer");
-  M355_REQUIRE(D % 2 == 0 && H % 2 == 0 && W % 2 == 0, M355_EUNSUPPORTED,
-               "avgpool3d_2x_bwd_add: odd spatial size (%d,%d,%d)", D, H, W);
-  const int64_t dense = (int64_t)C * D * H * W;
-  const int64_t dxbs = dense_or(dx_batch_stride, dense), abs_ = dense_or(add_batch_stride, dense);
-  const int64_t dybs = dense_or(dy_batch_stride, (int64_t)C * (D / 2) * (H / 2) * (W / 2));
-  const int64_t total = (int64_t)N * C * D * H * (W / 2);
-  hipLaunchKernelGGL(avgpool2_bwd_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream,
-                     dy, dx, N, C, D, H, W, dybs, dxbs, add, abs_);
+  const ResampleArgs a = {N, C, D, H, W, 0, {dy_batch_stride, add_batch_stride, dx_batch_stride},
+                          {(uintptr_t)dy, (uintptr_t)add, (uintptr_t)dx, 0}};
+  if (int rc = validate_resample(RS_AVG_BWD_ADD, a)) return rc;
+  const ResamplePlan p = plan_resample(RS_AVG_BWD_ADD, a);
+  hipLaunchKernelGGL(avgpool2_bwd_kernel, p.grid, dim3(256), 0, (hipStream_t)stream, dy, dx, N, C, D, H, W, p.bs[0], p.bs[2],
+                     add, p.bs[1]);
   return check_launch("avgpool3d_2x_bwd_add");
 }
 
@@ -704,22 +673,15 @@ extern "C" int m355_upsample_trilinear2x_fwd(const float* x, float* y, int32_t N
                                              int32_t D, int32_t H, int32_t W,
                                              int64_t x_batch_stride, int64_t y_batch_stride,
                                              void* stream) {
-  if (int rc = check_ncdhw(N, C, D, H, W, "upsample_trilinear2x_fwd")) return rc;
-  M355_REQUIRE(x && y, M355_EINVALID_ARG, "upsample_trilinear2x_fwd: null pointer");
-  const int64_t xbs = dense_or(x_batch_stride, (int64_t)C * D * H * W);
-  const int64_t ybs = dense_or(y_batch_stride, (int64_t)C * D * H * W * 8);
-  const int64_t total = (int64_t)N * C * D * H * W * 8;
-  const bool quads = W % 2 == 0 && ybs % 4 == 0 && ((uintptr_t)y & 15) == 0;
-  const size_t lds = (size_t)TRI_PZ * TRI_PY * W * sizeof(float);
-  if (quads && D >= 2 && H >= 2 && lds <= 48 * 1024 && (int64_t)N * C <= 65535 && ceil_div(2 * D, TRI_TZ) <= 65535) {
-    dim3 grid((unsigned)ceil_div(2 * H, TRI_TY), (unsigned)ceil_div(2 * D, TRI_TZ), (unsigned)(N * C));
-    hipLaunchKernelGGL(trilinear2_fwd_lds_kernel, grid, dim3(256), lds, (hipStream_t)stream, x, y, C, D, H, W, xbs, ybs);
-  } else if (quads && (int64_t)N * C * D * H * 4 < (1ll << 31))
-    hipLaunchKernelGGL(trilinear2_fwd_q_kernel, dim3(grid_for(total / 4, 256, 65536)), dim3(256), 0,
-                       (hipStream_t)stream, x, y, N, C, D, H, W, xbs, ybs);
-  else
-    hipLaunchKernelGGL(trilinear2_fwd_kernel, dim3(grid_for(total, 256, 16384)), dim3(256), 0,
-                       (hipStream_t)stream, x, y, N, C, D, H, W, xbs, ybs);
+  const ResampleArgs a = {N, C, D, H, W, 0, {x_batch_stride, y_batch_stride, 0}, {(uintptr_t)x, (uintptr_t)y, 0, 0}};
+  if (int rc = validate_resample(RS_TRI_FWD, a)) return rc;
+  const ResamplePlan p = plan_resample(RS_TRI_FWD, a);
+  const hipStream_t st = (hipStream_t)stream;
+  switch (p.variant) {   // (the tiled kernel has no N: grid.z = N * C)
+    case RS_LDS: hipLaunchKernelGGL(trilinear2_fwd_lds_kernel, p.grid, dim3(256), p.lds, st, x, y, C, D, H, W, p.bs[0], p.bs[1]); break;
+    case RS_QUADS: hipLaunchKernelGGL(trilinear2_fwd_q_kernel, p.grid, dim3(256), 0, st, x, y, N, C, D, H, W, p.bs[0], p.bs[1]); break;
+    default: hipLaunchKernelGGL(trilinear2_fwd_kernel, p.grid, dim3(256), 0, st, x, y, N, C, D, H, W, p.bs[0], p.bs[1]);
+  }
   return check_launch("upsample_trilinear2x_fwd");
 }
 
@@ -727,59 +689,39 @@ extern "C" int m355_upsample_trilinear2x_bwd(const float* dy, float* dx, int32_t
                                              int32_t D, int32_t H, int32_t W,
                                              int64_t dy_batch_stride, int64_t dx_batch_stride,
                                              void* stream) {
-  if (int rc = check_ncdhw(N, C, D, H, W, "upsample_trilinear2x_bwd")) return rc;
-  M355_REQUIRE(dy && dx, M355_EINVALID_ARG, "upsample_trilinear2x_bwd: null pointer");
-  const int64_t dxbs = dense_or(dx_batch_stride, (int64_t)C * D * H * W);
-  const int64_t dybs = dense_or(dy_batch_stride, (int64_t)C * D * H * W * 8);
-  const int64_t total = (int64_t)N * C * D * H * W;
-  hipLaunchKernelGGL(trilinear2_bwd_kernel, dim3(grid_for(total, 256, 65536)), dim3(256), 0,
-                     (hipStream_t)stream, dy, dx, N, C, D, H, W, dybs, dxbs);
+  const ResampleArgs a = {N, C, D, H, W, 0, {dy_batch_stride, dx_batch_stride, 0}, {(uintptr_t)dy, (uintptr_t)dx, 0, 0}};
+  if (int rc = validate_resample(RS_TRI_BWD, a)) return rc;
+  const ResamplePlan p = plan_resample(RS_TRI_BWD, a);
+  hipLaunchKernelGGL(trilinear2_bwd_kernel, p.grid, dim3(256), 0, (hipStream_t)stream, dy, dx, N, C, D, H, W, p.bs[0],
+                     p.bs[1]);
   return check_launch("upsample_trilinear2x_bwd");
-}
-
-static int check_c8_op(const char* who, const void* a, const void* b, int N, int C, int D, int H, int W, int compute,
-                       int64_t abs16, int64_t bbs16) {
-  M355_REQUIRE(a && b, M355_EINVALID_ARG, "%s: null pointer", who);
-  M355_REQUIRE(N > 0 && C > 0 && D > 0 && H > 0 && W > 0, M355_EINVALID_ARG, "%s: non-positive dimension", who);
-  M355_REQUIRE(compute == M355_COMPUTE_BF16 || compute == M355_COMPUTE_F16, M355_EINVALID_ARG,
-               "%s: compute must be M355_COMPUTE_BF16 or M355_COMPUTE_F16", who);
-  M355_REQUIRE((((uintptr_t)a | (uintptr_t)b) & 15) == 0 && abs16 % 8 == 0 && bbs16 % 8 == 0, M355_EINVALID_ARG,
-               "%s: c8 tensor not 16B aligned", who);
-  return M355_OK;
 }
 
 extern "C" int m355_upsample_trilinear2x_fwd_h16(const void* x16, void* y16, int32_t N, int32_t C, int32_t D, int32_t H,
                                                  int32_t W, int64_t x16_batch_stride, int64_t y16_batch_stride,
                                                  int32_t compute, void* stream) {
-  const int CB = (int)c8_blocks(C);
-  const int64_t S = (int64_t)D * H * W;
-  const int64_t xbs = dense_or(x16_batch_stride, CB * S * 8), ybs = dense_or(y16_batch_stride, CB * S * 64);
-  if (int rc = check_c8_op("upsample_trilinear2x_fwd_h16", x16, y16, N, C, D, H, W, compute, xbs, ybs)) return rc;
-  const int64_t total = (int64_t)N * CB * S * 8;
-  if (compute == M355_COMPUTE_BF16)
-    hipLaunchKernelGGL(trilinear2_fwd_c8_kernel<__bf16>, dim3(grid_for(total, 256, 65536)), dim3(256), 0,
-                       (hipStream_t)stream, (const __bf16*)x16, (__bf16*)y16, N, CB, D, H, W, xbs, ybs);
-  else
-    hipLaunchKernelGGL(trilinear2_fwd_c8_kernel<_Float16>, dim3(grid_for(total, 256, 65536)), dim3(256), 0,
-                       (hipStream_t)stream, (const _Float16*)x16, (_Float16*)y16, N, CB, D, H, W, xbs, ybs);
+  const ResampleArgs a = {N, C, D, H, W, compute, {x16_batch_stride, y16_batch_stride, 0}, {(uintptr_t)x16, (uintptr_t)y16, 0, 0}};
+  if (int rc = validate_resample(RS_TRI_FWD_H16, a)) return rc;
+  const ResamplePlan p = plan_resample(RS_TRI_FWD_H16, a);
+  with_h16(compute, [&](auto T) {
+    typedef typename decltype(T)::type HT;
+    hipLaunchKernelGGL(trilinear2_fwd_c8_kernel<HT>, p.grid, dim3(256), 0, (hipStream_t)stream, (const HT*)x16, (HT*)y16, N,
+                       (int)c8_blocks(C), D, H, W, p.bs[0], p.bs[1]);
+  });
   return check_launch("upsample_trilinear2x_fwd_h16");
 }
 
 extern "C" int m355_upsample_trilinear2x_bwd_h16(const void* dy16, void* dx16, int32_t N, int32_t C, int32_t D, int32_t H,
                                                  int32_t W, int64_t dy16_batch_stride, int64_t dx16_batch_stride,
                                                  int32_t compute, void* stream) {
-  const int CB = (int)c8_blocks(C);
-  const int64_t S = (int64_t)D * H * W;
-  const int64_t dybs = dense_or(dy16_batch_stride, CB * S * 64), dxbs = dense_or(dx16_batch_stride, CB * S * 8);
-  if (int rc = check_c8_op("upsample_trilinear2x_bwd_h16", dy16, dx16, N, C, D, H, W, compute, dybs, dxbs)) return rc;
-  const int64_t total = (int64_t)N * CB * S;
-  if (compute == M355_COMPUTE_BF16)
-    hipLaunchKernelGGL(trilinear2_bwd_c8_kernel<__bf16>, dim3(grid_for(total, 256, 65536)), dim3(256), 0,
-                       (hipStream_t)stream, (const __bf16*)dy16, (__bf16*)dx16, N, CB, D, H, W, dybs, dxbs, overflow_flag());
-  else
-    hipLaunchKernelGGL(trilinear2_bwd_c8_kernel<_Float16>, dim3(grid_for(total, 256, 65536)), dim3(256), 0,
-                       (hipStream_t)stream, (const _Float16*)dy16, (_Float16*)dx16, N, CB, D, H, W, dybs, dxbs,
-                       overflow_flag());
+  const ResampleArgs a = {N, C, D, H, W, compute, {dy16_batch_stride, dx16_batch_stride, 0}, {(uintptr_t)dy16, (uintptr_t)dx16, 0, 0}};
+  if (int rc = validate_resample(RS_TRI_BWD_H16, a)) return rc;
+  const ResamplePlan p = plan_resample(RS_TRI_BWD_H16, a);
+  with_h16(compute, [&](auto T) {
+    typedef typename decltype(T)::type HT;
+    hipLaunchKernelGGL(trilinear2_bwd_c8_kernel<HT>, p.grid, dim3(256), 0, (hipStream_t)stream, (const HT*)dy16, (HT*)dx16, N,
+                       (int)c8_blocks(C), D, H, W, p.bs[0], p.bs[1], overflow_flag());
+  });
   return check_launch("upsample_trilinear2x_bwd_h16");
 }
 
@@ -789,46 +731,60 @@ extern "C" int m355_act16_channel_scale(const void* x16, const float* scale, voi
   const int CB = (int)c8_blocks(C);
   const int64_t xbs = dense_or(x16_batch_stride, CB * S * 8), ybs = dense_or(y16_batch_stride, CB * S * 8);
   M355_REQUIRE(scale && S > 0, M355_EINVALID_ARG, "act16_channel_scale: null scale or empty tensor");
-  if (int rc = check_c8_op("act16_channel_scale", x16, y16, N, C, 1, 1, 1, compute, xbs, ybs)) return rc;
+  M355_REQUIRE(x16 && y16, M355_EINVALID_ARG, "act16_channel_scale: null pointer");
+  M355_REQUIRE(N > 0 && C > 0, M355_EINVALID_ARG, "act16_channel_scale: non-positive dimension");
+  M355_REQUIRE(compute == M355_COMPUTE_BF16 || compute == M355_COMPUTE_F16, M355_EINVALID_ARG,
+               "act16_channel_scale: compute must be M355_COMPUTE_BF16 or M355_COMPUTE_F16");
+  M355_REQUIRE((((uintptr_t)x16 | (uintptr_t)y16) & 15) == 0 && xbs % 8 == 0 && ybs % 8 == 0, M355_EINVALID_ARG,
+               "act16_channel_scale: c8 tensor not 16B aligned");
   const int64_t total = (int64_t)N * CB * S;
-  if (compute == M355_COMPUTE_BF16)
-    hipLaunchKernelGGL(channel_scale_c8_kernel<__bf16>, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream,
-                       (const __bf16*)x16, scale, (__bf16*)y16, N, C, CB, S, xbs, ybs, overflow_flag());
-  else
-    hipLaunchKernelGGL(channel_scale_c8_kernel<_Float16>, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream,
-                       (const _Float16*)x16, scale, (_Float16*)y16, N, C, CB, S, xbs, ybs, overflow_flag());
+  with_h16(compute, [&](auto T) {
+    typedef typename decltype(T)::type HT;
+    hipLaunchKernelGGL(channel_scale_c8_kernel<HT>, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, (const HT*)x16,
+                       scale, (HT*)y16, N, C, CB, S, xbs, ybs, overflow_flag());
+  });
   return check_launch("act16_channel_scale");
 }
 
-static int s2d_c8_common(const void* x16, void* y16, int N, int C, int D, int H, int W, int64_t xbs_, int64_t ybs_,
-                         int compute, void* stream, bool to_depth, const char* who) {
-  M355_REQUIRE(D % 2 == 0 && H % 2 == 0 && W % 2 == 0, M355_EUNSUPPORTED, "%s: odd spatial size (%d,%d,%d)", who, D, H, W);
-  const int64_t S = (int64_t)D * H * W;
-  const int64_t fdense = c8_blocks(C) * S * 8, pdense = (int64_t)C * (S / 8) * 8;   // packed: C blocks of 8 parities
-  const int64_t fbs = dense_or(to_depth ? xbs_ : ybs_, fdense), pbs = dense_or(to_depth ? ybs_ : xbs_, pdense);
-  if (int rc = check_c8_op(who, x16, y16, N, C, D, H, W, compute, fbs, pbs)) return rc;
-  const int64_t total = (int64_t)N * c8_blocks(C) * (S / 8);
-  const dim3 grid(grid_for(total, 256, 65536));
-#define M355_S2D(HT, TD) \
-  hipLaunchKernelGGL((s2d_c8_kernel<HT, TD>), grid, dim3(256), 0, (hipStream_t)stream, (const HT*)x16, (HT*)y16, N, C, D, H, W, fbs, pbs)
-  if (compute == M355_COMPUTE_BF16) {
-    if (to_depth) M355_S2D(__bf16, true); else M355_S2D(__bf16, false);
-  } else {
-    if (to_depth) M355_S2D(_Float16, true); else M355_S2D(_Float16, false);
-  }
-#undef M355_S2D
-  return check_launch(who);
+static int s2d_c8_common(ResampleOp op, const void* x16, void* y16, int N, int C, int D, int H, int W, int64_t xbs,
+                         int64_t ybs, int compute, void* stream) {
+  const ResampleArgs a = {N, C, D, H, W, compute, {xbs, ybs, 0}, {(uintptr_t)x16, (uintptr_t)y16, 0, 0}};
+  if (int rc = validate_resample(op, a)) return rc;
+  const ResamplePlan p = plan_resample(op, a);
+  with_h16(compute, [&](auto T) {
+    typedef typename decltype(T)::type HT;
+    with_bool(op == RS_S2D_H16, [&](auto TD) {
+      constexpr bool to_depth = decltype(TD)::value;
+      hipLaunchKernelGGL((s2d_c8_kernel<HT, to_depth>), p.grid, dim3(256), 0, (hipStream_t)stream, (const HT*)x16, (HT*)y16, N,
+                         C, D, H, W, p.bs[to_depth ? 0 : 1], p.bs[to_depth ? 1 : 0]);
+    });
+  });
+  return check_launch(RESAMPLE_ROWS[op].name);
 }
 
 extern "C" int m355_space_to_depth2_h16(const void* x16, void* y16, int32_t N, int32_t C, int32_t D, int32_t H, int32_t W,
                                         int64_t x16_batch_stride, int64_t y16_batch_stride, int32_t compute, void* stream) {
-  return s2d_c8_common(x16, y16, N, C, D, H, W, x16_batch_stride, y16_batch_stride, compute, stream, true,
-                       "space_to_depth2_h16");
+  return s2d_c8_common(RS_S2D_H16, x16, y16, N, C, D, H, W, x16_batch_stride, y16_batch_stride, compute, stream);
 }
 extern "C" int m355_depth_to_space2_h16(const void* x16, void* y16, int32_t N, int32_t C, int32_t D, int32_t H, int32_t W,
                                         int64_t x16_batch_stride, int64_t y16_batch_stride, int32_t compute, void* stream) {
-  return s2d_c8_common(x16, y16, N, C, D, H, W, x16_batch_stride, y16_batch_stride, compute, stream, false,
-                       "depth_to_space2_h16");
+  return s2d_c8_common(RS_D2S_H16, x16, y16, N, C, D, H, W, x16_batch_stride, y16_batch_stride, compute, stream);
+}
+
+// how the entry point `op` (ResampleOp) would serve this call: the same checks, the same code, no launch
+extern "C" int m355_resample_plan(int32_t op, int32_t N, int32_t C, int32_t D, int32_t H, int32_t W, const int64_t* strides3,
+                                  const uint64_t* pointers4, int32_t compute, int64_t* out8) {
+  M355_REQUIRE(strides3 && pointers4 && out8, M355_EINVALID_ARG, "resample_plan: null pointer");
+  M355_REQUIRE(op >= 0 && op < RS_COUNT, M355_EINVALID_ARG, "resample_plan: no op %d", op);
+  const ResampleRow& row = RESAMPLE_ROWS[op];
+  ResampleArgs a = {N, C, D, H, W, compute, {0, 0, 0}, {0, 0, 0, row.routes ? (uintptr_t)pointers4[3] : 0}};
+  for (int i = 0; i < 3; ++i)   // what the entry point does not take, it does not see
+    if (row.t[i] != RS_NONE) a.bs[i] = strides3[i], a.ptr[i] = (uintptr_t)pointers4[i];
+  if (int rc = validate_resample((ResampleOp)op, a)) return rc;
+  const ResamplePlan p = plan_resample((ResampleOp)op, a);
+  const int64_t out[8] = {p.variant, p.grid.x, p.grid.y, p.grid.z, (int64_t)p.lds, p.bs[0], p.bs[1], p.bs[2]};
+  std::copy(out, out + 8, out8);
+  return M355_OK;
 }
 
 extern "C" int m355_softmax_fwd(const float* x, float* y, int32_t N, int32_t C, int32_t inner,

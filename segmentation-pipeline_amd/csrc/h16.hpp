@@ -8,6 +8,8 @@
 // lane from HBM to LDS to the matrix core without touching them, a tap shift is a whole-item offset, and a
 // channel slice of a concat buffer that starts at a multiple of 8 channels is a contiguous run of blocks.
 #pragma once
+#include <type_traits>
+
 #include "common.hpp"
 
 namespace m355 {
@@ -65,6 +67,19 @@ __device__ __forceinline__ void report_nonfinite(float v, int* __restrict__ ofla
 }
 
 static inline int64_t c8_blocks(int64_t C) { return (C + 7) / 8; }
+
+// A kernel's template arguments chosen at run time, so that each launch is written once:
+//   with_bool(v, [&](auto V) { launch kernel<decltype(V)::value> });   with_h16(compute, [&](auto T) { ...<typename decltype(T)::type> });
+template <typename T>
+struct TypeTag { typedef T type; };
+template <typename F>
+static inline void with_bool(bool vec, F&& f) {
+  if (vec) f(std::true_type()); else f(std::false_type());
+}
+template <typename F>
+static inline void with_h16(int compute, F&& f) {
+  if (compute == M355_COMPUTE_BF16) f(TypeTag<__bf16>()); else f(TypeTag<_Float16>());
+}
 
 // fp32 NCDHW -> c8 (round to nearest even) and back; implemented in conv3d_h16.hip
 int launch_pack_act16(const float* x, void* x16, int N, int C, int64_t S, int64_t xbs, int64_t x16bs, int compute,

@@ -9,14 +9,9 @@
 // all -inf window routes to element 0, and [-0.0, +0.0, ...] returns -0.0.  The output is the selected element's
 // bits.  The route is the window position 0..7 = (dd * 2 + dh) * 2 + dw, one uint8 per pooled element; the backward
 // reads it instead of x, writes every dx element exactly once and needs no atomics.
-#include "common.hpp"
-#include "h16.hpp"
+#include "resample_host.hpp"
 
 namespace m355 {
-
-static inline unsigned mp_grid(int64_t work, int64_t cap) {
-  return (unsigned)std::max<int64_t>(1, std::min<int64_t>(ceil_div(work, 256), cap));
-}
 
 __device__ __forceinline__ void mp_scan(float v, int q, float& m, int& k) {
   if (v > m || v != v) {
@@ -230,76 +225,48 @@ __global__ __launch_bounds__(256) void maxpool2_bwd_c8_kernel(const HT* __restri
   report_saturation(sat, oflag);
 }
 
-// argument checks shared by the four entry points, in one order: null pointers, shape, odd sizes, compute mode
-// (compute < 0: an fp32 entry point, nothing to check)
-static int mp_check(const char* who, bool pointers, int N, int C, int D, int H, int W, int compute = -1) {
-  M355_REQUIRE(pointers, M355_EINVALID_ARG, "%s: null pointer", who);
-  M355_REQUIRE(N > 0 && C > 0 && D > 0 && H > 0 && W > 0, M355_EINVALID_ARG, "%s: non-positive dimension", who);
-  M355_REQUIRE(D % 2 == 0 && H % 2 == 0 && W % 2 == 0, M355_EUNSUPPORTED, "%s: odd spatial size (%d,%d,%d)", who, D, H, W);
-  M355_REQUIRE(compute < 0 || compute == M355_COMPUTE_BF16 || compute == M355_COMPUTE_F16, M355_EINVALID_ARG,
-               "%s: compute must be M355_COMPUTE_BF16 or M355_COMPUTE_F16", who);
-  return M355_OK;
-}
-
 }  // namespace m355
 
 using namespace m355;
 
 extern "C" int m355_maxpool3d_2x_fwd(const float* x, float* y, uint8_t* idx, int32_t N, int32_t C, int32_t D, int32_t H,
                                      int32_t W, int64_t x_batch_stride, int64_t y_batch_stride, void* stream) {
-  if (int rc = mp_check("maxpool3d_2x_fwd", x && y, N, C, D, H, W)) return rc;
-  const int64_t OS = (int64_t)(D / 2) * (H / 2) * (W / 2);
-  const int64_t xbs = dense_or(x_batch_stride, (int64_t)C * D * H * W);
-  const int64_t ybs = dense_or(y_batch_stride, (int64_t)C * OS);
-  // W % 4 == 0 makes every row offset a multiple of 4 elements and OS even; the rest is the caller's pointers
-  const bool vec = (W % 4 == 0) && (xbs % 4 == 0) && (ybs % 2 == 0) && ((uintptr_t)x & 15) == 0 &&
-                   ((uintptr_t)y & 7) == 0 && ((uintptr_t)idx & 1) == 0;
-  const int64_t total = (int64_t)N * C * (D / 2) * (H / 2) * (vec ? W / 4 : W / 2);
-  if (vec)
-    hipLaunchKernelGGL(maxpool2_fwd_kernel<true>, dim3(mp_grid(total, 8192)), dim3(256), 0, (hipStream_t)stream, x, y,
-                       idx, N, C, D, H, W, xbs, ybs);
-  else
-    hipLaunchKernelGGL(maxpool2_fwd_kernel<false>, dim3(mp_grid(total, 8192)), dim3(256), 0, (hipStream_t)stream, x, y,
-                       idx, N, C, D, H, W, xbs, ybs);
+  const ResampleArgs a = {N, C, D, H, W, 0, {x_batch_stride, y_batch_stride, 0}, {(uintptr_t)x, (uintptr_t)y, 0, (uintptr_t)idx}};
+  if (int rc = validate_resample(RS_MAX_FWD, a)) return rc;
+  const ResamplePlan p = plan_resample(RS_MAX_FWD, a);
+  with_bool(p.variant == RS_VECTOR, [&](auto V) {
+    hipLaunchKernelGGL(maxpool2_fwd_kernel<decltype(V)::value>, p.grid, dim3(256), 0, (hipStream_t)stream, x, y, idx, N, C, D,
+                       H, W, p.bs[0], p.bs[1]);
+  });
   return check_launch("maxpool3d_2x_fwd");
 }
 
 extern "C" int m355_maxpool3d_2x_bwd(const float* dy, const uint8_t* idx, const float* add, float* dx, int32_t N, int32_t C,
                                      int32_t D, int32_t H, int32_t W, int64_t dy_batch_stride, int64_t add_batch_stride,
                                      int64_t dx_batch_stride, void* stream) {
-  if (int rc = mp_check("maxpool3d_2x_bwd", dy && idx && dx, N, C, D, H, W)) return rc;
-  const int64_t dense = (int64_t)C * D * H * W;
-  const int64_t dxbs = dense_or(dx_batch_stride, dense), abs_ = dense_or(add_batch_stride, dense);
-  const int64_t dybs = dense_or(dy_batch_stride, dense / 8);
-  const bool vec = (W % 4 == 0) && (dxbs % 4 == 0) && (abs_ % 4 == 0) && (dybs % 2 == 0) && ((uintptr_t)dx & 15) == 0 &&
-                   ((uintptr_t)add & 15) == 0 && ((uintptr_t)dy & 7) == 0 && ((uintptr_t)idx & 1) == 0;
-  const int64_t total = (int64_t)N * C * D * H * (vec ? W / 4 : W / 2);
-  if (vec)
-    hipLaunchKernelGGL(maxpool2_bwd_kernel<true>, dim3(mp_grid(total, 8192)), dim3(256), 0, (hipStream_t)stream, dy, idx,
-                       add, dx, N, C, D, H, W, dybs, abs_, dxbs);
-  else
-    hipLaunchKernelGGL(maxpool2_bwd_kernel<false>, dim3(mp_grid(total, 8192)), dim3(256), 0, (hipStream_t)stream, dy, idx,
-                       add, dx, N, C, D, H, W, dybs, abs_, dxbs);
+  const ResampleArgs a = {N, C, D, H, W, 0, {dy_batch_stride, add_batch_stride, dx_batch_stride},
+                          {(uintptr_t)dy, (uintptr_t)add, (uintptr_t)dx, (uintptr_t)idx}};
+  if (int rc = validate_resample(RS_MAX_BWD, a)) return rc;
+  const ResamplePlan p = plan_resample(RS_MAX_BWD, a);
+  with_bool(p.variant == RS_VECTOR, [&](auto V) {
+    hipLaunchKernelGGL(maxpool2_bwd_kernel<decltype(V)::value>, p.grid, dim3(256), 0, (hipStream_t)stream, dy, idx, add, dx, N,
+                       C, D, H, W, p.bs[0], p.bs[1], p.bs[2]);
+  });
   return check_launch("maxpool3d_2x_bwd");
 }
 
 extern "C" int m355_maxpool3d_2x_fwd_h16(const void* x16, void* y16, uint8_t* idx8, int32_t N, int32_t C, int32_t D,
                                          int32_t H, int32_t W, int64_t x16_batch_stride, int64_t y16_batch_stride,
                                          int32_t compute, void* stream) {
-  if (int rc = mp_check("maxpool3d_2x_fwd_h16", x16 && y16, N, C, D, H, W, compute)) return rc;
-  const int CB = (int)c8_blocks(C);
-  const int64_t S = (int64_t)D * H * W;
-  const int64_t xbs = dense_or(x16_batch_stride, CB * S * 8), ybs = dense_or(y16_batch_stride, CB * (S / 8) * 8);
-  M355_REQUIRE((((uintptr_t)x16 | (uintptr_t)y16) & 15) == 0 && xbs % 8 == 0 && ybs % 8 == 0 && ((uintptr_t)idx8 & 7) == 0,
-               M355_EINVALID_ARG, "maxpool3d_2x_fwd_h16: c8 tensor not 16B aligned (route items: 8B)");
-  const int64_t total = (int64_t)N * CB * (S / 8);
-  const unsigned grid = mp_grid(total, 8192);
-  if (compute == M355_COMPUTE_BF16)
-    hipLaunchKernelGGL(maxpool2_c8_kernel<__bf16>, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const __bf16*)x16,
-                       (__bf16*)y16, idx8, C, CB, D, H, W, xbs, ybs, N);
-  else
-    hipLaunchKernelGGL(maxpool2_c8_kernel<_Float16>, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const _Float16*)x16,
-                       (_Float16*)y16, idx8, C, CB, D, H, W, xbs, ybs, N);
+  const ResampleArgs a = {N, C, D, H, W, compute, {x16_batch_stride, y16_batch_stride, 0},
+                          {(uintptr_t)x16, (uintptr_t)y16, 0, (uintptr_t)idx8}};
+  if (int rc = validate_resample(RS_MAX_FWD_H16, a)) return rc;
+  const ResamplePlan p = plan_resample(RS_MAX_FWD_H16, a);
+  with_h16(compute, [&](auto T) {
+    typedef typename decltype(T)::type HT;
+    hipLaunchKernelGGL(maxpool2_c8_kernel<HT>, p.grid, dim3(256), 0, (hipStream_t)stream, (const HT*)x16, (HT*)y16, idx8, C,
+                       (int)c8_blocks(C), D, H, W, p.bs[0], p.bs[1], N);
+  });
   return check_launch("maxpool3d_2x_fwd_h16");
 }
 
@@ -307,22 +274,15 @@ extern "C" int m355_maxpool3d_2x_bwd_h16(const void* dpool16, const uint8_t* idx
                                          int32_t C, int32_t D, int32_t H, int32_t W, int64_t dpool16_batch_stride,
                                          int64_t dskip16_batch_stride, int64_t dx16_batch_stride, int32_t compute,
                                          void* stream) {
-  if (int rc = mp_check("maxpool3d_2x_bwd_h16", dpool16 && idx8 && dx16, N, C, D, H, W, compute)) return rc;
-  const int CB = (int)c8_blocks(C);
-  const int64_t S = (int64_t)D * H * W;
-  const int64_t pbs = dense_or(dpool16_batch_stride, CB * (S / 8) * 8), sbs = dense_or(dskip16_batch_stride, CB * S * 8);
-  const int64_t xbs = dense_or(dx16_batch_stride, CB * S * 8);
-  M355_REQUIRE((((uintptr_t)dpool16 | (uintptr_t)dskip16 | (uintptr_t)dx16) & 15) == 0 && pbs % 8 == 0 && sbs % 8 == 0 &&
-                   xbs % 8 == 0 && ((uintptr_t)idx8 & 7) == 0,
-               M355_EINVALID_ARG, "maxpool3d_2x_bwd_h16: c8 tensor not 16B aligned (route items: 8B)");
-  const int64_t total = (int64_t)N * CB * S;
-  const unsigned grid = mp_grid(total, 16384);
-  if (compute == M355_COMPUTE_BF16)
-    hipLaunchKernelGGL(maxpool2_bwd_c8_kernel<__bf16>, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const __bf16*)dpool16,
-                       idx8, (const __bf16*)dskip16, (__bf16*)dx16, C, CB, D, H, W, pbs, sbs, xbs, N, overflow_flag());
-  else
-    hipLaunchKernelGGL(maxpool2_bwd_c8_kernel<_Float16>, dim3(grid), dim3(256), 0, (hipStream_t)stream,
-                       (const _Float16*)dpool16, idx8, (const _Float16*)dskip16, (_Float16*)dx16, C, CB, D, H, W, pbs, sbs,
-                       xbs, N, overflow_flag());
+  const ResampleArgs a = {N, C, D, H, W, compute, {dpool16_batch_stride, dskip16_batch_stride, dx16_batch_stride},
+                          {(uintptr_t)dpool16, (uintptr_t)dskip16, (uintptr_t)dx16, (uintptr_t)idx8}};
+  if (int rc = validate_resample(RS_MAX_BWD_H16, a)) return rc;
+  const ResamplePlan p = plan_resample(RS_MAX_BWD_H16, a);
+  with_h16(compute, [&](auto T) {
+    typedef typename decltype(T)::type HT;
+    hipLaunchKernelGGL(maxpool2_bwd_c8_kernel<HT>, p.grid, dim3(256), 0, (hipStream_t)stream, (const HT*)dpool16, idx8,
+                       (const HT*)dskip16, (HT*)dx16, C, (int)c8_blocks(C), D, H, W, p.bs[0], p.bs[1], p.bs[2], N,
+                       overflow_flag());
+  });
   return check_launch("maxpool3d_2x_bwd_h16");
 }

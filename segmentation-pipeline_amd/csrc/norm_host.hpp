@@ -3,8 +3,6 @@
 // and norm_pass() turns (plan, pass, pointers) into the vector-path verdict and the grid of that pass.  The workspace
 // query, the workspace check, m355_norm_plan and every launcher read these numbers and no others.
 #pragma once
-#include <type_traits>
-
 #include "h16.hpp"
 
 namespace m355 {
@@ -153,19 +151,6 @@ static inline NormLaunch norm_pass(const m355_norm_desc* d, const NormPlan& p, N
     default: break;
   }
   return L;
-}
-
-// A kernel's template arguments chosen at run time, so that each launch is written once:
-//   with_bool(v, [&](auto V) { launch kernel<decltype(V)::value> });   with_h16(compute, [&](auto T) { ...<typename decltype(T)::type> });
-template <typename T>
-struct TypeTag { typedef T type; };
-template <typename F>
-static inline void with_bool(bool vec, F&& f) {
-  if (vec) f(std::true_type()); else f(std::false_type());
-}
-template <typename F>
-static inline void with_h16(int compute, F&& f) {
-  if (compute == M355_COMPUTE_BF16) f(TypeTag<__bf16>()); else f(TypeTag<_Float16>());
 }
 
 // launchers that cross the three files.  Second backward pass with dx as fp32 and c8 (act16.hip):

@@ -20,6 +20,7 @@
 // (models/components.py:52-55,62-73) and of nn.AvgPool3d (models/modular_unet.py:64,92) under
 // `torch.cuda.amp.autocast` (segmentation_trainer.py:203-227).
 #include "norm_host.hpp"
+#include "resample_host.hpp"
 
 namespace m355 {
 
@@ -490,24 +491,14 @@ extern "C" int m355_norm_act_bwd_c8_apply(const m355_norm_desc* d, const void* x
 extern "C" int m355_avgpool3d_2x_bwd_h16(const void* dpool16, const void* dskip16, void* dx16, int32_t N, int32_t C, int32_t D,
                                          int32_t H, int32_t W, int64_t dpool16_batch_stride, int64_t dskip16_batch_stride,
                                          int64_t dx16_batch_stride, int32_t compute, void* stream) {
-  if (int rc = check_h16("avgpool3d_2x_bwd_h16", compute)) return rc;
-  M355_REQUIRE(dpool16 && dx16, M355_EINVALID_ARG, "avgpool3d_2x_bwd_h16: null pointer");
-  M355_REQUIRE(N > 0 && C > 0 && D > 0 && H > 0 && W > 0, M355_EINVALID_ARG, "avgpool3d_2x_bwd_h16: bad shape");
-  M355_REQUIRE(D % 2 == 0 && H % 2 == 0 && W % 2 == 0, M355_EUNSUPPORTED, "avgpool3d_2x_bwd_h16: odd spatial size (%d,%d,%d)", D, H, W);
-  const int CB = (int)c8_blocks(C);
-  const int64_t S = (int64_t)D * H * W;
-  const int64_t pbs = dense_or(dpool16_batch_stride, CB * (S / 8) * 8), sbs = dense_or(dskip16_batch_stride, CB * S * 8);
-  const int64_t xbs = dense_or(dx16_batch_stride, CB * S * 8);
-  M355_REQUIRE((((uintptr_t)dpool16 | (uintptr_t)dskip16 | (uintptr_t)dx16) & 15) == 0 && pbs % 8 == 0 && sbs % 8 == 0 && xbs % 8 == 0,
-               M355_EINVALID_ARG, "avgpool3d_2x_bwd_h16: c8 tensor not 16B aligned");
-  const int64_t total = (int64_t)N * CB * S;
-  const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(ceil_div(total, 256), 16384));
-  if (compute == M355_COMPUTE_BF16)
-    hipLaunchKernelGGL(avgpool2_bwd_c8_kernel<__bf16>, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const __bf16*)dpool16,
-                       (const __bf16*)dskip16, (__bf16*)dx16, CB, D, H, W, pbs, sbs, xbs, N, overflow_flag());
-  else
-    hipLaunchKernelGGL(avgpool2_bwd_c8_kernel<_Float16>, dim3(grid), dim3(256), 0, (hipStream_t)stream,
-                       (const _Float16*)dpool16, (const _Float16*)dskip16, (_Float16*)dx16, CB, D, H, W, pbs, sbs, xbs, N,
-                       overflow_flag());
+  const ResampleArgs a = {N, C, D, H, W, compute, {dpool16_batch_stride, dskip16_batch_stride, dx16_batch_stride},
+                          {(uintptr_t)dpool16, (uintptr_t)dskip16, (uintptr_t)dx16, 0}};
+  if (int rc = validate_resample(RS_AVG_BWD_H16, a)) return rc;
+  const ResamplePlan p = plan_resample(RS_AVG_BWD_H16, a);
+  with_h16(compute, [&](auto T) {
+    typedef typename decltype(T)::type HT;
+    hipLaunchKernelGGL(avgpool2_bwd_c8_kernel<HT>, p.grid, dim3(256), 0, (hipStream_t)stream, (const HT*)dpool16,
+                       (const HT*)dskip16, (HT*)dx16, (int)c8_blocks(C), D, H, W, p.bs[0], p.bs[1], p.bs[2], N, overflow_flag());
+  });
   return check_launch("avgpool3d_2x_bwd_h16");
 }

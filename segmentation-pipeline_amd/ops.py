@@ -285,6 +285,10 @@ class Act16:
     def batch_stride(self):
         return self.data.shape[1] * self.S * 8
 
+    def with_t(self, t):
+        """this activation with `t` as its autograd handle"""
+        return Act16(self.data, self.C, self.spatial, self.compute, self.cb0, t)
+
     def slot(self, c0, c1):
         if c0 % 8:
             raise _lib.M355Error(f"a c8 slot must start at a multiple of 8 channels (got {c0})")
@@ -298,6 +302,23 @@ class Act16:
         check(_lib.lib().m355_act16_unpack(self.ptr(), _p(x), N, self.C, self.S, self.batch_stride(), 0, self.compute,
                                            _stream()), "act16_unpack")
         return x
+
+
+def _c8_out_slot(x: Act16, out: Optional["OutSlot"], spatial, C: Optional[int] = None) -> Act16:
+    """the c8 output of an op on `x` (C channels, default x.C): its slot of the concat buffer, shape-checked, else a fresh
+    activation"""
+    shape = (x.shape[0], x.C if C is None else C) + tuple(spatial)
+    y16 = out.act16() if out is not None else None
+    if y16 is None:
+        return Act16.empty(shape[0], shape[1], shape[2:], x.compute, x.device)
+    if y16.shape != shape:
+        raise _lib.M355Error(f"c8 slot shape {y16.shape} != op output shape {shape}")
+    return y16
+
+
+def _c8_grad(N, C, S, compute, device) -> torch.Tensor:
+    """a dense c8 gradient tensor [N, ceil(C / 8), S, 8] for a backward kernel to fill"""
+    return torch.empty((N, (C + 7) // 8, S, 8), dtype=_DT16[compute], device=device)
 
 
 def pack_act16(x: torch.Tensor, compute: int, out: Optional[Act16] = None) -> Act16:
@@ -1060,7 +1081,7 @@ class _PoolC8Fn(torch.autograd.Function):
         sbs = 0
         if g_skip is not None:
             g_skip, sbs = _c8t(g_skip)
-        dx16 = torch.empty((N, (Cc + 7) // 8, D * H * W, 8), dtype=_DT16[compute], device=g_pool.device)
+        dx16 = _c8_grad(N, Cc, D * H * W, compute, g_pool.device)
         check(_lib.lib().m355_avgpool3d_2x_bwd_h16(_p(g_pool), _p(g_skip), _p(dx16), N, Cc, D, H, W, pbs, sbs, 0, compute,
                                                    _stream()), "avgpool3d_2x_bwd_h16")
         return dx16, None, None, None
@@ -1793,15 +1814,10 @@ def avgpool3d_2x_with_skip(x, out: Optional[OutSlot] = None):
     """-> (x as it continues into the skip connection, AvgPool3d(2, 2)(x)); see _PoolSkipFn.  `out` (c8 flow): the pooled
     tensor is written into this concat slot."""
     if isinstance(x, Act16):
-        N, Cc, D, H, W = x.shape
-        y16 = out.act16() if out is not None else None
-        if y16 is None:
-            y16 = Act16.empty(N, Cc, (D // 2, H // 2, W // 2), x.compute, x.device)
-        elif y16.shape != (N, Cc, D // 2, H // 2, W // 2):
-            raise _lib.M355Error(f"c8 slot shape {y16.shape} != op output shape {(N, Cc, D // 2, H // 2, W // 2)}")
+        D, H, W = x.spatial
+        y16 = _c8_out_slot(x, out, (D // 2, H // 2, W // 2))
         skip_t, pooled_t = _PoolC8Fn.apply(x.t, x, y16, True)
-        return (Act16(x.data, x.C, x.spatial, x.compute, x.cb0, skip_t),
-                Act16(y16.data, y16.C, y16.spatial, y16.compute, y16.cb0, pooled_t))
+        return x.with_t(skip_t), y16.with_t(pooled_t)
     return _PoolSkipFn.apply(x)
 
 
@@ -1813,7 +1829,7 @@ def avgpool3d_2x(x, out: Optional[OutSlot] = None):
         if y16 is None:
             y16 = Act16.empty(N, Cc, (D // 2, H // 2, W // 2), x.compute, x.device)
         if _act16_tracks(x):
-            return Act16(y16.data, y16.C, y16.spatial, y16.compute, y16.cb0, _PoolC8Fn.apply(x.t, x, y16, False))
+            return y16.with_t(_PoolC8Fn.apply(x.t, x, y16, False))
         check(_lib.lib().m355_avgpool3d_2x_fwd_h16(x.ptr(), y16.ptr(), N, Cc, D, H, W, x.batch_stride(),
                                                    y16.batch_stride(), x.compute, _stream()), "avgpool3d_2x_fwd_h16")
         return y16
@@ -1914,20 +1930,10 @@ class _MaxPoolC8Fn(torch.autograd.Function):
         sbs = 0
         if g_skip is not None:
             g_skip, sbs = _c8t(g_skip)
-        dx16 = torch.empty((N, (Cc + 7) // 8, D * H * W, 8), dtype=_DT16[compute], device=g_pool.device)
+        dx16 = _c8_grad(N, Cc, D * H * W, compute, g_pool.device)
         check(_lib.lib().m355_maxpool3d_2x_bwd_h16(_p(g_pool), _p(ctx.idx8), _p(g_skip), _p(dx16), N, Cc, D, H, W, pbs, sbs, 0,
                                                    compute, _stream()), "maxpool3d_2x_bwd_h16")
         return dx16, None, None, None
-
-
-def _maxpool_c8_slot(x: Act16, out: Optional[OutSlot]) -> Act16:
-    N, Cc, D, H, W = x.shape
-    y16 = out.act16() if out is not None else None
-    if y16 is None:
-        return Act16.empty(N, Cc, (D // 2, H // 2, W // 2), x.compute, x.device)
-    if y16.shape != (N, Cc, D // 2, H // 2, W // 2):
-        raise _lib.M355Error(f"c8 slot shape {y16.shape} != op output shape {(N, Cc, D // 2, H // 2, W // 2)}")
-    return y16
 
 
 def maxpool3d_2x_with_skip(x, out: Optional[OutSlot] = None):
@@ -1936,10 +1942,10 @@ def maxpool3d_2x_with_skip(x, out: Optional[OutSlot] = None):
     if isinstance(x, Act16):
         if not _act16_tracks(x):
             return x, maxpool3d_2x(x, out)
-        y16 = _maxpool_c8_slot(x, out)
+        D, H, W = x.spatial
+        y16 = _c8_out_slot(x, out, (D // 2, H // 2, W // 2))
         skip_t, pooled_t = _MaxPoolC8Fn.apply(x.t, x, y16, True)
-        return (Act16(x.data, x.C, x.spatial, x.compute, x.cb0, skip_t),
-                Act16(y16.data, y16.C, y16.spatial, y16.compute, y16.cb0, pooled_t))
+        return x.with_t(skip_t), y16.with_t(pooled_t)
     return _MaxPoolSkipFn.apply(x, _tracks(x))
 
 
@@ -1947,9 +1953,9 @@ def maxpool3d_2x(x, out: Optional[OutSlot] = None):
     """nn.MaxPool3d(kernel_size=2, stride=2), torch's tie / NaN routing; c8 -> c8 in the 16-bit flows."""
     if isinstance(x, Act16):
         N, Cc, D, H, W = x.shape
-        y16 = _maxpool_c8_slot(x, out)
+        y16 = _c8_out_slot(x, out, (D // 2, H // 2, W // 2))
         if _act16_tracks(x):
-            return Act16(y16.data, y16.C, y16.spatial, y16.compute, y16.cb0, _MaxPoolC8Fn.apply(x.t, x, y16, False))
+            return y16.with_t(_MaxPoolC8Fn.apply(x.t, x, y16, False))
         check(_lib.lib().m355_maxpool3d_2x_fwd_h16(x.ptr(), y16.ptr(), None, N, Cc, D, H, W, x.batch_stride(),
                                                    y16.batch_stride(), x.compute, _stream()), "maxpool3d_2x_fwd_h16")
         return y16
@@ -2004,7 +2010,7 @@ class _UpsampleC8Fn(torch.autograd.Function):
     def backward(ctx, dy16):
         N, Cc, D, H, W, compute = ctx.info
         dy16, dybs = _c8t(dy16)
-        dx16 = torch.empty((N, (Cc + 7) // 8, D * H * W, 8), dtype=_DT16[compute], device=dy16.device)
+        dx16 = _c8_grad(N, Cc, D * H * W, compute, dy16.device)
         check(_lib.lib().m355_upsample_trilinear2x_bwd_h16(_p(dy16), _p(dx16), N, Cc, D, H, W, dybs, 0, compute, _stream()),
               "upsample_trilinear2x_bwd_h16")
         return dx16, None, None
@@ -2014,13 +2020,9 @@ def upsample_trilinear2x(x, out: Optional[OutSlot] = None):
     """nn.Upsample(scale_factor=2, mode='trilinear', align_corners=True); c8 -> c8 in the 16-bit flows."""
     if isinstance(x, Act16):
         N, Cc, D, H, W = x.shape
-        y16 = out.act16() if out is not None else None
-        if y16 is None:
-            y16 = Act16.empty(N, Cc, (2 * D, 2 * H, 2 * W), x.compute, x.device)
-        elif y16.shape != (N, Cc, 2 * D, 2 * H, 2 * W):
-            raise _lib.M355Error(f"c8 slot shape {y16.shape} != op output shape {(N, Cc, 2 * D, 2 * H, 2 * W)}")
+        y16 = _c8_out_slot(x, out, (2 * D, 2 * H, 2 * W))
         if _act16_tracks(x):
-            return Act16(y16.data, y16.C, y16.spatial, y16.compute, y16.cb0, _UpsampleC8Fn.apply(x.t, x, y16))
+            return y16.with_t(_UpsampleC8Fn.apply(x.t, x, y16))
         check(_lib.lib().m355_upsample_trilinear2x_fwd_h16(x.ptr(), y16.ptr(), N, Cc, D, H, W, x.batch_stride(),
                                                            y16.batch_stride(), x.compute, _stream()),
               "upsample_trilinear2x_fwd_h16")
@@ -2153,7 +2155,7 @@ class _ChannelScaleC8Fn(torch.autograd.Function):
         (scale,) = ctx.saved_tensors
         N, Cc, S, compute = ctx.info
         dy16, dybs = _c8t(dy16)
-        dx16 = torch.empty((N, (Cc + 7) // 8, S, 8), dtype=_DT16[compute], device=dy16.device)
+        dx16 = _c8_grad(N, Cc, S, compute, dy16.device)
         _channel_scale_c8(_p(dy16), dybs, scale, _p(dx16), 0, N, Cc, S, compute)
         return dx16, None, None, None
 
@@ -2164,13 +2166,9 @@ def channel_scale(x, scale, out: Optional[OutSlot] = None):
     scale = scale.contiguous().view(-1)
     if isinstance(x, Act16):
         _require(scale)
-        y16 = out.act16() if out is not None else None
-        if y16 is None:
-            y16 = Act16.empty(x.shape[0], x.C, x.spatial, x.compute, x.device)
-        elif y16.shape != x.shape:
-            raise _lib.M355Error(f"c8 slot shape {y16.shape} != op output shape {x.shape}")
+        y16 = _c8_out_slot(x, out, x.spatial)
         if _act16_tracks(x):
-            return Act16(y16.data, y16.C, y16.spatial, y16.compute, y16.cb0, _ChannelScaleC8Fn.apply(x.t, scale, x, y16))
+            return y16.with_t(_ChannelScaleC8Fn.apply(x.t, scale, x, y16))
         _channel_scale_c8(x.ptr(), x.batch_stride(), scale, y16.ptr(), y16.batch_stride(), x.shape[0], x.C, x.S, x.compute)
         return y16
     y = _ChannelScaleFn.apply(x, scale)
@@ -2292,8 +2290,7 @@ class _S2DC8Fn(torch.autograd.Function):
     def backward(ctx, dy16):
         full, compute, to_depth, xshape = ctx.info
         dy16, dybs = _c8t(dy16)
-        S = xshape[2] * xshape[3] * xshape[4]
-        dx16 = torch.empty((xshape[0], (xshape[1] + 7) // 8, S, 8), dtype=_DT16[compute], device=dy16.device)
+        dx16 = _c8_grad(xshape[0], xshape[1], xshape[2] * xshape[3] * xshape[4], compute, dy16.device)
         _s2d_c8(_p(dy16), dybs, _p(dx16), 0, full, compute, not to_depth)
         return dx16, None, None, None
 
@@ -2306,13 +2303,9 @@ def _s2d_act16(x: Act16, to_depth: bool, out: Optional[OutSlot]):
         if Cc % 8:
             raise _lib.M355Error(f"depth_to_space2: {Cc} channels are not 8 parities per output channel")
         oshape = (N, Cc // 8, 2 * D, 2 * H, 2 * W)
-    y16 = out.act16() if out is not None else None
-    if y16 is None:
-        y16 = Act16.empty(oshape[0], oshape[1], oshape[2:], x.compute, x.device)
-    elif y16.shape != oshape:
-        raise _lib.M355Error(f"c8 slot shape {y16.shape} != op output shape {oshape}")
+    y16 = _c8_out_slot(x, out, oshape[2:], oshape[1])
     if _act16_tracks(x):
-        return Act16(y16.data, y16.C, y16.spatial, y16.compute, y16.cb0, _S2DC8Fn.apply(x.t, x, y16, to_depth))
+        return y16.with_t(_S2DC8Fn.apply(x.t, x, y16, to_depth))
     _s2d_c8(x.ptr(), x.batch_stride(), y16.ptr(), y16.batch_stride(), x.shape if to_depth else oshape, x.compute, to_depth)
     return y16
 

@@ -308,6 +308,19 @@ class RawOps:
         self._chk(self.lib.m355_conv_transpose3d_plan(C.byref(d), which, _p(y_side), out), "conv_transpose3d_plan")
         return tuple(out)
 
+    def resample_plan(self, op, shape, tensors, routes=None, compute=0):
+        """(variant, grid x, y, z, LDS bytes, three resolved batch strides) of a call of the resampling family
+        (m355_resample_plan).  op: index into _lib.RESAMPLE_OPS; shape: (N, C, D, H, W) as that entry point takes them;
+        tensors: its tensors in the order of its batch strides -- Slot, torch tensor (dense) or None; routes: the max-pool
+        route tensor"""
+        addr = lambda t: 0 if t is None else (t.ptr if isinstance(t, Slot) else t.data_ptr())   # noqa: E731
+        tensors = list(tensors) + [None] * (3 - len(tensors))
+        strides = (C.c_int64 * 3)(*[0 if t is None else _bs(t) for t in tensors])
+        pointers = (C.c_uint64 * 4)(*[addr(t) for t in tensors], addr(routes))
+        out = (C.c_int64 * 8)()
+        self._chk(self.lib.m355_resample_plan(op, *shape, strides, pointers, compute, out), "resample_plan")
+        return tuple(out)
+
     def conv3d_fwd_h16(self, x16, Cin, spatial, w, bias=None, add=None, compute=1, groups=None, eps=1e-5, softmax=False,
                        out=None):
         """forward on a c8 input; groups != None also returns the fused statistics (mean, rstd); softmax: the
@@ -821,6 +834,42 @@ class RawOps:
         self._chk(self.fn("avgpool3d_2x_bwd_add")(_p(dy), _p(add), _p(dx), N, Cc, D, H, W, _bs(dy), _bs(add), _bs(dx),
                                                   self._stream()), "avgpool_bwd_add")
         return dx
+
+    def maxpool_fwd(self, x, route=True, out=None):
+        """-> (y, route bytes [N, C, D/2, H/2, W/2] uint8 or None)"""
+        x = self.to(x)
+        N, Cc, D, H, W = x.shape
+        oshape = (N, Cc, D // 2, H // 2, W // 2)
+        y = self._out(out, oshape)
+        idx = torch.full(oshape, 255, dtype=torch.uint8, device=self.device) if route else None
+        self._chk(self.fn("maxpool3d_2x_fwd")(_p(x), _p(y), _p(idx), N, Cc, D, H, W, _bs(x), _bs(y), self._stream()), "maxpool_fwd")
+        return y, idx
+
+    def maxpool_bwd(self, dy, idx, add, x_shape, out=None):
+        dy, add = self.to(dy), self.to(add)
+        N, Cc, D, H, W = x_shape
+        dx = self._out(out, x_shape)
+        self._chk(self.fn("maxpool3d_2x_bwd")(_p(dy), _p(idx), _p(add), _p(dx), N, Cc, D, H, W, _bs(dy), _bs(add), _bs(dx),
+                                              self._stream()), "maxpool_bwd")
+        return dx
+
+    def maxpool_fwd_h16(self, x16, Cc, spatial, compute, route=True, out=None):
+        """-> (y16, route bytes [N, CB, S/8, 8] uint8 or None)"""
+        D, H, W = spatial
+        N, CB = x16.shape[0], (Cc + 7) // 8
+        y16 = self._out(out, (N, CB, D * H * W // 8, 8), x16.dtype, fill=7.0)
+        idx8 = torch.full((N, CB, D * H * W // 8, 8), 255, dtype=torch.uint8, device=self.device) if route else None
+        self._chk(self.fn("maxpool3d_2x_fwd_h16")(_p(x16), _p(y16), _p(idx8), N, Cc, D, H, W, _bs(x16), _bs(y16), compute,
+                                                  self._stream()), "maxpool_fwd_h16")
+        return y16, idx8
+
+    def maxpool_bwd_h16(self, dpool16, idx8, dskip16, Cc, spatial, compute, out=None):
+        D, H, W = spatial
+        N = dpool16.shape[0]
+        dx16 = self._out(out, (N, (Cc + 7) // 8, D * H * W, 8), dpool16.dtype, fill=7.0)
+        self._chk(self.fn("maxpool3d_2x_bwd_h16")(_p(dpool16), _p(idx8), _p(dskip16), _p(dx16), N, Cc, D, H, W, _bs(dpool16),
+                                                  _bs(dskip16), _bs(dx16), compute, self._stream()), "maxpool_bwd_h16")
+        return dx16
 
     def upsample_fwd(self, x, out=None):
         x = self.to(x)

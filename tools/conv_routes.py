@@ -15,7 +15,14 @@ predates the plan query (it then is the only one printed), "routes" covers the w
 --norm: the same for the normalisation plans (csrc/norm_host.hpp): per line m355_norm_num_stats, m355_norm_workspace,
 m355_act16_partials_slots(S) -- the "queries" hash -- and m355_norm_plan for which = 0..9 -- with them the "routes" hash.
 
-usage: python tools/conv_routes.py [--convt | --norm] [--hash-only] [--jobs N] > routes.txt"""
+--resample: the same for the factor-2 resampling family (csrc/resample_host.hpp).  "queries": the return codes of the 17
+entry points over argument tuples that are each REJECTED -- one fault or two out of null pointer, dimension <= 0, odd size,
+bad compute mode, misaligned pointers, misaligned strides; a tuple that its entry point would accept is never built, because
+the call would launch on the dummy pointers -- so this hash too compares with a library from before the plan query.
+"routes": m355_resample_plan for valid shapes, strides and pointer alignments, both sides of every grid cap and of the
+trilinear forward's kernel conditions.
+
+usage: python tools/conv_routes.py [--convt | --norm | --resample] [--hash-only] [--jobs N] > routes.txt"""
 import argparse
 import ctypes as C
 import hashlib
@@ -160,6 +167,81 @@ def norm_main(a):
           + (f" routes sha256 {hashlib.sha256(text.encode()).hexdigest()}" if plan else ""))
 
 
+# ---- --resample ----
+RS_BASE = dict(N=2, C=8, D=4, H=4, W=4, compute=1, bs=(0, 0, 0), ptr=(4096, 8192, 12288, 16384))
+# (name, check it trips, the fields it sets): the alignment faults move EVERY pointer / stride, so that they fault whichever
+# tensor an entry point looks at (the fp32 space / depth pair checks its full-resolution side only)
+RS_FAULTS = [("null0", "n", dict(ptr=(0, 8192, 12288, 16384))), ("null-all", "n", dict(ptr=(0, 0, 0, 0))),
+             *[(f"{k}=0", "d", {k: 0}) for k in "NCDHW"], ("C=-8", "d", dict(C=-8)),
+             *[(f"{k}=5", "o", {k: 5}) for k in "DHW"],
+             *[(f"compute={v}", "c", dict(compute=v)) for v in (0, 3, 7)],
+             ("ptr+4", "a", dict(ptr=(4100, 8196, 12292, 16388))), ("bs=4099", "a", dict(bs=(4099, 4099, 4099)))]
+
+
+def resample_faulty_calls():
+    """(op, label, arguments) of calls that are rejected by construction: at least one fault of a kind the entry point checks"""
+    from segmentation_pipeline_amd import _lib
+    singles = [(f,) for f in RS_FAULTS]
+    pairs = [(f, g) for f, g in itertools.combinations(RS_FAULTS, 2) if not set(f[2]) & set(g[2])]
+    for op, (name, _, _, checks) in enumerate(_lib.RESAMPLE_OPS):
+        for faults in singles + pairs:
+            if not any(kind in checks for _, kind, _ in faults):
+                continue   # e.g. an odd size alone on the trilinear ops: a valid call
+            a = dict(RS_BASE)
+            for _, _, fields in faults:
+                a.update(fields)
+            shape = tuple(a[k] for k in "NCDHW")
+            yield op, "+".join(f[0] for f in faults), _lib.resample_args(op, shape, a["bs"], a["ptr"], a["compute"])
+
+
+RS_VOLUMES = [(2, 2, 2), (2, 2, 6), (2, 4, 4), (4, 6, 8), (6, 2, 10), (8, 8, 8), (10, 36, 12), (16, 16, 18), (32, 32, 32),
+              (36, 10, 130), (64, 64, 64), (128, 128, 128), (132, 132, 132), (2, 130, 132)]
+# the trilinear ops take odd sizes; D = 1 / H = 1: no LDS tiling; W = 306 / 308: each side of the 48 KiB patch; the last
+# four: each side of the quad kernel's 2^31 limit (N = 1, 2) and of the tiled kernel's N * C <= 65535
+RS_TRI_VOLUMES = [(1, 2, 2), (2, 1, 4), (1, 1, 2), (2, 2, 3), (3, 5, 7), (2, 2, 306), (2, 2, 308), (2, 2, 310), (4, 4, 308),
+                  (4095, 2048, 308), (4096, 2048, 308), (4095, 4096, 308), (4096, 4096, 308)]
+RS_CHANNELS = [1, 3, 8, 9, 32]
+RS_PADS = [0, 8, 1, 2]       # batch strides: dense (0), dense + pad * (slot + 1) elements
+RS_OFFSETS = [0, 8, 4]       # bytes the pointers sit behind a 16-byte boundary (slot i: from slot i on, so each one moves alone too)
+
+
+def resample_main(a):
+    from segmentation_pipeline_amd import _lib
+    L = C.CDLL(_lib.LIB_PATH)   # (not _lib.lib(): a parent library has no m355_resample_plan)
+    qlines = []
+    for op, label, args in resample_faulty_calls():
+        fn = getattr(L, "m355_" + _lib.RESAMPLE_OPS[op][0])
+        fn.restype, fn.argtypes = _lib.SIGNATURES["m355_" + _lib.RESAMPLE_OPS[op][0]]
+        rc = fn(*args)
+        assert rc != 0, (op, label)
+        qlines.append(f"{_lib.RESAMPLE_OPS[op][0]} {label} rc={rc}")
+    qtext = "\n".join(qlines) + "\n"
+    plan = getattr(L, "m355_resample_plan", None)
+    lines = []
+    if plan:
+        plan.restype, plan.argtypes = _lib.SIGNATURES["m355_resample_plan"]
+        out = (C.c_int64 * 8)()
+        for op, (name, _, nstrides, checks) in enumerate(_lib.RESAMPLE_OPS):
+            tri = "o" not in checks
+            c8 = "c" in checks
+            for (D, H, W), Cc, N, pad, off in itertools.product(RS_VOLUMES + (RS_TRI_VOLUMES if tri else []), RS_CHANNELS, (1, 2),
+                                                                RS_PADS, RS_OFFSETS):
+                if c8 and (pad % 8 or off):
+                    continue   # rejected: covered by the queries
+                # a padded stride: one the largest tensor of any op fits in (the upsampled one, channels rounded up to 8)
+                big = 64 * (Cc + 7) * D * H * W
+                bs = (C.c_int64 * 3)(*[(big + pad * (i + 1)) if pad and i < nstrides else 0 for i in range(3)])
+                for first in range(3 if off else 1):
+                    ptr = (C.c_uint64 * 4)(*[(1 << 20) * (i + 1) + (off if i >= first else 0) for i in range(4)])
+                    rc = plan(op, N, Cc, D, H, W, bs, ptr, 1, out)
+                    lines.append(f"{name} N{N} C{Cc} {D}x{H}x{W} bs+{pad} ptr+{off}@{first} plan={rc}:" + "/".join(str(v) for v in out))
+    text = qtext + "\n".join(lines) + "\n"
+    if not a.hash_only:
+        sys.stdout.write(text if plan else qtext)
+    print(f"lines {len(qlines)} queries sha256 {hashlib.sha256(qtext.encode()).hexdigest()}"
+          + (f" routes ({len(lines)} more lines) sha256 {hashlib.sha256(text.encode()).hexdigest()}" if plan else ""))
+
+
 def _e(**kw):
     return {k: str(v) for k, v in kw.items()}
 
@@ -236,7 +318,10 @@ def main():
     ap.add_argument("--jobs", type=int, default=min(8, os.cpu_count() or 1))
     ap.add_argument("--convt", action="store_true", help="the conv-transpose routes (two hashes: queries, routes)")
     ap.add_argument("--norm", action="store_true", help="the normalisation plans (two hashes: queries, routes)")
+    ap.add_argument("--resample", action="store_true", help="the factor-2 resampling family (two hashes: queries, routes)")
     a = ap.parse_args()
+    if a.resample:
+        return resample_main(a)
     if a.convt:
         return convt_main(a)
     if a.norm:
