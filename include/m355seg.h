@@ -231,6 +231,32 @@ int m355_conv3d_bwd_weight_h16(const m355_conv3d_desc* d, const void* x16, int64
  * voxel-range splits).  Pure host function. */
 int m355_conv3d_plan(const m355_conv3d_desc* d, int32_t which, int32_t* out4);
 
+/* Introspection, as m355_resample_plan: what ONE call of a launching conv entry point would start.  entry: 0 conv3d_fwd,
+ * 1 _fwd_stats, 2 _bwd_data, 3 _bwd_weight, 4 _fwd_h16, 5 _fwd_h16_c8, 6 _bwd_data_h16, 7 _bwd_data_h16_c8,
+ * 8 _bwd_weight_h16, 9 _bwd_weight_c8.  batch_strides[2]: the entry point's stride ARGUMENTS (c8 entry points: first
+ * operand, then c8 output | dy16; 0 = dense; the fp32 strides are the descriptor's).  pointers[7]: the entry point's
+ * pointers as integers -- compared with zero and masked, never followed: [0] first operand (x | dy | x16 | dy16),
+ * [1] w (weight gradients: the second operand dy | dy16), [2] bias (m355_conv3d_bwd_weight_h16: its fp32 dy), [3] add,
+ * [4] output (y | dx | dw), [5] statistics partials (weight gradients: dbias), [6] workspace.  Runs the entry point's
+ * argument checks in its order and returns its code; on M355_OK out[0..11] =
+ *   [0] kernel variant.  Forward / data gradient: 0 direct, 1 conv3_mfma_fwd_kernel, 2 conv3_mfma_fwd_p_kernel, 3 packed-FMA
+ *       small-Cout (conv3_valu_smallcout_kernel), 4 Toeplitz small-Cout (conv3_mfma_fwd_smallcout_kernel), 5 conv3_f32x3_kernel,
+ *       conv3_h16_kernel 6 queue-driven with 4 waves / 7 with 8 waves / 8 one-shot, 9 conv3_c4_h16_kernel,
+ *       10 conv3_cout4_h16_kernel.  Weight gradient: 0 direct, conv3_mfma_bww_kernel 1 vector / 2 scalar,
+ *       3 conv3_mfma_bww2_kernel, 4 conv3_mfma_bww2c_kernel, 5 conv3_mfma_bww_small_kernel, 6 conv3_bww_x3_kernel,
+ *       7 conv3_bww_x3c_kernel, 8 conv3_bww_c8_kernel, 9 conv3_bww_c8_small_kernel
+ *   [1..3] grid x, y, z of the main launch (x = 0: none, a <= 16 channel output runs on the 16-row tile alone), [4] its block size
+ *   [5], [6] grid x and z of the 16-row tile launch (0: none)
+ *   [7] the auxiliary launches, a bit mask: 1 weight pack, 2 operand pack (fp32 -> c8) of the first operand, 4 of the second,
+ *       8 16-row tile, 16 split-K reduction, 32 ... that emits the statistics, slab reduction 64 transposed / 128 per tap /
+ *       256 plain, bias gradient 512 from the fp32 dy / 1024 from the c8 dy
+ *   [8] the workspace bytes the call was checked against, [9] grid x of the split-K / slab reduction (0: none)
+ *   [10], [11] workspace offsets: forward / data gradient the split-K slabs and the c8 staging copy (packed weights at 0);
+ *       weight gradient the bias gradient's scratch and the first c8 operand copy (slabs at 0).
+ * Pure host function. */
+int m355_conv3d_launch_plan(int32_t entry, const m355_conv3d_desc* d, const int64_t* batch_strides, const uint64_t* pointers,
+                            size_t workspace_bytes, int64_t* out12);
+
 /* dx = conv-transpose of dy with w (autograd of the op above w.r.t. x).
  * desc describes the FORWARD op; dx has x's shape and x_batch_stride,
  * dy has y's shape and y_batch_stride. */

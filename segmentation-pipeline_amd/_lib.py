@@ -182,6 +182,7 @@ SIGNATURES = {
     "m355_conv_transpose3d_bwd_data_h16": (C.c_int, [_CD, _P, _i64, _P, _P, _i64, _i32, _P]),
     "m355_conv_transpose3d_bwd_weight_h16": (C.c_int, [_CD, _P, _i64, _P, _i64, _P, _P, _f32, _i32, _P, _sz, _P]),
     "m355_conv3d_plan": (C.c_int, [_CD, _i32, C.POINTER(C.c_int32)]),
+    "m355_conv3d_launch_plan": (C.c_int, [_i32, _CD, C.POINTER(_i64), C.POINTER(C.c_uint64), _sz, C.POINTER(_i64)]),
     "m355_conv3d_bwd_data_workspace": (_sz, [_CD]),
     "m355_conv3d_bwd_data": (C.c_int, [_CD, _P, _P, _P, _P, _sz, _P]),
     "m355_conv3d_bwd_weight_workspace": (_sz, [_CD]),
@@ -296,6 +297,25 @@ def resample_args(op, shape, strides, pointers, compute):
     _, order, nstrides, checks = RESAMPLE_OPS[op]
     return (tuple(C.c_void_p(pointers[i]) for i in order) + tuple(shape) + tuple(strides[:nstrides])
             + ((compute,) if "c" in checks else ()) + (None,))
+
+
+# The launching conv entry points in the numbering of m355_conv3d_launch_plan's `entry`: (entry point, its arguments after the
+# descriptor: 0..6 = that slot of the query's `pointers`, "s0" / "s1" = that one of its `batch_strides`, "b" = workspace_bytes,
+# "u" = grad_unscale).
+CONV_ENTRIES = [
+    ("conv3d_fwd", (0, 1, 2, 3, 4, 6, "b")), ("conv3d_fwd_stats", (0, 1, 2, 3, 4, 5, 6, "b")),
+    ("conv3d_bwd_data", (0, 1, 4, 6, "b")), ("conv3d_bwd_weight", (0, 1, 4, 5, 6, "b")),
+    ("conv3d_fwd_h16", (0, "s0", 1, 2, 3, 4, 5, 6, "b")), ("conv3d_fwd_h16_c8", (0, "s0", 1, 2, 4, "s1", 5, 6, "b")),
+    ("conv3d_bwd_data_h16", (0, "s0", 1, 4, 6, "b")), ("conv3d_bwd_data_h16_c8", (0, "s0", 1, 4, "s1", 6, "b")),
+    ("conv3d_bwd_weight_h16", (0, "s0", 1, "s1", 2, 4, 5, 6, "b")), ("conv3d_bwd_weight_c8", (0, "s0", 1, "s1", 4, 5, "u", 6, "b")),
+]
+
+
+def conv_entry_args(entry, desc, strides, pointers, workspace_bytes):
+    """the argument tuple of entry point CONV_ENTRIES[entry] for what m355_conv3d_launch_plan takes (stream: the default one)"""
+    other = {"s0": strides[0], "s1": strides[1], "b": workspace_bytes, "u": 1.0}
+    return (C.byref(desc),) + tuple(C.c_void_p(pointers[k]) if isinstance(k, int) else other[k] for k in CONV_ENTRIES[entry][1]) \
+        + (None,)
 
 
 class M355Error(RuntimeError):

@@ -1523,17 +1523,15 @@ __global__ __launch_bounds__(256) void slab_reduce_tap_kernel(const float* __res
   }
 }
 
-// picks the reduction by shape: per-tap blocks where the (o, c-tile) grid alone cannot fill the chip
-void launch_slab_reduce_t(const float* slab, float* dw, int Cin, int Cout, int ctiles, const BwwClasses& k,
-                                 float scale, hipStream_t st) {
-  int max_ns = 1;
-  for (int c = 0; c < 4; ++c) max_ns = std::max(max_ns, k.ns[c]);
-  if ((int64_t)Cout * ctiles < 2 * (int64_t)num_cus() && max_ns >= 16)
-    hipLaunchKernelGGL(slab_reduce_tap_kernel, dim3((unsigned)Cout, (unsigned)ctiles, 27u), dim3(256), 0, st, slab, dw, Cin,
-                       Cout, k, scale, overflow_flag());
+// the transposed reduction the route chose: per-tap blocks where the (o, c-tile) grid alone cannot fill the chip
+static void launch_slab_reduce_t(const BwwRoute& r, const float* slab, float* dw, int Cin, int Cout, float scale,
+                                 hipStream_t st) {
+  if (r.aux & AUX_SLAB_TAP)
+    hipLaunchKernelGGL(slab_reduce_tap_kernel, r.reduce_grid, dim3(256), 0, st, slab, dw, Cin, Cout, r.kred, scale,
+                       overflow_flag());
   else
-    hipLaunchKernelGGL(slab_reduce_t_kernel, dim3((unsigned)Cout, (unsigned)ctiles), dim3(256), 0, st, slab, dw, Cin, Cout,
-                       k, scale, overflow_flag());
+    hipLaunchKernelGGL(slab_reduce_t_kernel, r.reduce_grid, dim3(256), 0, st, slab, dw, Cin, Cout, r.kred, scale,
+                       overflow_flag());
 }
 
 // ------------------------------------------- bwd-weight, tiny channel count on one side
@@ -1863,40 +1861,35 @@ __global__ __launch_bounds__(256) void conv3d_direct_bwd_weight_kernel(
   if (threadIdx.x == 0) dw[((int64_t)o * Cin + c) * k3 + tap] = (float)tot;
 }
 
-// ------------------------------------------------------------------ launcher
-// Everything the host layer (conv3d_host.hip) starts from this file's kernels: it hands over a resolved route, nothing
-// here decides which kernel family runs.
-size_t smallcout_packed_bytes(int Cin) { return (size_t)round_up((int64_t)round_up(Cin, 2) * TZ_K * 32 * 4, 256); }
+// ------------------------------------------------------------------ launchers
+// Everything the host layer (conv3d_host.hip) starts from this file's kernels: it hands over a resolved route
+// (conv3d_route.hpp) and the call's pointers; nothing here decides a kernel, a grid or an offset.
+static_assert(TZ_K == SMALLCOUT_TZ_K && VS_TZ == SMALLCOUT_VS_TZ && VS_TY == SMALLCOUT_VS_TY && VS_TX == SMALLCOUT_VS_TX,
+              "conv3d_route.hpp sizes the Cout <= 4 forward kernels' buffer and grids");
 
 template <int NTW, int GX>
-static void launch_fwd(const FwdPlan& p, const float* x, const float* wp, const float* bias,
-                       const float* add, float* y, float* slab, int N, int kin, int mout, int D,
-                       int H, int W, int64_t xbs, int64_t ybs, hipStream_t st, float* stat = nullptr,
-                       int* work_counter = nullptr) {
-  dim3 grid((unsigned)(p.tz_tiles * p.ty_tiles * p.tx_tiles * std::max(1, p.otiles)), 1u, (unsigned)(N * p.ksplit));
-  const int64_t slab_stride = (int64_t)N * mout * D * H * W;
-  const int64_t slots = (tuning().conv_slots ? tuning().conv_slots : (NTW <= 4 ? 2 : 1) * num_cus());
-  if (p.otiles > 0) {
-    if (p.persistent) {
-      hipLaunchKernelGGL((conv3_mfma_fwd_p_kernel<NTW, GX, false>), dim3((unsigned)slots), dim3(256), 0, st, x, wp, bias,
-                         add, y, slab, kin, mout, D, H, W, p.mout_pad, p.tz_tiles, p.ty_tiles, p.tx_tiles, p.otiles,
-                         p.nchunks, p.ksplit, N, xbs, ybs, slab_stride, stat, work_counter, 0, tuning().conv_cube);
+static void launch_fwd(const ConvRoute& r, const ConvCall& c, const float* wp, const float* bias, const float* add, float* slab,
+                       float* stat, int* work_counter) {
+  const FwdPlan& p = r.plan;
+  const m355_conv3d_desc* d = c.d;
+  const int N = d->N, D = d->D, H = d->H, W = d->W;
+  const int64_t slab_stride = (int64_t)N * r.mout * D * H * W;
+  if (r.grid.x) {
+    if (r.kind == ConvKind::MfmaF32Queue) {
+      hipLaunchKernelGGL((conv3_mfma_fwd_p_kernel<NTW, GX, false>), r.grid, dim3(256), 0, c.st, c.in, wp, bias, add, c.out,
+                         slab, r.kin, r.mout, D, H, W, p.mout_pad, p.tz_tiles, p.ty_tiles, p.tx_tiles, p.otiles, p.nchunks,
+                         p.ksplit, N, r.in_bs, r.out_bs, slab_stride, stat, work_counter, 0, r.sched);
     } else {
-      hipLaunchKernelGGL((conv3_mfma_fwd_kernel<NTW, GX>), grid, dim3(256), 0, st, x, wp, bias, add,
-                         y, slab, kin, mout, D, H, W, p.mout_pad, p.ty_tiles, p.tx_tiles, p.nchunks,
-                         p.ksplit, xbs, ybs, slab_stride, stat, p.otiles, tuning().conv_cube);
+      hipLaunchKernelGGL((conv3_mfma_fwd_kernel<NTW, GX>), r.grid, dim3(256), 0, c.st, c.in, wp, bias, add, c.out, slab,
+                         r.kin, r.mout, D, H, W, p.mout_pad, p.ty_tiles, p.tx_tiles, p.nchunks, p.ksplit, r.in_bs, r.out_bs,
+                         slab_stride, stat, p.otiles, r.sched);
     }
   }
   if constexpr (NTW <= 4) {
-    if (p.tile16) {  // the 16-row remainder tile: queue-driven kernel over (spatial tile x sample x split) items
-      const int64_t items = (int64_t)p.tz_tiles * p.ty_tiles * p.tx_tiles * N * p.ksplit;
-      // (up to two residencies one workgroup per item: see plan_mfma)
-      const int64_t g16 = (items <= 2 * slots && tuning().conv_persistent < 2) ? items : std::min<int64_t>(items, slots);
-      hipLaunchKernelGGL((conv3_mfma_fwd_p_kernel<NTW, GX, true>), dim3((unsigned)g16),
-                         dim3(256), 0, st, x, wp, bias, add, y, slab, kin, mout, D, H, W, p.mout_pad, p.tz_tiles,
-                         p.ty_tiles, p.tx_tiles, 1, p.nchunks, p.ksplit, N, xbs, ybs, slab_stride, stat, work_counter,
-                         32 * p.otiles, tuning().conv_cube);
-    }
+    if (r.aux & AUX_TILE16)   // the 16-row remainder tile: queue-driven kernel over (spatial tile x sample x split) items
+      hipLaunchKernelGGL((conv3_mfma_fwd_p_kernel<NTW, GX, true>), r.grid16, dim3(256), 0, c.st, c.in, wp, bias, add, c.out,
+                         slab, r.kin, r.mout, D, H, W, p.mout_pad, p.tz_tiles, p.ty_tiles, p.tx_tiles, 1, p.nchunks, p.ksplit,
+                         N, r.in_bs, r.out_bs, slab_stride, stat, work_counter, 32 * p.otiles, r.sched);
   }
 }
 
@@ -1936,50 +1929,43 @@ int launch_f32_conv(const ConvRoute& r, const ConvCall& c) {
   if (r.kind == ConvKind::Direct) {
     const int OD = out_dim(D, d->k, d->stride, d->pad), OH = out_dim(H, d->k, d->stride, d->pad),
               OW = out_dim(W, d->k, d->stride, d->pad);
-    const int64_t total = (int64_t)N * (c.transpose ? (int64_t)d->Cin * D * H * W : (int64_t)d->Cout * OD * OH * OW);
-    const int blocks = (int)std::min<int64_t>(ceil_div(total, 256), 65535);
-    if (c.transpose)   // in = dy, out = dx
-      hipLaunchKernelGGL(conv3d_direct_bwd_data_kernel, dim3(blocks), dim3(256), 0, st, c.in, c.w, c.out, N, d->Cin, d->Cout,
-                         D, H, W, OD, OH, OW, d->k, d->stride, d->pad, c.out_bs, c.in_bs);
+    if (r.transpose)   // in = dy, out = dx
+      hipLaunchKernelGGL(conv3d_direct_bwd_data_kernel, r.grid, dim3(256), 0, st, c.in, c.w, c.out, N, d->Cin, d->Cout,
+                         D, H, W, OD, OH, OW, d->k, d->stride, d->pad, r.out_bs, r.in_bs);
     else
-      hipLaunchKernelGGL(conv3d_direct_fwd_kernel, dim3(blocks), dim3(256), 0, st, c.in, c.w, c.bias, c.add, c.out, N,
-                         d->Cin, d->Cout, D, H, W, OD, OH, OW, d->k, d->stride, d->pad, c.in_bs, c.out_bs);
-    return check_launch(c.transpose ? "conv3d_direct_bwd_data" : "conv3d_direct_fwd");
+      hipLaunchKernelGGL(conv3d_direct_fwd_kernel, r.grid, dim3(256), 0, st, c.in, c.w, c.bias, c.add, c.out, N,
+                         d->Cin, d->Cout, D, H, W, OD, OH, OW, d->k, d->stride, d->pad, r.in_bs, r.out_bs);
+    return check_launch(r.transpose ? "conv3d_direct_bwd_data" : "conv3d_direct_fwd");
   }
-  float* wp = c.prepacked ? (float*)c.w : (float*)c.ws;
-  if (!c.prepacked) launch_pack_weights(r, d, c.transpose, c.w, wp, st);
+  int* work_counter = nullptr;
+  if (!is_smallcout(r.kind)) {
+    work_counter = queue_state(st);   // per (device, stream): concurrent launches over one model never share it
+    M355_REQUIRE(work_counter, M355_ELAUNCH, "conv3d: could not allocate the work-queue state");
+  }
+  float* wp = r.prepacked ? (float*)c.w : (float*)c.ws;
+  if (r.aux & AUX_PACK_W) launch_pack_weights(r, d, r.transpose, c.w, wp, st);
   if (r.kind == ConvKind::SmallCoutValu) {   // packed-FMA kernel (see conv3_valu_smallcout_kernel)
-    const int tyv = (int)ceil_div(H, VS_TY), txv = (int)ceil_div(W, VS_TX);
-    dim3 gv((unsigned)(ceil_div(D, VS_TZ) * tyv * txv), (unsigned)N);
-    hipLaunchKernelGGL(conv3_valu_smallcout_kernel, gv, dim3(256), 0, st, c.in, wp, c.bias, c.add, c.out, d->Cin, d->Cout,
-                       D, H, W, tyv, txv, c.in_bs, c.out_bs, c.softmax ? 1 : 0);
+    hipLaunchKernelGGL(conv3_valu_smallcout_kernel, r.grid, dim3(256), 0, st, c.in, wp, c.bias, c.add, c.out, d->Cin, d->Cout,
+                       D, H, W, (int)ceil_div(H, VS_TY), (int)ceil_div(W, VS_TX), r.in_bs, r.out_bs, r.softmax ? 1 : 0);
     return check_launch("conv3_valu_smallcout");
   }
   if (r.kind == ConvKind::SmallCoutToeplitz) {
-    const int tyt = (int)ceil_div(H, 8), txt = (int)ceil_div(W, 32);
-    dim3 grid((unsigned)(ceil_div(D, 8) * tyt * txt), (unsigned)N);
-    hipLaunchKernelGGL(conv3_mfma_fwd_smallcout_kernel, grid, dim3(256), 0, st, c.in, wp, c.bias, c.add, c.out, d->Cin,
-                       d->Cout, D, H, W, tyt, txt, (int)round_up(d->Cin, 2) / 2, c.in_bs, c.out_bs);
+    hipLaunchKernelGGL(conv3_mfma_fwd_smallcout_kernel, r.grid, dim3(256), 0, st, c.in, wp, c.bias, c.add, c.out, d->Cin,
+                       d->Cout, D, H, W, (int)ceil_div(H, 8), (int)ceil_div(W, 32), (int)round_up(d->Cin, 2) / 2, r.in_bs,
+                       r.out_bs);
     return check_launch("conv3_mfma_fwd_smallcout");
   }
-  const int kin = c.transpose ? d->Cout : d->Cin, mout = c.transpose ? d->Cin : d->Cout;
-  const float *in = c.in, *bias = c.bias, *add = c.add;
-  float *out = c.out, *stat = c.stat;
-  const int64_t in_bs = c.in_bs, out_bs = c.out_bs;
-  float* slab = (float*)((char*)c.ws + p.wp_bytes);
-  int* work_counter = queue_state(st);   // per (device, stream): concurrent launches over one model never share it
-  M355_REQUIRE(work_counter, M355_ELAUNCH, "conv3d: could not allocate the work-queue state");
-  const float* kb = p.ksplit == 1 ? bias : nullptr;
-  const float* ka = p.ksplit == 1 ? add : nullptr;
+  float* slab = (float*)((char*)c.ws + r.slab_off);
+  const bool split = (r.aux & AUX_SPLITK) != 0;   // bias, residual and statistics then come from the reduction pass
+  const float* kb = split ? nullptr : c.bias;
+  const float* ka = split ? nullptr : c.add;
+  float* kstat = split ? nullptr : c.stat;
   if (r.kind == ConvKind::X3) {
-    if (int rc = launch_x3_conv(p, in, wp, kb, ka, out, slab, N, kin, mout, D, H, W, in_bs, out_bs, st,
-                                p.ksplit == 1 ? stat : nullptr))
-      return rc;
+    if (int rc = launch_x3_conv(r, c.in, wp, kb, ka, c.out, slab, d, st, kstat)) return rc;
   } else {
-#define M355_FWD_CASE(NTW, GX)                                                              \
-  if (p.ntw == NTW && p.gx == GX) {                                                         \
-    launch_fwd<NTW, GX>(p, in, wp, kb, ka, out, slab, N, kin, mout, D, H, W, in_bs, out_bs, \
-                        st, p.ksplit == 1 ? stat : nullptr, work_counter);                  \
+#define M355_FWD_CASE(NTW, GX)                                          \
+  if (p.ntw == NTW && p.gx == GX) {                                     \
+    launch_fwd<NTW, GX>(r, c, wp, kb, ka, slab, kstat, work_counter);   \
   } else
   M355_FWD_CASE(8, 32) M355_FWD_CASE(4, 32) M355_FWD_CASE(2, 32) M355_FWD_CASE(1, 32)
   M355_FWD_CASE(8, 16) M355_FWD_CASE(4, 16) M355_FWD_CASE(2, 16) M355_FWD_CASE(1, 16)
@@ -1989,118 +1975,93 @@ int launch_f32_conv(const ConvRoute& r, const ConvCall& c) {
   }
 #undef M355_FWD_CASE
   }
-  if (p.ksplit > 1 && stat) {   // split plan + fused statistics: the reduction pass emits the partials
-    const int64_t S = (int64_t)D * H * W;
-    dim3 grid((unsigned)splitk_c8_slots(S), (unsigned)mout, (unsigned)N);
-    hipLaunchKernelGGL(splitk_reduce_stats_kernel, grid, dim3(256), 0, st, slab, bias, add, out, mout, S, p.ksplit,
-                       (int64_t)N * mout * S, out_bs, stat);
-  } else if (p.ksplit > 1) {
-    const int64_t S = (int64_t)D * H * W;
-    const int64_t total = (int64_t)N * mout * S;
-    const int blocks = (int)std::min<int64_t>(ceil_div(total, 256), 4096);
-    hipLaunchKernelGGL(splitk_reduce_kernel, dim3(blocks), dim3(256), 0, st, slab, bias, add, out,
-                       N, mout, S, p.ksplit, total, out_bs);
-  }
+  const int64_t S = (int64_t)D * H * W, total = (int64_t)N * r.mout * S;
+  if (r.aux & AUX_SPLITK_STATS)   // split plan + fused statistics: the reduction pass emits the partials
+    hipLaunchKernelGGL(splitk_reduce_stats_kernel, r.reduce_grid, dim3(256), 0, st, slab, c.bias, c.add, c.out, r.mout, S,
+                       p.ksplit, total, r.out_bs, c.stat);
+  else if (split)
+    hipLaunchKernelGGL(splitk_reduce_kernel, r.reduce_grid, dim3(256), 0, st, slab, c.bias, c.add, c.out, N, r.mout, S,
+                       p.ksplit, total, r.out_bs);
   return check_launch("conv3d_mfma");
 }
 
-// The choice of the MFMA weight-gradient kernel that a descriptor cannot make.  vec: float4 interior rows need 16-byte
-// aligned rows.  gen2: the second-generation kernels need float4 rows, and a sample must fit the 32-bit byte offsets of a
-// buffer descriptor (the hardware zero-fills what lies past it); otherwise conv3_mfma_bww_kernel<GX, vec>.
-struct BwwVariant { bool vec, gen2; };
-static BwwVariant bww_variant(const m355_conv3d_desc* d, const float* x, const float* dy, int64_t xbs) {
-  const int64_t spatial = (int64_t)d->D * d->H * d->W;
-  const bool vec = (d->W % 4 == 0) && (xbs % 4 == 0) && (((uintptr_t)x) & 15) == 0;
-  const bool gen2 = vec && ((uintptr_t)dy & 3) == 0 && (int64_t)d->Cin * spatial < (1ll << 29) &&
-                    (int64_t)d->Cout * spatial < (1ll << 29) && tuning().bww_gen == 2;
-  return {vec, gen2};
-}
-
-int launch_f32_bww(const BwwRoute& r, const m355_conv3d_desc* d, const float* x, const float* dy, float* dw, float* slab,
-                   int64_t xbs, int64_t ybs, hipStream_t st) {
+template <int GX>
+static void launch_bww_mfma(const BwwRoute& r, const float* x, const float* dy, float* slab, const m355_conv3d_desc* d,
+                            hipStream_t st) {
   const BwwPlan& p = r.plan;
   switch (r.kind) {
-    case BwwKind::Direct: {
-      const int OD = out_dim(d->D, d->k, d->stride, d->pad), OH = out_dim(d->H, d->k, d->stride, d->pad),
-                OW = out_dim(d->W, d->k, d->stride, d->pad);
-      const int k3 = d->k * d->k * d->k;
-      const int64_t nblk = (int64_t)d->Cout * d->Cin * k3;
-      M355_REQUIRE(nblk < (1ll << 31), M355_EUNSUPPORTED, "conv3d_bwd_weight: grid too large");
-      hipLaunchKernelGGL(conv3d_direct_bwd_weight_kernel, dim3((unsigned)nblk), dim3(256), 0, st, x,
-                         dy, dw, d->N, d->Cin, d->Cout, d->D, d->H, d->W, OD, OH, OW, d->k,
-                         d->stride, d->pad, xbs, ybs);
-      return M355_OK;
-    }
-    case BwwKind::X3:
-      M355_REQUIRE((((uintptr_t)x | (uintptr_t)dy) & 3) == 0, M355_EINVALID_ARG, "conv3d_bwd_weight: misaligned tensor");
-      if (int rc = launch_bww_x3(r.x3, x, dy, slab, d->N, d->Cin, d->Cout, d->D, d->H, d->W, xbs, ybs, st)) return rc;
-      launch_slab_reduce_t(slab, dw, d->Cin, d->Cout, r.x3.ctiles, r.x3.k, 1.f, st);   // k.ns: splits of each pair class
-      return M355_OK;
-    case BwwKind::Small: {
-      // narrow side (<= 4 channels) shares the lane index with the taps
+    case BwwKind::Small: {   // narrow side (<= 4 channels) shares the lane index with the taps
       const int swap = d->Cin <= 4 ? 0 : 1;
-      const float* P = swap ? x : dy;
-      const float* Q = swap ? dy : x;
-      const int CP = swap ? d->Cin : d->Cout, CQ = swap ? d->Cout : d->Cin;
-      const int64_t pbs = swap ? xbs : ybs, qbs = swap ? ybs : xbs;
-      dim3 g2((unsigned)ceil_div(CP, 32), (unsigned)p.nsplit);
-#define M355_BWS_LAUNCH(GXV)                                                                       \
-  hipLaunchKernelGGL((conv3_mfma_bww_small_kernel<GXV>), g2, dim3(256), 0, st, P, Q, slab, d->N, CP, \
-                     CQ, d->D, d->H, d->W, p.tz_tiles, p.ty_tiles, p.tx_tiles, p.nsplit, pbs, qbs,  \
-                     swap, d->Cin, d->Cout);
-      if (p.gx == 32) { M355_BWS_LAUNCH(32) } else if (p.gx == 16) { M355_BWS_LAUNCH(16) } else { M355_BWS_LAUNCH(8) }
-      const int64_t total = (int64_t)d->Cout * d->Cin * 27;
-      const int blocks = (int)std::min<int64_t>(ceil_div(total, 256), 2048);
-      hipLaunchKernelGGL(slab_reduce_kernel, dim3(blocks), dim3(256), 0, st, slab, dw, total, p.nsplit);
-      return M355_OK;
+      hipLaunchKernelGGL((conv3_mfma_bww_small_kernel<GX>), r.grid, dim3(256), 0, st, swap ? x : dy, swap ? dy : x, slab, d->N,
+                         swap ? d->Cin : d->Cout, swap ? d->Cout : d->Cin, d->D, d->H, d->W, p.tz_tiles, p.ty_tiles,
+                         p.tx_tiles, p.nsplit, swap ? r.xbs : r.ybs, swap ? r.ybs : r.xbs, swap, d->Cin, d->Cout);
+      break;
     }
-    case BwwKind::Mfma2: {
-      dim3 grid((unsigned)p.ctiles, (unsigned)p.otiles, (unsigned)p.nsplit);
-      const BwwVariant v = bww_variant(d, x, dy, xbs);
-      const bool vec = v.vec, gen2 = v.gen2;
-#define M355_BWW_LAUNCH(GXV)                                                                      \
-  {                                                                                               \
-    if (vec)                                                                                      \
-      hipLaunchKernelGGL((conv3_mfma_bww_kernel<GXV, true>), grid, dim3(256), 0, st, x, dy, slab, \
-                         d->N, d->Cin, d->Cout, d->D, d->H, d->W, p.tz_tiles, p.ty_tiles,       \
-                         p.tx_tiles, p.nsplit, xbs, ybs);                                        \
-    else                                                                                          \
-      hipLaunchKernelGGL((conv3_mfma_bww_kernel<GXV, false>), grid, dim3(256), 0, st, x, dy,      \
-                         slab, d->N, d->Cin, d->Cout, d->D, d->H, d->W, p.tz_tiles, p.ty_tiles, \
-                         p.tx_tiles, p.nsplit, xbs, ybs);                                        \
-  }
-#define M355_BWW2_LAUNCH(GXV)                                                                     \
-  hipLaunchKernelGGL((conv3_mfma_bww2_kernel<GXV>), dim3((unsigned)(p.ctiles * p.otiles * p.nsplit)),  \
-                     dim3(256), 0, st, x, dy, slab, d->N, d->Cin, d->Cout, d->D, d->H, d->W, p.tz_tiles, \
-                     p.ty_tiles, p.tx_tiles, p.nsplit, p.ctiles, p.otiles, xbs, ybs);
-#define M355_BWW2C_LAUNCH(GXV)                                                                    \
-  hipLaunchKernelGGL((conv3_mfma_bww2c_kernel<GXV>), dim3((unsigned)p.class_wgs), dim3(256), 0, st, x, dy, slab, d->N, \
-                     d->Cin, d->Cout, d->D, d->H, d->W, p.tz_tiles, p.ty_tiles, p.tx_tiles, p.k, xbs, ybs);
-      BwwClasses kred = p.k;   // what the reduction sums: the class splits, or the uniform count
-      if (gen2 && p.classes) {
-        if (p.gx == 32) { M355_BWW2C_LAUNCH(32) } else if (p.gx == 16) { M355_BWW2C_LAUNCH(16) } else { M355_BWW2C_LAUNCH(8) }
-      } else if (gen2) {
-        for (int c = 0; c < 4; ++c) kred.ns[c] = p.nsplit;
-        if (p.gx == 32) { M355_BWW2_LAUNCH(32) } else if (p.gx == 16) { M355_BWW2_LAUNCH(16) } else { M355_BWW2_LAUNCH(8) }
-      } else if (p.gx == 32)
-        M355_BWW_LAUNCH(32)
-      else if (p.gx == 16)
-        M355_BWW_LAUNCH(16)
-      else
-        M355_BWW_LAUNCH(8)
-      if (gen2) {
-        launch_slab_reduce_t(slab, dw, d->Cin, d->Cout, p.ctiles, kred, 1.f, st);
-      } else {
-        const int64_t total = (int64_t)d->Cout * d->Cin * 27;
-        const int blocks = (int)std::min<int64_t>(ceil_div(total, 64), 4096);
-        hipLaunchKernelGGL(slab_reduce_kernel, dim3(blocks), dim3(64), 0, st, slab, dw, total, p.nsplit);
-      }
-      return M355_OK;
-    }
+    case BwwKind::Mfma2c:
+      hipLaunchKernelGGL((conv3_mfma_bww2c_kernel<GX>), r.grid, dim3(256), 0, st, x, dy, slab, d->N, d->Cin, d->Cout, d->D,
+                         d->H, d->W, p.tz_tiles, p.ty_tiles, p.tx_tiles, p.k, r.xbs, r.ybs);
+      break;
+    case BwwKind::Mfma2:
+      hipLaunchKernelGGL((conv3_mfma_bww2_kernel<GX>), r.grid, dim3(256), 0, st, x, dy, slab, d->N, d->Cin, d->Cout, d->D,
+                         d->H, d->W, p.tz_tiles, p.ty_tiles, p.tx_tiles, p.nsplit, p.ctiles, p.otiles, r.xbs, r.ybs);
+      break;
     default:
-      set_error("conv3d_bwd_weight: no fp32 kernel for this route");
-      return M355_EUNSUPPORTED;
+      with_bool(r.kind == BwwKind::MfmaVec, [&](auto V) {
+        hipLaunchKernelGGL((conv3_mfma_bww_kernel<GX, decltype(V)::value>), r.grid, dim3(256), 0, st, x, dy, slab, d->N,
+                           d->Cin, d->Cout, d->D, d->H, d->W, p.tz_tiles, p.ty_tiles, p.tx_tiles, p.nsplit, r.xbs, r.ybs);
+      });
   }
+}
+
+int launch_bww(const BwwRoute& r, const BwwCall& c) {
+  const m355_conv3d_desc* d = c.d;
+  hipStream_t st = c.st;
+  const int64_t S = (int64_t)d->D * d->H * d->W;
+  float* slab = (float*)c.ws;
+  const void *x = c.x, *dy = c.dy;
+  if (r.via_pack) {
+    // fp32 NCDHW operands in a 16-bit compute mode (the model path hands over c8 tensors through
+    // m355_conv3d_bwd_weight_h16 / _c8): both operands are rounded into c8 copies and the c8 kernel runs
+    void* x16 = (char*)c.ws + r.x16_off;
+    void* dy16 = (char*)c.ws + r.dy16_off;
+    if (int rc = launch_pack_act16((const float*)x, x16, d->N, d->Cin, S, r.x32_bs, r.xbs, d->compute, st)) return rc;
+    if (int rc = launch_pack_act16((const float*)dy, dy16, d->N, d->Cout, S, r.dy_bs, r.ybs, d->compute, st)) return rc;
+    x = x16;
+    dy = dy16;
+  }
+  switch (r.kind) {
+    case BwwKind::Direct:
+      hipLaunchKernelGGL(conv3d_direct_bwd_weight_kernel, r.grid, dim3(256), 0, st, (const float*)x, (const float*)dy, c.dw,
+                         d->N, d->Cin, d->Cout, d->D, d->H, d->W, out_dim(d->D, d->k, d->stride, d->pad),
+                         out_dim(d->H, d->k, d->stride, d->pad), out_dim(d->W, d->k, d->stride, d->pad), d->k, d->stride,
+                         d->pad, r.xbs, r.ybs);
+      break;
+    case BwwKind::X3:
+    case BwwKind::X3c:
+      launch_bww_x3(r, (const float*)x, (const float*)dy, slab, d, st);
+      break;
+    case BwwKind::C8:
+    case BwwKind::C8Small:
+      launch_bww_c8(r, x, dy, slab, d, st);
+      if (int rc = check_launch(r.kind == BwwKind::C8 ? "conv3_bww_c8" : "conv3_bww_c8_small")) return rc;
+      break;
+    default:
+      if (r.plan.gx == 32) launch_bww_mfma<32>(r, (const float*)x, (const float*)dy, slab, d, st);
+      else if (r.plan.gx == 16) launch_bww_mfma<16>(r, (const float*)x, (const float*)dy, slab, d, st);
+      else launch_bww_mfma<8>(r, (const float*)x, (const float*)dy, slab, d, st);
+  }
+  if (r.aux & (AUX_SLAB_T | AUX_SLAB_TAP))
+    launch_slab_reduce_t(r, slab, c.dw, d->Cin, d->Cout, c.grad_unscale, st);
+  else if (r.aux & AUX_SLAB_PLAIN)
+    hipLaunchKernelGGL(slab_reduce_kernel, r.reduce_grid, dim3(r.reduce_block), 0, st, slab, c.dw, (int64_t)d->Cout * d->Cin * 27,
+                       r.plan.nsplit);
+  void* dbias_ws = (char*)c.ws + r.dbias_off;   // its scratch follows the slabs
+  if (r.aux & AUX_DBIAS_C8) {
+    if (int rc = launch_dbias_c8(dy, r.ybs, c.dbias, d->N, d->Cout, S, d->compute, c.grad_unscale, dbias_ws, st)) return rc;
+  } else if (r.aux & AUX_DBIAS_F32) {
+    launch_dbias(c.dy32, c.dbias, d->N, d->Cout, out_voxels(d), r.dy_bs, dbias_ws, st);
+  }
+  return check_launch(r.who);
 }
 
 }  // namespace m355

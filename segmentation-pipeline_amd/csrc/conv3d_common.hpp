@@ -1,9 +1,10 @@
-// Shared pieces of the 3x3x3 convolution code: device helpers of the kernels (conv3d.hip: fp32 kernels and their launcher;
-// conv3d_f32x3.hip: split kernels; conv3d_h16.hip: bf16 / fp16 operand kernels), the plans, and the routes that the host
-// layer (conv3d_host.hip: resolver, planners, every extern "C" entry point) resolves a descriptor to.
+// Shared pieces of the 3x3x3 convolution code: device helpers of the kernels (conv3d.hip: fp32 kernels and the launchers;
+// conv3d_f32x3.hip: split kernels; conv3d_h16.hip: bf16 / fp16 operand kernels) and what the host layer (conv3d_host.hip:
+// every extern "C" entry point) hands the launchers: a route (conv3d_route.hpp: planners, routes, checks) and a call.
 #pragma once
 #include "common.hpp"
 #include "h16.hpp"
+#include "conv3d_route.hpp"
 
 namespace m355 {
 
@@ -134,20 +135,6 @@ __device__ __forceinline__ void store_conv_tile(const f32x16 (&acc)[NTW], float*
 }
 
 
-// ------------------------------------------------------------------ planning
-struct FwdPlan {
-  bool mfma;
-  bool persistent;  // more items than resident workgroups: the queue-driven kernel variants
-  int gx, ntw;
-  int tz_tiles, ty_tiles, tx_tiles;
-  int otiles, kin_pad, mout_pad, nchunks, ksplit;   // otiles: 32-row output tiles
-  int tile16;       // + one 16-row remainder tile at channel 32 * otiles (fp32 path, mout % 32 in 1..16)
-  int nw;           // waves per workgroup = z slices of a tile: 4, or 8 (16-bit kernels, double-buffered variant)
-  int oneshot;      // 16-bit kernels: one item per workgroup instead of the work queue (items of 1-2 chunks)
-  int x3;           // M355_COMPUTE_F32X3 and the layer qualifies: conv3_f32x3_kernel (conv3d_f32x3.hip), 8-channel chunks
-  size_t wp_bytes, slab_bytes;
-};
-
 // ---- 16-row output tile (v_mfma_f32_16x16x4_f32) for the remainder of channel counts that are no multiple of
 // 32 (the reference's real widths are 40 / 80 / 120: research/msseg2/msseg2.py:87, main_config.py:123-127;
 // a 32-row tile for 8 remaining channels is 75 % padding).  Same flop rate as the 32x32x2 form; the K-step of 4
@@ -217,84 +204,10 @@ __device__ __forceinline__ void store_conv_tile16(const f32x4v (&acc)[NTW][2], f
   }
 }
 
-inline bool is16(int compute) { return compute == M355_COMPUTE_BF16 || compute == M355_COMPUTE_F16; }
-// M355_COMPUTE_F32X3 (conv3d_f32x3.hip): split + fragment-ordered weights, and the kernel launch of a plan with x3 != 0
-void launch_pack_w3_x3(const FwdPlan& p, const float* w, void* wp, int Cout_w, int Cin_w, bool transpose, hipStream_t st);
-int launch_x3_conv(const FwdPlan& p, const float* in, const void* wp, const float* bias, const float* add, float* out,
-                   float* slab, int N, int kin, int mout, int D, int H, int W, int64_t in_bs, int64_t out_bs, hipStream_t st,
-                   float* stat);
-// pair classes of a weight gradient whose channel counts leave a 1..16 channel remainder (conv3_mfma_bww2c_kernel,
-// conv3_bww_x3c_kernel)
-struct BwwClasses {
-  int of, cf, orem, crem;   // full 32-channel tiles per side, and whether a 16-row remainder tile follows them
-  int ns[4];                // voxel-range splits of a pair of class (o remainder ? 2 : 0) + (c remainder ? 1 : 0)
-  int start[4];             // first workgroup of each class
-};
-// ... and its weight gradient (conv3_bww_x3_kernel / conv3_bww_x3c_kernel): slab[split][27][Cout][Cin] partials, reduced by
-// the caller with k.ns[class] splits per pair class
-struct BwwX3Plan {
-  int tx, ty_tiles, tx_tiles, ctiles, otiles, nsplit;
-  bool classes;     // a 1..16 channel remainder on either side: the class kernel
-  BwwClasses k;     // always filled: without remainders one class with ns[*] = nsplit
-  int class_wgs;
-  size_t slab_bytes;
-};
-BwwX3Plan plan_bww_x3(int N, int Cin, int Cout, int D, int H, int W);
-int launch_bww_x3(const BwwX3Plan& p, const float* x, const float* dy, float* slab, int N, int Cin, int Cout, int D, int H,
-                  int W, int64_t xbs, int64_t ybs, hipStream_t st);
 // ConvTranspose3d k2 s2 forward on the split (conv3d_f32x3.hip; caller: convt.hip)
 int convt_fwd_x3_nvt(int Cin);
 void launch_convt_fwd_x3(int nvt, dim3 grid, const float* x, const float* w, const float* bias, float* y, int Cin, int Cout,
                          int D, int H, int W, int64_t xbs, int64_t ybs, int mt_per_wg, hipStream_t st);
-
-// ------------------------------------------------------------------ routes (conv3d_host.hip)
-// What a descriptor runs and what it needs, resolved ONCE per call on the host.  The queries return a route's numbers, the
-// launching entry points check their arguments against the same numbers and switch on `kind`: nothing else decides.
-enum class ConvKind {
-  Direct,             // not 3x3x3 / s1 / p1 (or >= 2^27 voxels): conv3d_direct_*_kernel
-  SmallCoutValu,      // Cout <= 4 forward: conv3_valu_smallcout_kernel (optional softmax epilogue)
-  SmallCoutToeplitz,  //   ... conv3_mfma_fwd_smallcout_kernel (M355_SMALLCOUT_VALU=0)
-  MfmaF32,            // conv3_mfma_fwd_kernel, one tile per workgroup
-  MfmaF32Queue,       // conv3_mfma_fwd_p_kernel
-  X3,                 // conv3_f32x3_kernel
-  H16Queue, H16Queue8, H16OneShot   // conv3_h16_kernel: queue-driven, its 8-wave variant, one item per workgroup
-};
-inline bool is_h16(ConvKind k) { return k == ConvKind::H16Queue || k == ConvKind::H16Queue8 || k == ConvKind::H16OneShot; }
-struct ConvRoute {            // forward (which = 0) or data gradient (which = 1) of one descriptor
-  ConvKind kind;
-  FwdPlan plan;               // the MFMA kinds (MfmaF32 .. H16OneShot)
-  size_t packed_bytes;        // m355_conv3d_packed_bytes
-  size_t workspace_bytes;     // fp32 NCDHW input (16-bit modes: + the c8 staging copy)
-  size_t h16_workspace_bytes; // c8 input handed over by the caller
-  int64_t stats_slots, stats_slots_c8;   // fused statistics partials per (sample, channel): fp32 / c8 output; 0 = none
-  bool fuses_softmax;
-  int32_t plan_code[4];       // m355_conv3d_plan
-};
-ConvRoute route_conv(const m355_conv3d_desc* d, int which);
-
-struct BwwPlan {
-  int gx, tz_tiles, ty_tiles, tx_tiles, otiles, ctiles, nsplit;
-  size_t slab_bytes;
-  bool classes;     // a 1..16 channel remainder on either side: conv3_mfma_bww2c_kernel (needs the gen-2 conditions)
-  BwwClasses k;     // always filled: without remainders one class with ns[*] = nsplit
-  int class_wgs;    // grid of the class kernel
-};
-enum class BwwKind {
-  Direct,       // conv3d_direct_bwd_weight_kernel
-  X3,           // conv3_bww_x3(c)_kernel
-  Mfma2,        // conv3_mfma_bww2(c)_kernel, or conv3_mfma_bww_kernel where the pointers rule them out (bww_gen2)
-  Small,        // conv3_mfma_bww_small_kernel (<= 4 channels on one side)
-  H16ViaPack    // 16-bit modes: both operands packed to c8, then the c8 kernel
-};
-struct BwwRoute {             // weight gradient of the plain entry point
-  BwwKind kind;
-  BwwPlan plan;               // Mfma2, Small
-  BwwX3Plan x3;               // X3
-  size_t slab_bytes;          // fp32 kinds: the slabs; the bias gradient's scratch follows them
-  size_t workspace_bytes;
-  int32_t plan_code[4];
-};
-BwwRoute route_bww(const m355_conv3d_desc* d);
 
 // ConvTranspose3d (convt.hip): the same contract.  `kind` names the kernel family of the call, the numbers are that
 // family's launch; the byte counts hold for every kind, so one workspace serves whichever side the pointers pick.
@@ -325,49 +238,52 @@ struct ConvtRoute {
 ConvtRoute route_convt(const m355_conv3d_desc* d, int which, bool y_side_ok);
 ConvtRoute route_convt_c8(const m355_conv3d_desc* d, int which);   // the c8 entry points (*_h16)
 
-// ------------------------------------------------------------------ fp32 launcher (conv3d.hip)
-// One forward / data-gradient call.  The logical conv has K-channels kin = transpose ? Cout : Cin of `in`, M-channels mout.
+// ------------------------------------------------------------------ launchers
+// The pointers of one forward / data-gradient call; everything else is in its route.
 struct ConvCall {
   const m355_conv3d_desc* d;
-  bool transpose;             // data gradient: flipped / transposed filter
-  const float* in;            // fp32 NCDHW, `in_bs` elements between samples ...
-  int64_t in_bs;
-  const void* in16;           // ... or c8 (16-bit kinds only), `in16_bs` elements between samples
-  int64_t in16_bs;
-  const float* w;             // weight tensor, or with `prepacked` the buffer m355_conv3d_pack filled for this route
-  bool prepacked;
+  const float* in;            // fp32 NCDHW input ...
+  const void* in16;           // ... or c8 (null: the 16-bit kinds round `in` into the staging copy first)
+  const float* w;             // weight tensor, or with M355_CONV_W_PACKED the buffer m355_conv3d_pack filled for this route
   const float* bias;
   const float* add;
-  float* out;                 // fp32 NCDHW, or with `out16` a c8 tensor; `out_bs` elements between samples
-  int64_t out_bs;
-  bool out16, softmax;
+  float* out;                 // fp32 NCDHW, or (route.out16) a c8 tensor
   float* stat;                // fused statistics partials (null: none)
   int* oflag;                 // overflow word of a c8 data gradient (fp16: the stores saturate and report there)
   void* ws;
-  size_t ws_bytes;
   hipStream_t st;
 };
-// every kind but the 16-bit ones: weight pack unless prepacked, the kernel, the split-K reduction
+// every kind but the 16-bit ones (conv3d.hip): weight pack unless prepacked, the kernel, the split-K reduction
 int launch_f32_conv(const ConvRoute& r, const ConvCall& c);
+// the 16-bit kinds (conv3d_h16.hip): operand pack of an fp32 input, weight pack unless prepacked, the kernel, the reduction
+int launch_h16_conv(const ConvRoute& r, const ConvCall& c);
 // packed weights of every kind with a packed form (m355_conv3d_pack)
 void launch_pack_weights(const ConvRoute& r, const m355_conv3d_desc* d, bool transpose, const float* w, void* packed,
                          hipStream_t st);
-size_t smallcout_packed_bytes(int Cin);
-// weight gradient of every kind but H16ViaPack into dw, slabs in `slab`
-int launch_f32_bww(const BwwRoute& r, const m355_conv3d_desc* d, const float* x, const float* dy, float* dw, float* slab,
-                   int64_t xbs, int64_t ybs, hipStream_t st);
-void launch_slab_reduce_t(const float* slab, float* dw, int Cin, int Cout, int ctiles, const BwwClasses& k, float scale,
-                          hipStream_t st);
-inline int out_dim(int in, int k, int s, int p) { return (in + 2 * p - k) / s + 1; }
-
-// 16-bit operand convolution (conv3d_h16.hip).  in16: c8 layout (h16.hpp) with `in16_bs` ELEMENTS between
-// samples; out: fp32 NCDHW.  Workspace: p.wp_bytes (packed weights + work queue) + p.slab_bytes.
-int run_h16_conv(const FwdPlan& p, int compute, const void* in16, int64_t in16_bs, const float* w, bool transpose,
-                 int Cout_w, int Cin_w, const float* bias, const float* add, float* out, int N, int kin, int mout,
-                 int D, int H, int W, int64_t out_bs, void* ws, size_t ws_bytes, hipStream_t st, float* stat,
-                 const void* prepacked = nullptr, bool out16 = false, bool softmax = false, int* oflag = nullptr);
 void launch_pack_w3_h16(const FwdPlan& p, int compute, const float* w, void* wp, int Cout_w, int Cin_w, bool transpose,
                         hipStream_t st);
+// M355_COMPUTE_F32X3 (conv3d_f32x3.hip): split + fragment-ordered weights, and the main and 16-row launches of an X3 route
+void launch_pack_w3_x3(const FwdPlan& p, const float* w, void* wp, int Cout_w, int Cin_w, bool transpose, hipStream_t st);
+int launch_x3_conv(const ConvRoute& r, const float* in, const void* wp, const float* bias, const float* add, float* out,
+                   float* slab, const m355_conv3d_desc* d, hipStream_t st, float* stat);
+
+// The pointers of one weight-gradient call.
+struct BwwCall {
+  const m355_conv3d_desc* d;
+  const void* x;              // fp32 NCDHW or c8, as the entry point takes them
+  const void* dy;
+  const float* dy32;          // the fp32 dy of the bias gradient (c8-only flow: none, it reads the c8 dy)
+  float* dw;
+  float* dbias;
+  float grad_unscale;         // c8-only flow: the loss scale removed in the fp32 epilogues
+  void* ws;
+  hipStream_t st;
+};
+// ONE weight-gradient launcher (conv3d.hip): operand packs, the kernel of r.kind, the slab reduction, the bias gradient
+int launch_bww(const BwwRoute& r, const BwwCall& c);
+// ... and the typed launchers of the other two files it switches to: slabs into `slab`
+void launch_bww_x3(const BwwRoute& r, const float* x, const float* dy, float* slab, const m355_conv3d_desc* d, hipStream_t st);
+void launch_bww_c8(const BwwRoute& r, const void* x16, const void* dy16, float* slab, const m355_conv3d_desc* d, hipStream_t st);
 
 // One entry of a batched weight pack (m355_conv3d_pack_batch): after optimizer.step every conv weight of a model is
 // re-packed (forward + data-gradient form), ~37 launches of 5-15 us each on the critical path of a train step; the batch
@@ -420,16 +336,6 @@ __device__ __forceinline__ void pack_w3_body(const float* __restrict__ w, float*
     wp[i] = v;
   }
 }
-// blocks along the voxel axis of splitk_reduce_c8_kernel == statistics slots it emits per sample
-inline int64_t splitk_c8_slots(int64_t S) { return std::max<int64_t>(1, std::min<int64_t>(ceil_div(S, 256), 2048)); }
-
-// weight gradient from c8 operands (tile 2 x 4 x 32 voxels); slab[split][27][Cout][Cin], summed by slab_reduce_t_kernel
-int launch_bww_c8(int compute, const void* x16, const void* dy16, float* slab, int N, int Cin, int Cout, int D, int H,
-                  int W, int nsplit, int64_t xbs16, int64_t ybs16, hipStream_t st);
-// the same for an edge layer (Cin <= 4 or Cout <= 4): narrow channel and tap share the MFMA column
-int launch_bww_c8_small(int compute, const void* x16, const void* dy16, float* slab, int N, int Cin, int Cout, int D, int H,
-                  int W, int nsplit, int64_t xbs16, int64_t ybs16, hipStream_t st);
-
 // y[n,o,s] = bias[o] + add[n,o,s] + sum_ks slab[ks][n,o,s]   (fixed order)
 __global__ void splitk_reduce_kernel(const float* __restrict__ slab, const float* __restrict__ bias,
                                      const float* __restrict__ add, float* __restrict__ y, int N,

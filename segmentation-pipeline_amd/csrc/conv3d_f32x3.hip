@@ -611,29 +611,28 @@ __global__ __launch_bounds__(256, 2) void conv3_f32x3_m16_kernel(
 }
 
 template <int NTW, int GX>
-static void launch_x3(const FwdPlan& p, const float* x, const void* wp, const float* bias, const float* add, float* y,
-                      float* slab, int N, int kin, int mout, int D, int H, int W, int64_t xbs, int64_t ybs, hipStream_t st,
-                      float* stat) {
-  const unsigned sp = (unsigned)(p.tz_tiles * p.ty_tiles * p.tx_tiles);
-  if (p.otiles > 0)
-    hipLaunchKernelGGL((conv3_f32x3_kernel<NTW, GX>), dim3(sp * p.otiles, 1u, (unsigned)(N * p.ksplit)), dim3(256), 0, st, x,
-                       (const u32x4*)wp, bias, add, y, slab, kin, mout, D, H, W, p.ty_tiles, p.tx_tiles, p.nchunks, p.ksplit, xbs,
-                       ybs, (int64_t)N * mout * D * H * W, stat, p.otiles, tuning().conv_cube & 2);
-  if (p.tile16)   // the 1..16 remaining channels: their own launch over the spatial tiles (disjoint channels of y / the slabs)
-    hipLaunchKernelGGL((conv3_f32x3_m16_kernel<NTW, GX>), dim3(sp, 1u, (unsigned)(N * p.ksplit)), dim3(256), 0, st, x,
-                       (const u32x4*)wp + (int64_t)p.otiles * p.nchunks * (X3_PAIRS * 3 * 64), bias, add, y, slab, kin, mout, D, H, W,
-                       p.ty_tiles, p.tx_tiles, p.nchunks, p.ksplit, xbs, ybs, (int64_t)N * mout * D * H * W, stat, p.otiles * 32);
+static void launch_x3(const ConvRoute& r, const float* x, const void* wp, const float* bias, const float* add, float* y,
+                      float* slab, const m355_conv3d_desc* d, hipStream_t st, float* stat) {
+  const FwdPlan& p = r.plan;
+  const int64_t slab_stride = (int64_t)d->N * r.mout * d->D * d->H * d->W;
+  if (r.grid.x)
+    hipLaunchKernelGGL((conv3_f32x3_kernel<NTW, GX>), r.grid, dim3(256), 0, st, x, (const u32x4*)wp, bias, add, y, slab, r.kin,
+                       r.mout, d->D, d->H, d->W, p.ty_tiles, p.tx_tiles, p.nchunks, p.ksplit, r.in_bs, r.out_bs, slab_stride,
+                       stat, p.otiles, r.sched);
+  if (r.aux & AUX_TILE16)   // the 1..16 remaining channels: their own launch over the spatial tiles (disjoint channels of y / the slabs)
+    hipLaunchKernelGGL((conv3_f32x3_m16_kernel<NTW, GX>), r.grid16, dim3(256), 0, st, x,
+                       (const u32x4*)wp + (int64_t)p.otiles * p.nchunks * (X3_PAIRS * 3 * 64), bias, add, y, slab, r.kin, r.mout,
+                       d->D, d->H, d->W, p.ty_tiles, p.tx_tiles, p.nchunks, p.ksplit, r.in_bs, r.out_bs, slab_stride, stat,
+                       p.otiles * 32);
 }
 
-// launches the kernel of plan p (p.x3 != 0); the caller (run_mfma_conv) has checked the workspace, packed the weights
-// and runs the split-K reduction
-int launch_x3_conv(const FwdPlan& p, const float* in, const void* wp, const float* bias, const float* add, float* out,
-                   float* slab, int N, int kin, int mout, int D, int H, int W, int64_t in_bs, int64_t out_bs, hipStream_t st,
-                   float* stat) {
-#define M355_X3_CASE(NTW, GX)                                                                          \
-  if (p.ntw == NTW && p.gx == GX) {                                                                    \
-    launch_x3<NTW, GX>(p, in, wp, bias, add, out, slab, N, kin, mout, D, H, W, in_bs, out_bs, st, stat); \
-    return M355_OK;                                                                                    \
+// the main and 16-row launches of an X3 route; the caller (launch_f32_conv) packs the weights and runs the split-K reduction
+int launch_x3_conv(const ConvRoute& r, const float* in, const void* wp, const float* bias, const float* add, float* out,
+                   float* slab, const m355_conv3d_desc* d, hipStream_t st, float* stat) {
+#define M355_X3_CASE(NTW, GX)                                              \
+  if (r.plan.ntw == NTW && r.plan.gx == GX) {                              \
+    launch_x3<NTW, GX>(r, in, wp, bias, add, out, slab, d, st, stat);      \
+    return M355_OK;                                                        \
   }
   M355_X3_CASE(4, 32)
   M355_X3_CASE(2, 32)
@@ -645,7 +644,7 @@ int launch_x3_conv(const FwdPlan& p, const float* in, const void* wp, const floa
   M355_X3_CASE(2, 8)
   M355_X3_CASE(1, 8)
 #undef M355_X3_CASE
-  set_error("conv3d(f32x3): no kernel for ntw=%d gx=%d", p.ntw, p.gx);
+  set_error("conv3d(f32x3): no kernel for ntw=%d gx=%d", r.plan.ntw, r.plan.gx);
   return M355_EUNSUPPORTED;
 }
 
@@ -1090,106 +1089,22 @@ __global__ __launch_bounds__(512, 1) void conv3_bww_x3c_kernel(
   }
 }
 
-// tile width: the padded volume decides (ties: the wider tile, whose rows coalesce better)
-static int bww_x3_tx(int H, int W) {
-  int best = 32;
-  int64_t best_v = -1;
-  for (int tx : {32, 16, 8}) {
-    const int ty = 64 / tx;
-    const int64_t v = round_up(W, tx) * round_up(H, ty);
-    if (best_v < 0 || v < best_v) best = tx, best_v = v;
-  }
-  return best;
+template <int TX>
+static void launch_bww_x3_t(const BwwRoute& r, const float* x, const float* dy, float* slab, const m355_conv3d_desc* d,
+                            hipStream_t st) {
+  const BwwX3Plan& p = r.x3;
+  if (r.kind == BwwKind::X3c)
+    hipLaunchKernelGGL((conv3_bww_x3c_kernel<TX>), r.grid, dim3(512), 0, st, x, dy, slab, d->N, d->Cin, d->Cout, d->D, d->H,
+                       d->W, p.ty_tiles, p.tx_tiles, p.k, r.xbs, r.ybs);
+  else
+    hipLaunchKernelGGL((conv3_bww_x3_kernel<TX>), r.grid, dim3(512), 0, st, x, dy, slab, d->N, d->Cin, d->Cout, d->D, d->H,
+                       d->W, p.ty_tiles, p.tx_tiles, p.nsplit, p.ctiles, p.otiles, r.xbs, r.ybs);
 }
 
-BwwX3Plan plan_bww_x3(int N, int Cin, int Cout, int D, int H, int W) {
-  BwwX3Plan p{};
-  p.tx = bww_x3_tx(H, W);
-  p.ty_tiles = (int)ceil_div(H, 64 / p.tx);
-  p.tx_tiles = (int)ceil_div(W, p.tx);
-  p.ctiles = (int)ceil_div(Cin, 32);
-  p.otiles = (int)ceil_div(Cout, 32);
-  const int64_t ntiles = (int64_t)N * p.ty_tiles * p.tx_tiles * D;
-  const auto rem16 = [](int c) { return c % 32 >= 1 && c % 32 <= 16 ? 1 : 0; };
-  p.k.orem = tuning().tile16 ? rem16(Cout) : 0;
-  p.k.crem = tuning().tile16 ? rem16(Cin) : 0;
-  p.k.of = p.otiles - p.k.orem;
-  p.k.cf = p.ctiles - p.k.crem;
-  p.classes = p.k.orem || p.k.crem;
-  // cost of a tile of each pair class in units of a full 32 x 32 pair (the (16, 16) class is bound by its staging)
-  const double cost[4] = {1.0, 0.5, 0.5, 0.35};
-  const int64_t npairs[4] = {(int64_t)p.k.of * p.k.cf, (int64_t)p.k.of * p.k.crem, (int64_t)p.k.orem * p.k.cf,
-                             (int64_t)p.k.orem * p.k.crem};
-  double units = 0;
-  for (int c = 0; c < 4; ++c) units += cost[c] * (double)npairs[c];
-  const int cus = num_cus();
-  // one workgroup per CU: time ~ residencies x (tiles per split x ~3.5 us + ~10 us of cold start and slab write) + the
-  // slab traffic (written here, read by the reduction)
-  const double slab_us = 2.0 * (double)Cout * Cin * 27 * 4 / 4.0e6;   // per split
-  int64_t cand[32];
-  int nc = 0;
-  for (int64_t ns = 1; ns < ntiles && nc < 20; ns *= 2) cand[nc++] = ns;
-  for (int r = 1; r <= 6; ++r) cand[nc++] = std::max<int64_t>(1, (int64_t)((double)cus * r / units));
-  cand[nc++] = std::max<int64_t>(1, ntiles);
-  std::sort(cand, cand + nc);
-  double best = 1e30;
-  int64_t nsplit = 1;
-  for (int i = 0; i < nc; ++i) {
-    const int64_t ns = std::min<int64_t>(cand[i], std::max<int64_t>(1, ntiles));
-    if (ns * Cout * Cin * 27 * 4 > (256ll << 20) && ns > 1) continue;
-    const double rounds = std::ceil(units * (double)ns / (double)cus - 1e-9);
-    const double cost_us = rounds * ((double)ceil_div(ntiles, ns) * 4.0 + 10.0) + (double)ns * slab_us;
-    if (cost_us < best * 0.97) {
-      best = cost_us;
-      nsplit = ns;
-    }
-  }
-  if (const int force = tuning().bww_nsplit) nsplit = std::min<int64_t>(force, std::max<int64_t>(1, ntiles));
-  p.nsplit = (int)nsplit;
-  int64_t max_ns = nsplit;
-  for (int c = 0; c < 4; ++c) p.k.ns[c] = p.nsplit;
-  if (p.classes) {
-    // the split count of a class is proportional to its cost, so that every workgroup of the launch lasts about equally
-    // long; the rounding of the per-class counts must not spill a workgroup into another residency
-    double base = (double)nsplit;
-    const int64_t budget = (int64_t)std::ceil(units * base / (double)cus - 1e-9) * cus;
-    for (;;) {
-      int wg = 0;
-      max_ns = 1;
-      for (int c = 0; c < 4; ++c) {
-        const int64_t ns = std::max<int64_t>(1, std::min<int64_t>(ntiles, (int64_t)(base * cost[c] + 0.5)));
-        p.k.ns[c] = npairs[c] ? (int)ns : 1;
-        p.k.start[c] = wg;
-        wg += (int)(npairs[c] * p.k.ns[c]);
-        if (npairs[c]) max_ns = std::max<int64_t>(max_ns, ns);
-      }
-      p.class_wgs = wg;
-      if (wg <= budget || base <= 1.0 || tuning().bww_nsplit) break;
-      base *= 0.99;
-    }
-  }
-  p.slab_bytes = (size_t)round_up(max_ns * Cout * Cin * 27 * 4, 256);
-  return p;
-}
-
-int launch_bww_x3(const BwwX3Plan& p, const float* x, const float* dy, float* slab, int N, int Cin, int Cout, int D, int H,
-                  int W, int64_t xbs, int64_t ybs, hipStream_t st) {
-  if (p.classes) {
-    const dim3 grid((unsigned)p.class_wgs);
-#define M355_X3_BWWC(TXV)                                                                                               \
-  hipLaunchKernelGGL((conv3_bww_x3c_kernel<TXV>), grid, dim3(512), 0, st, x, dy, slab, N, Cin, Cout, D, H, W, p.ty_tiles, \
-                     p.tx_tiles, p.k, xbs, ybs);
-    if (p.tx == 32) { M355_X3_BWWC(32) } else if (p.tx == 16) { M355_X3_BWWC(16) } else { M355_X3_BWWC(8) }
-#undef M355_X3_BWWC
-    return M355_OK;
-  }
-  const dim3 grid((unsigned)(p.ctiles * p.otiles * p.nsplit));
-#define M355_X3_BWW(TXV)                                                                                              \
-  hipLaunchKernelGGL((conv3_bww_x3_kernel<TXV>), grid, dim3(512), 0, st, x, dy, slab, N, Cin, Cout, D, H, W, p.ty_tiles, \
-                     p.tx_tiles, p.nsplit, p.ctiles, p.otiles, xbs, ybs);
-  if (p.tx == 32) { M355_X3_BWW(32) } else if (p.tx == 16) { M355_X3_BWW(16) } else { M355_X3_BWW(8) }
-#undef M355_X3_BWW
-  return M355_OK;
+void launch_bww_x3(const BwwRoute& r, const float* x, const float* dy, float* slab, const m355_conv3d_desc* d, hipStream_t st) {
+  if (r.x3.tx == 32) launch_bww_x3_t<32>(r, x, dy, slab, d, st);
+  else if (r.x3.tx == 16) launch_bww_x3_t<16>(r, x, dy, slab, d, st);
+  else launch_bww_x3_t<8>(r, x, dy, slab, d, st);
 }
 
 // ------------------------------------------------------------------------------------ ConvTranspose3d k2 s2, forward

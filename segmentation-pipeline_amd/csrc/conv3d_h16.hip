@@ -832,21 +832,6 @@ __global__ __launch_bounds__(256, 2) void conv3_c4_h16_kernel(
   report_saturation(sat, oflag);
 }
 
-template <typename HT>
-static bool launch_c4_h16(const FwdPlan& p, const HT* x16, int64_t xbs16, const HT* wp, const float* bias, HT* y16, int N,
-                          int mout, int D, int H, int W, int64_t ybs16, hipStream_t st, float* stat, int* oflag) {
-  const int64_t items = (int64_t)p.tz_tiles * p.ty_tiles * p.tx_tiles * p.otiles * N;
-  if (items <= 0 || items >= (1ll << 31)) return false;
-  const dim3 grid((unsigned)items);
-#define M355_C4(NTW)                                                                                                   \
-  hipLaunchKernelGGL((conv3_c4_h16_kernel<NTW, HT>), grid, dim3(256), 0, st, x16, wp, bias, y16, mout, D, H, W, p.mout_pad, \
-                     p.tz_tiles, p.ty_tiles, p.tx_tiles, p.otiles, xbs16, ybs16, stat, \
-                     oflag)
-  if (p.ntw == 4) M355_C4(4); else if (p.ntw == 2) M355_C4(2); else if (p.ntw == 1) M355_C4(1); else return false;
-#undef M355_C4
-  return true;
-}
-
 // ---- M-channels <= 4: the output convolution of a network (Cout = 3: out conv + softmax of cfg2) ----
 // conv3_h16_kernel spends a 32-row MFMA tile on 3 useful rows: 27 taps x 2 k-halves = 54 MFMAs per 32 voxels and chunk, 0.10 ms
 // for 0.02 ms of bytes (round-3 review, item 3).  Here the tap row dy moves from the K side to the M side: row m = 8 dy + o
@@ -1000,63 +985,6 @@ __global__ __launch_bounds__(256, 2) void conv3_cout4_h16_kernel(
 }
 
 template <typename HT>
-static bool launch_cout4_h16(const FwdPlan& p, const HT* x16, int64_t xbs16, const HT* wp, const float* bias, float* y, int N,
-                             int kin, int mout, int D, int H, int W, int64_t ybs, hipStream_t st, int softmax) {
-  const int64_t items = (int64_t)p.tz_tiles * p.ty_tiles * p.tx_tiles * N;
-  if (items <= 0 || items >= (1ll << 31) || p.ntw != 4) return false;
-  hipLaunchKernelGGL((conv3_cout4_h16_kernel<4, HT>), dim3((unsigned)items), dim3(256), 0, st, x16, wp, bias, y,
-                     (int)c8_blocks(kin), mout, D, H, W, p.mout_pad, p.tz_tiles, p.ty_tiles, p.tx_tiles, p.nchunks, xbs16, ybs,
-                     softmax);
-  return true;
-}
-
-template <int NTW, int GX, typename HT>
-static void launch_h16(const FwdPlan& p, const HT* x16, int64_t xbs16, const HT* wp, const float* bias,
-                       const float* add, float* y, float* slab, int N, int kin, int mout, int D, int H, int W,
-                       int64_t ybs, hipStream_t st, float* stat, int* work_counter, bool out16, int softmax,
-                       int* oflag) {
-  const int64_t items = (int64_t)p.tz_tiles * p.ty_tiles * p.tx_tiles * p.otiles * N * p.ksplit;
-  const int64_t slots = tuning().conv_slots ? tuning().conv_slots : (p.nw == 8 ? 1 : (NTW <= 4 ? 2 : 1)) * num_cus();
-  const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(items, slots));
-  const int64_t slab_stride = (int64_t)N * mout * D * H * W;
-  {
-    if (p.oneshot) {  // one item per workgroup
-      const unsigned g1 = (unsigned)items;
-      if (out16 && p.ksplit == 1)
-        hipLaunchKernelGGL((conv3_h16_kernel<NTW, GX, HT, true, 4, true>), dim3(g1), dim3(256), 0, st, x16, wp, bias, add, y,
-                           slab, (int)c8_blocks(kin), mout, D, H, W, p.mout_pad, p.tz_tiles, p.ty_tiles, p.tx_tiles,
-                           p.otiles, p.nchunks, p.ksplit, N, xbs16, ybs, slab_stride, stat, work_counter, tuning().h16_xcd, softmax, tuning().h16_order, oflag);
-      else
-        hipLaunchKernelGGL((conv3_h16_kernel<NTW, GX, HT, false, 4, true>), dim3(g1), dim3(256), 0, st, x16, wp, bias, add, y,
-                           slab, (int)c8_blocks(kin), mout, D, H, W, p.mout_pad, p.tz_tiles, p.ty_tiles, p.tx_tiles,
-                           p.otiles, p.nchunks, p.ksplit, N, xbs16, ybs, slab_stride, stat, work_counter, tuning().h16_xcd, softmax, tuning().h16_order, oflag);
-      return;
-    }
-  }
-  if constexpr (NTW == 2 && GX == 32) {
-    if (p.nw == 8) {  // 8-wave double-buffered variant
-      if (out16 && p.ksplit == 1)
-        hipLaunchKernelGGL((conv3_h16_kernel<NTW, GX, HT, true, 8>), dim3(grid), dim3(512), 0, st, x16, wp, bias, add, y,
-                           slab, (int)c8_blocks(kin), mout, D, H, W, p.mout_pad, p.tz_tiles, p.ty_tiles, p.tx_tiles,
-                           p.otiles, p.nchunks, p.ksplit, N, xbs16, ybs, slab_stride, stat, work_counter, 0, softmax, tuning().h16_order, oflag);
-      else
-        hipLaunchKernelGGL((conv3_h16_kernel<NTW, GX, HT, false, 8>), dim3(grid), dim3(512), 0, st, x16, wp, bias, add, y,
-                           slab, (int)c8_blocks(kin), mout, D, H, W, p.mout_pad, p.tz_tiles, p.ty_tiles, p.tx_tiles,
-                           p.otiles, p.nchunks, p.ksplit, N, xbs16, ybs, slab_stride, stat, work_counter, 0, softmax, tuning().h16_order, oflag);
-      return;
-    }
-  }
-  if (out16 && p.ksplit == 1)
-    hipLaunchKernelGGL((conv3_h16_kernel<NTW, GX, HT, true>), dim3(grid), dim3(256), 0, st, x16, wp, bias, add, y, slab,
-                       (int)c8_blocks(kin), mout, D, H, W, p.mout_pad, p.tz_tiles, p.ty_tiles, p.tx_tiles, p.otiles,
-                       p.nchunks, p.ksplit, N, xbs16, ybs, slab_stride, stat, work_counter, tuning().h16_stagger, softmax, tuning().h16_order, oflag);
-  else
-    hipLaunchKernelGGL((conv3_h16_kernel<NTW, GX, HT, false>), dim3(grid), dim3(256), 0, st, x16, wp, bias, add, y, slab,
-                       (int)c8_blocks(kin), mout, D, H, W, p.mout_pad, p.tz_tiles, p.ty_tiles, p.tx_tiles, p.otiles,
-                       p.nchunks, p.ksplit, N, xbs16, ybs, slab_stride, stat, work_counter, tuning().h16_stagger, softmax, tuning().h16_order, oflag);
-}
-
-template <typename HT>
 static void pack_w3_h16_t(const FwdPlan& p, const float* w, HT* wpb, int Cout_w, int Cin_w, bool transpose, hipStream_t st) {
   const int64_t total = (int64_t)p.nchunks * 27 * 2 * p.mout_pad * 8;
   const int blocks = (int)std::min<int64_t>(ceil_div(total, 256), 2048);
@@ -1072,44 +1000,69 @@ void launch_pack_w3_h16(const FwdPlan& p, int compute, const float* w, void* wp,
     pack_w3_h16_t<_Float16>(p, w, (_Float16*)wp, Cout_w, Cin_w, transpose, st);
 }
 
+// The kernel of a 16-bit route.  The generic kernel's argument list is spelled once: `kern` is the instantiation.
+template <int NTW, int GX, typename HT>
+static void launch_h16(const ConvRoute& r, const ConvCall& c, const HT* x16, const HT* wp, const float* bias, const float* add,
+                       float* slab, float* stat, int* work_counter) {
+  const FwdPlan& p = r.plan;
+  const m355_conv3d_desc* d = c.d;
+  const int N = d->N, D = d->D, H = d->H, W = d->W;
+  const bool out16 = r.out16 && p.ksplit == 1;   // a split plan writes fp32 slabs; its reduction writes the c8 output
+  if (r.kind == ConvKind::H16C4) {
+    if constexpr (GX == 32)
+      hipLaunchKernelGGL((conv3_c4_h16_kernel<NTW, HT>), r.grid, dim3(256), 0, c.st, x16, wp, bias, (HT*)c.out, r.mout, D, H, W,
+                         p.mout_pad, p.tz_tiles, p.ty_tiles, p.tx_tiles, p.otiles, r.in16_bs, r.out_bs, stat, c.oflag);
+    return;
+  }
+  if (r.kind == ConvKind::H16Cout4) {
+    if constexpr (GX == 32 && NTW == 4)
+      hipLaunchKernelGGL((conv3_cout4_h16_kernel<4, HT>), r.grid, dim3(256), 0, c.st, x16, wp, bias, c.out, (int)c8_blocks(r.kin),
+                         r.mout, D, H, W, p.mout_pad, p.tz_tiles, p.ty_tiles, p.tx_tiles, p.nchunks, r.in16_bs, r.out_bs,
+                         r.softmax ? 1 : 0);
+    return;
+  }
+  const auto launch = [&](auto kern) {
+    hipLaunchKernelGGL(kern, r.grid, dim3(r.block), 0, c.st, x16, wp, bias, add, c.out, slab, (int)c8_blocks(r.kin), r.mout, D, H,
+                       W, p.mout_pad, p.tz_tiles, p.ty_tiles, p.tx_tiles, p.otiles, p.nchunks, p.ksplit, N, r.in16_bs, r.out_bs,
+                       (int64_t)N * r.mout * D * H * W, stat, work_counter, r.sched, r.softmax ? 1 : 0, r.order, c.oflag);
+  };
+  with_bool(out16, [&](auto O) {
+    constexpr bool OUT16 = decltype(O)::value;
+    if (r.kind == ConvKind::H16OneShot) return launch(conv3_h16_kernel<NTW, GX, HT, OUT16, 4, true>);   // one item per workgroup
+    if constexpr (NTW == 2 && GX == 32)
+      if (r.kind == ConvKind::H16Queue8) return launch(conv3_h16_kernel<NTW, GX, HT, OUT16, 8>);   // 8-wave double-buffered variant
+    launch(conv3_h16_kernel<NTW, GX, HT, OUT16>);
+  });
+}
+
 template <typename HT>
-static int run_h16_conv_t(const FwdPlan& p, const HT* in16, int64_t in16_bs, const float* w, bool transpose,
-                          int Cout_w, int Cin_w, const float* bias, const float* add, float* out, int N, int kin,
-                          int mout, int D, int H, int W, int64_t out_bs, void* ws, size_t ws_bytes, hipStream_t st,
-                          float* stat, const void* prepacked, bool out16, bool softmax, int* oflag) {
-  // out16: `out` is a c8 tensor of the same 16-bit type (out_bs in elements of it); `add` must be null
+static int launch_h16_conv_t(const ConvRoute& r, const ConvCall& c, int* oflag) {
+  // r.out16: c.out is a c8 tensor of the same 16-bit type (r.out_bs in elements of it)
   // oflag: the overflow word the c8 stores report a saturated fp16 value to (null: saturate silently)
-  M355_REQUIRE(ws_bytes >= p.wp_bytes + p.slab_bytes, M355_EWORKSPACE,
-               "conv3d(16-bit operands): workspace too small (%zu < %zu)", ws_bytes, p.wp_bytes + p.slab_bytes);
-  M355_REQUIRE(((uintptr_t)ws & 15) == 0 && ((uintptr_t)in16 & 15) == 0 && (in16_bs % 8) == 0, M355_EINVALID_ARG,
-               "conv3d(16-bit operands): workspace / c8 input not 16B aligned");
-  M355_REQUIRE((int64_t)D * H * W * 32 < (1ll << 31) && (int64_t)mout * D * H * W < (1ll << 31), M355_EUNSUPPORTED,
-               "conv3d(16-bit operands): volume exceeds the 32-bit offsets of a buffer descriptor");
-  M355_REQUIRE(!stat || p.ksplit == 1 || out16, M355_EINVALID_ARG,
-               "conv3d(16-bit operands): fused statistics of a split-K plan exist only for the c8 output");
-  M355_REQUIRE(!out16 || (!add && ((uintptr_t)out & 15) == 0 && out_bs % 8 == 0), M355_EINVALID_ARG,
-               "conv3d(16-bit operands): a c8 output takes no fused `add` and must be 16B aligned");
-  M355_REQUIRE(!softmax || (mout <= 4 && p.ksplit == 1 && !add && !stat && !out16), M355_EUNSUPPORTED,
-               "conv3d(16-bit operands): the softmax epilogue needs Cout <= 4, an unsplit plan, fp32 output, no add / statistics");
-  HT* wpb = prepacked ? (HT*)prepacked : (HT*)ws;
-  float* slab = (float*)((char*)ws + p.wp_bytes);
+  const FwdPlan& p = r.plan;
+  const m355_conv3d_desc* d = c.d;
+  hipStream_t st = c.st;
+  const int64_t S = (int64_t)d->D * d->H * d->W;
   int* work_counter = queue_state(st);   // per (device, stream): concurrent launches over one model never share it
   M355_REQUIRE(work_counter, M355_ELAUNCH, "conv3d(16-bit operands): could not allocate the work-queue state");
-  if (!prepacked) pack_w3_h16_t<HT>(p, w, wpb, Cout_w, Cin_w, transpose, st);
-  const float* kb = p.ksplit == 1 ? bias : nullptr;
-  const float* ka = p.ksplit == 1 ? add : nullptr;
-  // edge layers with <= 4 K-channels and a c8 output: four taps per k-step (conv3_c4_h16_kernel)
-  if (kin <= 4 && out16 && p.ksplit == 1 && p.gx == 32 && p.nw == 4 && !softmax && !tuning().no_small &&
-      launch_c4_h16<HT>(p, in16, in16_bs, wpb, kb, (HT*)out, N, mout, D, H, W, out_bs, st, stat, oflag))
-    return check_launch("conv3_c4_h16");
-  // output convolution (<= 4 M-channels, fp32 result, optional softmax): tap rows folded onto the MFMA's M side
-  if (mout <= 4 && !out16 && !ka && !stat && p.ksplit == 1 && p.gx == 32 && p.nw == 4 && p.ntw == 4 && p.otiles == 1 &&
-      !tuning().no_small && launch_cout4_h16<HT>(p, in16, in16_bs, wpb, kb, out, N, kin, mout, D, H, W, out_bs, st, softmax ? 1 : 0))
-    return check_launch("conv3_cout4_h16");
-#define M355_H16_CASE(NTW, GX)                                                                               \
-  if (p.ntw == NTW && p.gx == GX) {                                                                          \
-    launch_h16<NTW, GX, HT>(p, in16, in16_bs, wpb, kb, ka, out, slab, N, kin, mout, D, H, W, out_bs, st,       \
-                            p.ksplit == 1 ? stat : nullptr, work_counter, out16, softmax ? 1 : 0, oflag);                                                        \
+  const HT* in16 = (const HT*)c.in16;
+  if (r.aux & AUX_PACK_IN) {
+    // fp32 NCDHW input: one conversion pass into the c8 layout (the model path hands over c8 tensors that its
+    // normalisation / pooling passes wrote, m355_conv3d_fwd_h16)
+    void* stage = (char*)c.ws + r.stage_off;
+    if (int rc = launch_pack_act16(c.in, stage, d->N, r.kin, S, r.in_bs, r.in16_bs, d->compute, st)) return rc;
+    in16 = (const HT*)stage;
+  }
+  HT* wpb = r.prepacked ? (HT*)c.w : (HT*)c.ws;
+  float* slab = (float*)((char*)c.ws + r.slab_off);
+  if (r.aux & AUX_PACK_W) pack_w3_h16_t<HT>(p, c.w, wpb, d->Cout, d->Cin, r.transpose, st);
+  const bool split = (r.aux & AUX_SPLITK) != 0;   // bias, residual and statistics then come from the reduction pass
+  ConvCall k = c;
+  k.oflag = oflag;
+#define M355_H16_CASE(NTW, GX)                                                                                   \
+  if (p.ntw == NTW && p.gx == GX) {                                                                              \
+    launch_h16<NTW, GX, HT>(r, k, in16, wpb, split ? nullptr : c.bias, split ? nullptr : c.add, slab,            \
+                            split ? nullptr : c.stat, work_counter);                                             \
   } else
   M355_H16_CASE(4, 32) M355_H16_CASE(2, 32) M355_H16_CASE(1, 32)
   M355_H16_CASE(4, 16) M355_H16_CASE(2, 16) M355_H16_CASE(1, 16)
@@ -1118,30 +1071,20 @@ static int run_h16_conv_t(const FwdPlan& p, const HT* in16, int64_t in16_bs, con
     return M355_EUNSUPPORTED;
   }
 #undef M355_H16_CASE
-  if (p.ksplit > 1 && out16) {
-    const int64_t S = (int64_t)D * H * W;
-    dim3 grid((unsigned)splitk_c8_slots(S), (unsigned)c8_blocks(mout), (unsigned)N);
-    hipLaunchKernelGGL(splitk_reduce_c8_kernel<HT>, grid, dim3(256), 0, st, slab, bias, (HT*)out, mout, S, p.ksplit,
-                       (int64_t)N * mout * S, out_bs, stat, oflag);
-  } else if (p.ksplit > 1) {
-    const int64_t S = (int64_t)D * H * W;
-    const int64_t total = (int64_t)N * mout * S;
-    const int blocks = (int)std::min<int64_t>(ceil_div(total, 256), 4096);
-    hipLaunchKernelGGL(splitk_reduce_kernel, dim3(blocks), dim3(256), 0, st, slab, bias, add, out, N, mout, S,
-                       p.ksplit, total, out_bs);
-  }
+  if (r.kind == ConvKind::H16C4) return check_launch("conv3_c4_h16");
+  if (r.kind == ConvKind::H16Cout4) return check_launch("conv3_cout4_h16");
+  if (split && r.out16)
+    hipLaunchKernelGGL(splitk_reduce_c8_kernel<HT>, r.reduce_grid, dim3(256), 0, st, slab, c.bias, (HT*)c.out, r.mout, S,
+                       p.ksplit, (int64_t)d->N * r.mout * S, r.out_bs, c.stat, oflag);
+  else if (split)
+    hipLaunchKernelGGL(splitk_reduce_kernel, r.reduce_grid, dim3(256), 0, st, slab, c.bias, c.add, c.out, d->N, r.mout, S,
+                       p.ksplit, (int64_t)d->N * r.mout * S, r.out_bs);
   return check_launch("conv3d_h16");
 }
 
-int run_h16_conv(const FwdPlan& p, int compute, const void* in16, int64_t in16_bs, const float* w, bool transpose,
-                 int Cout_w, int Cin_w, const float* bias, const float* add, float* out, int N, int kin, int mout,
-                 int D, int H, int W, int64_t out_bs, void* ws, size_t ws_bytes, hipStream_t st, float* stat,
-                 const void* prepacked, bool out16, bool softmax, int* oflag) {
-  if (compute == M355_COMPUTE_BF16)
-    return run_h16_conv_t<__bf16>(p, (const __bf16*)in16, in16_bs, w, transpose, Cout_w, Cin_w, bias, add, out, N, kin,
-                                  mout, D, H, W, out_bs, ws, ws_bytes, st, stat, prepacked, out16, softmax, nullptr);
-  return run_h16_conv_t<_Float16>(p, (const _Float16*)in16, in16_bs, w, transpose, Cout_w, Cin_w, bias, add, out, N,
-                                  kin, mout, D, H, W, out_bs, ws, ws_bytes, st, stat, prepacked, out16, softmax, oflag);
+int launch_h16_conv(const ConvRoute& r, const ConvCall& c) {
+  if (c.d->compute == M355_COMPUTE_BF16) return launch_h16_conv_t<__bf16>(r, c, nullptr);   // bf16 neither clamps nor reports
+  return launch_h16_conv_t<_Float16>(r, c, c.oflag);
 }
 
 
@@ -1559,39 +1502,25 @@ __global__ __launch_bounds__(256, 2) void conv3_bww_c8_small_kernel(
   }
 }
 
-int launch_bww_c8_small(int compute, const void* x16, const void* dy16, float* slab, int N, int Cin, int Cout, int D, int H,
-                        int W, int nsplit, int64_t xbs16, int64_t ybs16, hipStream_t st) {
-  const int swap = Cin <= 4 ? 0 : 1;
-  const void* P = swap ? x16 : dy16;
-  const void* Q = swap ? dy16 : x16;
-  const int CP = swap ? Cin : Cout, CQ = swap ? Cout : Cin;
-  const int64_t pbs = swap ? xbs16 : ybs16, qbs = swap ? ybs16 : xbs16;
-  const int ptiles = (int)ceil_div(CP, 32);
-  const int tz = (int)ceil_div(D, 2), ty = (int)ceil_div(H, 4), tx = (int)ceil_div(W, 32);
-  const dim3 grid((unsigned)(ptiles * nsplit));
-  if (compute == M355_COMPUTE_BF16)
-    hipLaunchKernelGGL(conv3_bww_c8_small_kernel<__bf16>, grid, dim3(256), 0, st, (const __bf16*)P, (const __bf16*)Q, slab, N,
-                       (int)c8_blocks(CP), CP, CQ, D, H, W, tz, ty, tx, nsplit, ptiles, pbs, qbs, swap, Cin, Cout);
-  else
-    hipLaunchKernelGGL(conv3_bww_c8_small_kernel<_Float16>, grid, dim3(256), 0, st, (const _Float16*)P, (const _Float16*)Q,
-                       slab, N, (int)c8_blocks(CP), CP, CQ, D, H, W, tz, ty, tx, nsplit, ptiles, pbs, qbs, swap, Cin, Cout);
-  return check_launch("conv3_bww_c8_small");
-}
-
-int launch_bww_c8(int compute, const void* x16, const void* dy16, float* slab, int N, int Cin, int Cout, int D, int H,
-                  int W, int nsplit, int64_t xbs16, int64_t ybs16, hipStream_t st) {
-  const int CBin = (int)c8_blocks(Cin), CBout = (int)c8_blocks(Cout);
-  const int ctiles = (int)ceil_div(Cin, 32), otiles = (int)ceil_div(Cout, 32);
-  const int tz = (int)ceil_div(D, 2), ty = (int)ceil_div(H, 4), tx = (int)ceil_div(W, 32);
-  const dim3 grid((unsigned)(ctiles * otiles * nsplit));
-  if (compute == M355_COMPUTE_BF16)
-    hipLaunchKernelGGL(conv3_bww_c8_kernel<__bf16>, grid, dim3(256), 0, st, (const __bf16*)x16, (const __bf16*)dy16, slab,
-                       N, CBin, CBout, Cin, Cout, D, H, W, tz, ty, tx, nsplit, ctiles, otiles, xbs16, ybs16);
-  else
-    hipLaunchKernelGGL(conv3_bww_c8_kernel<_Float16>, grid, dim3(256), 0, st, (const _Float16*)x16,
-                       (const _Float16*)dy16, slab, N, CBin, CBout, Cin, Cout, D, H, W, tz, ty, tx, nsplit, ctiles, otiles,
-                       xbs16, ybs16);
-  return check_launch("conv3_bww_c8");
+// weight gradient from c8 operands (tile 2 x 4 x 32 voxels); slab[split][27][Cout][Cin], summed by slab_reduce_t_kernel.
+// C8Small, an edge layer (Cin <= 4 or Cout <= 4): narrow channel and tap share the MFMA column
+void launch_bww_c8(const BwwRoute& r, const void* x16, const void* dy16, float* slab, const m355_conv3d_desc* d, hipStream_t st) {
+  const int Cin = d->Cin, Cout = d->Cout;
+  const int tz = (int)ceil_div(d->D, 2), ty = (int)ceil_div(d->H, 4), tx = (int)ceil_div(d->W, 32);
+  with_h16(d->compute, [&](auto T) {
+    typedef typename decltype(T)::type HT;
+    if (r.kind == BwwKind::C8Small) {
+      const int swap = Cin <= 4 ? 0 : 1;
+      const int CP = swap ? Cin : Cout, CQ = swap ? Cout : Cin;
+      hipLaunchKernelGGL(conv3_bww_c8_small_kernel<HT>, r.grid, dim3(256), 0, st, (const HT*)(swap ? x16 : dy16),
+                         (const HT*)(swap ? dy16 : x16), slab, d->N, (int)c8_blocks(CP), CP, CQ, d->D, d->H, d->W, tz, ty, tx,
+                         r.nsplit, (int)ceil_div(CP, 32), swap ? r.xbs : r.ybs, swap ? r.ybs : r.xbs, swap, Cin, Cout);
+    } else {
+      hipLaunchKernelGGL(conv3_bww_c8_kernel<HT>, r.grid, dim3(256), 0, st, (const HT*)x16, (const HT*)dy16, slab, d->N,
+                         (int)c8_blocks(Cin), (int)c8_blocks(Cout), Cin, Cout, d->D, d->H, d->W, tz, ty, tx, r.nsplit,
+                         (int)ceil_div(Cin, 32), (int)ceil_div(Cout, 32), r.xbs, r.ybs);
+    }
+  });
 }
 
 #ifdef M355_H16_STAMPS

@@ -300,6 +300,24 @@ class RawOps:
         self._chk(self.lib.m355_conv3d_plan(C.byref(d), which, out), "conv3d_plan")
         return tuple(out)
 
+    def conv_launch_plan(self, entry, x_shape, Cout, compute=0, flags=0, tensors=(), strides=(0, 0), workspace_bytes=1 << 40,
+                         xbs=0, ybs=0, k=3, stride=1, pad=1):
+        """the twelve numbers of m355_conv3d_launch_plan (variant, grid x / y / z, block, 16-row grid x / z, auxiliary launches,
+        workspace bytes, reduction grid, two workspace offsets) for a call of entry point _lib.CONV_ENTRIES[entry].  tensors:
+        up to seven Slot / torch tensor / integer address / None in the query's pointer order (first operand, w | second
+        operand, bias | fp32 dy, add, output, statistics | dbias, workspace); missing first operand, w, output and workspace
+        default to aligned dummies"""
+        addr = lambda t: 0 if t is None else (t if isinstance(t, int) else (t.ptr if isinstance(t, Slot) else t.data_ptr()))   # noqa: E731
+        ptrs = [addr(t) for t in tensors] + [0] * (7 - len(tensors))
+        for i in (0, 1, 4, 6):
+            ptrs[i] = ptrs[i] or 4096 * (i + 1)
+        d = self.conv_desc(x_shape, Cout, k, stride, pad, xbs=xbs, ybs=ybs, compute=compute)
+        d.flags = flags
+        out = (C.c_int64 * 12)()
+        self._chk(self.lib.m355_conv3d_launch_plan(entry, C.byref(d), (C.c_int64 * 2)(*strides), (C.c_uint64 * 7)(*ptrs),
+                                                   workspace_bytes, out), "conv3d_launch_plan")
+        return tuple(out)
+
     def convt_plan(self, x_shape, Cout, k=2, stride=2, pad=0, out_pad=0, compute=0, which=0, xbs=0, ybs=0, y_side=None):
         """(kernel family, three numbers of its launch) of a conv-transpose call (m355_conv_transpose3d_plan; which 0..2 the
         fp32 entry points, 3..5 the c8 ones).  y_side: the y / dy tensor or Slot the call would get (None: aligned)"""

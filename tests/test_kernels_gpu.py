@@ -86,7 +86,7 @@ def test_conv3d_f32x3_fwd_bwd(hip, oracle, case, tuning):
     products are below 2^-24 of each product; the split kernels add six partial products per 16 k-values to the accumulator
     where the fp32 MFMA adds eight)."""
     N, Ci, Co, D, H, W = case
-    tuning(M355_F32X3_EDGE=1)   # (3..7 K-channels on the split kernel too: opt-in, see x3_layer in conv3d_host.hip)
+    tuning(M355_F32X3_EDGE=1)   # (3..7 K-channels on the split kernel too: opt-in, see x3_layer in conv3d_route.hpp)
     plan = hip.conv_plan((N, Ci, D, H, W), Co, compute=X3)
     assert plan[0] == 7, f"expected conv3_f32x3_kernel for {case}, got family {plan}"
     # (a single z plane has no ring to walk: the weight gradient stays on the fp32 MFMA kernel)

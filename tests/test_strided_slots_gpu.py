@@ -23,12 +23,12 @@ channel blocks of 16-byte items in a 256-byte aligned allocation.
 
 Host / kernel branches on a stride or a pointer (file:line, condition, who takes the fast | the slow side):
   conv3d.hip:792    per sample: row vector stores need yn, an 16-B aligned, W % 4 == 0   test_conv3d_small_cout[aligned W=40 | odd, offset*, W=33]
-  conv3d.hip:1711   dbias VEC: S % 4, ybs % 4, dy 16-B aligned                           test_conv3d_bwd_weight[aligned S%4==0 cases | odd, offset*]
-  conv3d.hip:2111   (the host side of the same choice)                                  as above
-  conv3d.hip:2035   split weight gradient requires 4-byte aligned x / dy                every fp32 tensor is (no other side to take)
-  conv3d.hip:2013   bww float4 rows: W % 4, xbs % 4, x 16-B aligned (gen2 | gen1)        test_conv3d_bwd_weight[aligned W=36 family 9 | odd, offset* family 9]
-  conv3d.hip:2014   gen2 needs dy 4-byte aligned                                        always true for fp32 tensors
-  conv3d_host.hip:691/699/800, conv3d_h16.hip:1084/1090   c8 REQUIREs (16 B, % 8): act16_pack / _unpack, conv3d_bwd_weight_h16 / _c8,
+  conv3d.hip:1710   dbias VEC: S % 4, ybs % 4, dy 16-B aligned                           test_conv3d_bwd_weight[aligned S%4==0 cases | odd, offset*]
+  conv3d.hip:2072   (the host side of the same choice, launch_dbias)                    as above
+  conv3d_route.hpp:955   split weight gradient requires 4-byte aligned x / dy (check_bww)   every fp32 tensor is (no other side to take)
+  conv3d_route.hpp:911   bww float4 rows (route_bww): W % 4, xbs % 4, x 16-B aligned (gen2 | gen1)   test_conv3d_bwd_weight[aligned W=36 family 9 | odd, offset* family 9]
+  conv3d_route.hpp:912   gen2 needs dy 4-byte aligned                                   always true for fp32 tensors
+  conv3d_host.hip:159/167, conv3d_route.hpp:967 (check_bww) / 741 / 747 (check_conv)   c8 REQUIREs (16 B, % 8): act16_pack / _unpack, conv3d_bwd_weight_h16 / _c8,
                     the conv3d h16 forward / data gradient                               test_c8_conv3d, test_act16_pack_unpack | test_c8_rejects_misaligned_slots (each by name)
   convt.hip convt_y_side_ok -> route_convt   k2 s2 forward: ConvtKind MfmaF32 / X3 needs ybs % 2 == 0, y 8-B aligned, else Direct
                                                                                         test_conv_transpose3d[aligned, offset2 | odd (ybs odd), offset1, n1]

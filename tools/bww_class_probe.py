@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Relative cost of the weight-gradient pair classes (full 32 x 32 pair on 32x32x2 MFMAs vs the 16-channel
 sub-tile classes on 16x16x4): one pair per launch, same forced split count, 96^3 / 48^3 / 24^3 volumes.  The ratios
-calibrate the per-class split counts of plan_bww (csrc/conv3d_host.hip)."""
+calibrate the per-class split counts of plan_bww (csrc/conv3d_route.hpp)."""
 import os
 import sys
 import torch

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Every host answer of the conv3d route resolver (csrc/conv3d_host.hip) for a fixed descriptor list under a fixed list of
+"""Every host answer of the conv3d route resolver (csrc/conv3d_route.hpp) for a fixed descriptor list under a fixed list of
 tuning sets: one line per (tuning set, descriptor) with m355_conv3d_plan for which = 0, 1, 2, the workspace queries, the
 packed-weight sizes, the statistics slots and the softmax answer; then the line count and a SHA-256 of the lines.
 
@@ -22,7 +22,13 @@ the call would launch on the dummy pointers -- so this hash too compares with a 
 "routes": m355_resample_plan for valid shapes, strides and pointer alignments, both sides of every grid cap and of the
 trilinear forward's kernel conditions.
 
-usage: python tools/conv_routes.py [--convt | --norm | --resample] [--hash-only] [--jobs N] > routes.txt"""
+--launch: the conv table once more ("queries": the default mode's lines and hash) and, "routes", m355_conv3d_launch_plan (csrc/
+conv3d_route.hpp) for the ten launching entry points: over a thinned descriptor list with every guard volume, and over the
+shapes of tests/test_conv_launch_plans_gpu.py with the facts a call adds to its descriptor varied one at a time -- each
+pointer at +4 and +8 bytes, odd and padded batch strides, add / statistics / dbias present, the softmax and packed-weights
+flags, each side of the 65535-sample limit of the pack behind the plain weight gradient -- under every tuning set.
+
+usage: python tools/conv_routes.py [--convt | --norm | --resample | --launch] [--hash-only] [--jobs N] > routes.txt"""
 import argparse
 import ctypes as C
 import hashlib
@@ -82,8 +88,12 @@ def run_convt_set(idx):
         del os.environ[k]
     os.environ.update(env)
     from segmentation_pipeline_amd import _lib
-    L = _lib.lib()
-    _lib.reload_tuning()
+    L = C.CDLL(_lib.LIB_PATH)   # (not _lib.lib(): that insists on every symbol of this tree's header)
+    for name in ("m355_conv_transpose3d_workspace", "m355_conv_transpose3d_h16_bwd_supported",
+                 "m355_conv_transpose3d_h16_bwd_workspace", "m355_conv_transpose3d_plan"):
+        if getattr(L, name, None) is not None:
+            getattr(L, name).restype, getattr(L, name).argtypes = _lib.SIGNATURES[name]
+    L.m355_reload_tuning()
     plan = getattr(L, "m355_conv_transpose3d_plan", None)   # None: a library from before the plan query
     tag = ",".join(f"{k[5:]}={v}" for k, v in sorted(env.items())) or "default"
     d = _lib.ConvDesc()
@@ -280,17 +290,32 @@ TUNING_SETS = [
 TUNING_SETS = [dict(t) for t in dict.fromkeys(tuple(sorted(t.items())) for t in TUNING_SETS)]   # distinct, in order
 
 
-def run_set(args):
-    """All lines of one tuning set (a process of its own: the library reads the environment)."""
-    idx = args
+QUERIES = ["m355_conv3d_plan", "m355_conv3d_fwd_workspace", "m355_conv3d_bwd_data_workspace", "m355_conv3d_bwd_weight_workspace",
+           "m355_conv3d_h16_workspace", "m355_conv3d_packed_bytes", "m355_conv3d_bwd_weight_h16_workspace",
+           "m355_conv3d_bwd_weight_c8_workspace", "m355_conv3d_stats_slots", "m355_conv3d_stats_slots_c8", "m355_conv3d_fuses_softmax",
+           "m355_reload_tuning", "m355_conv3d_launch_plan"]
+
+
+def open_set(idx):
+    """(library with the tuning set's environment read, the set's tag): a process of its own per set, the library reads the
+    environment.  (Not _lib.lib(): that insists on every symbol, and a parent library has no m355_conv3d_launch_plan.)"""
     env = TUNING_SETS[idx]
     for k in [k for k in os.environ if k.startswith("M355_") and k != "M355_LIB_PATH"]:
         del os.environ[k]
     os.environ.update(env)
     from segmentation_pipeline_amd import _lib
-    L = _lib.lib()
-    _lib.reload_tuning()
-    tag = ",".join(f"{k[5:]}={v}" for k, v in sorted(env.items())) or "default"
+    L = C.CDLL(_lib.LIB_PATH)
+    for name in QUERIES:
+        if getattr(L, name, None) is not None:
+            getattr(L, name).restype, getattr(L, name).argtypes = _lib.SIGNATURES[name]
+    L.m355_reload_tuning()
+    return L, ",".join(f"{k[5:]}={v}" for k, v in sorted(env.items())) or "default"
+
+
+def run_set(idx):
+    """All lines of one tuning set."""
+    from segmentation_pipeline_amd import _lib
+    L, tag = open_set(idx)
     d = _lib.ConvDesc()
     ref = C.byref(d)
     out4 = (C.c_int32 * 4)()
@@ -312,6 +337,94 @@ def run_set(args):
     return idx, len(lines), text
 
 
+# ---- --launch ----
+LAUNCH_CHANNELS = [1, 3, 4, 8, 24, 32, 40, 80, 120]
+# tests/test_conv_launch_plans_gpu.py: volumes and (Cin, Cout)
+LAUNCH_TEST_VOLUMES = [(6, 9, 36), (5, 7, 33), (8, 4, 32)]
+LAUNCH_TEST_CHANNELS = [(3, 32), (32, 4), (40, 24), (32, 32), (8, 40)]
+NPTR = 7   # first operand, w | second operand, bias | fp32 dy, add, output, statistics | dbias, workspace
+
+
+def launch_descriptors():
+    """the thinned list: (N, Cin, Cout, D, H, W, k, stride, pad, compute)"""
+    for vol, ci, co, n, comp in itertools.product(VOLUMES, LAUNCH_CHANNELS, LAUNCH_CHANNELS, (1, 2), range(4)):
+        yield (n, ci, co) + vol + (3, 1, 1, comp)
+    small = [c for c in LAUNCH_CHANNELS if c <= 8]
+    for vol, ci, co, n, comp in itertools.product(GUARD_VOLUMES, small, small, (1, 2), range(4)):
+        yield (n, ci, co) + vol + (3, 1, 1, comp)
+    for ksp, vol, ci, co, comp in itertools.product(NON_K3, VOLUMES[:3], LAUNCH_CHANNELS, LAUNCH_CHANNELS, range(4)):
+        yield (2, ci, co) + vol + ksp + (comp,)
+
+
+def launch_variations(cin, cout, S):
+    """(label, flags, x / y batch stride of the descriptor, stride arguments, pointers) of one fact moved at a time"""
+    base = [(i + 1) << 20 for i in range(NPTR)]
+    mandatory = [p if i in (0, 1, 4, 6) else 0 for i, p in enumerate(base)]
+    yield "plain", 0, (0, 0), (0, 0), mandatory
+    for i in range(NPTR):
+        for off in (4, 8):
+            yield f"ptr{i}+{off}", 0, (0, 0), (0, 0), [p + (off if j == i else 0) for j, p in enumerate(base)]
+    for present in range(1, 8):   # bit 0 add, bit 1 statistics | dbias, bit 2 bias | fp32 dy
+        yield f"opt{present}", 0, (0, 0), (0, 0), [p if i in (0, 1, 4, 6) or (present >> {3: 0, 5: 1, 2: 2}[i]) & 1 else 0
+                                                     for i, p in enumerate(base)]
+    for pad in (1, 2, 4, 8):      # odd, even, float4 and c8-item padded batch strides
+        yield f"bs+{pad}", 0, ((cin + 8) * S + pad, (cout + 8) * S + pad), (8 * (cin // 8 + 2) * S + pad, 8 * (cout // 8 + 2) * S + pad), mandatory
+    yield "softmax", 2, (0, 0), (0, 0), mandatory
+    yield "packed", 1, (0, 0), (0, 0), mandatory
+    yield "softmax+add", 2, (0, 0), (0, 0), [p if i != 5 else 0 for i, p in enumerate(base)]
+
+
+def run_launch_set(idx):
+    """(index, line count of the queries, their text, line count of the routes, their text) of one tuning set"""
+    from segmentation_pipeline_amd import _lib
+    _, count, qtext = run_set(idx)
+    L, tag = open_set(idx)
+    plan = getattr(L, "m355_conv3d_launch_plan", None)
+    if plan is None:
+        return idx, count, qtext, 0, None
+    d = _lib.ConvDesc()
+    ref = C.byref(d)
+    out = (C.c_int64 * 12)()
+    lines = []
+    bs0 = (C.c_int64 * 2)(0, 0)
+    ptr0 = (C.c_uint64 * NPTR)(*[(i + 1) << 20 if i in (0, 1, 4, 6) else 0 for i in range(NPTR)])
+    for (d.N, d.Cin, d.Cout, d.D, d.H, d.W, d.k, d.stride, d.pad, d.compute) in launch_descriptors():
+        f = [tag, f"N{d.N} {d.Cin}->{d.Cout} {d.D}x{d.H}x{d.W} k{d.k}s{d.stride}p{d.pad} c{d.compute}"]
+        for entry in range(10):
+            rc = plan(entry, ref, bs0, ptr0, 1 << 62, out)
+            f.append(f"e{entry}={rc}" + (":" + "/".join(str(v) for v in out) if rc == 0 else ""))
+        lines.append(" ".join(f))
+    d.k, d.stride, d.pad = 3, 1, 1
+    shapes = [(n, ci, co) + vol for n in (2,) for vol in LAUNCH_TEST_VOLUMES for ci, co in LAUNCH_TEST_CHANNELS]
+    shapes += [(n, 8, 8, 2, 4, 8) for n in (65535, 65536)]
+    for (d.N, d.Cin, d.Cout, d.D, d.H, d.W), d.compute in itertools.product(shapes, range(4)):
+        S = d.D * d.H * d.W
+        for label, d.flags, (d.x_batch_stride, d.y_batch_stride), bs, ptrs in launch_variations(d.Cin, d.Cout, S):
+            f = [tag, f"N{d.N} {d.Cin}->{d.Cout} {d.D}x{d.H}x{d.W} c{d.compute} {label}"]
+            for entry in range(10):
+                rc = plan(entry, ref, (C.c_int64 * 2)(*bs), (C.c_uint64 * NPTR)(*ptrs), 1 << 62, out)
+                f.append(f"e{entry}={rc}" + (":" + "/".join(str(v) for v in out) if rc == 0 else ""))
+            lines.append(" ".join(f))
+        d.flags, d.x_batch_stride, d.y_batch_stride = 0, 0, 0
+    return idx, count, qtext, len(lines), "\n".join(lines) + "\n"
+
+
+def launch_main(a):
+    queries, routes, n, m, have_plan = hashlib.sha256(), hashlib.sha256(), 0, 0, True
+    with multiprocessing.get_context("spawn").Pool(a.jobs, maxtasksperchild=1) as pool:
+        for idx, count, qtext, rcount, text in pool.imap(run_launch_set, range(len(TUNING_SETS))):
+            have_plan = have_plan and text is not None
+            if a.hash_only:
+                print(f"set {idx:2d} {count} queries {hashlib.sha256(qtext.encode()).hexdigest()}"
+                      + (f" {rcount} routes {hashlib.sha256(text.encode()).hexdigest()}" if text else ""), flush=True)
+            else:
+                sys.stdout.write(text or qtext)
+            queries.update(qtext.encode())
+            routes.update((text or "").encode())
+            n, m = n + count, m + rcount
+    print(f"lines {n} queries sha256 {queries.hexdigest()}" + (f" routes ({m} lines) sha256 {routes.hexdigest()}" if have_plan else ""))
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--hash-only", action="store_true", help="print no lines, only one hash per tuning set and the total")
@@ -319,7 +432,10 @@ def main():
     ap.add_argument("--convt", action="store_true", help="the conv-transpose routes (two hashes: queries, routes)")
     ap.add_argument("--norm", action="store_true", help="the normalisation plans (two hashes: queries, routes)")
     ap.add_argument("--resample", action="store_true", help="the factor-2 resampling family (two hashes: queries, routes)")
+    ap.add_argument("--launch", action="store_true", help="the conv launch plans (two hashes: queries = the default table, routes)")
     a = ap.parse_args()
+    if a.launch:
+        return launch_main(a)
     if a.resample:
         return resample_main(a)
     if a.convt:
