@@ -588,6 +588,46 @@ int m355_upsample_trilinear2x_bwd(const float* dy, float* dx, int32_t N, int32_t
                                   int32_t D, int32_t H, int32_t W,
                                   int64_t dy_batch_stride, int64_t dx_batch_stride, void* stream);
 
+/* nn.Upsample(scale_factor=2) in its other two conventions (csrc/upsample.hip), with the argument lists of their
+ * m355_upsample_trilinear2x_* counterparts: N, C, D, H, W describe the INPUT (any positive size, odd and 1 included),
+ * the output is 2x; batch strides in elements, 0 = dense; the output may be a channel slice of a wider buffer and only
+ * 4-byte aligned (16-byte rows are a variant the host picks, see m355_upsample2x_plan).
+ *   nearest   mode='nearest' (= 'nearest-exact' at factor 2): y[2z+a, 2y+b, 2x+c] = x[z, y, x].  The forward moves bits
+ *             (NaN payloads, signed zeros, infinities and denormals come out unchanged); the backward is the sum of the
+ *             block's eight gradients in gather form, deterministic.
+ *   hp        mode='trilinear', align_corners=False (half-pixel): per axis y[2i] = 0.25 x[max(i-1, 0)] + 0.75 x[i],
+ *             y[2i+1] = 0.75 x[i] + 0.25 x[min(i+1, n-1)]; the backward is the gather-form transpose (4 taps per axis,
+ *             the tap past an edge folded onto the border output), fp32 sums, deterministic. */
+int m355_upsample_nearest2x_fwd(const float* x, float* y, int32_t N, int32_t C, int32_t D, int32_t H, int32_t W,
+                                int64_t x_batch_stride, int64_t y_batch_stride, void* stream);
+int m355_upsample_nearest2x_bwd(const float* dy, float* dx, int32_t N, int32_t C, int32_t D, int32_t H, int32_t W,
+                                int64_t dy_batch_stride, int64_t dx_batch_stride, void* stream);
+int m355_upsample_trilinear2x_hp_fwd(const float* x, float* y, int32_t N, int32_t C, int32_t D, int32_t H, int32_t W,
+                                     int64_t x_batch_stride, int64_t y_batch_stride, void* stream);
+int m355_upsample_trilinear2x_hp_bwd(const float* dy, float* dx, int32_t N, int32_t C, int32_t D, int32_t H, int32_t W,
+                                     int64_t dy_batch_stride, int64_t dx_batch_stride, void* stream);
+/* The same c8 -> c8 (compute: M355_COMPUTE_BF16 or M355_COMPUTE_F16; 16-byte aligned items): fp32 arithmetic, one
+ * rounding.  The nearest forward copies items.  The backward kernels round with saturation in fp16 and OR bit 0 into the
+ * overflow word (m355_overflow_flag_set) when a sum left the fp16 range. */
+int m355_upsample_nearest2x_fwd_h16(const void* x16, void* y16, int32_t N, int32_t C, int32_t D, int32_t H, int32_t W,
+                                    int64_t x16_batch_stride, int64_t y16_batch_stride, int32_t compute, void* stream);
+int m355_upsample_nearest2x_bwd_h16(const void* dy16, void* dx16, int32_t N, int32_t C, int32_t D, int32_t H, int32_t W,
+                                    int64_t dy16_batch_stride, int64_t dx16_batch_stride, int32_t compute, void* stream);
+int m355_upsample_trilinear2x_hp_fwd_h16(const void* x16, void* y16, int32_t N, int32_t C, int32_t D, int32_t H, int32_t W,
+                                         int64_t x16_batch_stride, int64_t y16_batch_stride, int32_t compute,
+                                         void* stream);
+int m355_upsample_trilinear2x_hp_bwd_h16(const void* dy16, void* dx16, int32_t N, int32_t C, int32_t D, int32_t H,
+                                         int32_t W, int64_t dy16_batch_stride, int64_t dx16_batch_stride, int32_t compute,
+                                         void* stream);
+/* Introspection, as m355_resample_plan, for the eight entry points above: mode 0 nearest, 1 hp; direction 0 forward,
+ * 1 backward; c8 0 fp32, 1 the _h16 one.  strides3 / pointers4: the two tensors in the entry point's argument order (the
+ * rest is ignored).  Runs the entry point's argument checks and returns its code; on M355_OK out8 as there:
+ *   out8[0] = 0 scalar / the only kernel, 1 vector (fp32: float4 stores / loads of the 2x tensor's rows; the backward also
+ *             stores float2);   out8[1..3] = grid;   out8[4] = 0;   out8[5..7] = the batch strides, dense ones resolved.
+ * Pure host function, launches nothing. */
+int m355_upsample2x_plan(int32_t mode, int32_t direction, int32_t c8, int32_t N, int32_t C, int32_t D, int32_t H, int32_t W,
+                         const int64_t* strides3, const uint64_t* pointers4, int32_t compute, int64_t* out8);
+
 /* Introspection, as m355_norm_plan: how an entry point of the factor-2 resampling family serves a call.  op:
  *   0 avgpool3d_2x_fwd   1 avgpool3d_2x_bwd   2 avgpool3d_2x_bwd_add   3 upsample_trilinear2x_fwd   4 upsample_trilinear2x_bwd
  *   5 space_to_depth2    6 depth_to_space2    7 maxpool3d_2x_fwd       8 maxpool3d_2x_bwd

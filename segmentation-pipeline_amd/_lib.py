@@ -218,6 +218,16 @@ SIGNATURES = {
     "m355_maxpool3d_2x_bwd_h16": (C.c_int, [_P, _P, _P, _P, _i32, _i32, _i32, _i32, _i32, _i64, _i64, _i64, _i32, _P]),
     "m355_upsample_trilinear2x_fwd": (C.c_int, [_P, _P, _i32, _i32, _i32, _i32, _i32, _i64, _i64, _P]),
     "m355_upsample_trilinear2x_bwd": (C.c_int, [_P, _P, _i32, _i32, _i32, _i32, _i32, _i64, _i64, _P]),
+    "m355_upsample_nearest2x_fwd": (C.c_int, [_P, _P, _i32, _i32, _i32, _i32, _i32, _i64, _i64, _P]),
+    "m355_upsample_nearest2x_bwd": (C.c_int, [_P, _P, _i32, _i32, _i32, _i32, _i32, _i64, _i64, _P]),
+    "m355_upsample_trilinear2x_hp_fwd": (C.c_int, [_P, _P, _i32, _i32, _i32, _i32, _i32, _i64, _i64, _P]),
+    "m355_upsample_trilinear2x_hp_bwd": (C.c_int, [_P, _P, _i32, _i32, _i32, _i32, _i32, _i64, _i64, _P]),
+    "m355_upsample_nearest2x_fwd_h16": (C.c_int, [_P, _P, _i32, _i32, _i32, _i32, _i32, _i64, _i64, _i32, _P]),
+    "m355_upsample_nearest2x_bwd_h16": (C.c_int, [_P, _P, _i32, _i32, _i32, _i32, _i32, _i64, _i64, _i32, _P]),
+    "m355_upsample_trilinear2x_hp_fwd_h16": (C.c_int, [_P, _P, _i32, _i32, _i32, _i32, _i32, _i64, _i64, _i32, _P]),
+    "m355_upsample_trilinear2x_hp_bwd_h16": (C.c_int, [_P, _P, _i32, _i32, _i32, _i32, _i32, _i64, _i64, _i32, _P]),
+    "m355_upsample2x_plan": (C.c_int, [_i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, C.POINTER(_i64), C.POINTER(C.c_uint64),
+                                       _i32, C.POINTER(_i64)]),
     "m355_softmax_fwd": (C.c_int, [_P, _P, _i32, _i32, _i32, _i64, _f32, _P]),
     "m355_softmax_bwd": (C.c_int, [_P, _P, _P, _i32, _i32, _i32, _i64, _P]),
     "m355_hybrid_loss_workspace": (_sz, [_i32, _i32, _i64]),
@@ -291,10 +301,22 @@ RESAMPLE_OPS = [
     ("maxpool3d_2x_fwd_h16", (0, 1, 3), 2, "ndoca"), ("maxpool3d_2x_bwd_h16", (0, 3, 1, 2), 3, "ndoca"),
 ]
 
+# The 2x upsamplers of csrc/upsample.hip in the numbering of m355_upsample2x_plan: UPSAMPLE2X_OPS[(mode, direction, c8)] with
+# mode 0 nearest / 1 half-pixel trilinear, direction 0 forward / 1 backward; entries as in RESAMPLE_OPS.
+UPSAMPLE2X_MODES = ("nearest", "trilinear_hp")
+UPSAMPLE2X_OPS = {
+    (mode, direction, c8): ("upsample_%s2x%s_%s%s" % ("nearest" if mode == 0 else "trilinear", "_hp" if mode else "",
+                                                     "bwd" if direction else "fwd", "_h16" if c8 else ""),
+                            (0, 1), 2, "ndca" if c8 else "dn")
+    for mode in (0, 1) for direction in (0, 1) for c8 in (0, 1)
+}
+
+
 
 def resample_args(op, shape, strides, pointers, compute):
-    """the argument tuple of entry point RESAMPLE_OPS[op] for what m355_resample_plan takes (stream: the default one)"""
-    _, order, nstrides, checks = RESAMPLE_OPS[op]
+    """the argument tuple of entry point RESAMPLE_OPS[op] (op a (mode, direction, c8) tuple: UPSAMPLE2X_OPS[op]) for what
+    m355_resample_plan / m355_upsample2x_plan takes (stream: the default one)"""
+    _, order, nstrides, checks = UPSAMPLE2X_OPS[op] if isinstance(op, tuple) else RESAMPLE_OPS[op]
     return (tuple(C.c_void_p(pointers[i]) for i in order) + tuple(shape) + tuple(strides[:nstrides])
             + ((compute,) if "c" in checks else ()) + (None,))
 

@@ -776,15 +776,7 @@ extern "C" int m355_resample_plan(int32_t op, int32_t N, int32_t C, int32_t D, i
                                   const uint64_t* pointers4, int32_t compute, int64_t* out8) {
   M355_REQUIRE(strides3 && pointers4 && out8, M355_EINVALID_ARG, "resample_plan: null pointer");
   M355_REQUIRE(op >= 0 && op < RS_COUNT, M355_EINVALID_ARG, "resample_plan: no op %d", op);
-  const ResampleRow& row = RESAMPLE_ROWS[op];
-  ResampleArgs a = {N, C, D, H, W, compute, {0, 0, 0}, {0, 0, 0, row.routes ? (uintptr_t)pointers4[3] : 0}};
-  for (int i = 0; i < 3; ++i)   // what the entry point does not take, it does not see
-    if (row.t[i] != RS_NONE) a.bs[i] = strides3[i], a.ptr[i] = (uintptr_t)pointers4[i];
-  if (int rc = validate_resample((ResampleOp)op, a)) return rc;
-  const ResamplePlan p = plan_resample((ResampleOp)op, a);
-  const int64_t out[8] = {p.variant, p.grid.x, p.grid.y, p.grid.z, (int64_t)p.lds, p.bs[0], p.bs[1], p.bs[2]};
-  std::copy(out, out + 8, out8);
-  return M355_OK;
+  return resample_plan_query((ResampleOp)op, N, C, D, H, W, strides3, pointers4, compute, out8);
 }
 
 extern "C" int m355_softmax_fwd(const float* x, float* y, int32_t N, int32_t C, int32_t inner,

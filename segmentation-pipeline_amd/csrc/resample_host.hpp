@@ -1,7 +1,8 @@
-// Host half of the factor-2 resampling family (elementwise.hip, maxpool.hip, act16.hip, train16.hip): average and max
-// pool, trilinear upsampling and space-to-depth, fp32 NCDHW and c8.  One row of data per entry point, one validator that
-// runs the row's checks in the row's order, and plan_resample(), which resolves a call to its batch strides, kernel variant
-// and grid.  The entry points, m355_resample_plan and nothing else read these numbers.
+// Host half of the factor-2 resampling family (elementwise.hip, maxpool.hip, upsample.hip, act16.hip, train16.hip): average
+// and max pool, trilinear (both conventions) and nearest upsampling and space-to-depth, fp32 NCDHW and c8.  One row of data
+// per entry point, one validator that runs the row's checks in the row's order, and plan_resample(), which resolves a call
+// to its batch strides, kernel variant and grid.  The entry points, m355_resample_plan, m355_upsample2x_plan and nothing
+// else read these numbers.
 #pragma once
 #include "h16.hpp"
 
@@ -10,7 +11,9 @@ namespace m355 {
 enum ResampleOp {
   RS_AVG_FWD, RS_AVG_BWD, RS_AVG_BWD_ADD, RS_TRI_FWD, RS_TRI_BWD, RS_S2D, RS_D2S, RS_MAX_FWD, RS_MAX_BWD,
   RS_AVG_FWD_H16, RS_AVG_BWD_H16, RS_TRI_FWD_H16, RS_TRI_BWD_H16, RS_S2D_H16, RS_D2S_H16, RS_MAX_FWD_H16, RS_MAX_BWD_H16,
-  RS_COUNT
+  RS_COUNT,   // the ops m355_resample_plan numbers; the rows behind them are m355_upsample2x_plan's (mode, direction, c8)
+  RS_NEAR_FWD = RS_COUNT, RS_NEAR_BWD, RS_HP_FWD, RS_HP_BWD, RS_NEAR_FWD_H16, RS_NEAR_BWD_H16, RS_HP_FWD_H16, RS_HP_BWD_H16,
+  RS_ROWS
 };
 
 // a tensor's size next to the (D, H, W) the entry point takes: those voxels, an eighth of them (pooled; RS_PACKED: with
@@ -33,7 +36,7 @@ struct ResampleRow {
 
 // The orders differ from row to row only in where the M355_EUNSUPPORTED checks sit: they are what each entry point has
 // always answered for a call that is wrong in two ways, so they stay.
-static const ResampleRow RESAMPLE_ROWS[RS_COUNT] = {
+static const ResampleRow RESAMPLE_ROWS[RS_ROWS] = {
     // name                         c8     tensors                           need routes work    /thr  cap    order
     {"avgpool3d_2x_fwd",             false, {RS_FULL, RS_HALF, RS_NONE},     0x3, false, RS_HALF, 1,  8192, "dno"},
     {"avgpool3d_2x_bwd",             false, {RS_HALF, RS_FULL, RS_NONE},     0x3, false, RS_FULL, 2,  8192, "dno"},
@@ -52,6 +55,16 @@ static const ResampleRow RESAMPLE_ROWS[RS_COUNT] = {
     {"depth_to_space2_h16",          true,  {RS_PACKED, RS_FULL, RS_NONE},   0x3, false, RS_HALF, 1, 65536, "ondca"},
     {"maxpool3d_2x_fwd_h16",         true,  {RS_FULL, RS_HALF, RS_NONE},     0x3, true,  RS_HALF, 1,  8192, "ndoca"},
     {"maxpool3d_2x_bwd_h16",         true,  {RS_HALF, RS_FULL, RS_FULL},     0xd, true,  RS_FULL, 1, 16384, "ndoca"},
+    // upsample.hip: nearest and half-pixel (hp, align_corners=False) trilinear.  A thread owns an input voxel (vector
+    // variant: an x pair) and its 2x2x2 outputs; in the c8 half-pixel forward, a pair of output items along x
+    {"upsample_nearest2x_fwd",          false, {RS_FULL, RS_X8, RS_NONE},    0x3, false, RS_FULL, 1, 65536, "dn"},
+    {"upsample_nearest2x_bwd",          false, {RS_X8, RS_FULL, RS_NONE},    0x3, false, RS_FULL, 1, 65536, "dn"},
+    {"upsample_trilinear2x_hp_fwd",     false, {RS_FULL, RS_X8, RS_NONE},    0x3, false, RS_FULL, 1, 65536, "dn"},
+    {"upsample_trilinear2x_hp_bwd",     false, {RS_X8, RS_FULL, RS_NONE},    0x3, false, RS_FULL, 1, 65536, "dn"},
+    {"upsample_nearest2x_fwd_h16",      true,  {RS_FULL, RS_X8, RS_NONE},    0x3, false, RS_FULL, 1, 65536, "ndca"},
+    {"upsample_nearest2x_bwd_h16",      true,  {RS_X8, RS_FULL, RS_NONE},    0x3, false, RS_FULL, 1, 65536, "ndca"},
+    {"upsample_trilinear2x_hp_fwd_h16", true,  {RS_FULL, RS_X8, RS_NONE},    0x3, false, RS_X8,   2, 65536, "ndca"},
+    {"upsample_trilinear2x_hp_bwd_h16", true,  {RS_X8, RS_FULL, RS_NONE},    0x3, false, RS_FULL, 1, 65536, "ndca"},
 };
 
 // A call as its entry point takes it.  Pointers are integers here: they are compared with zero and masked, never followed.
@@ -138,6 +151,14 @@ static inline ResamplePlan plan_resample(ResampleOp op, const ResampleArgs& a) {
     case RS_AVG_FWD: p.variant = vec(bs[0],         bs[1],  ptr[0],          ptr[1],  0);       break;   // x | y
     case RS_MAX_FWD: p.variant = vec(bs[0],         bs[1],  ptr[0],          ptr[1],  ptr[3]);  break;   // x | y | idx
     case RS_MAX_BWD: p.variant = vec(bs[1] | bs[2], bs[0],  ptr[1] | ptr[2], ptr[0],  ptr[3]);  break;   // add, dx | dy | idx
+    // upsample.hip, fp32: float4 stores of two inputs' four outputs per row (the 1/8 that is read stays scalar); the
+    // backward reads dy as float4 and stores its x pair as float2.  W % 2 == 0 makes every row offset a multiple of 4 (2)
+    case RS_NEAR_FWD: case RS_HP_FWD:
+      p.variant = a.W % 2 == 0 && bs[1] % 4 == 0 && (ptr[1] & 15) == 0;
+      break;
+    case RS_NEAR_BWD: case RS_HP_BWD:
+      p.variant = a.W % 2 == 0 && bs[0] % 4 == 0 && (ptr[0] & 15) == 0 && bs[1] % 2 == 0 && (ptr[1] & 7) == 0;
+      break;
     case RS_TRI_FWD: {
       // quads: float4 stores of y rows; lds: a block stages its input patch, grid = (y tiles, z tiles, N * C)
       const bool quads = a.W % 2 == 0 && bs[1] % 4 == 0 && (ptr[1] & 15) == 0;
@@ -159,6 +180,21 @@ static inline ResamplePlan plan_resample(ResampleOp op, const ResampleArgs& a) {
   else if (p.variant == RS_VECTOR) p.total /= 2;
   p.grid = dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>(ceil_div(p.total, 256), cap)));
   return p;
+}
+
+// The plan queries (m355_resample_plan, m355_upsample2x_plan) behind their own argument checks: the row's checks and its
+// code, then out8 = variant, grid x y z, LDS bytes, the three strides.
+static inline int resample_plan_query(ResampleOp op, int32_t N, int32_t C, int32_t D, int32_t H, int32_t W,
+                                      const int64_t* strides3, const uint64_t* pointers4, int32_t compute, int64_t* out8) {
+  const ResampleRow& row = RESAMPLE_ROWS[op];
+  ResampleArgs a = {N, C, D, H, W, compute, {0, 0, 0}, {0, 0, 0, row.routes ? (uintptr_t)pointers4[3] : 0}};
+  for (int i = 0; i < 3; ++i)   // what the entry point does not take, it does not see
+    if (row.t[i] != RS_NONE) a.bs[i] = strides3[i], a.ptr[i] = (uintptr_t)pointers4[i];
+  if (int rc = validate_resample(op, a)) return rc;
+  const ResamplePlan p = plan_resample(op, a);
+  const int64_t out[8] = {p.variant, p.grid.x, p.grid.y, p.grid.z, (int64_t)p.lds, p.bs[0], p.bs[1], p.bs[2]};
+  std::copy(out, out + 8, out8);
+  return M355_OK;
 }
 
 }  // namespace m355

@@ -53,14 +53,34 @@ def _is_avgpool2(m):
         return False
 
 
+_UPSAMPLE_SUPPORTED = ("nn.Upsample with scale_factor=2 (or (2, 2, 2)) and mode='nearest' / 'nearest-exact', "
+                       "mode='trilinear' with align_corners=True, or mode='trilinear' with align_corners=False / None; "
+                       "size= and recompute_scale_factor=True are not supported")
+
+
+def _upsample_route(m: nn.Upsample):
+    """the ops function that executes this nn.Upsample: one of the three 2x routes, else NotImplementedError"""
+    sf = m.scale_factor
+    if isinstance(sf, (tuple, list)):
+        sf = sf[0] if len(sf) == 3 and len(set(sf)) == 1 else None
+    try:
+        two = sf is not None and not isinstance(sf, bool) and float(sf) == 2.0
+    except (TypeError, ValueError):
+        two = False
+    ok = two and m.size is None and not getattr(m, "recompute_scale_factor", None)
+    if ok and m.mode in ('nearest', 'nearest-exact') and m.align_corners is None:
+        return ops.upsample_nearest2x           # at factor 2 the two index maps coincide: floor(o / 2) == floor((o + .5) / 2)
+    if ok and m.mode == 'trilinear' and m.align_corners is True:
+        return ops.upsample_trilinear2x
+    if ok and m.mode == 'trilinear' and m.align_corners in (False, None):
+        return ops.upsample_trilinear2x_hp      # align_corners=None means False in torch: the half-pixel convention
+    raise NotImplementedError(
+        f"{m!r} has no HIP kernel; supported: {_UPSAMPLE_SUPPORTED}")
+
+
 def _run_upsample(m, x, out=None):
     if isinstance(m, nn.Upsample):
-        sf = m.scale_factor
-        sf = sf if not isinstance(sf, (tuple, list)) else (sf[0] if len(set(sf)) == 1 else None)
-        if m.mode != 'trilinear' or not m.align_corners or sf is None or float(sf) != 2.0:
-            raise NotImplementedError(
-                "only Upsample(scale_factor=2, mode='trilinear', align_corners=True) has a HIP kernel")
-        return ops.upsample_trilinear2x(x, out=out)
+        return _upsample_route(m)(x, out=out)
     if isinstance(m, BlurConvTranspose3d):
         return m(x, out=out)
     if isinstance(m, nn.ConvTranspose3d):

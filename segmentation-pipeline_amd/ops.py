@@ -1962,29 +1962,37 @@ def maxpool3d_2x(x, out: Optional[OutSlot] = None):
     return _MaxPoolFn.apply(x, out, _tracks(x))
 
 
+# nn.Upsample(scale_factor=2): the entry point family of each convention -- align_corners=True trilinear
+# (csrc/elementwise.hip), nearest and half-pixel (align_corners=False) trilinear (csrc/upsample.hip).  <family>_fwd / _bwd
+# are the fp32 pair, <family>_fwd_h16 / _bwd_h16 the c8 pair; all four take the same argument lists.
+_UPSAMPLE_FAMILY = {"trilinear": "upsample_trilinear2x", "nearest": "upsample_nearest2x", "trilinear_hp": "upsample_trilinear2x_hp"}
+
+
+def _upsample_call(family, suffix, *args):
+    name = family + suffix
+    check(getattr(_lib.lib(), "m355_" + name)(*args), name)
+
+
 class _UpsampleFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, out):
-        L = _lib.lib()
+    def forward(ctx, x, out, family="upsample_trilinear2x"):
         _require(x)
         x, xbs = _dense_channels(x)
         N, Cc, D, H, W = x.shape
         y = _alloc_out(out, (N, Cc, 2 * D, 2 * H, 2 * W), x)
         y, ybs = _dense_channels(y)
-        check(L.m355_upsample_trilinear2x_fwd(_p(x), _p(y), N, Cc, D, H, W, xbs, ybs, _stream()),
-              "upsample_trilinear2x_fwd")
+        _upsample_call(family, "_fwd", _p(x), _p(y), N, Cc, D, H, W, xbs, ybs, _stream())
         ctx.shape = (N, Cc, D, H, W)
+        ctx.family = family
         return y
 
     @staticmethod
     def backward(ctx, dy):
-        L = _lib.lib()
         N, Cc, D, H, W = ctx.shape
         dy, dybs = _dense_channels(dy)
         dx = torch.empty(ctx.shape, dtype=dy.dtype, device=dy.device)
-        check(L.m355_upsample_trilinear2x_bwd(_p(dy), _p(dx), N, Cc, D, H, W, dybs, 0, _stream()),
-              "upsample_trilinear2x_bwd")
-        return dx, None
+        _upsample_call(ctx.family, "_bwd", _p(dy), _p(dx), N, Cc, D, H, W, dybs, 0, _stream())
+        return dx, None, None
 
 
 def _into_c8_slot(y32, out: Optional[OutSlot], compute):
@@ -1994,16 +2002,19 @@ def _into_c8_slot(y32, out: Optional[OutSlot], compute):
 
 
 class _UpsampleC8Fn(torch.autograd.Function):
-    """trilinear x2 upsampling c8 -> c8 (straight into its concat slot); backward: the gather-form kernel on the c8
-    gradient"""
+    """x2 upsampling c8 -> c8 (straight into its concat slot); backward: the gather-form kernel on the c8 gradient"""
 
     @staticmethod
-    def forward(ctx, x_t, x: Act16, y16: Act16):
+    def forward(ctx, x_t, x: Act16, y16: Act16, family="upsample_trilinear2x"):
         N, Cc, D, H, W = x.shape
-        check(_lib.lib().m355_upsample_trilinear2x_fwd_h16(x.ptr(), y16.ptr(), N, Cc, D, H, W, x.batch_stride(),
-                                                           y16.batch_stride(), x.compute, _stream()),
-              "upsample_trilinear2x_fwd_h16")
+        _upsample_call(family, "_fwd_h16", x.ptr(), y16.ptr(), N, Cc, D, H, W, x.batch_stride(), y16.batch_stride(),
+                       x.compute, _stream())
         ctx.info = (N, Cc, D, H, W, x.compute)
+        ctx.family = family
+        if x.compute == _lib.COMPUTE_F16 and family != "upsample_trilinear2x":
+            # the backward's sums report their saturation in the overflow word; as in _MaxPoolC8Fn, the op installs it
+            # itself (it is also used on its own: pack -> upsample -> backward)
+            _overflow_word(x.device)
         return y16.alias()
 
     @staticmethod
@@ -2011,23 +2022,40 @@ class _UpsampleC8Fn(torch.autograd.Function):
         N, Cc, D, H, W, compute = ctx.info
         dy16, dybs = _c8t(dy16)
         dx16 = _c8_grad(N, Cc, D * H * W, compute, dy16.device)
-        check(_lib.lib().m355_upsample_trilinear2x_bwd_h16(_p(dy16), _p(dx16), N, Cc, D, H, W, dybs, 0, compute, _stream()),
-              "upsample_trilinear2x_bwd_h16")
-        return dx16, None, None
+        _upsample_call(ctx.family, "_bwd_h16", _p(dy16), _p(dx16), N, Cc, D, H, W, dybs, 0, compute, _stream())
+        return dx16, None, None, None
 
 
-def upsample_trilinear2x(x, out: Optional[OutSlot] = None):
-    """nn.Upsample(scale_factor=2, mode='trilinear', align_corners=True); c8 -> c8 in the 16-bit flows."""
+def _upsample2x(x, out, family):
     if isinstance(x, Act16):
         N, Cc, D, H, W = x.shape
         y16 = _c8_out_slot(x, out, (2 * D, 2 * H, 2 * W))
         if _act16_tracks(x):
-            return y16.with_t(_UpsampleC8Fn.apply(x.t, x, y16))
-        check(_lib.lib().m355_upsample_trilinear2x_fwd_h16(x.ptr(), y16.ptr(), N, Cc, D, H, W, x.batch_stride(),
-                                                           y16.batch_stride(), x.compute, _stream()),
-              "upsample_trilinear2x_fwd_h16")
+            return y16.with_t(_UpsampleC8Fn.apply(x.t, x, y16, family))
+        _upsample_call(family, "_fwd_h16", x.ptr(), y16.ptr(), N, Cc, D, H, W, x.batch_stride(), y16.batch_stride(),
+                       x.compute, _stream())
         return y16
-    return _UpsampleFn.apply(x, out)
+    return _UpsampleFn.apply(x, out, family)
+
+
+def upsample_trilinear2x(x, out: Optional[OutSlot] = None, mode: str = "trilinear"):
+    """nn.Upsample(scale_factor=2, mode='trilinear', align_corners=True); c8 -> c8 in the 16-bit flows.
+    mode: 'trilinear' (this default), or 'nearest' / 'trilinear_hp' = upsample_nearest2x / upsample_trilinear2x_hp."""
+    if mode not in _UPSAMPLE_FAMILY:
+        raise ValueError(f"upsample mode {mode!r} not in {sorted(_UPSAMPLE_FAMILY)}")
+    return _upsample2x(x, out, _UPSAMPLE_FAMILY[mode])
+
+
+def upsample_nearest2x(x, out: Optional[OutSlot] = None):
+    """nn.Upsample(scale_factor=2, mode='nearest') (= 'nearest-exact' at this factor): the forward copies bits, the
+    backward sums each 2x2x2 block; c8 -> c8 in the 16-bit flows."""
+    return _upsample2x(x, out, "upsample_nearest2x")
+
+
+def upsample_trilinear2x_hp(x, out: Optional[OutSlot] = None):
+    """nn.Upsample(scale_factor=2, mode='trilinear', align_corners=False): the half-pixel convention (weights 0.25 / 0.75,
+    edges clamped); c8 -> c8 in the 16-bit flows."""
+    return _upsample2x(x, out, "upsample_trilinear2x_hp")
 
 
 # ------------------------------------------------------------------- softmax
