@@ -90,8 +90,10 @@ enum { M355_F32 = 0 };
  * into their workspace first. */
 enum { M355_COMPUTE_F32 = 0, M355_COMPUTE_BF16 = 1, M355_COMPUTE_F16 = 2, M355_COMPUTE_F32X3 = 3 };
 
-/* activation fused into the normalise pass (components.py:26,54-55) */
-enum { M355_ACT_NONE = 0, M355_ACT_RELU = 1, M355_ACT_LEAKY_RELU = 2 };
+/* activation fused into the normalise pass (components.py:26,54-55).  3..6 are the smooth ones, evaluated in fp32 in every
+ * flow: nn.ELU(alpha), nn.GELU() (erf), nn.GELU(approximate='tanh'), nn.SiLU().  7 is not a code. */
+enum { M355_ACT_NONE = 0, M355_ACT_RELU = 1, M355_ACT_LEAKY_RELU = 2, M355_ACT_ELU = 3, M355_ACT_GELU = 4,
+       M355_ACT_GELU_TANH = 5, M355_ACT_SILU = 6 };
 
 int m355_version(void);
 const char* m355_last_error(void);
@@ -326,7 +328,7 @@ typedef struct m355_norm_desc {
   int32_t groups;           /* 0 = batch norm */
   int32_t act;              /* M355_ACT_* */
   float eps;
-  float act_slope;          /* leaky relu negative slope */
+  float act_slope;          /* the activation's parameter: LeakyReLU negative slope, ELU alpha; ignored by codes 0, 1, 4-6 */
   int64_t x_batch_stride;   /* elements; 0 = dense */
   int64_t y_batch_stride;
   int64_t add_batch_stride; /* batch stride of the fused residual `add` (0 = dense C*S) */

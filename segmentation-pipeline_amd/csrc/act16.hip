@@ -6,19 +6,14 @@
 // (models/components.py:52-55, + the residual sum :67-68) and nn.AvgPool3d(2, 2)
 // (models/modular_unet.py:22,41,64,92), for the data flow conv -> norm/act -> conv under BASELINE cfg3 / cfg5.
 #include "norm_host.hpp"
+#include "activation.hpp"
 #include "resample_host.hpp"
 
 namespace m355 {
 
-__device__ __forceinline__ float act16_fwd(float v, int act, float slope) {
-  if (act == M355_ACT_RELU) return v > 0.f ? v : 0.f;
-  if (act == M355_ACT_LEAKY_RELU) return v > 0.f ? v : v * slope;
-  return v;
-}
-
 // grid: (chunks over S, channel blocks, N).  x: fp32 NCDHW conv output; y16: c8; y32 (may be null): fp32
 // NCDHW copy for consumers that are not convolutions.
-template <typename HT, bool VEC>
+template <typename HT, bool VEC, bool SMOOTH>
 __global__ __launch_bounds__(256) void norm_act_fwd_c8_kernel(
     const float* __restrict__ x, const float* __restrict__ mean, const float* __restrict__ rstd,
     const float* __restrict__ gamma, const float* __restrict__ beta, const float* __restrict__ add,
@@ -66,12 +61,12 @@ __global__ __launch_bounds__(256) void norm_act_fwd_c8_kernel(
 #pragma unroll
       for (int u = 0; u < U; ++u)
 #pragma unroll
-        for (int j = 0; j < 8; ++j) v[u][j] = act16_fwd(fmaf(v[u][j], sc[j], sh[j]), act, slope) + a[u][j];
+        for (int j = 0; j < 8; ++j) v[u][j] = act_fwd<SMOOTH>(fmaf(v[u][j], sc[j], sh[j]), act, slope) + a[u][j];
     } else {
 #pragma unroll
       for (int u = 0; u < U; ++u)
 #pragma unroll
-        for (int j = 0; j < 8; ++j) v[u][j] = act16_fwd(fmaf(v[u][j], sc[j], sh[j]), act, slope);
+        for (int j = 0; j < 8; ++j) v[u][j] = act_fwd<SMOOTH>(fmaf(v[u][j], sc[j], sh[j]), act, slope);
     }
 #pragma unroll
     for (int u = 0; u < U; ++u) {
@@ -96,13 +91,7 @@ __global__ __launch_bounds__(256) void norm_act_fwd_c8_kernel(
 // dx is the output gradient of the convolution in front of the norm, whose data- and weight-gradient kernels read
 // it as c8; emitting the twin here replaces a separate conversion pass (read 4 + write 2 bytes per element) by
 // 2 bytes per element written.
-__device__ __forceinline__ float act16_grad(float pre, int act, float slope) {
-  if (act == M355_ACT_RELU) return pre > 0.f ? 1.f : 0.f;
-  if (act == M355_ACT_LEAKY_RELU) return pre > 0.f ? 1.f : slope;
-  return 1.f;
-}
-
-template <typename HT>
+template <typename HT, bool SMOOTH>
 __global__ __launch_bounds__(256) void norm_bwd_apply_c8_kernel(
     const float* __restrict__ x, const float* __restrict__ dy, const float* __restrict__ mean,
     const float* __restrict__ rstd, const float* __restrict__ gamma, const float* __restrict__ beta,
@@ -152,7 +141,7 @@ __global__ __launch_bounds__(256) void norm_bwd_apply_c8_kernel(
       for (int j = 0; j < 8; ++j) {
         const float xh = (xv[u][j] - m[j]) * r[j];
         const float pre = fmaf(xv[u][j], sc[j], sh[j]);
-        const float gg = dv[u][j] * act16_grad(pre, act, slope) * g[j];
+        const float gg = dv[u][j] * act_grad<SMOOTH>(pre, act, slope) * g[j];
         const float v = r[j] * (gg - m1[j] - xh * m2[j]);
         o[j] = to_h16_sat<HT>(j < nc ? v : 0.f, sat);
         if (j < nc) op[(int64_t)j * S + i] = v;
@@ -168,9 +157,11 @@ int launch_norm_bwd_apply_c8(const m355_norm_desc* d, const NormPlan& p, const f
                              void* dx16, int64_t dx16bs, int compute, hipStream_t st) {
   with_h16(compute, [&](auto T) {
     typedef typename decltype(T)::type HT;   // (bf16 has fp32's range: nothing to clamp, no overflow word)
-    hipLaunchKernelGGL(norm_bwd_apply_c8_kernel<HT>, norm_pass(d, p, NORM_BWD2_H16).grid, dim3(256), 0, st, x, dy, mean, rstd,
-                       gamma, beta, stat_m, dx, (HT*)dx16, d->C, d->S, d->groups, d->act, d->act_slope, p.xbs, p.ybs, dx16bs,
-                       std::is_same<HT, __bf16>::value ? nullptr : overflow_flag());
+    with_bool(act_is_smooth(d->act), [&](auto SM) {
+      hipLaunchKernelGGL((norm_bwd_apply_c8_kernel<HT, decltype(SM)::value>), norm_pass(d, p, NORM_BWD2_H16).grid, dim3(256), 0,
+                         st, x, dy, mean, rstd, gamma, beta, stat_m, dx, (HT*)dx16, d->C, d->S, d->groups, d->act, d->act_slope,
+                         p.xbs, p.ybs, dx16bs, std::is_same<HT, __bf16>::value ? nullptr : overflow_flag());
+    });
   });
   return check_launch("norm_bwd_apply_c8");
 }
@@ -209,7 +200,7 @@ __global__ __launch_bounds__(256) void avgpool2_c8_kernel(const HT* __restrict__
 // c8 -> c8 normalise + activation (+ residual, also c8): the pre-norm tensor was written by the conv epilogue as
 // c8 (m355_conv3d_fwd_h16_c8), so the pass is purely elementwise on 16-byte items: 2 + 2 bytes per element
 // instead of 4 + 4 for the fp32 pass.  U items per thread, a grid stride apart, in flight together.
-template <typename HT>
+template <typename HT, bool SMOOTH>
 __global__ __launch_bounds__(256) void norm_act_c8c8_kernel(
     const HT* __restrict__ x16, const float* __restrict__ mean, const float* __restrict__ rstd,
     const float* __restrict__ gamma, const float* __restrict__ beta, const HT* __restrict__ add16,
@@ -248,7 +239,7 @@ __global__ __launch_bounds__(256) void norm_act_c8c8_kernel(
       hx8 o;
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
-        float t = act16_fwd(fmaf((float)v[u][j], sc[j], sh[j]), act, slope);
+        float t = act_fwd<SMOOTH>(fmaf((float)v[u][j], sc[j], sh[j]), act, slope);
         if (asrc) t += (float)a[u][j];
         o[j] = (HT)(j < nc ? t : 0.f);
       }
@@ -321,9 +312,11 @@ extern "C" int m355_norm_act_fwd_h16(const m355_norm_desc* d, const float* x, co
   with_h16(compute, [&](auto T) {
     typedef typename decltype(T)::type HT;
     with_bool(L.vec, [&](auto V) {
-      hipLaunchKernelGGL((norm_act_fwd_c8_kernel<HT, decltype(V)::value>), L.grid, dim3(256), 0, (hipStream_t)stream, x, mean,
-                         rstd, gamma, beta, add, y, (HT*)y16, d->C, d->S, d->groups, d->act, d->act_slope, p.xbs, p.ybs, p.abs_,
-                         y16bs);
+      with_bool(act_is_smooth(d->act), [&](auto SM) {
+        hipLaunchKernelGGL((norm_act_fwd_c8_kernel<HT, decltype(V)::value, decltype(SM)::value>), L.grid, dim3(256), 0,
+                           (hipStream_t)stream, x, mean, rstd, gamma, beta, add, y, (HT*)y16, d->C, d->S, d->groups, d->act,
+                           d->act_slope, p.xbs, p.ybs, p.abs_, y16bs);
+      });
     });
   });
   return check_launch("norm_act_fwd_h16");
@@ -356,9 +349,11 @@ extern "C" int m355_norm_act_fwd_c8(const m355_norm_desc* d, const void* x16, in
                    abs_ % 8 == 0, M355_EINVALID_ARG, "norm_act_fwd_c8: c8 tensor not 16B aligned");
   with_h16(compute, [&](auto T) {
     typedef typename decltype(T)::type HT;
-    hipLaunchKernelGGL(norm_act_c8c8_kernel<HT>, norm_pass(d, p, NORM_FWD_C8).grid, dim3(256), 0, (hipStream_t)stream,
-                       (const HT*)x16, mean, rstd, gamma, beta, (const HT*)add16, (HT*)y16, d->C, d->S, d->groups, d->act,
-                       d->act_slope, xbs, abs_, ybs);
+    with_bool(act_is_smooth(d->act), [&](auto SM) {
+      hipLaunchKernelGGL((norm_act_c8c8_kernel<HT, decltype(SM)::value>), norm_pass(d, p, NORM_FWD_C8).grid, dim3(256), 0,
+                         (hipStream_t)stream, (const HT*)x16, mean, rstd, gamma, beta, (const HT*)add16, (HT*)y16, d->C, d->S,
+                         d->groups, d->act, d->act_slope, xbs, abs_, ybs);
+    });
   });
   return check_launch("norm_act_fwd_c8");
 }

@@ -12,6 +12,7 @@
 // the partials in fixed order.  Pass 2 (apply): float4 streaming, one (n,c)
 // channel chunk per block so gamma/beta/mean/rstd are block-uniform.
 #include "norm_host.hpp"
+#include "activation.hpp"
 
 namespace m355 {
 
@@ -187,19 +188,8 @@ __global__ void norm_from_running_kernel(const float* __restrict__ rm, const flo
   rstd[c] = 1.f / sqrtf(rv[c] + eps);
 }
 
-__device__ __forceinline__ float act_fwd(float v, int act, float slope) {
-  if (act == M355_ACT_RELU) return v > 0.f ? v : 0.f;
-  if (act == M355_ACT_LEAKY_RELU) return v > 0.f ? v : v * slope;
-  return v;
-}
-__device__ __forceinline__ float act_grad(float pre, int act, float slope) {
-  if (act == M355_ACT_RELU) return pre > 0.f ? 1.f : 0.f;
-  if (act == M355_ACT_LEAKY_RELU) return pre > 0.f ? 1.f : slope;
-  return 1.f;
-}
-
 // grid: (chunks over S, C, N).  y = act((x-mean)*rstd*gamma + beta) + add
-template <bool VEC>
+template <bool VEC, bool SMOOTH>
 __global__ __launch_bounds__(256) void norm_act_fwd_kernel(
     const float* __restrict__ x, const float* __restrict__ mean, const float* __restrict__ rstd,
     const float* __restrict__ gamma, const float* __restrict__ beta, const float* __restrict__ add,
@@ -218,10 +208,10 @@ __global__ __launch_bounds__(256) void norm_act_fwd_kernel(
     const int64_t S4 = S >> 2;
     for (int64_t i = blockIdx.x * 256ll + threadIdx.x; i < S4; i += gridDim.x * 256ll) {
       float4 v = reinterpret_cast<const float4*>(xp)[i];
-      v.x = act_fwd(fmaf(v.x, sc, sh), act, slope);
-      v.y = act_fwd(fmaf(v.y, sc, sh), act, slope);
-      v.z = act_fwd(fmaf(v.z, sc, sh), act, slope);
-      v.w = act_fwd(fmaf(v.w, sc, sh), act, slope);
+      v.x = act_fwd<SMOOTH>(fmaf(v.x, sc, sh), act, slope);
+      v.y = act_fwd<SMOOTH>(fmaf(v.y, sc, sh), act, slope);
+      v.z = act_fwd<SMOOTH>(fmaf(v.z, sc, sh), act, slope);
+      v.w = act_fwd<SMOOTH>(fmaf(v.w, sc, sh), act, slope);
       if (ap) {
         const float4 a = reinterpret_cast<const float4*>(ap)[i];
         v.x += a.x; v.y += a.y; v.z += a.z; v.w += a.w;
@@ -230,7 +220,7 @@ __global__ __launch_bounds__(256) void norm_act_fwd_kernel(
     }
   } else {
     for (int64_t i = blockIdx.x * 256ll + threadIdx.x; i < S; i += gridDim.x * 256ll) {
-      float v = act_fwd(fmaf(xp[i], sc, sh), act, slope);
+      float v = act_fwd<SMOOTH>(fmaf(xp[i], sc, sh), act, slope);
       if (ap) v += ap[i];
       yp[i] = v;
     }
@@ -243,6 +233,7 @@ __global__ __launch_bounds__(256) void norm_act_fwd_kernel(
 // the pool's own pass over the activated tensor (a full re-read of the level) disappears.  Summation order and the
 // normalise expression are those of avgpool2_fwd_kernel / norm_act_fwd_kernel: bit-identical to the two-pass result.
 // grid: (chunks over pooled voxels, C, N)
+template <bool SMOOTH>
 __global__ __launch_bounds__(256) void norm_act_pool_fwd_kernel(
     const float* __restrict__ x, const float* __restrict__ mean, const float* __restrict__ rstd,
     const float* __restrict__ gamma, const float* __restrict__ beta, float* __restrict__ y, float* __restrict__ pooled,
@@ -269,8 +260,8 @@ __global__ __launch_bounds__(256) void norm_act_pool_fwd_kernel(
     for (int q = 0; q < 4; ++q) v[q] = *reinterpret_cast<const float2*>(xp + off[q]);
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
-      v[q].x = act_fwd(fmaf(v[q].x, sc, sh), act, slope);
-      v[q].y = act_fwd(fmaf(v[q].y, sc, sh), act, slope);
+      v[q].x = act_fwd<SMOOTH>(fmaf(v[q].x, sc, sh), act, slope);
+      v[q].y = act_fwd<SMOOTH>(fmaf(v[q].y, sc, sh), act, slope);
       *reinterpret_cast<float2*>(yp + off[q]) = v[q];
     }
     pp[i] = (((((((v[0].x + v[0].y) + v[1].x) + v[1].y) + v[2].x) + v[2].y) + v[3].x) + v[3].y) * 0.125f;
@@ -279,7 +270,7 @@ __global__ __launch_bounds__(256) void norm_act_pool_fwd_kernel(
 
 // Backward pass 1: per (n,c) partial sums A = sum g, B = sum g*xhat with
 // g = dy * act'(pre).  partial[((n*C + c)*nblk + b)*2 + {0,1}]
-template <bool VEC>
+template <bool VEC, bool SMOOTH>
 __global__ __launch_bounds__(256) void norm_bwd_partial_kernel(
     const float* __restrict__ x, const float* __restrict__ dy, const float* __restrict__ mean,
     const float* __restrict__ rstd, const float* __restrict__ gamma, const float* __restrict__ beta,
@@ -298,7 +289,7 @@ __global__ __launch_bounds__(256) void norm_bwd_partial_kernel(
   auto acc = [&](float xv, float dv) {
     const float xh = (xv - m) * r;
     const float pre = fmaf(xv, sc, sh);
-    const float gg = dv * act_grad(pre, act, slope);
+    const float gg = dv * act_grad<SMOOTH>(pre, act, slope);
     a1 += gg;
     a2 = fmaf(gg, xh, a2);
   };
@@ -394,7 +385,7 @@ __global__ __launch_bounds__(64) void norm_bwd_reduce_kernel(const double* __res
 }
 
 // Backward pass 2: dx = rstd * (g*gamma - m1 - xhat*m2)
-template <bool VEC>
+template <bool VEC, bool SMOOTH>
 __global__ __launch_bounds__(256) void norm_bwd_apply_kernel(
     const float* __restrict__ x, const float* __restrict__ dy, const float* __restrict__ mean,
     const float* __restrict__ rstd, const float* __restrict__ gamma, const float* __restrict__ beta,
@@ -412,7 +403,7 @@ __global__ __launch_bounds__(256) void norm_bwd_apply_kernel(
   auto f = [&](float xv, float dv) {
     const float xh = (xv - m) * r;
     const float pre = fmaf(xv, sc, sh);
-    const float gg = dv * act_grad(pre, act, slope) * g;
+    const float gg = dv * act_grad<SMOOTH>(pre, act, slope) * g;
     return r * (gg - m1 - xh * m2);
   };
   if (VEC) {
@@ -490,8 +481,11 @@ static int bwd_reduce_half(const m355_norm_desc* d, const NormPlan& p, const flo
   M355_REQUIRE(workspace_bytes >= p.workspace_bytes, M355_EWORKSPACE, "%s: workspace too small", who);
   const NormLaunch L = norm_pass(d, p, NORM_BWD1, (uintptr_t)x | (uintptr_t)dy);
   with_bool(L.vec, [&](auto V) {
-    hipLaunchKernelGGL(norm_bwd_partial_kernel<decltype(V)::value>, L.grid, dim3(256), 0, st, x, dy, mean, rstd, gamma, beta,
-                       p.partial(workspace), d->C, d->S, d->groups, d->act, d->act_slope, p.xbs, p.ybs, L.nblk);
+    with_bool(act_is_smooth(d->act), [&](auto SM) {
+      hipLaunchKernelGGL((norm_bwd_partial_kernel<decltype(V)::value, decltype(SM)::value>), L.grid, dim3(256), 0, st, x, dy, mean,
+                         rstd, gamma, beta, p.partial(workspace), d->C, d->S, d->groups, d->act, d->act_slope, p.xbs, p.ybs,
+                         L.nblk);
+    });
   });
   return launch_norm_bwd_reduce(d, p, p.partial(workspace), gamma, dgamma, dbeta, stat_m, training, count_ptr, 1.f, nullptr, st);
 }
@@ -506,8 +500,10 @@ static int bwd_apply_half(const m355_norm_desc* d, const NormPlan& p, const floa
                                     st);
   const NormLaunch L = norm_pass(d, p, NORM_BWD2, (uintptr_t)x | (uintptr_t)dy | (uintptr_t)dx);
   with_bool(L.vec, [&](auto V) {
-    hipLaunchKernelGGL(norm_bwd_apply_kernel<decltype(V)::value>, L.grid, dim3(256), 0, st, x, dy, mean, rstd, gamma, beta,
-                       stat_m, dx, d->C, d->S, d->groups, d->act, d->act_slope, p.xbs, p.ybs);
+    with_bool(act_is_smooth(d->act), [&](auto SM) {
+      hipLaunchKernelGGL((norm_bwd_apply_kernel<decltype(V)::value, decltype(SM)::value>), L.grid, dim3(256), 0, st, x, dy, mean,
+                         rstd, gamma, beta, stat_m, dx, d->C, d->S, d->groups, d->act, d->act_slope, p.xbs, p.ybs);
+    });
   });
   return check_launch(who);
 }
@@ -617,8 +613,11 @@ extern "C" int m355_norm_act_fwd(const m355_norm_desc* d, const float* x, const 
   const NormPlan p = plan_norm(d, NORM_F32);
   const NormLaunch L = norm_pass(d, p, NORM_FWD, (uintptr_t)x | (uintptr_t)y | (uintptr_t)add);
   with_bool(L.vec, [&](auto V) {
-    hipLaunchKernelGGL(norm_act_fwd_kernel<decltype(V)::value>, L.grid, dim3(256), 0, (hipStream_t)stream, x, mean, rstd,
-                       gamma, beta, add, y, d->C, d->S, d->groups, d->act, d->act_slope, p.xbs, p.ybs, p.abs_);
+    with_bool(act_is_smooth(d->act), [&](auto SM) {
+      hipLaunchKernelGGL((norm_act_fwd_kernel<decltype(V)::value, decltype(SM)::value>), L.grid, dim3(256), 0,
+                         (hipStream_t)stream, x, mean, rstd, gamma, beta, add, y, d->C, d->S, d->groups, d->act, d->act_slope,
+                         p.xbs, p.ybs, p.abs_);
+    });
   });
   return check_launch("norm_act_fwd");
 }
@@ -636,8 +635,11 @@ extern "C" int m355_norm_act_pool_fwd(const m355_norm_desc* d, const float* x, c
   const int64_t pbs = dense_or(pooled_batch_stride, (int64_t)d->C * (d->S / 8));
   M355_REQUIRE((((uintptr_t)x | (uintptr_t)y) & 7) == 0 && p.xbs % 2 == 0 && p.ybs % 2 == 0, M355_EINVALID_ARG,
                "norm_act_pool_fwd: x / y not 8B aligned");
-  hipLaunchKernelGGL(norm_act_pool_fwd_kernel, norm_pass(d, p, NORM_POOL_FWD).grid, dim3(256), 0, (hipStream_t)stream, x, mean,
-                     rstd, gamma, beta, y, pooled, d->C, D, H, W, d->groups, d->act, d->act_slope, p.xbs, p.ybs, pbs);
+  with_bool(act_is_smooth(d->act), [&](auto SM) {
+    hipLaunchKernelGGL(norm_act_pool_fwd_kernel<decltype(SM)::value>, norm_pass(d, p, NORM_POOL_FWD).grid, dim3(256), 0,
+                       (hipStream_t)stream, x, mean, rstd, gamma, beta, y, pooled, d->C, D, H, W, d->groups, d->act,
+                       d->act_slope, p.xbs, p.ybs, pbs);
+  });
   return check_launch("norm_act_pool_fwd");
 }
 

@@ -75,8 +75,8 @@ static inline NormPlan plan_norm(const m355_norm_desc* d, NormLayout layout) {
 
 // One validator for the family.  fp32 layout: grid.y = C, so N, C <= 65535 (M355_EUNSUPPORTED past them, checked last);
 // every layout with a c8 side: grid.y = channel blocks, the limit is part of the shape check (M355_EINVALID_ARG, as
-// before).  The activation code is checked for the fp32 layout only: the c8 forward passes treat an unknown code as
-// "none", the c8 backward checks it itself (norm_bwd_c8_check).
+// before).  The activation code (0..6, activation.hpp) is checked for the fp32 layout only: the c8 forward passes treat an
+// unknown code as "none", the c8 backward checks it itself (norm_bwd_c8_check).
 static inline int validate_norm(const m355_norm_desc* d, const char* who, NormLayout layout) {
   M355_REQUIRE(d != nullptr, M355_EINVALID_ARG, "%s: null descriptor", who);
   if (layout == NORM_F32)
@@ -87,7 +87,7 @@ static inline int validate_norm(const m355_norm_desc* d, const char* who, NormLa
   M355_REQUIRE(d->groups >= 0 && (d->groups == 0 || d->C % d->groups == 0), M355_EINVALID_ARG,
                "%s: C=%d not divisible by groups=%d", who, d->C, d->groups);
   if (layout != NORM_F32) return M355_OK;
-  M355_REQUIRE(d->act >= M355_ACT_NONE && d->act <= M355_ACT_LEAKY_RELU, M355_EINVALID_ARG, "%s: bad activation %d", who,
+  M355_REQUIRE(d->act >= M355_ACT_NONE && d->act <= M355_ACT_SILU, M355_EINVALID_ARG, "%s: bad activation %d", who,
                d->act);
   M355_REQUIRE(d->N <= 65535 && d->C <= 65535, M355_EUNSUPPORTED, "%s: N or C > 65535", who);
   return M355_OK;

@@ -20,15 +20,10 @@
 // (models/components.py:52-55,62-73) and of nn.AvgPool3d (models/modular_unet.py:64,92) under
 // `torch.cuda.amp.autocast` (segmentation_trainer.py:203-227).
 #include "norm_host.hpp"
+#include "activation.hpp"
 #include "resample_host.hpp"
 
 namespace m355 {
-
-__device__ __forceinline__ float act16_grad_t(float pre, int act, float slope) {
-  if (act == M355_ACT_RELU) return pre > 0.f ? 1.f : 0.f;
-  if (act == M355_ACT_LEAKY_RELU) return pre > 0.f ? 1.f : slope;
-  return 1.f;
-}
 
 // ---------------------------------------------------------------- scaled layout conversion
 template <typename HT>
@@ -117,7 +112,7 @@ struct GradSrc {
 // ---------------------------------------------------------------- normalisation backward, pass 1
 // partial[((n*C + c)*nblk + b)*2 + {0,1}] = (sum g', sum g' * xhat) over chunk b of channel (n, c), g' = g * act'(pre):
 // the layout of norm_bwd_partial_kernel, so norm_bwd_reduce_kernel finalizes both.  grid (nblk, CB, N).
-template <typename HT, bool POOL>
+template <typename HT, bool POOL, bool SMOOTH>
 __global__ __launch_bounds__(256) void norm_bwd_partial_c8_kernel(
     const HT* __restrict__ x16, const HT* __restrict__ dy16, const HT* __restrict__ dp16, const float* __restrict__ mean,
     const float* __restrict__ rstd, const float* __restrict__ gamma, const float* __restrict__ beta,
@@ -172,7 +167,7 @@ __global__ __launch_bounds__(256) void norm_bwd_partial_c8_kernel(
         const float xf = (float)xv[u][j];
         const float xh = (xf - m[j]) * r[j];
         const float pre = fmaf(xf, sc[j], sh[j]);
-        const float gg = g[u][j] * act16_grad_t(pre, act, slope);
+        const float gg = g[u][j] * act_grad<SMOOTH>(pre, act, slope);
         a1[j] += gg;
         a2[j] = fmaf(gg, xh, a2[j]);
       }
@@ -202,7 +197,7 @@ __global__ __launch_bounds__(256) void norm_bwd_partial_c8_kernel(
 
 // ---------------------------------------------------------------- normalisation backward, pass 2 (c8 -> c8)
 // dx = rstd * (g' * gamma - m1 - xhat * m2), written as c8 only.  grid (chunks, CB, N); U items per thread in flight.
-template <typename HT, bool POOL>
+template <typename HT, bool POOL, bool SMOOTH>
 __global__ __launch_bounds__(256) void norm_bwd_apply_c8c8_kernel(
     const HT* __restrict__ x16, const HT* __restrict__ dy16, const HT* __restrict__ dp16, const float* __restrict__ mean,
     const float* __restrict__ rstd, const float* __restrict__ gamma, const float* __restrict__ beta,
@@ -257,7 +252,7 @@ __global__ __launch_bounds__(256) void norm_bwd_apply_c8c8_kernel(
         const float xf = (float)xv[u][j];
         const float xh = (xf - m[j]) * r[j];
         const float pre = fmaf(xf, sc[j], sh[j]);
-        const float gg = g[u][j] * act16_grad_t(pre, act, slope) * gm[j];
+        const float gg = g[u][j] * act_grad<SMOOTH>(pre, act, slope) * gm[j];
         const float v = r[j] * (gg - m1[j] - xh * m2[j]);
         o[j] = j < nc ? to_h16_sat<HT>(v, sat) : (HT)0.f;
       }
@@ -374,7 +369,7 @@ static int norm_bwd_c8_check(const char* who, const m355_norm_desc* d, const voi
   if (int rc = check_h16(who, compute)) return rc;
   M355_REQUIRE(d && x16 && (dy16 || dpool16) && dx16_or_ws, M355_EINVALID_ARG, "%s: null pointer", who);
   if (int rc = validate_norm(d, who, NORM_C8)) return rc;
-  M355_REQUIRE(d->act >= M355_ACT_NONE && d->act <= M355_ACT_LEAKY_RELU, M355_EINVALID_ARG, "%s: bad activation", who);
+  M355_REQUIRE(d->act >= M355_ACT_NONE && d->act <= M355_ACT_SILU, M355_EINVALID_ARG, "%s: bad activation", who);
   M355_REQUIRE(!dpool16 || (D > 0 && H > 0 && W > 0 && D % 2 == 0 && H % 2 == 0 && W % 2 == 0 && (int64_t)D * H * W == d->S),
                M355_EINVALID_ARG, "%s: a pooled gradient needs even D, H, W with D*H*W == S", who);
   return M355_OK;
@@ -408,9 +403,12 @@ static int norm_bwd_c8_reduce_half(const m355_norm_desc* d, const NormPlan& p, c
   with_h16(compute, [&](auto T) {
     typedef typename decltype(T)::type HT;
     with_bool(a.dpool16 != nullptr, [&](auto POOL) {
-      hipLaunchKernelGGL((norm_bwd_partial_c8_kernel<HT, decltype(POOL)::value>), L.grid, dim3(256), 0, st, (const HT*)a.x16,
-                         (const HT*)a.dy16, (const HT*)a.dpool16, mean, rstd, gamma, beta, p.partial(workspace), d->C, d->S,
-                         d->groups, d->act, d->act_slope, a.xbs, a.ybs, a.pbs, a.H, a.W, L.nblk);
+      with_bool(act_is_smooth(d->act), [&](auto SM) {
+        hipLaunchKernelGGL((norm_bwd_partial_c8_kernel<HT, decltype(POOL)::value, decltype(SM)::value>), L.grid, dim3(256), 0, st,
+                           (const HT*)a.x16, (const HT*)a.dy16, (const HT*)a.dpool16, mean, rstd, gamma, beta,
+                           p.partial(workspace), d->C, d->S, d->groups, d->act, d->act_slope, a.xbs, a.ybs, a.pbs, a.H, a.W,
+                           L.nblk);
+      });
     });
   });
   return launch_norm_bwd_reduce(d, p, p.partial(workspace), gamma, dgamma, dbeta, stat_m, training, count_ptr, grad_unscale,
@@ -424,10 +422,12 @@ static int norm_bwd_c8_apply_half(const m355_norm_desc* d, const NormPlan& p, co
   with_h16(compute, [&](auto T) {
     typedef typename decltype(T)::type HT;
     with_bool(a.dpool16 != nullptr, [&](auto POOL) {
-      hipLaunchKernelGGL((norm_bwd_apply_c8c8_kernel<HT, decltype(POOL)::value>), norm_pass(d, p, NORM_BWD2_C8).grid, dim3(256),
-                         0, st, (const HT*)a.x16, (const HT*)a.dy16, (const HT*)a.dpool16, mean, rstd, gamma, beta, stat_m,
-                         (HT*)a.dx16, d->C, d->S, d->groups, d->act, d->act_slope, a.xbs, a.ybs, a.pbs, a.dxbs, a.H, a.W,
-                         overflow_flag());
+      with_bool(act_is_smooth(d->act), [&](auto SM) {
+        hipLaunchKernelGGL((norm_bwd_apply_c8c8_kernel<HT, decltype(POOL)::value, decltype(SM)::value>),
+                           norm_pass(d, p, NORM_BWD2_C8).grid, dim3(256), 0, st, (const HT*)a.x16, (const HT*)a.dy16,
+                           (const HT*)a.dpool16, mean, rstd, gamma, beta, stat_m, (HT*)a.dx16, d->C, d->S, d->groups, d->act,
+                           d->act_slope, a.xbs, a.ybs, a.pbs, a.dxbs, a.H, a.W, overflow_flag());
+      });
     });
   });
   return check_launch(who);

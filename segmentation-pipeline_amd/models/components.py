@@ -20,7 +20,7 @@ from torch import nn
 import torch.nn.functional as F
 
 from .. import ops
-from .._lib import ACT_LEAKY_RELU, ACT_NONE, ACT_RELU
+from .._lib import ACT_ELU, ACT_GELU, ACT_GELU_TANH, ACT_LEAKY_RELU, ACT_NONE, ACT_RELU, ACT_SILU
 
 
 def _volume(stride):
@@ -195,14 +195,23 @@ def run_conv(m, x, add=None, out=None, stats=None, c8_out=False, softmax=False):
 
 
 def _act_code(m):
+    """(M355_ACT_* code, its one parameter) of an activation module; `inplace` has no meaning for a fused pass.  Exact
+    types for the smooth ones: a subclass may compute something else (nn.ReLU6 is an nn.Hardtanh, not an nn.ReLU)."""
     if m is None or isinstance(m, nn.Identity):
         return ACT_NONE, 0.0
     if isinstance(m, nn.ReLU):
         return ACT_RELU, 0.0
     if isinstance(m, nn.LeakyReLU):
         return ACT_LEAKY_RELU, float(m.negative_slope)
+    if type(m) is nn.ELU:
+        return ACT_ELU, float(m.alpha)
+    if type(m) is nn.GELU and m.approximate in ('none', 'tanh'):
+        return (ACT_GELU if m.approximate == 'none' else ACT_GELU_TANH), 0.0
+    if type(m) is nn.SiLU:
+        return ACT_SILU, 0.0
+    name = type(m).__name__ + (f"(approximate={m.approximate!r})" if type(m) is nn.GELU else "")
     raise NotImplementedError(
-        f"activation_class {type(m).__name__} has no HIP kernel (supported: ReLU, LeakyReLU, Identity)")
+        f"activation_class {name} has no HIP kernel (supported: ReLU, LeakyReLU, Identity, ELU, GELU, SiLU)")
 
 
 def _check_norm_module(m):
