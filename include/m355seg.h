@@ -749,6 +749,22 @@ int m355_patch_aggregate_grid(const float* tiles, const int32_t* starts, int32_t
                               int32_t C, int32_t V0, int32_t V1, int32_t V2, int32_t ps0, int32_t ps1, int32_t ps2,
                               int32_t b0, int32_t b1, int32_t b2, void* stream);
 
+/* The same pass with a separable window (torchio GridAggregator('hann'): PatchPredict(overlap_mode='hann')).  Tiles,
+ * starts, border and out as above; window = w0 | w1 | w2, ps0 + ps1 + ps2 device floats given as data (for 'hann' axis
+ * x holds torch.hann_window(psx + 2, periodic=False)[1:-1], psx strictly positive values; the kernel evaluates no
+ * cosine, so any positive window blends).  With d = v + border - start the offset of a voxel inside a covering tile,
+ *   w(d)      = (w0[d0] * w1[d1]) * w2[d2]
+ *   sum[c, v] = sum over the covering tiles, in tile order, of tile[c, d] * w(d)
+ *   wsum[v]   = sum over the covering tiles, in tile order, of w(d)            (one weight sum for all channels)
+ *   out[c, v] = sum[c, v] / wsum[v]
+ * each product, sum and the quotient one rounded fp32 operation, never contracted into an fma: the bits of torchio's
+ * sequential `out[...] += patch * win; mask[...] += win` over the tiles followed by `out / mask`.  A voxel under one
+ * tile gives (t * w) / w, within an ulp or so of t.  An all-ones window gives m355_patch_aggregate_grid's bits. */
+int m355_patch_aggregate_grid_weighted(const float* tiles, const int32_t* starts, int32_t n0, int32_t n1, int32_t n2,
+                                       const float* window /* device, ps0 + ps1 + ps2 floats: w0 | w1 | w2 */,
+                                       float* out, int32_t C, int32_t V0, int32_t V1, int32_t V2,
+                                       int32_t ps0, int32_t ps1, int32_t ps2, int32_t b0, int32_t b1, int32_t b2, void* stream);
+
 /* ------------------------------------------------- sliding-window patches
  * PatchPredict (prediction.py:124-152) delegates tiling/aggregation to torchio
  * 0.18.45 GridSampler / GridAggregator(overlap_mode='average').  These entry

@@ -290,6 +290,72 @@ __global__ __launch_bounds__(256) void patch_aggregate_grid_kernel(const float* 
   }
 }
 
+// Weighted one-pass aggregation (GridAggregator('hann'), or any separable window): as patch_aggregate_grid_kernel, but a
+// covering tile contributes t * w to the sum and w to a weight sum that all channels share, with
+//   w(di, dj, dk) = (w0[di] * w1[dj]) * w2[dk],   window = w0 | w1 | w2  (ps0 + ps1 + ps2 floats, given as data),
+//   out[c, v] = (sum over covering tiles, a then b then q ascending, of tile[c, d] * w(d)) / (same sum of w(d)).
+// Every product, sum and the quotient is one rounded fp32 operation (no fma: contraction is off for the whole body), so
+// the bits are those of torchio's sequential `out[...] += patch * win; mask[...] += win` per tile, then `out / mask`
+// (the first term is added to zero, which is exact).  The covering tiles are searched once per voxel and the weight is
+// computed once per covering tile, for a register group of CH channels (the average kernel searches per channel):
+// CH = min(C, 4), chosen on the host; the last group of a C that is no multiple of CH re-reads channel C - 1 into the
+// registers it does not store, which keeps the inner loop free of branches and its loads in flight together.
+// The loops run over the whole start lists with wave-uniform counters, so the starts are scalar loads, and the three
+// window factors are loaded next to the tile values: one memory latency per covering tile (walking only the covering run
+// [lo, hi] of each lane makes the counters per-lane and every start, then every factor, a dependent vector load).
+// Same traffic as the average kernel: tiles read once, output written once.
+template <int CH>
+__global__ __launch_bounds__(256) void patch_aggregate_grid_weighted_kernel(
+    const float* __restrict__ tiles, const int32_t* __restrict__ starts, int n0, int n1, int n2,
+    const float* __restrict__ window, float* __restrict__ out, int C, int V0, int V1, int V2, int ps0, int ps1, int ps2,
+    int b0, int b1, int b2) {
+#pragma clang fp contract(off)
+  const int64_t V = (int64_t)V0 * V1 * V2;
+  const int64_t PS = (int64_t)ps0 * ps1 * ps2;
+  const int32_t* s0 = starts;
+  const int32_t* s1 = starts + n0;
+  const int32_t* s2 = starts + n0 + n1;
+  const float* w0 = window;
+  const float* w1 = window + ps0;
+  const float* w2 = window + ps0 + ps1;
+  for (int64_t v = blockIdx.x * 256ll + threadIdx.x; v < V; v += gridDim.x * 256ll) {
+    const int k = (int)(v % V2) + b2;                       // coordinates in the padded volume
+    const int j = (int)((v / V2) % V1) + b1;
+    const int i = (int)(v / ((int64_t)V2 * V1)) + b0;
+    for (int c0 = 0; c0 < C; c0 += CH) {
+      float sum[CH];
+      int64_t coff[CH];                                     // channel offsets into a tile, clamped to the last channel
+#pragma unroll
+      for (int u = 0; u < CH; ++u) {
+        sum[u] = 0.f;
+        coff[u] = (int64_t)min(c0 + u, C - 1) * PS;
+      }
+      float wsum = 0.f;
+      for (int a = 0; a < n0; ++a) {
+        const int di = i - s0[a];
+        if (di < 0 || di >= ps0) continue;
+        for (int b = 0; b < n1; ++b) {
+          const int dj = j - s1[b];
+          if (dj < 0 || dj >= ps1) continue;
+          for (int q = 0; q < n2; ++q) {
+            const int dk = k - s2[q];
+            if (dk < 0 || dk >= ps2) continue;
+            const float w = (w0[di] * w1[dj]) * w2[dk];
+            const int64_t p = ((int64_t)a * n1 + b) * n2 + q;
+            const float* t = tiles + p * C * PS + ((int64_t)di * ps1 + dj) * ps2 + dk;
+            wsum = wsum + w;
+#pragma unroll
+            for (int u = 0; u < CH; ++u) sum[u] = sum[u] + t[coff[u]] * w;
+          }
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < CH; ++u)
+        if (c0 + u < C) out[(int64_t)(c0 + u) * V + v] = sum[u] / wsum;
+    }
+  }
+}
+
 // ------------------------------------------------------- argmax + confusion
 // counts[(n*C + c)*4 + {TP, FP, FN, TN}]; block-level reduction then one atomic per
 // (block, class, stat) -- integer adds, so the result is order-independent.
@@ -595,6 +661,24 @@ extern "C" int m355_patch_aggregate_grid(const float* tiles, const int32_t* star
   hipLaunchKernelGGL(patch_aggregate_grid_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, tiles, starts, n0, n1, n2,
                      out, C, V0, V1, V2, ps0, ps1, ps2, b0, b1, b2);
   return check_launch("patch_aggregate_grid");
+}
+
+extern "C" int m355_patch_aggregate_grid_weighted(const float* tiles, const int32_t* starts, int32_t n0, int32_t n1,
+                                                  int32_t n2, const float* window, float* out, int32_t C, int32_t V0,
+                                                  int32_t V1, int32_t V2, int32_t ps0, int32_t ps1, int32_t ps2, int32_t b0,
+                                                  int32_t b1, int32_t b2, void* stream) {
+  M355_REQUIRE(tiles && starts && window && out, M355_EINVALID_ARG, "patch_aggregate_grid_weighted: null pointer");
+  M355_REQUIRE(n0 > 0 && n1 > 0 && n2 > 0 && C > 0 && V0 > 0 && V1 > 0 && V2 > 0 && ps0 > 0 && ps1 > 0 && ps2 > 0 && b0 >= 0 &&
+                   b1 >= 0 && b2 >= 0, M355_EINVALID_ARG, "patch_aggregate_grid_weighted: bad shape");
+  const int64_t V = (int64_t)V0 * V1 * V2;
+  const unsigned blocks = (unsigned)std::min<int64_t>(ceil_div(V, 256), 32768);
+  auto kernel = C == 1 ? patch_aggregate_grid_weighted_kernel<1>
+              : C == 2 ? patch_aggregate_grid_weighted_kernel<2>
+              : C == 3 ? patch_aggregate_grid_weighted_kernel<3>
+                       : patch_aggregate_grid_weighted_kernel<4>;
+  hipLaunchKernelGGL(kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, tiles, starts, n0, n1, n2, window, out, C, V0,
+                     V1, V2, ps0, ps1, ps2, b0, b1, b2);
+  return check_launch("patch_aggregate_grid_weighted");
 }
 
 extern "C" int m355_patch_accumulate(const float* patches, const int32_t* loc, float* accum,

@@ -2507,9 +2507,11 @@ def patch_accumulate(patches, locations, accum, count):
                                   ps0, ps1, ps2, _stream()), "patch_accumulate")
 
 
-def patch_aggregate_grid(tiles, axes, volume_shape, border=(0, 0, 0)):
+def patch_aggregate_grid(tiles, axes, volume_shape, border=(0, 0, 0), window=None):
     """tiles [n0*n1*n2, C, *patch] in GridSampler order over the per-axis start lists `axes` (padded coordinates) ->
-    the averaged volume [C, *volume_shape] (the padded volume's interior when `border` > 0); one pass."""
+    the averaged volume [C, *volume_shape] (the padded volume's interior when `border` > 0); one pass.
+    window: None (plain average), or three 1-D fp32 tensors, one per axis and as long as the patch: the covering tiles
+    are blended with the weight (w0[d0] * w1[d1]) * w2[d2] (prediction.hann_window_axes for overlap_mode='hann')."""
     L = _lib.lib()
     _require(tiles)
     tiles = tiles.contiguous()
@@ -2517,10 +2519,23 @@ def patch_aggregate_grid(tiles, axes, volume_shape, border=(0, 0, 0)):
     n0, n1, n2 = (len(a) for a in axes)
     if P != n0 * n1 * n2:
         raise _lib.M355Error(f"patch_aggregate_grid: {P} tiles for a {n0} x {n1} x {n2} grid")
+    if window is not None:
+        window = list(window)
+        if len(window) != 3 or any(not torch.is_tensor(w) or w.dim() != 1 or w.dtype != torch.float32 for w in window):
+            raise _lib.M355Error("patch_aggregate_grid: window must be three 1-D float32 tensors")
+        if tuple(w.numel() for w in window) != (ps0, ps1, ps2):
+            raise _lib.M355Error(f"patch_aggregate_grid: window lengths {tuple(w.numel() for w in window)} for "
+                                 f"{ps0} x {ps1} x {ps2} tiles")
+        window = torch.cat(window).to(tiles.device)         # w0 | w1 | w2: one copy when the window lives on the host
     starts = torch.tensor([int(v) for a in axes for v in a], dtype=torch.int32, device=tiles.device)
     out = torch.empty((Cc,) + tuple(volume_shape), dtype=torch.float32, device=tiles.device)
-    check(L.m355_patch_aggregate_grid(_p(tiles), _p(starts), n0, n1, n2, _p(out), Cc, *[int(v) for v in volume_shape], ps0, ps1,
-                                      ps2, *[int(b) for b in border], _stream()), "patch_aggregate_grid")
+    if window is None:
+        check(L.m355_patch_aggregate_grid(_p(tiles), _p(starts), n0, n1, n2, _p(out), Cc, *[int(v) for v in volume_shape], ps0,
+                                          ps1, ps2, *[int(b) for b in border], _stream()), "patch_aggregate_grid")
+    else:
+        check(L.m355_patch_aggregate_grid_weighted(_p(tiles), _p(starts), n0, n1, n2, _p(window), _p(out), Cc,
+                                                   *[int(v) for v in volume_shape], ps0, ps1, ps2, *[int(b) for b in border],
+                                                   _stream()), "patch_aggregate_grid_weighted")
     return out
 
 

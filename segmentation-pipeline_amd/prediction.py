@@ -5,8 +5,8 @@
 * StandardPredict.predict (:73-102): optional sagittal split, one model call; the
   prediction stays on the device (the reference's per-subject `.detach().cpu()`, :97,
   is an evaluator concern and forces a sync every iteration).
-* PatchPredict.predict (:124-152): torchio GridSampler / GridAggregator('average')
-  become a deterministic tile list + the patch_gather / patch_accumulate kernels;
+* PatchPredict.predict (:124-152): torchio GridSampler / GridAggregator('average' or
+  'hann') become a deterministic tile list + the patch_gather / patch_aggregate_grid kernels;
   inside `distributed.unit_sharding()` the tiles are sharded over the ranks and
   returned by a single all_gather (distributed.gather_tiles).
 """
@@ -58,6 +58,14 @@ def grid_axes(volume_shape, patch_size, patch_overlap):
 
 def _triple(v):
     return tuple(v) if isinstance(v, (tuple, list)) else (v, v, v)
+
+
+def hann_window_axes(patch_size):
+    """The per-axis factors of torchio's GridAggregator('hann') window for `patch_size`: three 1-D fp32 CPU tensors,
+    axis x holding torch.hann_window(p + 2, periodic=False)[1:-1] -- p strictly positive values, symmetric, [1.] for
+    p = 1.  The weight of voxel (di, dj, dk) of a tile is (w0[di] * w1[dj]) * w2[dk]."""
+    return tuple(torch.hann_window(int(p) + 2, periodic=False, dtype=torch.float32)[1:-1].contiguous()
+                 for p in _triple(patch_size))
 
 
 class StandardPredict:
@@ -134,6 +142,11 @@ class GraphedForward:
 class PatchPredict:
     """Sliding-window prediction with overlap averaging (reference :105-152).
 
+    overlap_mode (reference :115,134 -> torchio GridAggregator): 'average' (every covering tile has the same vote) or
+    'hann' (each tile is weighted by a Hann window that fades towards its faces, `hann_window_axes`, and the sum is
+    divided by the summed weights: no seams at tile borders).  'hann' needs a backend with `patch_aggregate_grid`;
+    'crop' is not implemented.
+
     padding_mode (reference :114,132 -> torchio GridSampler): None, a number (constant fill) or one of numpy.pad's
     'constant' / 'edge' / 'reflect' / 'symmetric' / 'wrap': the volume is treated as padded by patch_overlap // 2
     voxels per side before tiling, and the aggregate is cropped back (index math in the gather / finalize
@@ -150,8 +163,11 @@ class PatchPredict:
     def __init__(self, image_names: Sequence[str] = ("X",), patch_batch_size: int = 16, patch_size=None,
                  patch_overlap=(0, 0, 0), padding_mode=None, overlap_mode: str = "average", ops_backend=ops,
                  result_on: str = "all", timings: Optional[dict] = None, graph: bool = False):
-        if overlap_mode != "average":
-            raise NotImplementedError("only overlap_mode='average' (the mode the reference uses) is implemented")
+        if overlap_mode not in ("average", "hann"):
+            raise NotImplementedError("only overlap_mode='average' (the mode the reference uses) and 'hann' are implemented")
+        if overlap_mode != "average" and not hasattr(ops_backend, "patch_aggregate_grid"):
+            raise NotImplementedError(f"overlap_mode={overlap_mode!r} needs an ops backend with patch_aggregate_grid: the "
+                                      "accumulate / finalize fallback serves 'average' only")
         self.pad_value = 0.0
         if padding_mode is not None and not isinstance(padding_mode, str):
             self.pad_value, padding_mode = float(padding_mode), "constant"
@@ -170,6 +186,7 @@ class PatchPredict:
         self.timings = timings
         self.graph = graph
         self._graphed = None     # (model, GraphedForward)
+        self._window = None      # (patch size, hann_window_axes of it)
         self._ops = ops_backend  # the HIP ops; tests inject a CPU double for the gloo plumbing test
 
     def _stamp(self, name, t0, device):
@@ -181,6 +198,11 @@ class PatchPredict:
         now = time.perf_counter()
         self.timings[name] = self.timings.get(name, 0.0) + (now - t0)
         return now
+
+    def _hann_window(self):
+        if self._window is None or self._window[0] != self.patch_size:
+            self._window = (self.patch_size, hann_window_axes(self.patch_size))
+        return self._window[1]
 
     def predict_volume(self, model, volume: torch.Tensor) -> Optional[torch.Tensor]:
         """volume [C, V0, V1, V2] on the device -> averaged prediction [C_out, V0, V1, V2]."""
@@ -232,9 +254,14 @@ class PatchPredict:
         # the covering tiles summed in tile order, divided by their count) where the backend has it -- no accumulator /
         # count volumes, no zero-fill, no read-modify-write; the same bits as the batch-by-batch loop below.
         if hasattr(k, "patch_aggregate_grid"):
-            out = k.patch_aggregate_grid(tiles, grid_axes(pshape, self.patch_size, self.patch_overlap), vshape, border)
+            axes = grid_axes(pshape, self.patch_size, self.patch_overlap)
+            if self.overlap_mode == "hann":
+                out = k.patch_aggregate_grid(tiles, axes, vshape, border, window=self._hann_window())
+            else:
+                out = k.patch_aggregate_grid(tiles, axes, vshape, border)
             self._stamp("aggregate", t, dev)
             return out
+        # (backends without it: the batch-by-batch accumulate / finalize, 'average' only -- see the constructor)
         accum = torch.zeros((c_out,) + pshape, dtype=torch.float32, device=dev)
         count = torch.zeros(pshape, dtype=torch.float32, device=dev)
         all_loc = torch.tensor(locs, dtype=torch.int32, device=dev)
