@@ -148,9 +148,15 @@ enum {
    * hypothesis of ModularUNet, models/modular_unet.py:99-100); allowed when m355_conv3d_fuses_softmax(desc) != 0
    * (the fp32 Cout <= 4 kernel, where a voxel's channels sit in one thread's registers).  Same bits as
    * m355_conv3d_fwd followed by m355_softmax_fwd. */
-  M355_CONV_SOFTMAX = 2
+  M355_CONV_SOFTMAX = 2,
+  /* forward only: nn.Sigmoid applied per element in the conv epilogue (hypothesis_class=nn.Sigmoid: binary and multi-label
+   * heads); allowed when m355_conv3d_fuses_sigmoid(desc) != 0, which holds exactly where m355_conv3d_fuses_softmax does
+   * (one epilogue slot, one tuning switch).  Same bits as m355_conv3d_fwd followed by m355_sigmoid_fwd.  Setting both
+   * head flags is M355_EINVALID_ARG; a head flag on a descriptor that does not fuse it is M355_EUNSUPPORTED. */
+  M355_CONV_SIGMOID = 4
 };
 int32_t m355_conv3d_fuses_softmax(const m355_conv3d_desc* d);
+int32_t m355_conv3d_fuses_sigmoid(const m355_conv3d_desc* d);
 /* which: 0 = forward, 1 = data gradient.  0 bytes = this descriptor has no packed form (generic direct kernels). */
 size_t m355_conv3d_packed_bytes(const m355_conv3d_desc* d, int32_t which);
 int m355_conv3d_pack(const m355_conv3d_desc* d, int32_t which, const float* w, void* packed, void* stream);
@@ -656,6 +662,15 @@ int m355_softmax_fwd(const float* x, float* y, int32_t N, int32_t C, int32_t inn
                      int64_t S, float diag_bias, void* stream);
 int m355_softmax_bwd(const float* y, const float* dy, float* dx, int32_t N, int32_t C,
                      int32_t inner, int64_t S, void* stream);
+
+/* ---------------------------------------------------------------- sigmoid
+ * nn.Sigmoid as hypothesis_class (models/modular_unet.py:26-27,84,100): y = 1 / (1 + expf(-x)) over n dense fp32
+ * elements, and its gradient dx = dy * (y * (1 - y)) from the saved y.  The stand-alone form of the M355_CONV_SIGMOID
+ * epilogue (same expression, same bits), for output convolutions that do not fuse it.  float4 accesses when every
+ * pointer is 16-byte aligned, scalar otherwise.
+ */
+int m355_sigmoid_fwd(const float* x, float* y, int64_t n, void* stream);
+int m355_sigmoid_bwd(const float* y, const float* dy, float* dx, int64_t n, void* stream);
 
 /* ------------------------------------------------------- hybrid dice loss
  * HybridLogisticDiceLoss.forward (criterions/hybrid_logistic_dice_loss.py:13-43).

@@ -16,7 +16,7 @@ M355_OK = 0
 ACT_NONE, ACT_RELU, ACT_LEAKY_RELU = 0, 1, 2
 ACT_ELU, ACT_GELU, ACT_GELU_TANH, ACT_SILU = 3, 4, 5, 6   # smooth: evaluated in fp32 in every flow (csrc/activation.hpp)
 COMPUTE_F32, COMPUTE_BF16, COMPUTE_F16, COMPUTE_F32X3 = 0, 1, 2, 3
-CONV_W_PACKED, CONV_SOFTMAX = 1, 2
+CONV_W_PACKED, CONV_SOFTMAX, CONV_SIGMOID = 1, 2, 4
 
 
 class ConvDesc(C.Structure):
@@ -139,6 +139,7 @@ SIGNATURES = {
     "m355_queue_pool_set": (C.c_int, [_P, _sz, _i32]),
     "m355_overflow_flag_set": (C.c_int, [_P, _i32]),
     "m355_conv3d_fuses_softmax": (_i32, [_CD]),
+    "m355_conv3d_fuses_sigmoid": (_i32, [_CD]),
     "m355_conv3d_packed_bytes": (_sz, [_CD, _i32]),
     "m355_conv3d_pack": (C.c_int, [_CD, _i32, _P, _P, _P]),
     "m355_conv3d_pack_batch": (C.c_int, [_P, _i32, _P]),
@@ -231,6 +232,8 @@ SIGNATURES = {
                                        _i32, C.POINTER(_i64)]),
     "m355_softmax_fwd": (C.c_int, [_P, _P, _i32, _i32, _i32, _i64, _f32, _P]),
     "m355_softmax_bwd": (C.c_int, [_P, _P, _P, _i32, _i32, _i32, _i64, _P]),
+    "m355_sigmoid_fwd": (C.c_int, [_P, _P, _i64, _P]),
+    "m355_sigmoid_bwd": (C.c_int, [_P, _P, _P, _i64, _P]),
     "m355_hybrid_loss_workspace": (_sz, [_i32, _i32, _i64]),
     "m355_hybrid_loss_fwd": (C.c_int, [_P, _P, _i32, _i32, _i64, _f32, _P, _i32, _P, _P, _P, _sz, _P]),
     "m355_hybrid_loss_bwd": (C.c_int, [_P, _P, _P, _P, _i32, _i32, _i64, _f32, _P, _i32, _P, _P]),

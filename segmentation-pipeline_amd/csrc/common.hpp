@@ -64,6 +64,11 @@ __device__ __forceinline__ T block_sum(T v, T* scratch) {
   return r;
 }
 
+// nn.Sigmoid of the hypothesis head: the one expression of m355_sigmoid_fwd and of the conv epilogues behind
+// M355_CONV_SIGMOID, so fused and unfused results have the same bits (act_fwd's SiLU form, accurate expf).
+// v < -88.7: expf(-v) = +inf and the result is +0; large v: 1; no finite input gives NaN, NaN in gives NaN out.
+__device__ __forceinline__ float sigmoid_f32(float v) { return 1.f / (1.f + expf(-v)); }
+
 // Tuning overrides (test / sweep hooks).  The M355_* environment variables are read ONCE, when the
 // library is first used, and again only on m355_reload_tuning(): the launch paths never call getenv.
 // 0 / unset = use the built-in heuristic.
@@ -71,7 +76,7 @@ struct Tuning {
   int conv_ntw = 0, conv_ksplit = 0, conv_slots = 0, conv_persistent = 1;
   int no_small = 0, smallcout_valu = 1, bww_nsplit = 0, bww_gen = 2, bww_queue = 1, h16_persistent = 1, tile16 = 1, convt_h16 = 1, h16_w8 = 1, h16_oneshot = 1, h16_xcd = 1;
   int conv_cube = 3, h16_order = 3;   // item order of the conv kernels: bit 0 = (y, z) tiles in 4x4 cubes, bit 1 = channel tile fastest
-  int fuse_softmax = 1;
+  int fuse_softmax = 1;   // M355_FUSE_SOFTMAX: the hypothesis head (softmax or sigmoid) in the output conv's epilogue
   int f32x3 = 1;         // M355_COMPUTE_F32X3 layers run conv3_f32x3_kernel (0: they run the fp32 MFMA kernels)
   int f32x3_bww = 1;     // ... and conv3_bww_x3_kernel for the weight gradient
   int f32x3_edge = 0;    // 1: the split kernel also for layers with 3..7 K-channels (M355_F32X3_EDGE; see x3_layer, conv3d_route.hpp)

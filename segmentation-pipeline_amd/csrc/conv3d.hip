@@ -686,7 +686,8 @@ __global__ void pack_w3_valu_kernel(const float* __restrict__ w, float* __restri
 __global__ __launch_bounds__(256, 2) void conv3_valu_smallcout_kernel(
     const float* __restrict__ x, const float* __restrict__ wq, const float* __restrict__ bias,
     const float* __restrict__ add, float* __restrict__ y, int Cin, int Cout, int D, int H, int W,
-    int ty_tiles, int tx_tiles, int64_t xbs, int64_t ybs, int softmax) {
+    int ty_tiles, int tx_tiles, int64_t xbs, int64_t ybs, int head) {
+  // head (wave-uniform): 0 none, 1 nn.Softmax(dim=1), 2 nn.Sigmoid (sigmoid_f32 per element, the bits of m355_sigmoid_fwd).
   // softmax: nn.Softmax(dim=1) of the hypothesis (models/modular_unet.py:100) applied in the epilogue -- all
   // (<= 4) channels of a voxel are in this thread's registers, so the logits never travel through HBM.  Same
   // formula and order as softmax_fwd_kernel (max, sum of expf in channel order, one reciprocal): identical bits.
@@ -810,7 +811,7 @@ __global__ __launch_bounds__(256, 2) void conv3_valu_smallcout_kernel(
       }
     }
   }
-  if (softmax) {
+  if (head == 1) {
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
       float mx = -INFINITY;
@@ -826,6 +827,12 @@ __global__ __launch_bounds__(256, 2) void conv3_valu_smallcout_kernel(
       for (int o = 0; o < 4; ++o)
         if (o < Cout) val[o][k] = expf(val[o][k] - mx) * inv;
     }
+  } else if (head == 2) {
+#pragma unroll
+    for (int o = 0; o < 4; ++o)
+#pragma unroll
+      for (int k = 0; k < 8; ++k)
+        if (o < Cout) val[o][k] = sigmoid_f32(val[o][k]);
   }
 #pragma unroll
   for (int o = 0; o < 4; ++o) {
@@ -1946,7 +1953,7 @@ int launch_f32_conv(const ConvRoute& r, const ConvCall& c) {
   if (r.aux & AUX_PACK_W) launch_pack_weights(r, d, r.transpose, c.w, wp, st);
   if (r.kind == ConvKind::SmallCoutValu) {   // packed-FMA kernel (see conv3_valu_smallcout_kernel)
     hipLaunchKernelGGL(conv3_valu_smallcout_kernel, r.grid, dim3(256), 0, st, c.in, wp, c.bias, c.add, c.out, d->Cin, d->Cout,
-                       D, H, W, (int)ceil_div(H, VS_TY), (int)ceil_div(W, VS_TX), r.in_bs, r.out_bs, r.softmax ? 1 : 0);
+                       D, H, W, (int)ceil_div(H, VS_TY), (int)ceil_div(W, VS_TX), r.in_bs, r.out_bs, r.head);
     return check_launch("conv3_valu_smallcout");
   }
   if (r.kind == ConvKind::SmallCoutToeplitz) {

@@ -359,6 +359,26 @@ __device__ __forceinline__ void store_conv_tile_softmax(const f32x16 (&acc)[NTW]
   }
 }
 
+// ... and with nn.Sigmoid (M355_CONV_SIGMOID): sigmoid_f32 of bias + accumulator per channel, the bits of m355_sigmoid_fwd.
+template <int NTW, int GY>
+__device__ __forceinline__ void store_conv_tile_sigmoid(const f32x16 (&acc)[NTW], float* __restrict__ dst,
+                                                        const float* __restrict__ bias, int Cout, int z, int y0, int xg,
+                                                        int ly, int half, int D, int H, int W, bool lane_ok) {
+  const int64_t HW = (int64_t)H * W, DHW = HW * D;
+  float bb[4];
+#pragma unroll
+  for (int c = 0; c < 4; ++c) bb[c] = (bias && c < Cout) ? bias[c] : 0.f;
+#pragma unroll
+  for (int g = 0; g < NTW; ++g) {
+    const int yg = y0 + g * GY + ly;
+    if (!(lane_ok && half == 0 && yg < H)) continue;
+    const int64_t base = (int64_t)z * HW + (int64_t)yg * W + xg;
+#pragma unroll
+    for (int c = 0; c < 4; ++c)
+      if (c < Cout) dst[base + (int64_t)c * DHW] = sigmoid_f32(acc[g][c] + bb[c]);
+  }
+}
+
 // ------------------------------------------------------------------ the kernel
 #ifdef M355_H16_STAMPS
 // Diagnostic build only (tools/h16_stamps.py): per-workgroup cycle sums of the phases of a chunk, wave 0.
@@ -378,13 +398,16 @@ __device__ unsigned long long m355_h16_stamps[1024][8];
 // the chain ticket -> loads -> commit -> MFMAs -> stores of a persistent workgroup is mostly latency (a single-chunk
 // item has ~1 us of MFMAs but costs ~8 us), and what hides latency there is simply MORE independent workgroups:
 // two resident per CU, the next one dispatched by the hardware the moment one retires.
-template <int NTW, int GX, typename HT, bool OUT16, int NW = 4, bool ONE = false>
+// SIGMOID: the head epilogue (`head` != 0) is nn.Sigmoid instead of nn.Softmax(dim=1).  Instantiations of their own,
+// launched for M355_CONV_SIGMOID alone: with the choice made at run time six of the existing instantiations gained
+// registers and one lost an occupancy step (profiles/sigmoid_head_resources.txt).
+template <int NTW, int GX, typename HT, bool OUT16, int NW = 4, bool ONE = false, bool SIGMOID = false>
 __global__ __launch_bounds__(NW * 64, (NW == 8 ? 1 : (NTW <= 4 ? 2 : 1))) void conv3_h16_kernel(
     const HT* __restrict__ x16, const HT* __restrict__ wp, const float* __restrict__ bias,
     const float* __restrict__ add, float* __restrict__ y, float* __restrict__ slab, int CB, int Cout, int D, int H,
     int W, int cout_pad, int tz_tiles, int ty_tiles, int tx_tiles, int otiles, int nchunks, int ksplit, int nbatch,
     int64_t xbs16, int64_t ybs, int64_t slab_stride, float* __restrict__ stat, int* __restrict__ work_counter,
-    int stagger, int softmax, int order, int* __restrict__ oflag) {
+    int stagger, int head, int order, int* __restrict__ oflag) {
   using T = FwdTile<NTW, GX>;
   using hx8 = typename H16<HT>::x8;
   constexpr int GY = T::GY, TZ = NW, TY = T::TY, TX = T::TX, RS = T::RS, PS = T::PS, HV = (TZ + 2) * PS;
@@ -722,7 +745,10 @@ __global__ __launch_bounds__(NW * 64, (NW == 8 ? 1 : (NTW <= 4 ? 2 : 1))) void c
         if constexpr (OUT16)
           store_conv_tile_c8<NTW, GY, HT>(acc, reinterpret_cast<HT*>(y) + (int64_t)cur.n * ybs, bias, cur.o0, Cout, z,
                                           cur.y0, xg, ly, half, H, W, (int64_t)S, lane_ok, st, sat);
-        else if (softmax)   // (host: Cout <= 4, one channel tile, no residual, no statistics)
+        else if (head && SIGMOID)
+          store_conv_tile_sigmoid<NTW, GY>(acc, y + (int64_t)cur.n * ybs, bias, Cout, z, cur.y0, xg, ly, half, D, H, W,
+                                           lane_ok);
+        else if (head)   // (host: Cout <= 4, one channel tile, no residual, no statistics)
           store_conv_tile_softmax<NTW, GY>(acc, y + (int64_t)cur.n * ybs, bias, Cout, z, cur.y0, xg, ly, half, D, H, W,
                                            lane_ok);
         else
@@ -847,7 +873,7 @@ template <int NTW, typename HT>
 __global__ __launch_bounds__(256, 2) void conv3_cout4_h16_kernel(
     const HT* __restrict__ x16, const HT* __restrict__ wp, const float* __restrict__ bias, float* __restrict__ y, int CB,
     int Cout, int D, int H, int W, int cout_pad, int tz_tiles, int ty_tiles, int tx_tiles, int nchunks, int64_t xbs16,
-    int64_t ybs, int softmax) {
+    int64_t ybs, int head) {   // head: 0 none, 1 softmax, 2 sigmoid (wave-uniform)
   using T = FwdTile<NTW, 32>;
   using hx8 = typename H16<HT>::x8;
   constexpr int TZ = 4, TY = T::TY, RS = T::RS, PS = T::PS, HV = (TZ + 2) * PS;
@@ -967,7 +993,7 @@ __global__ __launch_bounds__(256, 2) void conv3_cout4_h16_kernel(
         if (c < Cout) mx = fmaxf(mx, v[c]);
       }
       const int64_t base = (int64_t)z * iHW + (int64_t)yg * W + xg;
-      if (softmax) {
+      if (head == 1) {
 #pragma unroll
         for (int c = 0; c < 4; ++c)
           if (c < Cout) sum += expf(v[c] - mx);
@@ -975,6 +1001,10 @@ __global__ __launch_bounds__(256, 2) void conv3_cout4_h16_kernel(
 #pragma unroll
         for (int c = 0; c < 4; ++c)
           if (c < Cout) dst[base + (int64_t)c * DHW] = expf(v[c] - mx) * inv;
+      } else if (head == 2) {
+#pragma unroll
+        for (int c = 0; c < 4; ++c)
+          if (c < Cout) dst[base + (int64_t)c * DHW] = sigmoid_f32(v[c]);
       } else {
 #pragma unroll
         for (int c = 0; c < 4; ++c)
@@ -1018,14 +1048,20 @@ static void launch_h16(const ConvRoute& r, const ConvCall& c, const HT* x16, con
     if constexpr (GX == 32 && NTW == 4)
       hipLaunchKernelGGL((conv3_cout4_h16_kernel<4, HT>), r.grid, dim3(256), 0, c.st, x16, wp, bias, c.out, (int)c8_blocks(r.kin),
                          r.mout, D, H, W, p.mout_pad, p.tz_tiles, p.ty_tiles, p.tx_tiles, p.nchunks, r.in16_bs, r.out_bs,
-                         r.softmax ? 1 : 0);
+                         r.head);
     return;
   }
   const auto launch = [&](auto kern) {
     hipLaunchKernelGGL(kern, r.grid, dim3(r.block), 0, c.st, x16, wp, bias, add, c.out, slab, (int)c8_blocks(r.kin), r.mout, D, H,
                        W, p.mout_pad, p.tz_tiles, p.ty_tiles, p.tx_tiles, p.otiles, p.nchunks, p.ksplit, N, r.in16_bs, r.out_bs,
-                       (int64_t)N * r.mout * D * H * W, stat, work_counter, r.sched, r.softmax ? 1 : 0, r.order, c.oflag);
+                       (int64_t)N * r.mout * D * H * W, stat, work_counter, r.sched, r.head, r.order, c.oflag);
   };
+  if (r.sigmoid) {   // (check_conv: fp32 output, unsplit plan) the instantiations with the sigmoid epilogue
+    if (r.kind == ConvKind::H16OneShot) return launch(conv3_h16_kernel<NTW, GX, HT, false, 4, true, true>);
+    if constexpr (NTW == 2 && GX == 32)
+      if (r.kind == ConvKind::H16Queue8) return launch(conv3_h16_kernel<NTW, GX, HT, false, 8, false, true>);
+    return launch(conv3_h16_kernel<NTW, GX, HT, false, 4, false, true>);
+  }
   with_bool(out16, [&](auto O) {
     constexpr bool OUT16 = decltype(O)::value;
     if (r.kind == ConvKind::H16OneShot) return launch(conv3_h16_kernel<NTW, GX, HT, OUT16, 4, true>);   // one item per workgroup

@@ -35,6 +35,7 @@ extern "C" size_t m355_conv3d_packed_bytes(const m355_conv3d_desc* d, int32_t wh
 extern "C" int64_t m355_conv3d_stats_slots(const m355_conv3d_desc* d) { return d ? query_conv(d, 0).stats_slots : 0; }
 extern "C" int64_t m355_conv3d_stats_slots_c8(const m355_conv3d_desc* d) { return d ? query_conv(d, 0).stats_slots_c8 : 0; }
 extern "C" int32_t m355_conv3d_fuses_softmax(const m355_conv3d_desc* d) { return d && query_conv(d, 0).fuses_softmax ? 1 : 0; }
+extern "C" int32_t m355_conv3d_fuses_sigmoid(const m355_conv3d_desc* d) { return m355_conv3d_fuses_softmax(d); }   // the same epilogue slot
 // (the codes: include/m355seg.h; 2 = the small-Cout forward, conv3_valu_smallcout_kernel unless M355_SMALLCOUT_VALU=0)
 extern "C" int m355_conv3d_plan(const m355_conv3d_desc* d, int32_t which, int32_t* out4) {
   M355_REQUIRE(d && out4, M355_EINVALID_ARG, "conv3d_plan: null pointer");

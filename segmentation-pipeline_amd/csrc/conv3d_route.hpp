@@ -543,11 +543,12 @@ struct ConvRoute {
   size_t workspace_bytes;     // fp32 NCDHW input (16-bit modes: + the c8 staging copy)
   size_t h16_workspace_bytes; // c8 input handed over by the caller
   int64_t stats_slots, stats_slots_c8;   // fused statistics partials per (sample, channel): fp32 / c8 output; 0 = none
-  bool fuses_softmax;
+  bool fuses_softmax;         // ... and m355_conv3d_fuses_sigmoid: one epilogue slot, either head
   int32_t plan_code[4];       // m355_conv3d_plan
   // the call
   bool transpose;             // data gradient: flipped / transposed filter, K-channels = Cout
-  bool prepacked, out16, softmax;
+  bool prepacked, out16, softmax, sigmoid;
+  int head;                   // kernel argument of the epilogue: 0 none, 1 softmax, 2 sigmoid
   int kin, mout;
   int64_t in_bs, in16_bs, out_bs;   // elements between samples: fp32 input, c8 input (the staging copy: dense), output
   dim3 grid;                  // main launch; grid.x == 0: none (every channel of a <= 16 channel output is on the 16-row tile)
@@ -593,6 +594,8 @@ static inline ConvRoute route_conv(const m355_conv3d_desc* d, const ConvArgs& a)
   r.prepacked = (d->flags & M355_CONV_W_PACKED) != 0;
   r.out16 = conv_entry_c8_out(a.entry);
   r.softmax = !dgrad && !r.out16 && (d->flags & M355_CONV_SOFTMAX) != 0;
+  r.sigmoid = !dgrad && !r.out16 && (d->flags & M355_CONV_SIGMOID) != 0;
+  r.head = r.softmax ? 1 : (r.sigmoid ? 2 : 0);
   const int64_t x_dense = (int64_t)d->Cin * S, y_dense = (int64_t)d->Cout * OS;
   r.in_bs = dgrad ? dense_or(d->y_batch_stride, y_dense) : dense_or(d->x_batch_stride, x_dense);
   r.in16_bs = dense_or(in16 ? a.bs[0] : 0, c8_blocks(kin) * S * 8);
@@ -645,7 +648,7 @@ static inline ConvRoute route_conv(const m355_conv3d_desc* d, const ConvArgs& a)
     // -- four taps per k-step --, <= 4 M-channels into a plain fp32 output -- tap rows folded onto the MFMA's M side
     const bool edge = p.ksplit == 1 && p.gx == 32 && p.nw == 4 && !tuning().no_small;
     const int64_t items = sp * p.otiles * d->N, items_cout4 = sp * d->N;
-    if (edge && kin <= 4 && r.out16 && !r.softmax && items > 0 && items < (1ll << 31)) {
+    if (edge && kin <= 4 && r.out16 && !r.head && items > 0 && items < (1ll << 31)) {
       r.kind = ConvKind::H16C4;
       r.grid = dim3((unsigned)items);
     } else if (edge && mout <= 4 && !r.out16 && !a.add && !a.stat && p.ntw == 4 && p.otiles == 1 && items_cout4 > 0 &&
@@ -706,12 +709,15 @@ static inline int check_conv(const ConvArgs& a, const m355_conv3d_desc* d, ConvR
   const bool dgrad = conv_entry_dgrad(a.entry), c8_entry = a.entry >= CE_FWD_H16;
   M355_REQUIRE(a.entry != CE_FWD_STATS || a.stat, M355_EINVALID_ARG, "conv3d_fwd_stats: null statistics buffer");
   if (int rc = validate_conv(d, who)) return rc;
+  const bool softmax_flag = (d->flags & M355_CONV_SOFTMAX) != 0, sigmoid_flag = (d->flags & M355_CONV_SIGMOID) != 0;
+  M355_REQUIRE(!(softmax_flag && sigmoid_flag), M355_EINVALID_ARG, "%s: M355_CONV_SOFTMAX and M355_CONV_SIGMOID exclude each other", who);
   const ConvRoute& r = *route = route_conv(d, a);
-  const bool softmax_flag = (d->flags & M355_CONV_SOFTMAX) != 0;
   if (!c8_entry) {
     if (!dgrad) {
       M355_REQUIRE(!softmax_flag || r.fuses_softmax, M355_EUNSUPPORTED,
                    "conv3d_fwd: M355_CONV_SOFTMAX needs m355_conv3d_fuses_softmax(desc) != 0");
+      M355_REQUIRE(!sigmoid_flag || r.fuses_softmax, M355_EUNSUPPORTED,
+                   "conv3d_fwd: M355_CONV_SIGMOID needs m355_conv3d_fuses_sigmoid(desc) != 0");
       M355_REQUIRE(!a.stat || r.stats_slots > 0, M355_EINVALID_ARG,
                    "conv3d_fwd_stats: this descriptor has no fused statistics (m355_conv3d_stats_slots() == 0)");
     }
@@ -728,6 +734,8 @@ static inline int check_conv(const ConvArgs& a, const m355_conv3d_desc* d, ConvR
                  "%s: this descriptor has no fused statistics (m355_conv3d_stats_slots%s() == 0)", who, r.out16 ? "_c8" : "");
     M355_REQUIRE(!r.softmax || r.fuses_softmax, M355_EUNSUPPORTED,
                  "%s: M355_CONV_SOFTMAX needs m355_conv3d_fuses_softmax(desc) != 0", who);
+    M355_REQUIRE(!r.sigmoid || r.fuses_softmax, M355_EUNSUPPORTED,
+                 "%s: M355_CONV_SIGMOID needs m355_conv3d_fuses_sigmoid(desc) != 0", who);
   }
   M355_REQUIRE(a.ws_bytes >= r.need && (a.ws || !r.need), M355_EWORKSPACE, "conv3d: workspace too small (%zu < %zu)",
                a.ws_bytes, r.need);
@@ -747,6 +755,8 @@ static inline int check_conv(const ConvArgs& a, const m355_conv3d_desc* d, ConvR
                "conv3d(16-bit operands): a c8 output takes no fused `add` and must be 16B aligned");
   M355_REQUIRE(!r.softmax || (r.mout <= 4 && r.plan.ksplit == 1 && !a.add && !a.stat && !r.out16), M355_EUNSUPPORTED,
                "conv3d(16-bit operands): the softmax epilogue needs Cout <= 4, an unsplit plan, fp32 output, no add / statistics");
+  M355_REQUIRE(!r.sigmoid || (r.mout <= 4 && r.plan.ksplit == 1 && !a.add && !a.stat && !r.out16), M355_EUNSUPPORTED,
+               "conv3d(16-bit operands): the sigmoid epilogue needs Cout <= 4, an unsplit plan, fp32 output, no add / statistics");
   return M355_OK;
 }
 

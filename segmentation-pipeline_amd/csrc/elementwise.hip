@@ -390,6 +390,42 @@ __global__ __launch_bounds__(256) void add_kernel(const float* __restrict__ a,
   }
 }
 
+// -------------------------------------------------------------------- sigmoid
+// nn.Sigmoid over n dense elements (the hypothesis head where the output conv has no epilogue for it).  VEC: every
+// pointer is 16-byte aligned -- a float4 body and a scalar tail of n % 4 elements; otherwise one element per thread.
+template <bool VEC>
+__global__ __launch_bounds__(256) void sigmoid_fwd_kernel(const float* __restrict__ x, float* __restrict__ y, int64_t n) {
+  const int64_t tid = blockIdx.x * 256ll + threadIdx.x, step = gridDim.x * 256ll;
+  if (VEC) {
+    const int64_t n4 = n / 4;
+    for (int64_t i = tid; i < n4; i += step) {
+      const float4 v = reinterpret_cast<const float4*>(x)[i];
+      reinterpret_cast<float4*>(y)[i] = make_float4(sigmoid_f32(v.x), sigmoid_f32(v.y), sigmoid_f32(v.z), sigmoid_f32(v.w));
+    }
+    for (int64_t i = n4 * 4 + tid; i < n; i += step) y[i] = sigmoid_f32(x[i]);
+  } else {
+    for (int64_t i = tid; i < n; i += step) y[i] = sigmoid_f32(x[i]);
+  }
+}
+
+// dx = dy * (y * (1 - y))
+template <bool VEC>
+__global__ __launch_bounds__(256) void sigmoid_bwd_kernel(const float* __restrict__ y, const float* __restrict__ dy,
+                                                          float* __restrict__ dx, int64_t n) {
+  const int64_t tid = blockIdx.x * 256ll + threadIdx.x, step = gridDim.x * 256ll;
+  if (VEC) {
+    const int64_t n4 = n / 4;
+    for (int64_t i = tid; i < n4; i += step) {
+      const float4 v = reinterpret_cast<const float4*>(y)[i], g = reinterpret_cast<const float4*>(dy)[i];
+      reinterpret_cast<float4*>(dx)[i] = make_float4(g.x * (v.x * (1.f - v.x)), g.y * (v.y * (1.f - v.y)),
+                                                     g.z * (v.z * (1.f - v.z)), g.w * (v.w * (1.f - v.w)));
+    }
+    for (int64_t i = n4 * 4 + tid; i < n; i += step) dx[i] = dy[i] * (y[i] * (1.f - y[i]));
+  } else {
+    for (int64_t i = tid; i < n; i += step) dx[i] = dy[i] * (y[i] * (1.f - y[i]));
+  }
+}
+
 // ---------------------------------------------- space-to-depth / depth-to-space (factor 2)
 // TO_DEPTH: full[n,c,2z+pz,2y+py,2x+px] -> packed[n,c*8+p,z,y,x]; otherwise the inverse.
 // One thread per (row pair of the full tensor): reads/writes float2 on the full-resolution side.
@@ -801,6 +837,26 @@ extern "C" int m355_softmax_bwd(const float* y, const float* dy, float* dx, int3
   hipLaunchKernelGGL(softmax_bwd_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, y,
                      dy, dx, N, C, inner, S);
   return check_launch("softmax_bwd");
+}
+
+extern "C" int m355_sigmoid_fwd(const float* x, float* y, int64_t n, void* stream) {
+  M355_REQUIRE(x && y, M355_EINVALID_ARG, "sigmoid_fwd: null pointer");
+  M355_REQUIRE(n > 0, M355_EINVALID_ARG, "sigmoid_fwd: non-positive size");
+  if ((((uintptr_t)x | (uintptr_t)y) & 15) == 0)
+    hipLaunchKernelGGL(sigmoid_fwd_kernel<true>, dim3(grid_for(ceil_div(n, 4))), dim3(256), 0, (hipStream_t)stream, x, y, n);
+  else
+    hipLaunchKernelGGL(sigmoid_fwd_kernel<false>, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, x, y, n);
+  return check_launch("sigmoid_fwd");
+}
+
+extern "C" int m355_sigmoid_bwd(const float* y, const float* dy, float* dx, int64_t n, void* stream) {
+  M355_REQUIRE(y && dy && dx, M355_EINVALID_ARG, "sigmoid_bwd: null pointer");
+  M355_REQUIRE(n > 0, M355_EINVALID_ARG, "sigmoid_bwd: non-positive size");
+  if ((((uintptr_t)y | (uintptr_t)dy | (uintptr_t)dx) & 15) == 0)
+    hipLaunchKernelGGL(sigmoid_bwd_kernel<true>, dim3(grid_for(ceil_div(n, 4))), dim3(256), 0, (hipStream_t)stream, y, dy, dx, n);
+  else
+    hipLaunchKernelGGL(sigmoid_bwd_kernel<false>, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, y, dy, dx, n);
+  return check_launch("sigmoid_bwd");
 }
 
 extern "C" int m355_copy_channels(const float* src, float* dst, int32_t N, int32_t C, int64_t S,

@@ -102,11 +102,14 @@ def _run_hypothesis(m, x):
         if m.dim != 1:
             raise NotImplementedError("only Softmax(dim=1) has a HIP kernel")
         return ops.softmax_channels(x)
+    if type(m) is nn.Sigmoid:   # the exact type: nn.LogSigmoid, nn.Hardsigmoid ... compute something else
+        return ops.sigmoid(x)
     if isinstance(m, StochasticMatrix):
         return m(x)
     if isinstance(m, nn.Identity):
         return x
-    raise NotImplementedError(f"hypothesis_class {type(m).__name__} has no HIP kernel")
+    raise NotImplementedError(f"hypothesis_class {type(m).__name__} has no HIP kernel "
+                              "(supported: Softmax(dim=1), Sigmoid, StochasticMatrix, Identity)")
 
 
 class ModularUNet(nn.Module):
@@ -235,5 +238,8 @@ class ModularUNet(nn.Module):
         if isinstance(self.hypothesis, nn.Softmax) and self.hypothesis.dim == 1 and isinstance(self.out_conv, nn.Conv3d):
             # out conv + Softmax(dim=1) (:99-100) as one op: the softmax runs in the conv epilogue
             return run_conv(self.out_conv, x, softmax=True)
+        if type(self.hypothesis) is nn.Sigmoid and isinstance(self.out_conv, nn.Conv3d):
+            # out conv + Sigmoid as one op, the same way
+            return run_conv(self.out_conv, x, sigmoid=True)
         x = run_conv(self.out_conv, x)
         return _run_hypothesis(self.hypothesis, ops.as_f32(x))

@@ -154,4 +154,6 @@ class NestedResUNet(nn.Module):
         if isinstance(self.hypothesis, nn.Softmax) and self.hypothesis.dim == 1:
             # out conv + Softmax(dim=1) (:103-104) as one op: the softmax runs in the conv epilogue where the variant has one
             return run_conv(self.out_conv, x0_3, softmax=True)
+        if type(self.hypothesis) is nn.Sigmoid and isinstance(self.out_conv, nn.Conv3d):
+            return run_conv(self.out_conv, x0_3, sigmoid=True)   # ... or Sigmoid, the same way
         return _run_hypothesis(self.hypothesis, ops.as_f32(run_conv(self.out_conv, x0_3)))

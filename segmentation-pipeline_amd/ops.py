@@ -664,10 +664,11 @@ def _c8_channel_partials(x16: Act16, stats: dict):
     stats["partials"], stats["slots"] = part, slots
 
 
-def _conv3d_act16(x16: Act16, weight, bias, add, stats, c8_out=False, softmax=False):
+def _conv3d_act16(x16: Act16, weight, bias, add, stats, c8_out=False, softmax=False, sigmoid=False):
     """3x3x3 / s1 / p1 forward on a c8 input (no autograd: the c8 flow only exists under no_grad).  c8_out: the
     result (a pre-norm tensor) is written by the conv epilogue as c8 too and returned as an Act16.  softmax:
-    nn.Softmax(dim=1) of the result (the conv's epilogue where the kernel variant has one, else a separate pass)."""
+    nn.Softmax(dim=1) of the result (the conv's epilogue where the kernel variant has one, else a separate pass);
+    sigmoid: nn.Sigmoid of it, the same way."""
     L = _lib.lib()
     _require(weight, bias, add)
     weight = weight.contiguous()
@@ -680,7 +681,9 @@ def _conv3d_act16(x16: Act16, weight, bias, add, stats, c8_out=False, softmax=Fa
     wbuf, flags = _packed_weight(weight, d, 0)
     fuse_sm = (softmax and not c8_out and add is None and stats is None
                and L.m355_conv3d_fuses_softmax(C.byref(d)) != 0)
-    d = _with_flags(d, flags | (_lib.CONV_SOFTMAX if fuse_sm else 0))
+    fuse_sg = (sigmoid and not c8_out and add is None and stats is None
+               and L.m355_conv3d_fuses_sigmoid(C.byref(d)) != 0)
+    d = _with_flags(d, flags | (_lib.CONV_SOFTMAX if fuse_sm else 0) | (_lib.CONV_SIGMOID if fuse_sg else 0))
     ws = _workspace(L.m355_conv3d_h16_workspace(C.byref(d), 0), x16.device)
     prof, plan = _prof_gate("conv3d_fwd", d, 0)
     if prof is not None:
@@ -709,6 +712,8 @@ def _conv3d_act16(x16: Act16, weight, bias, add, stats, c8_out=False, softmax=Fa
         _c8_channel_partials(y, stats)
     if softmax and not fuse_sm:
         y = softmax_channels(as_f32(y))
+    if sigmoid and not fuse_sg:
+        y = _SigmoidFn.apply(as_f32(y))
     return y
 
 
@@ -797,8 +802,9 @@ class _C8ConvMeta:
     x16: "Act16"                      # the whole (possibly concatenated) conv input
     part_blocks: Sequence[int]        # channel blocks of each autograd part of it
     out16: Optional["Act16"] = None   # c8 destination (None with f32_out)
-    f32_out: bool = False             # fp32 NCDHW result (the out conv), optionally with the fused softmax
+    f32_out: bool = False             # fp32 NCDHW result (the out conv), optionally with the fused softmax / sigmoid
     softmax: bool = False
+    sigmoid: bool = False
     stats: Optional[dict] = None
     has_add: bool = False
 
@@ -819,7 +825,8 @@ class _Conv3dC8Fn(torch.autograd.Function):
         d = _conv_desc(N, Cin, Cout, D, H, W, 3, 1, 1, 0, 0, compute=x16.compute)
         wbuf, flags = _packed_weight(weight, d, 0)
         fuse_sm = meta.softmax and add is None and L.m355_conv3d_fuses_softmax(C.byref(d)) != 0
-        dk = _with_flags(d, flags | (_lib.CONV_SOFTMAX if fuse_sm else 0))
+        fuse_sg = meta.sigmoid and add is None and L.m355_conv3d_fuses_sigmoid(C.byref(d)) != 0
+        dk = _with_flags(d, flags | (_lib.CONV_SOFTMAX if fuse_sm else 0) | (_lib.CONV_SIGMOID if fuse_sg else 0))
         ws = _workspace(L.m355_conv3d_h16_workspace(C.byref(d), 0), x16.device)
         prof, plan = _prof_gate("conv3d_fwd", d, 0)
         if prof is not None:
@@ -841,6 +848,9 @@ class _Conv3dC8Fn(torch.autograd.Function):
             if meta.softmax and not fuse_sm:
                 logits, y = y, torch.empty_like(y)
                 check(L.m355_softmax_fwd(_p(logits), _p(y), N, Cout, 1, D * H * W, 0.0, _stream()), "softmax_fwd")
+            if meta.sigmoid and not fuse_sg:
+                logits, y = y, torch.empty_like(y)
+                check(L.m355_sigmoid_fwd(_p(logits), _p(y), y.numel(), _stream()), "sigmoid_fwd")
             if x16.compute == _lib.COMPUTE_F16:     # the head of an fp16 pass: size-derived estimate (capture fallback)
                 _gs().auto = _auto_grad_scale(N * D * H * W)
                 _overflow_word(x16.device)
@@ -859,7 +869,7 @@ class _Conv3dC8Fn(torch.autograd.Function):
         ctx.has_bias = bias is not None
         ctx.x_info = (x16.C, x16.spatial, x16.compute)
         xa = x16.alias()
-        if meta.softmax:
+        if meta.softmax or meta.sigmoid:
             ctx.save_for_backward(xa, weight, out)
         else:
             ctx.save_for_backward(xa, weight)
@@ -877,11 +887,18 @@ class _Conv3dC8Fn(torch.autograd.Function):
             check(L.m355_softmax_bwd(_p(y), _p(dy), _p(dl), d.N, d.Cout, 1, y.numel() // (d.N * d.Cout), _stream()),
                   "softmax_bwd")
             dy = dl
+        elif meta.sigmoid:
+            xa, weight, y = ctx.saved_tensors
+            dy = dy.contiguous()
+            dl = torch.empty_like(y)
+            check(L.m355_sigmoid_bwd(_p(y), _p(dy), _p(dl), y.numel(), _stream()), "sigmoid_bwd")
+            dy = dl
         else:
             xa, weight = ctx.saved_tensors
         dadd = dy if (meta.has_add and ctx.needs_input_grad[2]) else None
         if meta.f32_out:        # the gradient enters the c8 flow here: this node fixes the scale of the pass
-            scale = ctx.gs.resolve(compute, dy, (id(weight), tuple(dy.shape)))
+            key = (id(weight), tuple(dy.shape), "sigmoid") if meta.sigmoid else (id(weight), tuple(dy.shape))
+            scale = ctx.gs.resolve(compute, dy, key)
             dy16 = _pack_scaled(dy, compute, scale)
         else:
             scale = ctx.gs.get(compute)
@@ -932,7 +949,7 @@ class _Conv3dC8Fn(torch.autograd.Function):
         return (dw if need_w else None, db if need_b else None, dadd, None, *dparts)
 
 
-def _conv3d_c8_train(x16: Act16, parts, weight, bias, add, stats, c8_out, softmax, out16=None):
+def _conv3d_c8_train(x16: Act16, parts, weight, bias, add, stats, c8_out, softmax, out16=None, sigmoid=False):
     """dispatch of `_conv3d_act16` while autograd records (c8 training flow)"""
     if parts is None:
         parts = [x16]
@@ -941,8 +958,8 @@ def _conv3d_c8_train(x16: Act16, parts, weight, bias, add, stats, c8_out, softma
     if c8_out and out16 is None:
         N, _, D, H, W = x16.shape
         out16 = Act16.empty(N, weight.shape[0], (D, H, W), x16.compute, x16.device)
-    meta = _C8ConvMeta(x16, [p.CB for p in parts], out16=out16, f32_out=not c8_out, softmax=softmax, stats=stats,
-                       has_add=add is not None)
+    meta = _C8ConvMeta(x16, [p.CB for p in parts], out16=out16, f32_out=not c8_out, softmax=softmax, sigmoid=sigmoid,
+                       stats=stats, has_add=add is not None)
     out = _Conv3dC8Fn.apply(weight, bias, add, meta, *[p.t for p in parts])
     if not c8_out:
         return out
@@ -1170,6 +1187,7 @@ class _ConvMeta:
     tag: str = "conv3d"
     stats: Optional[dict] = None   # filled with {"partials", "slots"} when the statistics are fused
     softmax: bool = False          # Softmax(dim=1) over the output channels fused into this op (out conv + hypothesis)
+    sigmoid: bool = False          # ... or Sigmoid, per element
     h16_train: int = 0             # set by the forward: the 16-bit compute code when the c8 training flow ran
 
 
@@ -1208,13 +1226,14 @@ class _Conv3dFn(torch.autograd.Function):
         d = _conv_desc(N, Cin, Cout, D, H, W, k, meta.stride, meta.pad, xbs, ybs, compute=_COMPUTE[_compute_mode])
         wbuf, flags = _packed_weight(weight, d, 0)
         fuse_sm = meta.softmax and L.m355_conv3d_fuses_softmax(C.byref(d)) != 0
-        dk = _with_flags(d, flags | (_lib.CONV_SOFTMAX if fuse_sm else 0))
+        fuse_sg = meta.sigmoid and L.m355_conv3d_fuses_sigmoid(C.byref(d)) != 0
+        dk = _with_flags(d, flags | (_lib.CONV_SOFTMAX if fuse_sm else 0) | (_lib.CONV_SIGMOID if fuse_sg else 0))
         # 16-bit training flow: the conv input is packed to c8 ONCE here (the library would stage the same copy
         # internally), consumed by the forward kernel and kept for the weight gradient (m355_conv3d_bwd_weight_h16
         # reads both operands as c8); the fp32 input is then not saved at all
         x16 = None
         if (H16_TRAIN_C8 and d.compute in _DT16 and k == 3 and meta.stride == 1 and meta.pad == 1
-                and Cin > 4 and Cout > 4 and not meta.softmax and D * H * W * 64 < 2 ** 31
+                and Cin > 4 and Cout > 4 and not meta.softmax and not meta.sigmoid and D * H * W * 64 < 2 ** 31
                 and ctx.needs_input_grad[0]):
             x16 = _c8_twin(x, d.compute)
             if x16 is None:
@@ -1252,11 +1271,15 @@ class _Conv3dFn(torch.autograd.Function):
             y = torch.empty_like(logits)
             check(L.m355_softmax_fwd(_p(logits), _p(y), N, Cout, 1, oshape[2] * oshape[3] * oshape[4], 0.0, _stream()),
                   "softmax_fwd")
+        if meta.sigmoid and not fuse_sg:   # ... or a separate sigmoid pass
+            logits = y.contiguous()
+            y = torch.empty_like(logits)
+            check(L.m355_sigmoid_fwd(_p(logits), _p(y), y.numel(), _stream()), "sigmoid_fwd")
         ctx.meta, ctx.desc = meta, d
         ctx.has_bias, ctx.has_add = bias is not None, add is not None
         ctx.part_channels = [p.shape[1] for p in parts]
         ctx.x16 = None
-        if meta.softmax:
+        if meta.softmax or meta.sigmoid:
             ctx.save_for_backward(x, weight, y)
         elif x16 is not None:
             ctx.x16 = (x16.C, x16.spatial, x16.compute)
@@ -1277,6 +1300,12 @@ class _Conv3dFn(torch.autograd.Function):
             dl = torch.empty_like(y)
             check(L.m355_softmax_bwd(_p(y.contiguous()), _p(dy), _p(dl), d.N, d.Cout, 1, y.numel() // (d.N * d.Cout),
                                      _stream()), "softmax_bwd")
+            dy = dl
+        elif meta.sigmoid:   # dlogits = dy * y * (1 - y)
+            x, weight, y = ctx.saved_tensors
+            dy, y = dy.contiguous(), y.contiguous()
+            dl = torch.empty_like(y)
+            check(L.m355_sigmoid_bwd(_p(y), _p(dy), _p(dl), y.numel(), _stream()), "sigmoid_bwd")
             dy = dl
         else:
             x, weight = ctx.saved_tensors
@@ -1351,13 +1380,17 @@ class _Conv3dFn(torch.autograd.Function):
 
 
 def conv3d(x, weight, bias=None, add=None, stride=1, padding=1, out: Optional[OutSlot] = None,
-           stats: Optional[dict] = None, c8_out: bool = False, softmax: bool = False):
+           stats: Optional[dict] = None, c8_out: bool = False, softmax: bool = False, sigmoid: bool = False):
     """nn.Conv3d forward (cubic kernel).  `x` is a tensor or a `Concat`; `add` is fused
     into the epilogue (y = conv(x) + bias + add).  `stats`: an empty dict asks the kernel to also
     emit the partial sums the following normalisation needs (filled in when the kernel variant
     supports it; pass it on as `NormCfg.stats`).  `c8_out`: in the c8 flow (x is an `Act16`) return the result
     as an `Act16` written by the conv epilogue (for the normalisation pass that follows).  `softmax`: apply
-    nn.Softmax(dim=1) to the result (fused into the conv epilogue where the kernel variant allows)."""
+    nn.Softmax(dim=1) to the result (fused into the conv epilogue where the kernel variant allows); `sigmoid`: apply
+    nn.Sigmoid to it, the same way.  The two exclude each other."""
+    if softmax and sigmoid:
+        raise ValueError("conv3d: softmax and sigmoid exclude each other (one hypothesis head per output convolution)")
+    head = softmax or sigmoid
     k = weight.shape[2]
     if not (weight.shape[2] == weight.shape[3] == weight.shape[4]):
         raise NotImplementedError("only cubic kernels are supported")
@@ -1371,17 +1404,17 @@ def conv3d(x, weight, bias=None, add=None, stride=1, padding=1, out: Optional[Ou
             if torch.is_grad_enabled() and (weight.requires_grad or _act16_tracks(x, *(c8_parts or ()))):
                 # c8 training flow (a conv with a fused fp32 `add` keeps its result in fp32)
                 return _conv3d_c8_train(x, c8_parts, weight, bias, as_f32(add) if add is not None else None, stats,
-                                        c8_out and not softmax and add is None, softmax)
-            return _conv3d_act16(x, weight, bias, as_f32(add) if add is not None else None, stats, c8_out and not softmax,
-                                 softmax)
+                                        c8_out and not head and add is None, softmax, sigmoid=sigmoid)
+            return _conv3d_act16(x, weight, bias, as_f32(add) if add is not None else None, stats, c8_out and not head,
+                                 softmax, sigmoid)
         if c8_parts is not None and _act16_tracks(*c8_parts):
             raise NotImplementedError("c8 training flow: only 3x3x3 / stride 1 / padding 1 convolutions read a concat buffer")
         x = x.to_f32()
     if isinstance(x, Concat):
-        meta = _ConvMeta(k, stride, padding, catbuf=x.buf, out=out, stats=stats, softmax=softmax)
+        meta = _ConvMeta(k, stride, padding, catbuf=x.buf, out=out, stats=stats, softmax=softmax, sigmoid=sigmoid)
         y = _Conv3dFn.apply(weight, bias, add, meta, *x.parts)
     else:
-        meta = _ConvMeta(k, stride, padding, out=out, stats=stats, softmax=softmax)
+        meta = _ConvMeta(k, stride, padding, out=out, stats=stats, softmax=softmax, sigmoid=sigmoid)
         y = _Conv3dFn.apply(weight, bias, add, meta, x)
     if meta.h16_train and add is None:
         # 16-bit training flow: the normalisation that follows may emit its input gradient (= this conv's output
@@ -2083,6 +2116,30 @@ class _SoftmaxFn(torch.autograd.Function):
         dx = torch.empty_like(y)
         check(L.m355_softmax_bwd(_p(y), _p(dy), _p(dx), N, Cc, inner, S, _stream()), "softmax_bwd")
         return dx, None, None
+
+
+class _SigmoidFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x):
+        _require(x)
+        x = x.contiguous()
+        y = torch.empty_like(x)
+        check(_lib.lib().m355_sigmoid_fwd(_p(x), _p(y), x.numel(), _stream()), "sigmoid_fwd")
+        ctx.save_for_backward(y)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        (y,) = ctx.saved_tensors
+        dy = dy.contiguous()
+        dx = torch.empty_like(y)
+        check(_lib.lib().m355_sigmoid_bwd(_p(y), _p(dy), _p(dx), y.numel(), _stream()), "sigmoid_bwd")
+        return dx
+
+
+def sigmoid(x):
+    """nn.Sigmoid (the hypothesis head where the output convolution has no epilogue for it)"""
+    return _SigmoidFn.apply(as_f32(x))
 
 
 def softmax_channels(x, inner=1, diag_bias=0.0):
