@@ -144,12 +144,14 @@ def _workspace(nbytes, device):
 
 def _dense_channels(t):
     """Return (tensor, batch_stride) for a 5-D tensor whose (C, D, H, W) block is
-    dense; channel slices of a concat buffer qualify.  Anything else is compacted."""
+    dense and whose samples do not overlap (batch stride >= C*S); channel slices of a
+    concat buffer qualify.  Anything else is compacted -- a batch-expanded gradient
+    (stride 0, what `y.sum(dim=0)` hands back) among them: 0 means "dense" in the C ABI."""
     N, Cc, D, H, W = t.shape
     st = t.stride()
     S = D * H * W
     ok = ((W == 1 or st[4] == 1) and (H == 1 or st[3] == W) and (D == 1 or st[2] == H * W)
-          and (Cc == 1 or st[1] == S))
+          and (Cc == 1 or st[1] == S) and (N == 1 or st[0] >= Cc * S))
     if not ok:
         t = t.contiguous()
         return t, Cc * S
@@ -724,10 +726,12 @@ def _conv3d_act16(x16: Act16, weight, bias, add, stats, c8_out=False, softmax=Fa
 # operands through the `Act16` objects in `meta` (pointers, batch strides) and take the handles only as graph edges.
 def _c8t(t):
     """(tensor, batch stride) of a [N, CB, S, 8] c8 tensor whose samples are dense -- a slot alias or a slice of a
-    gradient buffer along the block axis; anything else is compacted first"""
+    gradient buffer along the block axis; anything else (overlapping samples, such as a batch-expanded gradient with
+    stride 0, included) is compacted first"""
     N, CB, S, _ = t.shape
     st = t.stride()
-    if st[3] != 1 or st[2] != 8 or (CB > 1 and st[1] != S * 8) or (N > 1 and st[0] % 8):
+    if (st[3] != 1 or st[2] != 8 or (CB > 1 and st[1] != S * 8)
+            or (N > 1 and (st[0] % 8 or st[0] < CB * S * 8))):
         t = t.contiguous()
         return t, CB * S * 8
     return t, (st[0] if N > 1 else CB * S * 8)
@@ -1049,7 +1053,9 @@ class _NormActC8Fn(torch.autograd.Function):
                                          _p(gamma), _p(beta), _p(dx16), 0, _p(dgamma), _p(dbeta), training, unscale, compute,
                                          _p(ws), ws.numel(), _stream()), "norm_act_bwd_c8")
         dadd = dy16 if (ctx.has_add and ctx.needs_input_grad[3]) else None
-        return dx16, dgamma, dbeta, dadd, None
+        # (x_t is None for the output of a convolution without history -- frozen weight and bias on the network input: autograd
+        # refuses a gradient for an input that was not a tensor)
+        return dx16 if ctx.needs_input_grad[0] else None, dgamma, dbeta, dadd, None
 
 
 def _norm_act_c8_train(x: Act16, gamma, beta, add, cfg: "NormCfg", pool=False):
@@ -1174,6 +1180,12 @@ class _ConvTC8Fn(torch.autograd.Function):
 def _act16_tracks(*xs):
     """autograd is recording and one of these c8 activations carries a gradient"""
     return torch.is_grad_enabled() and any(isinstance(x, Act16) and x.requires_grad for x in xs)
+
+
+def _tracks_any(*ts):
+    """one of these tensors (parameters: weight, bias; a fused fp32 `add`) requires grad -- a frozen weight with a
+    trainable bias still needs the autograd function"""
+    return any(isinstance(t, torch.Tensor) and t.requires_grad for t in ts)
 
 
 # ------------------------------------------------------------------ conv3d
@@ -1401,7 +1413,7 @@ def conv3d(x, weight, bias=None, add=None, stride=1, padding=1, out: Optional[Ou
         return pack_act16(conv3d(x, weight, bias, add, stride, padding, None, stats), out.buf16.compute, out.act16())
     if isinstance(x, Act16):
         if k == 3 and stride == 1 and padding == 1:
-            if torch.is_grad_enabled() and (weight.requires_grad or _act16_tracks(x, *(c8_parts or ()))):
+            if torch.is_grad_enabled() and (_tracks_any(weight, bias, add) or _act16_tracks(x, add, *(c8_parts or ()))):
                 # c8 training flow (a conv with a fused fp32 `add` keeps its result in fp32)
                 return _conv3d_c8_train(x, c8_parts, weight, bias, as_f32(add) if add is not None else None, stats,
                                         c8_out and not head and add is None, softmax, sigmoid=sigmoid)
@@ -1476,7 +1488,7 @@ def conv_transpose3d(x, weight, bias=None, stride=2, padding=0, output_padding=0
     k = weight.shape[2]
     if isinstance(x, Act16):
         if k == 2 and stride == 2 and padding == 0 and output_padding == 0:   # c8 -> c8 kernel
-            if torch.is_grad_enabled() and (weight.requires_grad or x.requires_grad):
+            if torch.is_grad_enabled() and (_tracks_any(weight, bias) or x.requires_grad):
                 y16 = out.act16() if (out is not None and out.buf16 is not None) else None
                 if y16 is None:
                     N, Cin, D, H, W = x.shape
