@@ -690,6 +690,35 @@ int m355_hybrid_loss_bwd(const float* p, const float* t, const float* sums,
                          float dice_weight, const float* class_weights, int32_t square_dice,
                          float* dp, void* stream);
 
+/* ------------------------------------------------ binary cross-entropy + dice loss
+ * HybridBinaryLogisticDiceLoss (criterions/hybrid_binary_logistic_dice_loss.py): the loss of a sigmoid
+ * head, every channel a binary problem of its own.  x and the target t (values in [0, 1], soft targets allowed):
+ * dense fp32 [N, C, S], rows at nc * S for any S (no alignment requirement).  eps = 1e-8.
+ *   from_logits == 0   x = p (probabilities): q = 1 - p, lp = log((p + eps) / (1 + eps)), lq = log((q + eps) / (1 + eps));
+ *                      no expf is evaluated
+ *   from_logits != 0   x = z (logits): p = 1 / (1 + expf(-z)), the bits of m355_sigmoid_fwd; lp = -softplus(-z),
+ *                      lq = -softplus(z), softplus(v) = max(v, 0) + log1p(exp(-|v|)); no eps
+ *   dice_nc     = 2 sum(p t) / (sum p^2 + sum t^2 + eps)                (sum p + sum t without square_dice)
+ *   logistic_nc = cw[c] * (pw[c] * sum(t lp) + sum((1 - t) lq)) / S     (cw = class_weights, pw = pos_weight, or 1)
+ *   out3 = {loss, dice_loss, logistic_loss} = {(1 - w) logistic_loss + w dice_loss, mean(1 - dice_nc), mean(-logistic_nc)}
+ * sums (kept for backward): [N*C*5] = {sum p t, sum p(^2), sum t(^2), sum t lp, sum (1 - t) lq}, unweighted.
+ * The Dice sums and expressions are those of m355_hybrid_loss_fwd: without from_logits, out3[1] has its bits.
+ * Deterministic (fp64 block and cross-chunk sums in a fixed order, no float atomics).  Errors as m355_hybrid_loss_*:
+ * null pointer / non-positive size M355_EINVALID_ARG, N*C > 65535 M355_EUNSUPPORTED, workspace M355_EWORKSPACE; nothing
+ * is launched then.  m355_binary_loss_workspace is 0 for a non-positive size.
+ */
+size_t m355_binary_loss_workspace(int32_t N, int32_t C, int64_t S);
+int m355_binary_loss_fwd(const float* x, const float* t, int32_t N, int32_t C, int64_t S, float dice_weight,
+                         const float* class_weights /* [C] or NULL */, const float* pos_weight /* [C] or NULL */,
+                         int32_t square_dice, int32_t from_logits, float* out3, float* sums /* [N*C*5] */,
+                         void* workspace, size_t workspace_bytes, void* stream);
+/* dx = dloss * d(loss)/dx in one pass, closed form from the saved sums: the gradient with respect to p, or with
+ * from_logits to z directly (log part cw (-pw t sigmoid(-z) + (1 - t) sigmoid(z)) / (N C S), Dice part times
+ * p sigmoid(-z)), which stays alive where a sigmoid's own backward multiplies by p (1 - p) = 0.  Writes dx[0, N*C*S). */
+int m355_binary_loss_bwd(const float* x, const float* t, const float* sums, const float* dloss /* device scalar */,
+                         int32_t N, int32_t C, int64_t S, float dice_weight, const float* class_weights,
+                         const float* pos_weight, int32_t square_dice, int32_t from_logits, float* dx, void* stream);
+
 /* ------------------------------------------------------------ elementwise
  * torch.cat([x_up, x_skip], dim=1) (models/modular_unet.py:97) when the
  * producer could not write into the concat buffer directly: strided copy of
@@ -1054,6 +1083,22 @@ int m355_eval_confusion(const m355_eval_map_desc* descs, int32_t n, void* dev_de
 int m355_eval_scores(const m355_eval_scores_desc* descs, int32_t n, void* dev_descs, int32_t scores_dtype, int32_t C,
                      const int32_t* table, int32_t mask_kind, int32_t mask_axis, int32_t mask_upper,
                      const int32_t* labels, int32_t L, int32_t nokey, uint64_t* counts, void* stream);
+/* Thresholded (multi-label) counts for sigmoid heads: counts[subject][c][{TP, FP, FN}] (device uint64, zeroed here) of
+ * predicted = ((float) score > thresholds[c]) against positive = (target != 0), each of the C channels
+ * (1 <= C <= M355_EV_MAX_CHANNELS) on its own.  Scores [C, S] float32, bfloat16 or float16 (16-bit values are widened
+ * exactly); a NaN score is not predicted (torch's `>`).  Targets [C, S] of any M355_EV_* type, BF16 / F16 included; a
+ * NaN target is positive (torch's `!= 0`), -0.0 is not; NULL is an argument error.  thresholds: host floats [C], +-inf
+ * allowed.  Host descriptors are copied to `dev_descs` on the stream; one launch for all n subjects whatever their
+ * sizes, no synchronisation; integer atomics only, so the counts are exact. */
+typedef struct {
+  const void* scores;          /* [C, S] */
+  const void* target;          /* [C, S] */
+  int64_t S;
+  int32_t target_dtype;
+} m355_eval_multilabel_desc;
+int m355_eval_multilabel(const m355_eval_multilabel_desc* descs, int32_t n, void* dev_descs, int32_t scores_dtype,
+                         int32_t C, const float* thresholds /* host, [C] */,
+                         uint64_t* counts /* device [n][C][3], zeroed here */, void* stream);
 
 /* ------------------------------------------ contour images
  * The device half of the reference's FindInterestingSlice and ContourImageEvaluator (evaluators.py).

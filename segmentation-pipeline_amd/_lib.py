@@ -100,6 +100,11 @@ SLICE_MAX_DIM = 2048
 PLANE_SAGGITAL, PLANE_CORONAL, PLANE_AXIAL = 0, 1, 2
 
 
+class EvalMultilabelDesc(C.Structure):
+    """m355_eval_multilabel_desc"""
+    _fields_ = [("scores", C.c_void_p), ("target", C.c_void_p), ("S", C.c_int64), ("target_dtype", C.c_int32)]
+
+
 class SliceCountsDesc(C.Structure):
     """m355_slice_counts_desc"""
     _fields_ = [("data", C.c_void_p), ("counts_offset", C.c_int64), ("size3", C.c_int32 * 3), ("dtype", C.c_int32),
@@ -237,6 +242,9 @@ SIGNATURES = {
     "m355_hybrid_loss_workspace": (_sz, [_i32, _i32, _i64]),
     "m355_hybrid_loss_fwd": (C.c_int, [_P, _P, _i32, _i32, _i64, _f32, _P, _i32, _P, _P, _P, _sz, _P]),
     "m355_hybrid_loss_bwd": (C.c_int, [_P, _P, _P, _P, _i32, _i32, _i64, _f32, _P, _i32, _P, _P]),
+    "m355_binary_loss_workspace": (_sz, [_i32, _i32, _i64]),
+    "m355_binary_loss_fwd": (C.c_int, [_P, _P, _i32, _i32, _i64, _f32, _P, _P, _i32, _i32, _P, _P, _P, _sz, _P]),
+    "m355_binary_loss_bwd": (C.c_int, [_P, _P, _P, _P, _i32, _i32, _i64, _f32, _P, _P, _i32, _i32, _P, _P]),
     "m355_copy_channels": (C.c_int, [_P, _P, _i32, _i32, _i64, _i64, _i64, _P]),
     "m355_channel_scale": (C.c_int, [_P, _P, _P, _i32, _i32, _i64, _P]),
     "m355_add": (C.c_int, [_P, _P, _P, _i64, _P]),
@@ -286,6 +294,7 @@ SIGNATURES = {
     "m355_eval_confusion": (C.c_int, [C.POINTER(EvalMapDesc), _i32, _P, _I3, _i32, _i32, _P, _P]),
     "m355_eval_scores": (C.c_int, [C.POINTER(EvalScoresDesc), _i32, _P, _i32, _i32, _I3, _i32, _i32, _i32, _I3, _i32,
                                    _i32, _P, _P]),
+    "m355_eval_multilabel": (C.c_int, [C.POINTER(EvalMultilabelDesc), _i32, _P, _i32, _i32, C.POINTER(C.c_float), _P, _P]),
     "m355_slice_counts": (C.c_int, [C.POINTER(SliceCountsDesc), _i32, _P, _P, _P]),
     "m355_slice_rank": (C.c_int, [_P, C.POINTER(SliceSeg), _i32, _P, _P, _P, _P, _P]),
     "m355_slice_mosaic": (C.c_int, [C.POINTER(SliceMosaicDesc), _i32, C.POINTER(SliceTileDesc), _i32, _P, _P]),

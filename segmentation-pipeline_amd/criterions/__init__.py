@@ -1,2 +1,3 @@
 """Drop-in for `segmentation_pipeline.criterions` (reference criterions/__init__.py:1)."""
 from .hybrid_logistic_dice_loss import HybridLogisticDiceLoss
+from .hybrid_binary_logistic_dice_loss import HybridBinaryLogisticDiceLoss

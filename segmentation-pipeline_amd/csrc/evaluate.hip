@@ -5,6 +5,8 @@
 //   ev_scores_kernel     the same counts straight from model scores: first-maximum argmax over the channels (a NaN is
 //                        the maximum, as torch.argmax), a channel -> label value table chosen per voxel by a mask (the
 //                        inverse of a masked CustomRemapLabels), optionally the int64 label maps written out
+//   ev_multilabel_kernel counts[subject, channel, {TP, FP, FN}] of (score > threshold[channel]) against (target != 0),
+//                        every channel on its own (sigmoid heads; evaluators.MultiLabelEvaluator)
 //
 // Voxel values are compared as the reference's `data == label_value` does: the label is first cast to the map's element
 // type (uint8 -1 is 255, float32 compares with float(label)), then compared.  Every value becomes an int32 key on load;
@@ -401,6 +403,116 @@ __global__ __launch_bounds__(EV_NT) void ev_scores_kernel(const m355_eval_scores
   cnt.flush(red, counts + (int64_t)blockIdx.y * 3 * la.L);
 }
 
+// ---------------------------------------------------------------------------------------------- multi-label
+struct MultiArgs {
+  float thr[M355_EV_MAX_CHANNELS];
+  int32_t C;
+};
+
+// `!= 0` of a target element of any type: a float is positive unless it is +-0 (a NaN is), as torch's `!= 0`
+__device__ __forceinline__ bool ml_pos1(const void* p, int dt, int64_t i) {
+  switch (dt) {
+    case M355_EV_I16: return ((const int16_t*)p)[i] != 0;
+    case M355_EV_BF16:
+    case M355_EV_F16: return (((const uint16_t*)p)[i] & 0x7fffu) != 0;
+    case M355_EV_I32: return ((const int32_t*)p)[i] != 0;
+    case M355_EV_I64: return ((const int64_t*)p)[i] != 0;
+    case M355_EV_F32: return (((const uint32_t*)p)[i] & 0x7fffffffu) != 0;
+    default: return ((const uint8_t*)p)[i] != 0;   // bool, uint8, int8
+  }
+}
+
+// the same for EV_V consecutive elements from element i (a multiple of EV_V, the map 16-byte aligned): bit j = element j
+__device__ __forceinline__ uint32_t ml_pos8(const void* p, int dt, int64_t i) {
+  uint32_t m = 0;
+  switch (dt) {
+    case M355_EV_I16:
+    case M355_EV_BF16:
+    case M355_EV_F16: {
+      const uint4 r = *(const uint4*)((const uint16_t*)p + i);
+      const uint32_t w[4] = {r.x, r.y, r.z, r.w};
+      const uint32_t keep = dt == M355_EV_I16 ? 0xffffu : 0x7fffu;
+#pragma unroll
+      for (int j = 0; j < EV_V; ++j) m |= (uint32_t)(((w[j >> 1] >> (16 * (j & 1))) & keep) != 0) << j;
+      break;
+    }
+    case M355_EV_I32:
+    case M355_EV_F32: {
+      const uint4 a = *(const uint4*)((const uint32_t*)p + i), b = *(const uint4*)((const uint32_t*)p + i + 4);
+      const uint32_t w[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+      const uint32_t keep = dt == M355_EV_I32 ? 0xffffffffu : 0x7fffffffu;
+#pragma unroll
+      for (int j = 0; j < EV_V; ++j) m |= (uint32_t)((w[j] & keep) != 0) << j;
+      break;
+    }
+    case M355_EV_I64: {
+#pragma unroll
+      for (int h = 0; h < EV_V / 2; ++h) {
+        const longlong2 r = *(const longlong2*)((const int64_t*)p + i + 2 * h);
+        m |= (uint32_t)(r.x != 0) << (2 * h) | (uint32_t)(r.y != 0) << (2 * h + 1);
+      }
+      break;
+    }
+    default: {   // bool, uint8, int8
+      const uint2 r = *(const uint2*)((const uint8_t*)p + i);
+      const uint32_t w[2] = {r.x, r.y};
+#pragma unroll
+      for (int j = 0; j < EV_V; ++j) m |= (uint32_t)(((w[j >> 2] >> (8 * (j & 3))) & 0xffu) != 0) << j;
+    }
+  }
+  return m;
+}
+
+// counts[subject][c][{TP, FP, FN}] of (score > thr[c]) against (target != 0), channel by channel: three counters per
+// lane, summed over the wave, added to the block's LDS table [C][3] by one lane, and from there with one 64-bit atomic
+// per (block, channel, stat) that is not zero.  A lane counts fewer than 2^32 voxels (S < 2^40, 256 lanes a block).
+template <int SD>
+__global__ __launch_bounds__(EV_NT) void ev_multilabel_kernel(const m355_eval_multilabel_desc* __restrict__ descs,
+                                                             MultiArgs a, unsigned long long* __restrict__ counts) {
+  __shared__ unsigned long long hist[3 * M355_EV_MAX_CHANNELS];
+  const m355_eval_multilabel_desc d = descs[blockIdx.y];
+  for (int i = threadIdx.x; i < 3 * a.C; i += EV_NT) hist[i] = 0;
+  __syncthreads();
+  const int64_t S = d.S;
+  const int dt = d.target_dtype;
+  const int64_t g = (int64_t)blockIdx.x * EV_NT + threadIdx.x, gs = (int64_t)gridDim.x * EV_NT;
+  const bool aligned = S % EV_V == 0 && ((uintptr_t)d.scores & 15) == 0 && ((uintptr_t)d.target & 15) == 0;
+  const int64_t Sv = aligned ? S : 0;
+  for (int c = 0; c < a.C; ++c) {
+    const float thr = a.thr[c];
+    const int64_t row = (int64_t)c * S;
+    uint32_t tp = 0, fp = 0, fn = 0;
+    for (int64_t i = g * EV_V; i < Sv; i += gs * EV_V) {
+      float s[EV_V];
+      load_scores8<SD>(d.scores, row + i, s);
+      const uint32_t m = ml_pos8(d.target, dt, row + i);
+#pragma unroll
+      for (int j = 0; j < EV_V; ++j) {
+        const bool pr = s[j] > thr, ps = (m >> j) & 1u;   // a NaN score is not predicted
+        tp += pr & ps;
+        fp += pr & !ps;
+        fn += !pr & ps;
+      }
+    }
+    for (int64_t i = Sv + g; i < S; i += gs) {
+      const bool pr = load_score1<SD>(d.scores, row + i) > thr, ps = ml_pos1(d.target, dt, row + i);
+      tp += pr & ps;
+      fp += pr & !ps;
+      fn += !pr & ps;
+    }
+    const unsigned long long w0 = m355::wave_sum((unsigned long long)tp), w1 = m355::wave_sum((unsigned long long)fp),
+                             w2 = m355::wave_sum((unsigned long long)fn);
+    if ((threadIdx.x & 63) == 0) {
+      if (w0) atomicAdd(&hist[3 * c + 0], w0);
+      if (w1) atomicAdd(&hist[3 * c + 1], w1);
+      if (w2) atomicAdd(&hist[3 * c + 2], w2);
+    }
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < 3 * a.C; i += EV_NT)
+    if (hist[i]) atomicAdd(&counts[(int64_t)blockIdx.y * 3 * a.C + i], hist[i]);
+}
+
 int check_labels(const char* what, const int32_t* labels, int32_t L, int32_t nokey, LabelArgs& la) {
   M355_REQUIRE(L >= 1 && L <= M355_EV_MAX_LABELS, M355_EUNSUPPORTED, "%s: %d labels (1 .. %d)", what, L,
                M355_EV_MAX_LABELS);
@@ -514,4 +626,38 @@ extern "C" int m355_eval_scores(const m355_eval_scores_desc* descs, int32_t n, v
   else { EV_LAUNCH(M355_EV_F16) }
 #undef EV_LAUNCH
   return m355::check_launch("eval_scores");
+}
+
+extern "C" int m355_eval_multilabel(const m355_eval_multilabel_desc* descs, int32_t n, void* dev_descs, int32_t scores_dtype,
+                                    int32_t C, const float* thresholds, uint64_t* counts, void* stream) {
+  M355_REQUIRE(descs && dev_descs && counts && thresholds, M355_EINVALID_ARG, "eval_multilabel: null pointer");
+  M355_REQUIRE(n >= 1 && n <= 65535, M355_EINVALID_ARG, "eval_multilabel: %d subjects (1 .. 65535)", n);
+  M355_REQUIRE(C >= 1 && C <= M355_EV_MAX_CHANNELS, M355_EUNSUPPORTED, "eval_multilabel: %d channels (1 .. %d)", C,
+               M355_EV_MAX_CHANNELS);
+  if (int rc = check_dt("eval_multilabel", scores_dtype, true)) return rc;
+  MultiArgs a{};
+  a.C = C;
+  for (int c = 0; c < C; ++c) a.thr[c] = thresholds[c];
+  int64_t maxS = 1;
+  for (int i = 0; i < n; ++i) {
+    const m355_eval_multilabel_desc& d = descs[i];
+    M355_REQUIRE(d.scores, M355_EINVALID_ARG, "eval_multilabel: subject %d: null scores", i);
+    M355_REQUIRE(d.target, M355_EINVALID_ARG, "eval_multilabel: subject %d: null target", i);
+    M355_REQUIRE(d.S >= 1 && d.S * C < ((int64_t)1 << 40), M355_EINVALID_ARG, "eval_multilabel: subject %d: %lld voxels", i,
+                 (long long)d.S);
+    M355_REQUIRE(d.target_dtype >= M355_EV_BOOL && d.target_dtype <= M355_EV_F16, M355_EINVALID_ARG,
+                 "eval_multilabel: subject %d: target element type %d", i, d.target_dtype);
+    maxS = std::max<int64_t>(maxS, d.S);
+  }
+  hipStream_t st = (hipStream_t)stream;
+  if (hipMemcpyAsync(dev_descs, descs, sizeof(m355_eval_multilabel_desc) * n, hipMemcpyHostToDevice, st) != hipSuccess ||
+      hipMemsetAsync(counts, 0, sizeof(uint64_t) * 3 * C * n, st) != hipSuccess)
+    return m355::check_launch("eval_multilabel: descriptor copy / memset");
+  const dim3 g = ev_grid(maxS, EV_V, n), b(EV_NT);
+  auto* dd = (const m355_eval_multilabel_desc*)dev_descs;
+  auto* c = (unsigned long long*)counts;
+  if (scores_dtype == M355_EV_F32) hipLaunchKernelGGL(ev_multilabel_kernel<M355_EV_F32>, g, b, 0, st, dd, a, c);
+  else if (scores_dtype == M355_EV_BF16) hipLaunchKernelGGL(ev_multilabel_kernel<M355_EV_BF16>, g, b, 0, st, dd, a, c);
+  else hipLaunchKernelGGL(ev_multilabel_kernel<M355_EV_F16>, g, b, 0, st, dd, a, c);
+  return m355::check_launch("eval_multilabel");
 }

@@ -25,7 +25,7 @@ from ._lib import M355Error
 from .post_processing import _OP_COPY, _OP_POSITIVE, _ccl, _connectivity, _device_volume, _histogram, _to_i32
 
 __all__ = ["overlap_histogram", "msseg_detection_test", "instance_segmentation_stats", "MAX_OVERLAP_ENTRIES", "STAT_NAMES",
-           "LabeledTensor", "LabelMap", "Evaluator", "SegmentationEvaluator", "LabelMapEvaluator",
+           "LabeledTensor", "LabelMap", "Evaluator", "SegmentationEvaluator", "MultiLabelEvaluator", "LabelMapEvaluator",
            "InstanceSegmentationEvaluator", "label_counts", "ScalarImage", "find_interesting_slices",
            "FindInterestingSlice", "ContourImageEvaluator", "render_contours"]
 
@@ -374,6 +374,55 @@ class SegmentationEvaluator(Evaluator):
                 stats = self._stats(tp, fp, fn, int(sizes[i]))
                 for stat_name in self.stats_to_output:
                     table[subject['name'], label_name, stat_name] = stats[stat_name].item()
+        return _finish(table, self.summary_stats_to_output)
+
+
+class MultiLabelEvaluator(Evaluator):
+    """SegmentationEvaluator's statistics for a sigmoid head: per subject and channel, `scores > threshold` against
+    `target != 0`, every channel a binary problem of its own (a voxel may carry several labels or none).
+    subject[prediction_name] / subject[target_name]: images with `.data` (ScalarImage, LabelMap) or bare tensors
+    [C, W, H, D]; scores float32 / bfloat16 / float16, targets of any evaluation element type.  `threshold`: a float or
+    one per channel.  The label keys are `channel_names` (default "0" .. "C-1"), 'size' of the statistics is the voxels
+    of one channel.  One ops.eval_multilabel launch for all subjects and one copy back; the output has the layout of
+    SegmentationEvaluator's, so the same scoring functions read it."""
+
+    def __init__(self, prediction_name: str, target_name: str, channel_names: Optional[Sequence[str]] = None,
+                 threshold=0.5,
+                 stats_to_output: Sequence[str] = ('target_volume', 'prediction_volume',
+                                                   'TP', 'FP', 'TN', 'FN', 'dice', 'precision', 'recall'),
+                 summary_stats_to_output: Sequence[str] = ('mean', 'std', 'min', 'max')):
+        self.prediction_name = prediction_name
+        self.target_name = target_name
+        self.channel_names = channel_names
+        self.threshold = threshold
+        self.stats_to_output = stats_to_output
+        self.summary_stats_to_output = summary_stats_to_output
+
+    @staticmethod
+    def _data(image):
+        return image if torch.is_tensor(image) else image.data
+
+    def _channel_names(self, channels):
+        if self.channel_names is None:
+            return [str(c) for c in range(channels)]
+        if len(self.channel_names) != channels:
+            raise M355Error(f"{len(self.channel_names)} channel names {list(self.channel_names)} for {channels} channels")
+        return list(self.channel_names)
+
+    def __call__(self, subjects):
+        scores = [self._data(s[self.prediction_name]) for s in subjects]
+        targets = [self._data(s[self.target_name]) for s in subjects]
+        dev = next((t.device for t in scores if t.is_cuda), None) or torch.device("cuda", torch.cuda.current_device())
+        names = self._channel_names(scores[0].shape[0])
+        table = _subject_table(subjects, self.stats_to_output, names)
+        counts = ops.eval_multilabel([s.to(dev) for s in scores], [t.to(dev) for t in targets], self.threshold).cpu().numpy()
+        for i, subject in enumerate(subjects):
+            size = scores[i][0].numel()
+            for c, name in enumerate(names):
+                tp, fp, fn = (int(v) for v in counts[i, c])
+                stats = SegmentationEvaluator._stats(tp, fp, fn, size)
+                for stat_name in self.stats_to_output:
+                    table[subject['name'], name, stat_name] = stats[stat_name].item()
         return _finish(table, self.summary_stats_to_output)
 
 

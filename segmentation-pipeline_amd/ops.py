@@ -2204,6 +2204,58 @@ def hybrid_logistic_dice_loss(prediction, target, dice_weight=0.5, class_weights
     return _HybridLossFn.apply(prediction, target, dice_weight, class_weights, square_dice)
 
 
+class _BinaryLossFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, t, dice_weight, class_weights, pos_weight, square_dice, from_logits):
+        L = _lib.lib()
+        # (the argument errors come before the device check: they are the same on a host without a GPU)
+        for name, v in (("prediction", x), ("target", t), ("class_weights", class_weights), ("pos_weight", pos_weight)):
+            if v is not None and v.dtype != torch.float32:
+                raise _lib.M355Error(f"{name}: expected torch.float32, got {v.dtype}")
+        if x.dim() < 2 or x.shape != t.shape:
+            raise _lib.M355Error(f"prediction {tuple(x.shape)} and target {tuple(t.shape)}: expected one shape [N, C, ...]")
+        N, Cc = x.shape[0], x.shape[1]
+        for name, w in (("class_weights", class_weights), ("pos_weight", pos_weight)):
+            if w is not None and (w.dim() != 1 or w.numel() != Cc):
+                raise _lib.M355Error(f"{name} of shape {tuple(w.shape)} for {Cc} channels")
+        _require(x, t, class_weights, pos_weight)
+        x, t = x.contiguous(), t.contiguous()
+        class_weights = None if class_weights is None else class_weights.contiguous()
+        pos_weight = None if pos_weight is None else pos_weight.contiguous()
+        S = x.numel() // (N * Cc)
+        out3 = torch.empty(3, dtype=torch.float32, device=x.device)
+        sums = torch.empty(N * Cc * 5, dtype=torch.float32, device=x.device)
+        ws = _workspace(L.m355_binary_loss_workspace(N, Cc, S), x.device)
+        sq, fl = (1 if square_dice else 0), (1 if from_logits else 0)
+        check(L.m355_binary_loss_fwd(_p(x), _p(t), N, Cc, S, float(dice_weight), _p(class_weights), _p(pos_weight), sq, fl,
+                                     _p(out3), _p(sums), _p(ws), ws.numel(), _stream()), "binary_loss_fwd")
+        ctx.args = (N, Cc, S, float(dice_weight), sq, fl)
+        ctx.save_for_backward(x, t, sums, class_weights, pos_weight)
+        st = out3.untyped_storage()   # three tensors over one storage, as _HybridLossFn returns them
+        loss, dice, logistic = (torch.empty((), dtype=torch.float32, device=x.device).set_(st, i, ()) for i in range(3))
+        ctx.mark_non_differentiable(dice, logistic)
+        return loss, dice, logistic
+
+    @staticmethod
+    def backward(ctx, dloss, _d1, _d2):
+        L = _lib.lib()
+        x, t, sums, cw, pw = ctx.saved_tensors
+        N, Cc, S, dwt, sq, fl = ctx.args
+        dloss = dloss.contiguous().to(torch.float32)
+        dx = torch.empty_like(x)
+        check(L.m355_binary_loss_bwd(_p(x), _p(t), _p(sums), _p(dloss), N, Cc, S, dwt, _p(cw), _p(pw), sq, fl, _p(dx),
+                                     _stream()), "binary_loss_bwd")
+        return dx, None, None, None, None, None, None
+
+
+def binary_logistic_dice_loss(x, target, dice_weight=0.5, class_weights=None, pos_weight=None, square_dice=True,
+                              from_logits=False):
+    """HybridBinaryLogisticDiceLoss.forward -> (loss, dice_loss, logistic_loss): binary cross-entropy + Dice per channel
+    of `x` [N, C, ...] fp32 -- probabilities, or logits with from_logits -- against `target` in [0, 1].
+    class_weights / pos_weight: fp32 device tensors [C] or None.  The gradient flows through `loss`."""
+    return _BinaryLossFn.apply(x, target, dice_weight, class_weights, pos_weight, square_dice, from_logits)
+
+
 # ---------------------------------------------------------------- elementwise
 class _ChannelScaleFn(torch.autograd.Function):
     @staticmethod
@@ -2775,6 +2827,49 @@ def eval_scores(scores, table, labels, targets=None, masks=None, half=None, writ
         check(_lib.lib().m355_eval_scores(descs, n, _p(dev_descs), sd, Cc, tab, mask_kind, axis, upper, arr, L, nokey,
                                           _p(counts), _stream()), "eval_scores")
     return counts, (pred_outs if write_pred else None), (target_outs if write_target else None)
+
+
+_EV_TARGET_DTYPE = {**_EV_MAP_DTYPE, torch.bfloat16: _lib.EV_BF16, torch.float16: _lib.EV_F16}
+
+
+def eval_multilabel(scores, targets, thresholds=0.5):
+    """Thresholded counts of sigmoid scores: int64 [n, C, 3] = (TP, FP, FN) per subject and channel of
+    `scores[i][c] > thresholds[c]` against `targets[i][c] != 0`, the channels independent, every subject of whatever
+    size in one launch.  scores[i]: device tensors [C, *spatial] (float32 / bfloat16 / float16, one type and one C for
+    all); targets[i]: the same shape, any evaluation element type or a 16-bit float.  thresholds: a float or C floats
+    (+-inf allowed).  torch's comparison rules: a NaN score is not predicted, a NaN target is positive."""
+    n = len(scores)
+    if n == 0 or len(targets) != n:
+        raise _lib.M355Error(f"eval_multilabel: {n} score maps and {len(targets)} targets; one target per subject, at "
+                             "least one subject")
+    Cc = scores[0].shape[0] if scores[0].dim() >= 1 else 0
+    if not 1 <= Cc <= _lib.EV_MAX_CHANNELS:
+        raise _lib.M355Error(f"eval_multilabel: {Cc} channels (1 .. {_lib.EV_MAX_CHANNELS})")
+    thr = [float(thresholds)] * Cc if isinstance(thresholds, (int, float)) else [float(v) for v in thresholds]
+    if len(thr) != Cc:
+        raise _lib.M355Error(f"eval_multilabel: {len(thr)} thresholds for {Cc} channels")
+    sd = _ev_code(scores[0], _EV_SCORE_DTYPE, "eval_multilabel: scores")
+    descs = (_lib.EvalMultilabelDesc * n)()
+    keep = []
+    dev = scores[0].device
+    for i, (s, t) in enumerate(zip(scores, targets)):
+        if s.dim() < 2 or s.shape[0] != Cc or s.dtype != scores[0].dtype or s.device != dev:
+            raise _lib.M355Error(f"eval_multilabel: subject {i}: scores {tuple(s.shape)} {s.dtype} on {s.device}; expected "
+                                 f"[{Cc}, ...] {scores[0].dtype} on {dev}")
+        if t is None or tuple(t.shape) != tuple(s.shape) or t.device != dev:
+            raise _lib.M355Error(f"eval_multilabel: subject {i}: target "
+                                 f"{None if t is None else (tuple(t.shape), t.device)} for scores {tuple(s.shape)} on {dev}")
+        s, t = s.contiguous(), t.contiguous()
+        keep += [s, t]
+        d = descs[i]
+        d.scores, d.target, d.S = s.data_ptr(), t.data_ptr(), s[0].numel()
+        d.target_dtype = _ev_code(t, _EV_TARGET_DTYPE, f"eval_multilabel: subject {i}: target")
+    with torch.cuda.device(dev):
+        dev_descs = torch.empty(C.sizeof(descs), dtype=torch.uint8, device=dev)
+        counts = torch.empty((n, Cc, 3), dtype=torch.int64, device=dev)
+        check(_lib.lib().m355_eval_multilabel(descs, n, _p(dev_descs), sd, Cc, (C.c_float * Cc)(*thr), _p(counts),
+                                              _stream()), "eval_multilabel")
+    return counts
 
 
 # ----------------------------------------------------------------- contour images (csrc/contour.hip, DESIGN §4.13)

@@ -424,6 +424,17 @@ def _tensor(v):
     return v if torch.is_tensor(v) else v.data
 
 
+def split_batch(batch, pred_name="y_pred", target_name="y"):
+    """One batch dict of stacked [N, C, D, H, W] tensors (optionally 'name': a list) as a list of N subject dicts: the
+    scores, the target and every other 5-D tensor are indexed (views), anything else is shared."""
+    n = next(_tensor(v).shape[0] for k, v in batch.items() if k in (pred_name, target_name))
+    names = batch.get("name", [None] * n)
+    return [{k: (_tensor(v)[i] if k in (pred_name, target_name) or
+                 (torch.is_tensor(v) and v.dim() == 5) else v)
+             for k, v in batch.items() if k != "name"} | ({"name": names[i]} if names[i] is not None else {})
+            for i in range(n)]
+
+
 def add_evaluation_labels(subjects, transform, label_values=None, write=False, pred_name="y_pred", target_name="y"):
     """Add 'y_pred_eval' / 'y_eval' label maps (evaluators.LabelMap: int64 [1, D, H, W] and 'label_values') to every
     subject that has 'y_pred' scores ([C, D, H, W]) or a one-hot 'y', inverting the label transforms of `transform`,
@@ -434,12 +445,7 @@ def add_evaluation_labels(subjects, transform, label_values=None, write=False, p
     straight from the scores without writing them.  write=True: compute them now, in one launch.
     A masked remap whose mask is a label map reads it from the subject under its name.  Returns the subjects."""
     if isinstance(subjects, dict):
-        n = next(_tensor(v).shape[0] for k, v in subjects.items() if k in (pred_name, target_name))
-        names = subjects.get("name", [None] * n)
-        subjects = [{k: (_tensor(v)[i] if k in (pred_name, target_name) or
-                         (torch.is_tensor(v) and v.dim() == 5) else v)
-                     for k, v in subjects.items() if k != "name"} | ({"name": names[i]} if names[i] is not None else {})
-                    for i in range(n)]
+        subjects = split_batch(subjects, pred_name, target_name)
     plan = transform if isinstance(transform, EvaluationPlan) else EvaluationPlan(transform, target_name)
     values = plan.label_values(label_values)
     sources = []

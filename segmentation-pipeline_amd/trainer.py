@@ -366,13 +366,16 @@ class TrainLoop:
             subject[name] = ScalarImage(data.detach() if channel is None else data.detach()[channel:channel + 1])
 
     def _training_evaluations(self, due, batch, label_transform, label_values, evaluation_images=None):
-        from .prediction import add_evaluation_labels
+        from .prediction import add_evaluation_labels, split_batch
         if not due:
             return {}
         n = batch["y_pred"].shape[0]
         names = batch.get("name") or [str(i) for i in range(n)]
-        subjects = add_evaluation_labels({"y_pred": batch["y_pred"].detach(), "y": batch["y"], "name": list(names)},
-                                         label_transform, label_values)
+        subjects = {"y_pred": batch["y_pred"].detach(), "y": batch["y"], "name": list(names)}
+        if label_transform is None:   # no label maps (a sigmoid head: MultiLabelEvaluator reads the attached images)
+            subjects = split_batch(subjects)
+        else:
+            subjects = add_evaluation_labels(subjects, label_transform, label_values)
         for i, subject in enumerate(subjects):
             self._attach_images(subject, batch, evaluation_images, i)
         return {s.log_name: s.evaluator(subjects) for s in due}
@@ -405,7 +408,8 @@ class TrainLoop:
                     source = dict(out, X=batch["X"][0]) if torch.is_tensor(batch.get("X")) else out   # (the device copy)
                     self._attach_images(out, source, evaluation_images)
                     evaluated[id(subject)] = out
-        add_evaluation_labels(list(evaluated.values()), label_transform, label_values)
+        if label_transform is not None:
+            add_evaluation_labels(list(evaluated.values()), label_transform, label_values)
         by_name = {s["name"]: s for s in evaluated.values()}
         results = {}
         for s in due:
@@ -431,7 +435,9 @@ class TrainLoop:
         `validation_predictor` (default: `predictor`) under no_grad.  Both get 'y_pred_eval' / 'y_eval' from
         prediction.add_evaluation_labels(label_transform, label_values): `label_transform` is the preprocessing
         Compose that produced 'y', `label_values` the training target's label_values after it.  Outputs go into the
-        log dict (and so to `scoring_function`) under each evaluator's log_name.
+        log dict (and so to `scoring_function`) under each evaluator's log_name.  `label_transform=None`: no label
+        maps are added (a sigmoid head has no argmax to invert); the subjects carry 'y_pred', 'y', 'name' and the
+        `evaluation_images`, e.g. {"scores": "y_pred", "truth": "y"} for evaluators.MultiLabelEvaluator("scores", "truth").
 
         `evaluation_images`: {image name: key or (key, channel)} -- every evaluated subject gets subject[image name], an
         evaluators.ScalarImage whose `.data` is a view (no copy) of the batch's or validation subject's tensor under
