@@ -1155,6 +1155,45 @@ int m355_slice_rank(const int32_t* counts, const m355_slice_seg* segs, int32_t n
 int m355_slice_mosaic(const m355_slice_mosaic_desc* mosaics, int32_t nmosaics, const m355_slice_tile_desc* tiles,
                       int32_t ntiles, void* dev_descs, void* stream);
 
+/* ------------------------------------------ distance transform and surface distances
+ * The exact Euclidean distance transform under post_processing.distance_transform_edt, and the device half of
+ * evaluators.SurfaceDistanceEvaluator (Hausdorff distance, its percentile, average symmetric surface distance; DESIGN
+ * §4.20).  Volumes are [W, H, D], contiguous with D fastest, fewer than 2^31 voxels.  Every entry point enqueues on
+ * `stream` and never synchronises; arguments are checked on the host before any launch: a null pointer, a size < 1,
+ * 2^31 voxels or more, or a spacing that is not finite and > 0 is M355_EINVALID_ARG; a dimension above
+ * M355_EDT_MAX_DIM (m355_edt_sq only: a line of the volume is staged in LDS) is M355_EUNSUPPORTED.
+ *   m355_edt_sq          d2[v] = min over the voxels s with sites[s] != 0 of sum_a (spacing3[a] * (v_a - s_a))^2, the
+ *                        SQUARED distance to the nearest site; +inf everywhere when there is no site.  spacing3: three
+ *                        host floats for the axes W, H, D.  Three launches: a nearest-site sweep along D, then a
+ *                        minimum pass along H and one along W.  fp32 throughout, every term formed as
+ *                        (spacing3[a] * k) squared, each product and each sum rounded once, in a fixed order: the
+ *                        result does not depend on the launch geometry.  With spacing (1, 1, 1) every intermediate is
+ *                        an integer and d2 is EXACT while (W-1)^2 + (H-1)^2 + (D-1)^2 < 2^24 (always, within
+ *                        M355_EDT_MAX_DIM: 3 * 511^2 < 2^20); otherwise the candidates carry rounding error only --
+ *                        the search never drops a site whose rounded value is the smallest.  Workspace:
+ *                        m355_edt_workspace(size3) bytes (0 for a null or non-positive size).  sites and d2 must not
+ *                        overlap.
+ *   m355_edt_sqrt        d[i] = the correctly rounded fp32 square root of d2[i] (+inf stays +inf); d may be d2.
+ *   m355_surface_mask    x: an int32 label volume (m355_label_convert_in's output).  border[v] = 1 when x[v] == value
+ *                        and v lies on a face of the volume or one of its six face neighbours differs from value (a
+ *                        neighbour of another label counts as outside), else 0: mask ^ binary_erosion(mask, 6-connected
+ *                        structure, border_value=0).  *count (device int32, zeroed by the CALLER) grows by the number
+ *                        of border voxels; integer atomics, so it is exact.
+ *   m355_surface_gather  for every voxel with border[v] != 0: out[k] = the correctly rounded sqrt(d2[v]) with k =
+ *                        atomicAdd(cursor, 1), when k < capacity.  *cursor (device int32, the caller sets the first
+ *                        slot, normally 0) keeps counting past capacity, so a short buffer shows.  The order of the
+ *                        entries is unspecified: callers sort.  capacity >= 0.
+ */
+#define M355_EDT_MAX_DIM 512
+size_t m355_edt_workspace(const int32_t* size3);
+int m355_edt_sq(const uint8_t* sites, const int32_t* size3, const float* spacing3 /* host */, float* d2, void* workspace,
+                void* stream);
+int m355_edt_sqrt(const float* d2, float* d, int64_t n, void* stream);
+int m355_surface_mask(const int32_t* x, int32_t value, const int32_t* size3, uint8_t* border, int32_t* count,
+                      void* stream);
+int m355_surface_gather(const uint8_t* border, const float* d2, int64_t nvox, float* out, int32_t* cursor,
+                        int32_t capacity, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

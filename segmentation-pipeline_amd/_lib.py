@@ -97,6 +97,7 @@ class EvalScoresDesc(C.Structure):
 
 
 SLICE_MAX_DIM = 2048
+EDT_MAX_DIM = 512
 PLANE_SAGGITAL, PLANE_CORONAL, PLANE_AXIAL = 0, 1, 2
 
 
@@ -298,6 +299,11 @@ SIGNATURES = {
     "m355_slice_counts": (C.c_int, [C.POINTER(SliceCountsDesc), _i32, _P, _P, _P]),
     "m355_slice_rank": (C.c_int, [_P, C.POINTER(SliceSeg), _i32, _P, _P, _P, _P, _P]),
     "m355_slice_mosaic": (C.c_int, [C.POINTER(SliceMosaicDesc), _i32, C.POINTER(SliceTileDesc), _i32, _P, _P]),
+    "m355_edt_workspace": (_sz, [_I3]),
+    "m355_edt_sq": (C.c_int, [_P, _I3, C.POINTER(C.c_float), _P, _P, _P]),
+    "m355_edt_sqrt": (C.c_int, [_P, _P, _i64, _P]),
+    "m355_surface_mask": (C.c_int, [_P, _i32, _I3, _P, _P, _P]),
+    "m355_surface_gather": (C.c_int, [_P, _P, _i64, _P, _P, _i32, _P]),
 }
 
 

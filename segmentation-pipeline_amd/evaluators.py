@@ -10,6 +10,7 @@ the background of either map), built by one pass of m355_label_histogram over th
 above MAX_OVERLAP_ENTRIES entries.  The detection test and every statistic derived from the table run on the host in
 float32, the dtype of the reference's table (so N == 0 or M == 0 gives the same nan results).
 """
+import ctypes
 import io
 import itertools
 import random
@@ -20,14 +21,15 @@ from typing import Callable, Dict, Optional, Sequence
 import numpy as np
 import torch
 
-from . import ops
-from ._lib import M355Error
-from .post_processing import _OP_COPY, _OP_POSITIVE, _ccl, _connectivity, _device_volume, _histogram, _to_i32
+from . import _lib, ops
+from ._lib import M355Error, check
+from .post_processing import _DTYPE_CODE, _OP_COPY, _OP_POSITIVE, _ccl, _connectivity, _device_volume, _histogram, _to_i32
 
 __all__ = ["overlap_histogram", "msseg_detection_test", "instance_segmentation_stats", "MAX_OVERLAP_ENTRIES", "STAT_NAMES",
            "LabeledTensor", "LabelMap", "Evaluator", "SegmentationEvaluator", "MultiLabelEvaluator", "LabelMapEvaluator",
            "InstanceSegmentationEvaluator", "label_counts", "ScalarImage", "find_interesting_slices",
-           "FindInterestingSlice", "ContourImageEvaluator", "render_contours"]
+           "FindInterestingSlice", "ContourImageEvaluator", "render_contours", "SurfaceDistanceEvaluator",
+           "surface_distances", "SURFACE_STAT_NAMES"]
 
 MAX_OVERLAP_ENTRIES = 1 << 26   # (N + 1) * (M + 1): 512 MiB of int64 counts
 
@@ -495,6 +497,189 @@ class InstanceSegmentationEvaluator(Evaluator):
                                                 self.detection_test, self.detection_test_params)
             for stat_name in self.stats_to_output:
                 table[subject['name'], stat_name] = stats[stat_name]
+        return _finish(table, self.summary_stats_to_output)
+
+
+# ---------------------------------------------------------------------------------------------- surface distances
+SURFACE_STAT_NAMES = ('hd', 'hd95', 'assd', 'asd_pred_to_target', 'asd_target_to_pred', 'nsd', 'pred_surface',
+                      'target_surface')
+_SURFACE_DEVICE_STATS = 6   # the first six are taken on the device; the two surface sizes are the counts themselves
+
+
+def _volume3(data):
+    """a label map's data ([1, W, H, D] or [W, H, D]; numpy or tensor) as a contiguous integer device volume [W, H, D]"""
+    if getattr(data, "ndim", 0) == 4:
+        if data.shape[0] != 1:
+            raise M355Error(f"surface distances: a label map of shape {tuple(data.shape)}; expected [1, W, H, D]")
+        data = data[0]
+    return _device_volume(data)[0]
+
+
+def _to_i32_unchecked(t, status):
+    """_to_i32 without the read-back: `status` (a device int32 slot) is left for the caller to look at"""
+    out = torch.empty(t.shape, dtype=torch.int32, device=t.device)
+    check(_lib.lib().m355_label_convert_in(ops._p(t), _DTYPE_CODE[t.dtype], _OP_COPY, ops._p(out), t.numel(),
+                                           ops._p(status), ops._stream()), "label_convert_in")
+    return out
+
+
+def _surface_table(pairs, values, spacings, percentile, tolerance):
+    """float64 numpy [n, L, 8] in the order of SURFACE_STAT_NAMES for the (prediction, target) volumes `pairs`, the int
+    label values `values` and one spacing triple per subject.  Two passes over the subjects, so device memory holds one
+    subject's volumes at a time: the first only counts the border voxels (one copy to the host sizes the pooled gather
+    buffer exactly), the second converts and masks again -- both cheap next to the transforms -- and fills the buffer.
+    At most two device -> host copies, whatever n and L."""
+    n, L = len(pairs), len(values)
+    if not 0.0 <= float(percentile) <= 100.0:
+        raise M355Error(f"percentile {percentile!r} (0 .. 100)")
+    for i, (p, t) in enumerate(pairs):
+        if p.shape != t.shape or p.device != t.device:
+            raise M355Error(f"surface distances: subject {i}: prediction {tuple(p.shape)} on {p.device}, target "
+                            f"{tuple(t.shape)} on {t.device}")
+    dev = pairs[0][0].device
+    out = np.full((n, L, len(SURFACE_STAT_NAMES)), np.nan)
+    with torch.cuda.device(dev):
+        head = torch.zeros(2 * n * L + 2 * n, dtype=torch.int32, device=dev)   # border counts [n, L, 2], cast flags [n, 2]
+        max_vox = max(p.numel() for p, _ in pairs)
+        borders = torch.empty((2, max_vox), dtype=torch.uint8, device=dev)
+
+        def masks(l, counts):
+            """the borders of label l in the current subject's two int32 volumes, into the scratch; counts: two int32 slots"""
+            made = []
+            for side, x in enumerate(converted):
+                b = borders[side, :x.numel()].view(x.shape)
+                ops.surface_mask(x, values[l], border=b, count=counts[side:side + 1])
+                made.append(b)
+            return made
+
+        for i, (p, t) in enumerate(pairs):
+            at = 2 * n * L + 2 * i
+            converted = [_to_i32_unchecked(p, head[at:at + 1]), _to_i32_unchecked(t, head[at + 1:at + 2])]
+            for l in range(L):
+                masks(l, head[2 * (i * L + l):2 * (i * L + l) + 2])
+        host = head.cpu().numpy()                                             # copy 1
+        if host[2 * n * L:].any():
+            raise M355Error("label values must fit int32")
+        counts = host[:2 * n * L].reshape(n, L, 2).astype(np.int64)
+        out[:, :, 6:] = counts
+        todo = [(i, l) for i in range(n) for l in range(L) if counts[i, l].min() > 0]
+        if not todo:
+            return out
+        offsets, total = {}, 0
+        for i, l in todo:
+            offsets[(i, l)] = total
+            total += int(counts[i, l].sum())
+        pool = torch.empty(total, dtype=torch.float32, device=dev)
+        cursors = torch.zeros(2 * len(todo), dtype=torch.int32, device=dev)
+        junk = torch.zeros(2, dtype=torch.int32, device=dev)
+        table = torch.empty((len(todo), _SURFACE_DEVICE_STATS), dtype=torch.float64, device=dev)
+        d2 = torch.empty(max_vox, dtype=torch.float32, device=dev)
+        workspace = None
+        last = -1
+        for k, (i, l) in enumerate(todo):
+            if i != last:
+                p, t = pairs[i]
+                converted = [_to_i32_unchecked(p, junk[0:1]), _to_i32_unchecked(t, junk[1:2])]
+                size3 = (ctypes.c_int32 * 3)(*p.shape)
+                workspace = torch.empty(max(int(_lib.lib().m355_edt_workspace(size3)), 16), dtype=torch.uint8, device=dev)
+                last = i
+            border_p, border_t = masks(l, junk)
+            n_p, n_t = int(counts[i, l, 0]), int(counts[i, l, 1])
+            a = pool[offsets[(i, l)]:offsets[(i, l)] + n_p]
+            b = pool[offsets[(i, l)] + n_p:offsets[(i, l)] + n_p + n_t]
+            dist = d2[:p.numel()].view(p.shape)
+            ops.edt_sq(border_t, spacings[i], out=dist, workspace=workspace)
+            ops.surface_gather(border_p, dist, a, cursors[2 * k:2 * k + 1])
+            ops.edt_sq(border_p, spacings[i], out=dist, workspace=workspace)
+            ops.surface_gather(border_t, dist, b, cursors[2 * k + 1:2 * k + 2])
+            # the gather order is not specified: every sum below runs over a sorted segment, so the bits repeat
+            mean_a = torch.sort(a).values.double().sum() / n_p
+            mean_b = torch.sort(b).values.double().sum() / n_t
+            both = torch.sort(pool[offsets[(i, l)]:offsets[(i, l)] + n_p + n_t]).values.double()
+            rank = float(percentile) / 100.0 * (n_p + n_t - 1)
+            lo = min(int(np.floor(rank)), n_p + n_t - 1)
+            hi = min(lo + 1, n_p + n_t - 1)
+            table[k] = torch.stack([both[-1], both[lo] + (both[hi] - both[lo]) * (rank - lo), (mean_a + mean_b) / 2,
+                                    mean_a, mean_b, (both <= float(tolerance)).sum().double() / (n_p + n_t)])
+        table = table.cpu().numpy()                                           # copy 2
+    for k, (i, l) in enumerate(todo):
+        out[i, l, :_SURFACE_DEVICE_STATS] = table[k]
+    return out
+
+
+def _image_spacing(image, override):
+    if override is not None:
+        return ops._spacing3(override)
+    spacing = getattr(image, "spacing", None)
+    if spacing is None and isinstance(image, Mapping) and "spacing" in image:
+        spacing = image["spacing"]
+    return (1.0, 1.0, 1.0) if spacing is None else ops._spacing3(spacing)
+
+
+def surface_distances(pred, target, label_values, spacing=(1, 1, 1), percentile=95, tolerance=1.0):
+    """Surface distances of one prediction / target pair of label maps ([W, H, D] or [1, W, H, D]; numpy or tensors) for
+    every entry of `label_values` ({label name: value}): {label name: {stat: float}} with the eight statistics of
+    SURFACE_STAT_NAMES, defined under SurfaceDistanceEvaluator.  The functional form of that evaluator for one subject:
+    the same launches and the same two copies."""
+    p, t = _volume3(pred), _volume3(target)
+    table = _surface_table([(p, t.to(p.device))], [int(v) for v in label_values.values()], [ops._spacing3(spacing)],
+                           percentile, tolerance)
+    return {name: {stat: float(table[0, l, s]) for s, stat in enumerate(SURFACE_STAT_NAMES)}
+            for l, name in enumerate(label_values)}
+
+
+class SurfaceDistanceEvaluator(Evaluator):
+    """Boundary statistics of a predicted against a target label map per subject and label, in SegmentationEvaluator's
+    output layout (so ScheduledEvaluation, the loggers and the scoring functions read it unchanged).  With dP and dT the
+    borders of `pred == value` and `target == value` -- the voxels of the label that lie on a face of the volume or have
+    a six-neighbour outside the label: mask ^ binary_erosion(mask), border_value 0 -- and the multisets
+    A = {d(p, dT) : p in dP}, B = {d(t, dP) : t in dT} of Euclidean distances in units of `spacing` (the medpy
+    conventions):
+      'hd'                  max(A u B), the Hausdorff distance
+      'hd95'                numpy.percentile(A + B, percentile), linear interpolation (the key keeps its name for any
+                            percentile)
+      'asd_pred_to_target'  mean(A);  'asd_target_to_pred'  mean(B)
+      'assd'                the mean of those two means
+      'nsd'                 (#{a <= tolerance} + #{b <= tolerance}) / (|A| + |B|): a surface Dice over border VOXELS, not
+                            the area-weighted one of the surface-distance literature
+      'pred_surface'        |A|;  'target_surface'  |B|
+    When either border is empty (the label is absent from a map) every distance statistic and 'nsd' is nan.
+
+    `spacing`: the constructor's argument, else the prediction image's `.spacing` (torchio), else its 'spacing' key, else
+    1.  Label names and values come from subjects[0][prediction_label_map_name]['label_values']; predictions are read
+    through `.data`, so a pending ScoreLabelMap writes itself.  Distances are fp32 (exact squares for unit spacing,
+    correctly rounded roots), the order statistics and fp64 means are taken on the device over sorted segments:
+    results repeat bit for bit.  Two device -> host copies per call whatever the number of subjects and labels: the
+    border counts, then the table."""
+
+    def __init__(self, prediction_label_map_name: str, target_label_map_name: str, spacing=None, percentile=95,
+                 tolerance=1.0, stats_to_output: Sequence[str] = ('hd', 'hd95', 'assd'),
+                 summary_stats_to_output: Sequence[str] = ('mean', 'std', 'min', 'max')):
+        unknown = [s for s in stats_to_output if s not in SURFACE_STAT_NAMES]
+        if unknown:
+            raise M355Error(f"unknown surface distance stats {unknown} (known: {', '.join(SURFACE_STAT_NAMES)})")
+        self.prediction_label_map_name = prediction_label_map_name
+        self.target_label_map_name = target_label_map_name
+        self.spacing = spacing
+        self.percentile = percentile
+        self.tolerance = tolerance
+        self.stats_to_output = stats_to_output
+        self.summary_stats_to_output = summary_stats_to_output
+
+    def __call__(self, subjects):
+        label_values = subjects[0][self.prediction_label_map_name]['label_values']
+        table = _subject_table(subjects, self.stats_to_output, list(label_values.keys()))
+        pairs, spacings = [], []
+        for subject in subjects:
+            image = subject[self.prediction_label_map_name]
+            p = _volume3(image.data)
+            pairs.append((p, _volume3(subject[self.target_label_map_name].data).to(p.device)))
+            spacings.append(_image_spacing(image, self.spacing))
+        stats = _surface_table(pairs, [int(v) for v in label_values.values()], spacings, self.percentile, self.tolerance)
+        for i, subject in enumerate(subjects):
+            for l, label_name in enumerate(label_values):
+                for stat_name in self.stats_to_output:
+                    table[subject['name'], label_name, stat_name] = stats[i, l, SURFACE_STAT_NAMES.index(stat_name)]
         return _finish(table, self.summary_stats_to_output)
 
 

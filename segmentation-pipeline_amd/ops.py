@@ -3022,3 +3022,106 @@ def slice_mosaic(mosaics):
         dev_descs = torch.empty(C.sizeof(td), dtype=torch.uint8, device=dev)
         check(_lib.lib().m355_slice_mosaic(md, len(plans), td, ntiles, _p(dev_descs), _stream()), "slice_mosaic")
     return outs, buf
+
+
+# ----------------------------------------------------------------- distance transform, surface distances (csrc/distance.hip)
+def _dist_arg(t, dtypes, what, shape=None):
+    """a tensor argument of the distance family: element type, contiguity, device, shape -- in that order"""
+    if not isinstance(t, torch.Tensor) or t.dtype not in dtypes:
+        got = t.dtype if isinstance(t, torch.Tensor) else type(t).__name__
+        raise _lib.M355Error(f"{what}: element type {got} (expected {' or '.join(str(d) for d in dtypes)})")
+    if not t.is_contiguous():
+        raise _lib.M355Error(f"{what}: expected a contiguous tensor, got strides {tuple(t.stride())} for shape {tuple(t.shape)}")
+    if not t.is_cuda:
+        raise _lib.M355Error(f"{what}: expected a device tensor")
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        raise _lib.M355Error(f"{what}: shape {tuple(t.shape)}, expected {tuple(shape)}")
+    return t
+
+
+def _size3(t, what):
+    if t.dim() != 3:
+        raise _lib.M355Error(f"{what}: expected one volume [W, H, D], got shape {tuple(t.shape)}")
+    return (C.c_int32 * 3)(*t.shape)
+
+
+def _spacing3(spacing):
+    s = [float(spacing)] * 3 if isinstance(spacing, (int, float)) else [float(v) for v in spacing]
+    if len(s) != 3:
+        raise _lib.M355Error(f"spacing {spacing!r}: a number or three numbers (W, H, D)")
+    return tuple(s)
+
+
+def edt_sq(sites, spacing=(1., 1., 1.), out=None, workspace=None):
+    """Squared Euclidean distance of every voxel to the nearest voxel with sites != 0, float32 [W, H, D]; +inf
+    everywhere without a site.  sites: a contiguous uint8 or bool device volume [W, H, D] (every axis at most
+    _lib.EDT_MAX_DIM); spacing: a number or three (W, H, D), used in fp32.  Exact for unit spacing.  `out` (float32,
+    the volume's shape) and `workspace` (uint8, at least m355_edt_workspace bytes) may be handed in to reuse scratch from
+    call to call.  Three launches, no synchronisation."""
+    _dist_arg(sites, (torch.uint8, torch.bool), "edt_sq: sites")
+    size3 = _size3(sites, "edt_sq: sites")
+    sp = (C.c_float * 3)(*_spacing3(spacing))
+    L = _lib.lib()
+    with torch.cuda.device(sites.device):
+        nbytes = int(L.m355_edt_workspace(size3))
+        if workspace is None:
+            workspace = _workspace(nbytes, sites.device)
+        elif _dist_arg(workspace, (torch.uint8,), "edt_sq: workspace").numel() < nbytes:
+            raise _lib.M355Error(f"edt_sq: workspace of {workspace.numel()} bytes, {nbytes} needed")
+        if out is None:
+            out = torch.empty(sites.shape, dtype=torch.float32, device=sites.device)
+        else:
+            _dist_arg(out, (torch.float32,), "edt_sq: out", sites.shape)
+        check(L.m355_edt_sq(_p(sites), size3, sp, _p(out), _p(workspace), _stream()), "edt_sq")
+    return out
+
+
+def edt_sqrt(d2, out=None):
+    """The correctly rounded float32 square root of every element of d2 (float32, contiguous, on the device); out may be
+    d2.  One launch."""
+    _dist_arg(d2, (torch.float32,), "edt_sqrt: d2")
+    if out is None:
+        out = torch.empty_like(d2)
+    else:
+        _dist_arg(out, (torch.float32,), "edt_sqrt: out", d2.shape)
+    with torch.cuda.device(d2.device):
+        check(_lib.lib().m355_edt_sqrt(_p(d2), _p(out), d2.numel(), _stream()), "edt_sqrt")
+    return out
+
+
+def surface_mask(x_i32, value, border=None, count=None):
+    """-> (border, count).  border (uint8, x's shape): 1 where x == value and the voxel lies on a face of the volume or
+    one of its six face neighbours differs from value, else 0.  count (int32 device tensor of one element): grows by the
+    number of border voxels; a fresh zero unless one is handed in (the caller zeroes that one).  x_i32: a contiguous
+    int32 device volume [W, H, D].  One launch, no synchronisation."""
+    _dist_arg(x_i32, (torch.int32,), "surface_mask: x")
+    size3 = _size3(x_i32, "surface_mask: x")
+    with torch.cuda.device(x_i32.device):
+        if border is None:
+            border = torch.empty(x_i32.shape, dtype=torch.uint8, device=x_i32.device)
+        else:
+            _dist_arg(border, (torch.uint8,), "surface_mask: border", x_i32.shape)
+        if count is None:
+            count = torch.zeros(1, dtype=torch.int32, device=x_i32.device)
+        elif _dist_arg(count, (torch.int32,), "surface_mask: count").numel() != 1:
+            raise _lib.M355Error(f"surface_mask: count of {count.numel()} elements (one)")
+        check(_lib.lib().m355_surface_mask(_p(x_i32), int(value), size3, _p(border), _p(count), _stream()), "surface_mask")
+    return border, count
+
+
+def surface_gather(border, d2, out, cursor):
+    """out[k] = sqrt(d2[v]) (correctly rounded) for every voxel with border[v] != 0, k from cursor (int32 device tensor of
+    one element, advanced by the number of border voxels even past out.numel(): a short buffer shows); the order is
+    unspecified.  border uint8, d2 float32 of the same shape, out float32 1-D, all contiguous on one device.  One launch,
+    no synchronisation.  Returns out."""
+    _dist_arg(border, (torch.uint8,), "surface_gather: border")
+    _dist_arg(d2, (torch.float32,), "surface_gather: d2", border.shape)
+    _dist_arg(out, (torch.float32,), "surface_gather: out")
+    if _dist_arg(cursor, (torch.int32,), "surface_gather: cursor").numel() != 1:
+        raise _lib.M355Error(f"surface_gather: cursor of {cursor.numel()} elements (one)")
+    if border.numel() == 0 or out.numel() >= 1 << 31:
+        raise _lib.M355Error(f"surface_gather: {border.numel()} voxels into {out.numel()} slots")
+    with torch.cuda.device(border.device):
+        check(_lib.lib().m355_surface_gather(_p(border), _p(d2), border.numel(), _p(out), _p(cursor), out.numel(),
+                                             _stream()), "surface_gather")
+    return out

@@ -10,6 +10,9 @@ Inputs: a 3-D numpy array (computed on the current GPU, returned as numpy), a CU
 CPU tensor (computed on the current GPU, returned on the CPU); dtypes bool, uint8, int8, int16, int32 and int64 (values
 must fit int32).  Results have the input's dtype; the input is never modified.
 
+`distance_transform_edt` (scipy.ndimage's, next to `label`) is the exact Euclidean distance transform of
+csrc/distance.hip; it also takes float32 volumes and returns float32 distances.
+
 Ties: the reference ranks sizes with numpy's default (unstable) argsort.  Here equal sizes keep numpy's STABLE order --
 ascending value for ascending sorts, and the reverse of the stable ascending order for the descending component sort.
 """
@@ -19,11 +22,11 @@ import operator
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, ops
 from ._lib import M355Error, check
 from .ops import _p, _stream
 
-__all__ = ["label", "remove_holes", "keep_components", "remove_small_components"]
+__all__ = ["label", "remove_holes", "keep_components", "remove_small_components", "distance_transform_edt"]
 
 _DTYPE_CODE = {torch.bool: 0, torch.uint8: 0, torch.int8: 1, torch.int16: 2, torch.int32: 3, torch.int64: 4}
 _OP_COPY, _OP_IS_ZERO, _OP_POSITIVE = 0, 1, 2
@@ -31,8 +34,9 @@ _MODE_VALUES, _MODE_NONPOSITIVE = 0, 1    # m355_ccl_label modes
 _MAX_CLASS_RANGE = 1 << 24                # keep_components: max - min + 1 of the class values (documented there)
 
 
-def _device_volume(img):
-    """(contiguous 3-D tensor on a GPU, function mapping a result tensor back to the caller's kind)."""
+def _device_volume(img, also=()):
+    """(contiguous 3-D tensor on a GPU, function mapping a result tensor back to the caller's kind); `also`: element
+    types taken besides the integer ones."""
     if isinstance(img, np.ndarray):
         t = torch.from_numpy(np.ascontiguousarray(img)).to(torch.device("cuda", torch.cuda.current_device()))
         back = lambda r: r.cpu().numpy()   # noqa: E731
@@ -46,7 +50,7 @@ def _device_volume(img):
         raise TypeError(f"expected a numpy array or a torch tensor, got {type(img).__name__}")
     if t.dim() != 3:
         raise M355Error(f"expected one 3-D volume [D, H, W], got shape {tuple(t.shape)}")
-    if t.dtype not in _DTYPE_CODE:
+    if t.dtype not in _DTYPE_CODE and t.dtype not in also:
         raise M355Error(f"unsupported dtype {t.dtype} (bool, uint8, int8, int16, int32, int64)")
     if t.numel() == 0 or t.numel() >= 1 << 31:
         raise M355Error(f"volume of {t.numel()} voxels: need 1 .. 2^31 - 1")
@@ -124,6 +128,22 @@ def label(img, connectivity=None, return_num=False):
     labels, n = _ccl(_to_i32(t), conn)
     out = back(_from_i32(labels, torch.int64))
     return (out, n) if return_num else out
+
+
+def distance_transform_edt(img, sampling=None):
+    """scipy.ndimage.distance_transform_edt(img, sampling=sampling) for one volume: the Euclidean distance from every
+    nonzero voxel to the nearest zero voxel, 0 on the zero voxels.  sampling: the voxel spacing, a number or one per
+    axis (None: 1).  Takes the element types of `label` and float32; a numpy array comes back as numpy, a device tensor
+    stays on its device, a CPU tensor returns to the CPU.
+
+    The result is float32 (scipy returns float64): exact squared distances for unit sampling -- with a correctly
+    rounded square root -- and fp32 rounding of each term otherwise.  A volume without a zero voxel gives +inf
+    everywhere (scipy's result is undefined there).  Every axis at most _lib.EDT_MAX_DIM.  Three launches of
+    ops.edt_sq and one square-root pass (csrc/distance.hip)."""
+    t, back = _device_volume(img, also=(torch.float32,))
+    with torch.cuda.device(t.device):
+        d2 = ops.edt_sq(t == 0, (1., 1., 1.) if sampling is None else sampling)
+        return back(ops.edt_sqrt(d2, out=d2))
 
 
 def _fill_holes(w, hole_size, max_dilations):
