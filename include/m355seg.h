@@ -397,6 +397,18 @@ int m355_norm_act_bwd(const m355_norm_desc* d, const float* x, const float* dy,
                       const float* mean, const float* rstd, const float* gamma,
                       const float* beta, float* dx, float* dgamma, float* dbeta,
                       int training, void* workspace, size_t workspace_bytes, void* stream);
+/* The backward of m355_norm_act_pool_fwd: the gradient of the activated tensor is dskip (fp32 [N, C, D, H, W] with its
+ * own batch stride, 0 = dense; NULL: the skip path carries no gradient) + the un-pooled dpool (fp32 [N, C, D/2, H/2, W/2],
+ * own batch stride, 0 = dense), summed inside both passes of the normalisation backward: the pass of
+ * m355_avgpool3d_2x_bwd[_add] that writes the sum, and its re-read, do not happen.  x and dx share desc->x_batch_stride;
+ * desc->y_batch_stride is not used.  D * H * W must equal desc->S (M355_EINVALID_ARG), all even (M355_EUNSUPPORTED).
+ * dx, dgamma and dbeta are bit-identical to m355_avgpool3d_2x_bwd[_add] into a dense tensor followed by
+ * m355_norm_act_bwd.  No pointer needs more than 4-byte alignment.  Workspace: m355_norm_workspace(desc) bytes. */
+int m355_norm_act_bwd_pool(const m355_norm_desc* d, const float* x, const float* dskip, int64_t dskip_batch_stride,
+                           const float* dpool, int64_t dpool_batch_stride, int32_t D, int32_t H, int32_t W,
+                           const float* mean, const float* rstd, const float* gamma, const float* beta, float* dx,
+                           float* dgamma, float* dbeta, int training, void* workspace, size_t workspace_bytes,
+                           void* stream);
 /* The same with dx ALSO written as a c8 tensor (h16 layout above) by the second pass: in the 16-bit training flow dx
  * is the output gradient of the convolution in front of the normalisation, and that convolution's data- and
  * weight-gradient kernels read it as c8 (m355_conv3d_bwd_data_h16 / m355_conv3d_bwd_weight_h16). */

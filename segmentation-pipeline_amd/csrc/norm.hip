@@ -421,6 +421,133 @@ __global__ __launch_bounds__(256) void norm_bwd_apply_kernel(
   }
 }
 
+// ---- the backward of a block whose output also went through nn.AvgPool3d(2, 2) (norm_act_pool_fwd_kernel) ----
+// The gradient of the activated tensor is the skip-path gradient (may be absent) plus the un-pooled gradient of the
+// pooled output.  avgpool2_bwd_kernel forms that sum and writes it so that the two passes above can read it back; the
+// POOL kernels below form it in registers instead, with that kernel's expression (skip + dpool * 0.125f; the product
+// is exact, so contraction cannot change it), and the pass over the level that wrote and re-read it is gone.
+// One channel's sources; offsets within a channel fit 32 bits (the entry point checks S).
+struct PoolGradSrc {
+  const float* ds;   // dskip of this (n, c), null: no skip gradient
+  const float* dp;   // dpool of this (n, c): [D/2][H/2][W/2]
+  uint32_t W, HW, OW, OHW;
+  __device__ __forceinline__ uint32_t pooled(uint32_t i) const {
+    const uint32_t z = i / HW, rem = i - z * HW;
+    const uint32_t y = rem / W, xw = rem - y * W;
+    return (z >> 1) * OHW + (y >> 1) * OW + (xw >> 1);
+  }
+  __device__ __forceinline__ float one(uint32_t i) const {
+    const float g = dp[pooled(i)] * 0.125f;
+    return ds ? ds[i] + g : g;
+  }
+  // elements i .. i+3, i % 4 == 0.  GVEC: W % 4 == 0 (the four share a row and two pooled voxels) and ds 16-byte aligned
+  template <bool GVEC>
+  __device__ __forceinline__ float4 four(uint32_t i) const {
+    if (GVEC) {
+      const uint32_t q = pooled(i);
+      const float g0 = dp[q] * 0.125f, g1 = dp[q + 1] * 0.125f;
+      if (!ds) return make_float4(g0, g0, g1, g1);
+      const float4 a = *reinterpret_cast<const float4*>(ds + i);
+      return make_float4(a.x + g0, a.y + g0, a.z + g1, a.w + g1);
+    }
+    return make_float4(one(i), one(i + 1), one(i + 2), one(i + 3));
+  }
+};
+
+__device__ __forceinline__ PoolGradSrc pool_grad_src(const float* dskip, int64_t dsbs, const float* dpool, int64_t dpbs,
+                                                     int n, int c, int64_t S, int H, int W) {
+  PoolGradSrc g;
+  g.ds = dskip ? dskip + (int64_t)n * dsbs + (int64_t)c * S : nullptr;
+  g.dp = dpool + (int64_t)n * dpbs + (int64_t)c * (S >> 3);
+  g.W = (uint32_t)W;
+  g.HW = (uint32_t)H * (uint32_t)W;
+  g.OW = (uint32_t)W >> 1;
+  g.OHW = ((uint32_t)H >> 1) * g.OW;
+  return g;
+}
+
+// norm_bwd_partial_kernel on that sum.  MAP4 is the element-to-thread mapping of its VEC variant (four consecutive
+// elements per thread), chosen by the host exactly where the two-step form would have run VEC on the dense sum, and
+// the accumulation order within a thread is the same: the partials are bit-identical to the two-step form whether the
+// gradient sources allow vector loads (GVEC) or not.
+template <bool MAP4, bool GVEC, bool SMOOTH>
+__global__ __launch_bounds__(256) void norm_bwd_partial_pool_kernel(
+    const float* __restrict__ x, const float* __restrict__ dskip, const float* __restrict__ dpool,
+    const float* __restrict__ mean, const float* __restrict__ rstd, const float* __restrict__ gamma,
+    const float* __restrict__ beta, double* __restrict__ partial, int C, int64_t S, int H, int W, int groups, int act,
+    float slope, int64_t xbs, int64_t dsbs, int64_t dpbs, int nblk) {
+  __shared__ double scratch[4];
+  const int b = blockIdx.x, c = blockIdx.y, n = blockIdx.z;
+  const int64_t s = groups == 0 ? c : (int64_t)n * groups + c / (C / groups);
+  const float m = mean[s], r = rstd[s];
+  const float g = gamma ? gamma[c] : 1.f, bt = beta ? beta[c] : 0.f;
+  const float* xp = x + (int64_t)n * xbs + (int64_t)c * S;
+  const PoolGradSrc src = pool_grad_src(dskip, dsbs, dpool, dpbs, n, c, S, H, W);
+  const int64_t begin = (int64_t)b * NORM_CHUNK, end = min(S, begin + NORM_CHUNK);
+  float a1 = 0.f, a2 = 0.f;
+  const float sc = r * g, sh = bt - m * sc;  // same expression as the forward pass
+  auto acc = [&](float xv, float dv) {
+    const float xh = (xv - m) * r;
+    const float pre = fmaf(xv, sc, sh);
+    const float gg = dv * act_grad<SMOOTH>(pre, act, slope);
+    a1 += gg;
+    a2 = fmaf(gg, xh, a2);
+  };
+  if (MAP4) {
+    for (int64_t i = begin + threadIdx.x * 4; i < end; i += 1024) {
+      const float4 xv = *reinterpret_cast<const float4*>(xp + i);
+      const float4 dv = src.four<GVEC>((uint32_t)i);
+      acc(xv.x, dv.x); acc(xv.y, dv.y); acc(xv.z, dv.z); acc(xv.w, dv.w);
+    }
+  } else {
+    for (int64_t i = begin + threadIdx.x; i < end; i += 256) acc(xp[i], src.one((uint32_t)i));
+  }
+  const double t1 = block_sum<double, 256>((double)a1, scratch);
+  const double t2 = block_sum<double, 256>((double)a2, scratch);
+  if (threadIdx.x == 0) {
+    const int64_t o = (((int64_t)n * C + c) * nblk + b) * 2;
+    partial[o] = t1;
+    partial[o + 1] = t2;
+  }
+}
+
+// norm_bwd_apply_kernel on that sum (element-wise: any mapping gives the same dx; MAP4 also asks for an aligned dx)
+template <bool MAP4, bool GVEC, bool SMOOTH>
+__global__ __launch_bounds__(256) void norm_bwd_apply_pool_kernel(
+    const float* __restrict__ x, const float* __restrict__ dskip, const float* __restrict__ dpool,
+    const float* __restrict__ mean, const float* __restrict__ rstd, const float* __restrict__ gamma,
+    const float* __restrict__ beta, const float* __restrict__ stat_m, float* __restrict__ dx, int C, int64_t S, int H,
+    int W, int groups, int act, float slope, int64_t xbs, int64_t dsbs, int64_t dpbs) {
+  const int c = blockIdx.y, n = blockIdx.z;
+  const int64_t s = groups == 0 ? c : (int64_t)n * groups + c / (C / groups);
+  const float m = mean[s], r = rstd[s];
+  const float g = gamma ? gamma[c] : 1.f, bt = beta ? beta[c] : 0.f;
+  const float m1 = stat_m[s * 2], m2 = stat_m[s * 2 + 1];
+  const float* xp = x + (int64_t)n * xbs + (int64_t)c * S;
+  float* op = dx + (int64_t)n * xbs + (int64_t)c * S;
+  const PoolGradSrc src = pool_grad_src(dskip, dsbs, dpool, dpbs, n, c, S, H, W);
+  const float sc = r * g, sh = bt - m * sc;  // same expression as the forward pass
+  auto f = [&](float xv, float dv) {
+    const float xh = (xv - m) * r;
+    const float pre = fmaf(xv, sc, sh);
+    const float gg = dv * act_grad<SMOOTH>(pre, act, slope) * g;
+    return r * (gg - m1 - xh * m2);
+  };
+  if (MAP4) {
+    const int64_t S4 = S >> 2;
+    for (int64_t i = blockIdx.x * 256ll + threadIdx.x; i < S4; i += gridDim.x * 256ll) {
+      const float4 xv = reinterpret_cast<const float4*>(xp)[i];
+      const float4 dv = src.four<GVEC>((uint32_t)(i * 4));
+      float4 o;
+      o.x = f(xv.x, dv.x); o.y = f(xv.y, dv.y); o.z = f(xv.z, dv.z); o.w = f(xv.w, dv.w);
+      reinterpret_cast<float4*>(op)[i] = o;
+    }
+  } else {
+    for (int64_t i = blockIdx.x * 256ll + threadIdx.x; i < S; i += gridDim.x * 256ll)
+      op[i] = f(xp[i], src.one((uint32_t)i));
+  }
+}
+
 // ---------------------------------------------------------------- host half
 // Every entry point: validate, plan (norm_host.hpp), check the workspace against the plan, launch.  Each kernel of this
 // file is launched from exactly one function.
@@ -531,9 +658,65 @@ static int norm_act_bwd_impl(const m355_norm_desc* d, const float* x, const floa
                         (hipStream_t)stream, "norm_act_bwd");
 }
 
+// The backward behind norm_act_pool_fwd: both halves read skip + un-pooled gradient from their sources (the POOL
+// kernels).  The chunk geometry, the workspace and the element-to-thread mapping are those of norm_act_bwd_impl on a
+// dense, aligned sum tensor, so every result has the bits of m355_avgpool3d_2x_bwd[_add] + m355_norm_act_bwd.
+static int norm_act_bwd_pool_impl(const m355_norm_desc* d0, const float* x, const float* dskip, int64_t dskip_bs,
+                                  const float* dpool, int64_t dpool_bs, int D, int H, int W, const float* mean,
+                                  const float* rstd, const float* gamma, const float* beta, float* dx, float* dgamma,
+                                  float* dbeta, int training, void* workspace, size_t workspace_bytes, hipStream_t st) {
+  const char* who = "norm_act_bwd_pool";
+  if (int rc = validate_norm(d0, who, NORM_F32)) return rc;
+  M355_REQUIRE(x && dpool && mean && rstd && dx && workspace, M355_EINVALID_ARG, "%s: null pointer", who);
+  M355_REQUIRE(D > 0 && H > 0 && W > 0 && (int64_t)D * H * W == d0->S, M355_EINVALID_ARG, "%s: D*H*W != desc->S", who);
+  M355_REQUIRE(D % 2 == 0 && H % 2 == 0 && W % 2 == 0, M355_EUNSUPPORTED, "%s: odd spatial size (%d,%d,%d)", who, D, H, W);
+  M355_REQUIRE(d0->S <= INT32_MAX, M355_EUNSUPPORTED, "%s: more than 2^31 - 1 voxels per channel", who);
+  m355_norm_desc dd = *d0;   // the sum tensor of the two-step form is dense
+  dd.y_batch_stride = 0;
+  const m355_norm_desc* d = &dd;
+  const NormPlan p = plan_norm(d, NORM_F32);
+  M355_REQUIRE(workspace_bytes >= p.workspace_bytes, M355_EWORKSPACE, "%s: workspace too small", who);
+  const int64_t dsbs = dense_or(dskip_bs, (int64_t)d->C * d->S), dpbs = dense_or(dpool_bs, (int64_t)d->C * (d->S / 8));
+  const bool gvec = W % 4 == 0 && (!dskip || (((uintptr_t)dskip & 15) == 0 && dsbs % 4 == 0));
+  float* stat_m = p.stat_m(workspace);
+  // MAP4 / GVEC: (1,1), (1,0) or (0,0)
+  auto variant = [&](bool map4, auto&& launch) {
+    with_bool(act_is_smooth(d->act), [&](auto SM) {
+      if (map4 && gvec) launch(std::true_type{}, std::true_type{}, SM);
+      else if (map4) launch(std::true_type{}, std::false_type{}, SM);
+      else launch(std::false_type{}, std::false_type{}, SM);
+    });
+  };
+  const NormLaunch L1 = norm_pass(d, p, NORM_BWD1, (uintptr_t)x);
+  variant(L1.vec, [&](auto M4, auto GV, auto SM) {
+    hipLaunchKernelGGL((norm_bwd_partial_pool_kernel<decltype(M4)::value, decltype(GV)::value, decltype(SM)::value>), L1.grid,
+                       dim3(256), 0, st, x, dskip, dpool, mean, rstd, gamma, beta, p.partial(workspace), d->C, d->S, H, W,
+                       d->groups, d->act, d->act_slope, p.xbs, dsbs, dpbs, L1.nblk);
+  });
+  if (int rc = launch_norm_bwd_reduce(d, p, p.partial(workspace), gamma, dgamma, dbeta, stat_m, training, nullptr, 1.f, nullptr,
+                                      st))
+    return rc;
+  const NormLaunch L2 = norm_pass(d, p, NORM_BWD2, (uintptr_t)x | (uintptr_t)dx);
+  variant(L2.vec, [&](auto M4, auto GV, auto SM) {
+    hipLaunchKernelGGL((norm_bwd_apply_pool_kernel<decltype(M4)::value, decltype(GV)::value, decltype(SM)::value>), L2.grid,
+                       dim3(256), 0, st, x, dskip, dpool, mean, rstd, gamma, beta, stat_m, dx, d->C, d->S, H, W, d->groups,
+                       d->act, d->act_slope, p.xbs, dsbs, dpbs);
+  });
+  return check_launch(who);
+}
+
 }  // namespace m355
 
 using namespace m355;
+
+extern "C" int m355_norm_act_bwd_pool(const m355_norm_desc* d, const float* x, const float* dskip, int64_t dskip_batch_stride,
+                                      const float* dpool, int64_t dpool_batch_stride, int32_t D, int32_t H, int32_t W,
+                                      const float* mean, const float* rstd, const float* gamma, const float* beta, float* dx,
+                                      float* dgamma, float* dbeta, int training, void* workspace, size_t workspace_bytes,
+                                      void* stream) {
+  return norm_act_bwd_pool_impl(d, x, dskip, dskip_batch_stride, dpool, dpool_batch_stride, D, H, W, mean, rstd, gamma, beta,
+                                dx, dgamma, dbeta, training, workspace, workspace_bytes, (hipStream_t)stream);
+}
 
 extern "C" int64_t m355_norm_num_stats(const m355_norm_desc* d) {
   if (!d) return 0;

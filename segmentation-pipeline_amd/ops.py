@@ -544,6 +544,11 @@ def fp16_overflow(device=None) -> int:
     return hit
 # an encoder block's last norm + activation pass also emits the AvgPool3d(2, 2) the next level consumes
 FUSE_POOL = os.environ.get("M355_FUSE_POOL", "1") != "0"
+# ... and its backward sums the skip gradient and the un-pooled gradient inside the two normalisation-backward passes
+# (m355_norm_act_bwd_pool); 0: m355_avgpool3d_2x_bwd[_add] writes the sum first, the launches before that entry existed
+FUSE_POOL_BWD = os.environ.get("M355_FUSE_POOL_BWD", "1") != "0"
+# how often a backward took a fused path since import (the tests read and reset it)
+fused_bwd_counts = {"pool": 0}
 
 
 # Parameters that own packed forms (id -> weak reference).  optimizer.step changes every one of them at once; the first
@@ -1718,8 +1723,9 @@ class _NormActFn(torch.autograd.Function):
 class _NormActPoolFn(torch.autograd.Function):
     """norm + activation with AvgPool3d(2, 2) of the result as a second output (m355_norm_act_pool_fwd): the last
     pass of an encoder block also produces the next level's input, so the pool never re-reads the activated tensor.
-    Backward: the two incoming gradients (skip path, pooled path) are summed in the pool-backward pass
-    (m355_avgpool3d_2x_bwd_add), then the usual normalisation backward."""
+    Backward: the two incoming gradients (skip path, pooled path) are summed inside the two passes of the normalisation
+    backward (m355_norm_act_bwd_pool).  With FUSE_POOL_BWD off, and for synchronised batch norm (two halves around an
+    all-reduce), the pool-backward pass writes the sum first (m355_avgpool3d_2x_bwd_add), then the usual backward."""
 
     @staticmethod
     def forward(ctx, x, gamma, beta, cfg: NormCfg):
@@ -1752,7 +1758,22 @@ class _NormActPoolFn(torch.autograd.Function):
         x, mean, rstd, gamma, beta = ctx.saved_tensors
         d0 = ctx.desc
         D, H, W = ctx.dims
-        if dpool is not None:   # gradient of the activated tensor = skip-path gradient + un-pooled gradient, one pass
+        if dpool is not None and FUSE_POOL_BWD and ctx.sync is None:
+            # gradient of the activated tensor = skip-path gradient + un-pooled gradient, formed inside both passes
+            dpool, gpbs = _dense_channels(dpool)
+            gsbs = 0
+            if dy is not None:
+                dy, gsbs = _dense_channels(dy)
+            dx = torch.empty_like(x)
+            dgamma = torch.empty(d0.C, dtype=torch.float32, device=x.device) if ctx.has_affine else None
+            dbeta = torch.empty(d0.C, dtype=torch.float32, device=x.device) if ctx.has_affine else None
+            ws = _workspace(L.m355_norm_workspace(C.byref(d0)), x.device)
+            check(L.m355_norm_act_bwd_pool(C.byref(d0), _p(x), _p(dy), gsbs, _p(dpool), gpbs, D, H, W, _p(mean), _p(rstd),
+                                           _p(gamma), _p(beta), _p(dx), _p(dgamma), _p(dbeta), 1 if ctx.batch_stats else 0,
+                                           _p(ws), ws.numel(), _stream()), "norm_act_bwd_pool")
+            fused_bwd_counts["pool"] += 1
+            return dx, dgamma, dbeta, None
+        if dpool is not None:   # the two-step form: the sum in one pass of its own
             dpool, gpbs = _dense_channels(dpool)
             tot = torch.empty_like(x)
             if dy is None:
