@@ -1206,6 +1206,44 @@ int m355_surface_mask(const int32_t* x, int32_t value, const int32_t* size3, uin
 int m355_surface_gather(const uint8_t* border, const float* d2, int64_t nvox, float* out, int32_t* cursor,
                         int32_t capacity, void* stream);
 
+/* ------------------------------------------ statistics of image values grouped by the label of the voxel
+ * The device half of ops.region_stats, evaluators.ImageRegionEvaluator and data_processing.dataset_fingerprint (DESIGN
+ * §4.22).  One label volume [W, H, D] (contiguous, D fastest; any M355_EV_* type up to float32), K >= 0 images
+ * [channels, W, H, D] on the same grid (float32, float16, bfloat16, uint8 or int16: each converts to fp32 exactly), L
+ * label values (0 <= L <= M355_EV_MAX_LABELS).  Regions, in this order: the L values as given (`data == value` as
+ * torch decides it, the value cast to the map's type; of two equal values the first gets the voxels), then 'all'
+ * (label != 0) and 'whole' (every voxel): R = L + 2 rows.
+ *   count[R]        int64 voxels of the region
+ *   bounds[R][6]    int32 (min, max) index along W, H, D; an empty region has (axis size, -1)
+ *   stats[R][K][5]  float32 mean, unbiased std, median, min, max of image k inside the region, its channels pooled (the
+ *                   mask broadcasts over them), n = count * channels values.  The median is torch.median's: the value of
+ *                   rank (n - 1) / 2 of the sorted values.  n == 0: all five NaN; n == 1: std NaN; a NaN among the
+ *                   values: all five NaN, for that region and image only; +-inf are ordinary values for min, max and
+ *                   median.  min, max and median are exact; mean and std are accumulated in fp64 (sum, then sum of
+ *                   (x - mean)^2 in a second pass) and rounded to float32 once.  median == 0 skips the select passes
+ *                   and leaves that column NaN.
+ * Counts, bounds, min / max and the radix-select histograms use integer atomics; floating-point sums go through
+ * per-block partials that one wave per region adds in a fixed order: the same call twice gives the same bits.  A call only
+ * enqueues (2 + K * (median ? 9 : 4) launches) and never synchronises; the select resolves prefix and rank on
+ * the device.  Workspace: m355_region_stats_workspace(L, K, median) bytes (0 for K <= 0 or an L out of range; K == 0
+ * needs none), not preserved between calls.  Arguments are checked on the host before any launch: L < 0, K < 0, a null
+ * pointer, a size or channel count < 1 is M355_EINVALID_ARG; L above M355_EV_MAX_LABELS, another element type, a label
+ * value float32 cannot hold inside int32, or an image of 2^32 values or more is M355_EUNSUPPORTED; a short workspace is
+ * M355_EWORKSPACE.
+ *   m355_region_stats_plan  plan4 = {blocks of a pass at most, threads of a block, voxels per thread and loop trip,
+ *                           regions per block of a select pass}: a pass takes a second trip through its grid-stride
+ *                           loop above plan4[0] * plan4[1] * plan4[2] voxels. */
+typedef struct {
+  const void* data;            /* [channels, W, H, D] */
+  int32_t dtype;               /* M355_EV_F32, _F16, _BF16, _U8 or _I16 */
+  int32_t channels;
+} m355_region_image;
+size_t m355_region_stats_workspace(int32_t L, int32_t K, int32_t median);
+int m355_region_stats_plan(int32_t* plan4);
+int m355_region_stats(const void* labels, int32_t label_dtype, const int32_t* size3, const m355_region_image* images,
+                      int32_t K, const int32_t* values /* host */, int32_t L, int32_t median, int64_t* count,
+                      int32_t* bounds, float* stats, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -101,6 +101,11 @@ EDT_MAX_DIM = 512
 PLANE_SAGGITAL, PLANE_CORONAL, PLANE_AXIAL = 0, 1, 2
 
 
+class RegionImage(C.Structure):
+    """m355_region_image"""
+    _fields_ = [("data", C.c_void_p), ("dtype", C.c_int32), ("channels", C.c_int32)]
+
+
 class EvalMultilabelDesc(C.Structure):
     """m355_eval_multilabel_desc"""
     _fields_ = [("scores", C.c_void_p), ("target", C.c_void_p), ("S", C.c_int64), ("target_dtype", C.c_int32)]
@@ -306,6 +311,9 @@ SIGNATURES = {
     "m355_edt_sqrt": (C.c_int, [_P, _P, _i64, _P]),
     "m355_surface_mask": (C.c_int, [_P, _i32, _I3, _P, _P, _P]),
     "m355_surface_gather": (C.c_int, [_P, _P, _i64, _P, _P, _i32, _P]),
+    "m355_region_stats_workspace": (_sz, [_i32, _i32, _i32]),
+    "m355_region_stats_plan": (C.c_int, [_I3]),
+    "m355_region_stats": (C.c_int, [_P, _i32, _I3, C.POINTER(RegionImage), _i32, _I3, _i32, _i32, _P, _P, _P, _P, _sz, _P]),
 }
 
 

@@ -29,7 +29,7 @@ __all__ = ["overlap_histogram", "msseg_detection_test", "instance_segmentation_s
            "LabeledTensor", "LabelMap", "Evaluator", "SegmentationEvaluator", "MultiLabelEvaluator", "LabelMapEvaluator",
            "InstanceSegmentationEvaluator", "label_counts", "ScalarImage", "find_interesting_slices",
            "FindInterestingSlice", "ContourImageEvaluator", "render_contours", "SurfaceDistanceEvaluator",
-           "surface_distances", "SURFACE_STAT_NAMES"]
+           "surface_distances", "SURFACE_STAT_NAMES", "ImageRegionEvaluator", "IMAGE_REGION_STAT_NAMES"]
 
 MAX_OVERLAP_ENTRIES = 1 << 26   # (N + 1) * (M + 1): 512 MiB of int64 counts
 
@@ -469,6 +469,62 @@ class LabelMapEvaluator(Evaluator):
                 for stat_name in self.stats_to_output:
                     table[subject['name'], label_name, stat_name] = stats[stat_name].item()
         return _finish(table, self.summary_stats_to_output)
+
+
+IMAGE_REGION_STAT_NAMES = ops.REGION_STATS + ('volume',)
+
+
+def _device_tensors(tensors):
+    """the tensors on one device: that of the first device tensor among them, else the current device when there is one
+    (host tensors are then uploaded); without any device they stay where they are and the op refuses them"""
+    dev = next((t.device for t in tensors if t.is_cuda), None)
+    if dev is None and torch.cuda.is_available():
+        dev = torch.device("cuda", torch.cuda.current_device())
+    return list(tensors) if dev is None else [t.to(dev) for t in tensors]
+
+
+class ImageRegionEvaluator(Evaluator):
+    """Summary statistics of images inside the mask of every label per subject (image_region_evaluator.py, reference,
+    which declares the table and stops): a ['subject', 'label', 'image_name', 'stat'] table with 'mean', 'std'
+    (unbiased), 'median' (torch.median's lower middle value), 'min', 'max' of the image's values where
+    `label map == label value`, the channels of an image pooled, and 'volume', the voxels of the label (the same for
+    every image).  An absent label has volume 0 and NaN statistics; a one-voxel label has std NaN.  Label names and
+    values come from subjects[0][label_map_name]['label_values'].  The images are read as they are: an intensity
+    normalisation applied before the evaluation is not inverted.  One ops.region_stats call for all subjects, labels
+    and images, and one device -> host copy."""
+
+    def __init__(self, label_map_name: str, image_names: Sequence[str], stats_to_output: Sequence[str] = None,
+                 summary_stats_to_output: Sequence[str] = None):
+        self.label_map_name = label_map_name
+        self.image_names = image_names
+        self.stats_to_output = IMAGE_REGION_STAT_NAMES if stats_to_output is None else stats_to_output
+        self.summary_stats_to_output = ('mean', 'std', 'min', 'max') if summary_stats_to_output is None \
+            else summary_stats_to_output
+        unknown = [s for s in self.stats_to_output if s not in IMAGE_REGION_STAT_NAMES]
+        if unknown:
+            raise M355Error(f"unknown image region stats {unknown} (known: {', '.join(IMAGE_REGION_STAT_NAMES)})")
+
+    def __call__(self, subjects):
+        label_values = subjects[0][self.label_map_name]['label_values']
+        label_names = list(label_values.keys())
+        image_names = list(self.image_names)
+        subject_stats = LabeledTensor(dim_names=['subject', 'label', 'image_name', 'stat'],
+                                      dim_keys=[[subject['name'] for subject in subjects], label_names, image_names,
+                                                list(self.stats_to_output)])
+        labels, images = [], []
+        for subject in subjects:
+            tensors = _device_tensors([subject[self.label_map_name].data] + [subject[name].data for name in image_names])
+            labels.append(tensors[0])
+            images.append(tensors[1:])
+        need_median = 'median' in self.stats_to_output
+        res = ops.region_stats(labels, images, [int(v) for v in label_values.values()], median=need_median)
+        L = len(label_names)
+        for j, stat_name in enumerate(self.stats_to_output):
+            if stat_name == 'volume':
+                subject_stats.data[..., j] = res.count[:, :L, None].float()
+            else:
+                subject_stats.data[..., j] = res.stats[:, :L, :, ops.REGION_STATS.index(stat_name)]
+        return _finish(subject_stats, self.summary_stats_to_output)
 
 
 class InstanceSegmentationEvaluator(Evaluator):

@@ -8,7 +8,7 @@ import ctypes as C
 import os
 import weakref
 from dataclasses import dataclass
-from typing import List, Optional, Sequence
+from typing import List, NamedTuple, Optional, Sequence
 
 import numpy as np
 import torch
@@ -3146,3 +3146,183 @@ def surface_gather(border, d2, out, cursor):
         check(_lib.lib().m355_surface_gather(_p(border), _p(d2), border.numel(), _p(out), _p(cursor), out.numel(),
                                              _stream()), "surface_gather")
     return out
+
+
+# ----------------------------------------------------------------- statistics per label region (csrc/region_stats.hip)
+REGION_STATS = ('mean', 'std', 'median', 'min', 'max')   # the last axis of RegionStats.stats
+_RS_IMAGE_DTYPE = {torch.float32: _lib.EV_F32, torch.float16: _lib.EV_F16, torch.bfloat16: _lib.EV_BF16,
+                   torch.uint8: _lib.EV_U8, torch.int16: _lib.EV_I16}
+
+
+class RegionStats(NamedTuple):
+    """count int64 [R], bounds int32 [R, 6] (min, max index along W, H, D; an empty region: axis size, -1), stats
+    float32 [R, K, 5] in the order of REGION_STATS.  R = L + 2: the listed values, then 'all' (label != 0) and 'whole'
+    (every voxel).  The list form of region_stats stacks the subjects in front: [n, R], [n, R, 6], [n, R, K, 5]."""
+    count: torch.Tensor
+    bounds: torch.Tensor
+    stats: torch.Tensor
+
+
+def region_stats_plan():
+    """(blocks of a pass at most, threads of a block, voxels per thread and trip of the grid-stride loops, regions per
+    block of a select pass) of the region statistics kernels"""
+    plan = (C.c_int32 * 4)()
+    check(_lib.lib().m355_region_stats_plan(plan), "region_stats_plan")
+    return tuple(plan)
+
+
+def _rs_chunks(values):
+    values = [int(v) for v in values]
+    uniq = list(dict.fromkeys(values))
+    chunks = [uniq[i:i + _lib.EV_MAX_LABELS] for i in range(0, len(uniq), _lib.EV_MAX_LABELS)] or [[]]
+    return values, uniq, chunks
+
+
+def _rs_record(L, K):
+    """byte offsets of count, bounds and stats in the record of one launch set, and the record's size"""
+    R = L + 2
+    bounds = 8 * R
+    stats = bounds + (24 * R + 7) // 8 * 8
+    return 0, bounds, stats, stats + (20 * R * K + 7) // 8 * 8
+
+
+def region_stats_bytes(n_values, K, median=True):
+    """(result bytes of one subject, workspace bytes) of a region_stats call with that many distinct label values and
+    K images: what region_stats(..., result=, workspace=) expects at least"""
+    chunks = [min(_lib.EV_MAX_LABELS, n_values - i) for i in range(0, n_values, _lib.EV_MAX_LABELS)] or [0]
+    ws = max(int(_lib.lib().m355_region_stats_workspace(Lc, K, int(bool(median)))) for Lc in chunks) if K else 0
+    return sum(_rs_record(Lc, K)[3] for Lc in chunks), ws
+
+
+def _rs_subject(labels, images, i):
+    what = f"region_stats: subject {i}"
+    if not torch.is_tensor(labels) or labels.dim() not in (3, 4) or (labels.dim() == 4 and labels.shape[0] != 1):
+        raise _lib.M355Error(f"{what}: a label volume [W, H, D] or [1, W, H, D], got "
+                             f"{tuple(labels.shape) if torch.is_tensor(labels) else type(labels).__name__}")
+    code = _ev_code(labels, _EV_MAP_DTYPE, f"{what}: label map")
+    size = tuple(labels.shape[-3:])
+    if min(size) < 1:
+        raise _lib.M355Error(f"{what}: empty label volume {size}")
+    labels = labels.contiguous()
+    out = []
+    for k, img in enumerate(images):
+        if not torch.is_tensor(img) or img.dim() not in (3, 4) or tuple(img.shape[-3:]) != size:
+            raise _lib.M355Error(f"{what}: image {k}: expected [C, {size[0]}, {size[1]}, {size[2]}], got "
+                                 f"{tuple(img.shape) if torch.is_tensor(img) else type(img).__name__}")
+        dt = _ev_code(img, _RS_IMAGE_DTYPE, f"{what}: image {k}")
+        if img.device != labels.device:
+            raise _lib.M355Error(f"{what}: image {k} is on {img.device}, the label map on {labels.device}")
+        channels = img.shape[0] if img.dim() == 4 else 1
+        if channels < 1:
+            raise _lib.M355Error(f"{what}: image {k} has no channel")
+        out.append((img.contiguous(), dt, channels))
+    return labels, code, size, out
+
+
+def _rs_enqueue(subjects, plans, median, result=None, workspace=None):
+    """launches for every (subject, chunk of its label values); plans[i] = _rs_chunks of subject i.
+    -> (result buffer, record offsets [subject][chunk])"""
+    L = _lib.lib()
+    dev = subjects[0][0].device
+    need, ws_bytes = 0, 0
+    for (_, _, _, images), (_, _, chunks) in zip(subjects, plans):
+        K = len(images)
+        need += sum(_rs_record(len(c), K)[3] for c in chunks)
+        if K:
+            ws_bytes = max([ws_bytes] + [int(L.m355_region_stats_workspace(len(c), K, int(median))) for c in chunks])
+    with torch.cuda.device(dev):
+        if result is None:
+            result = torch.empty(need, dtype=torch.uint8, device=dev)
+        elif (result.dtype != torch.uint8 or not result.is_contiguous() or result.device != dev or result.data_ptr() % 8
+              or result.numel() < need):
+            raise _lib.M355Error(f"region_stats: result must be a contiguous uint8 tensor of at least {need} bytes on "
+                                 f"{dev}, 8-byte aligned")
+        if workspace is None:
+            workspace = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
+        elif (workspace.dtype != torch.uint8 or not workspace.is_contiguous() or workspace.device != dev
+              or workspace.data_ptr() % 8 or workspace.numel() < ws_bytes):
+            raise _lib.M355Error(f"region_stats: workspace must be a contiguous uint8 tensor of at least {ws_bytes} "
+                                 f"bytes on {dev}, 8-byte aligned")
+        base = result.data_ptr()
+        records = []
+        at = 0
+        for (labels, code, size, images), (_, _, chunks) in zip(subjects, plans):
+            if labels.device != dev:
+                raise _lib.M355Error(f"region_stats: subjects on {labels.device} and {dev}")
+            K = len(images)
+            descs = (_lib.RegionImage * max(K, 1))()
+            for k, (img, dt, channels) in enumerate(images):
+                descs[k].data, descs[k].dtype, descs[k].channels = img.data_ptr(), dt, channels
+            size3 = (C.c_int32 * 3)(*size)
+            row = []
+            for chunk in chunks:
+                o_count, o_bounds, o_stats, nbytes = _rs_record(len(chunk), K)
+                vals = (C.c_int32 * max(len(chunk), 1))(*chunk)
+                check(L.m355_region_stats(_p(labels), code, size3, descs if K else None, K, vals if chunk else None,
+                                          len(chunk), int(median), C.c_void_p(base + at + o_count),
+                                          C.c_void_p(base + at + o_bounds), C.c_void_p(base + at + o_stats) if K else None,
+                                          _p(workspace) if K else None, workspace.numel() if K else 0, _stream()),
+                      "region_stats")
+                row.append(at)
+                at += nbytes
+            records.append(row)
+    return result, records
+
+
+def _rs_unpack(buf, row, plan, K):
+    """RegionStats of one subject from the (device or host) byte buffer: rows in the order of its values, then all,
+    whole"""
+    values, uniq, chunks = plan
+    pos = {v: i for i, v in enumerate(uniq)}
+    rows = [pos[v] for v in values]
+    counts, bounds, stats = [], [], []
+    for j, (chunk, at) in enumerate(zip(chunks, row)):
+        R = len(chunk) + 2
+        o_count, o_bounds, o_stats, _ = _rs_record(len(chunk), K)
+        c = buf[at + o_count:at + o_count + 8 * R].view(torch.int64)
+        b = buf[at + o_bounds:at + o_bounds + 24 * R].view(torch.int32).view(R, 6)
+        s = buf[at + o_stats:at + o_stats + 20 * R * K].view(torch.float32).view(R, K, 5)
+        counts.append(c[:-2])
+        bounds.append(b[:-2])
+        stats.append(s[:-2])
+        if j == 0:
+            tail = (c[-2:], b[-2:], s[-2:])
+    if len(chunks) == 1 and rows == list(range(len(uniq))):
+        return RegionStats(c, b, s)
+    idx = torch.tensor(rows, dtype=torch.int64, device=buf.device)
+    return RegionStats(*(torch.cat([torch.cat(part)[idx], t]) for part, t in zip((counts, bounds, stats), tail)))
+
+
+def region_stats(labels, images, values, median=True, result=None, workspace=None):
+    """Statistics of image values grouped by the label of the voxel.  labels: a device label volume [W, H, D] or
+    [1, W, H, D] (bool / (u)int8 / int16 / int32 / int64 / float32 holding integers); images: K >= 0 device tensors
+    [C, W, H, D] (or [W, H, D]) on the same grid, float32 / float16 / bfloat16 / uint8 / int16, the channels of an image
+    pooled; values: the int label values of the listed regions, any number (more than 64 distinct ones run as several
+    launch sets).  -> RegionStats of device tensors; nothing is copied or synchronised.
+
+    List form: labels a list of n label volumes, images a list of n lists of K images (shapes may differ between
+    subjects) -> RegionStats of HOST tensors with the subjects stacked in front, from one device-to-host copy.  With
+    `values` a list of n lists (each subject its own values; the number of images may then differ too) the result is a
+    list of n host RegionStats instead, still from one copy.
+
+    median=False skips the select passes; that column is NaN.  `result` / `workspace`: uint8 device tensors to use
+    instead of fresh ones (sizes: region_stats_bytes, added up over the subjects for `result`)."""
+    single = torch.is_tensor(labels)
+    label_list = [labels] if single else list(labels)
+    image_lists = [list(images)] if single else [list(im) for im in images]
+    if not label_list or len(label_list) != len(image_lists):
+        raise _lib.M355Error("region_stats: one list of images per label volume, at least one subject")
+    values = list(values)
+    own_values = not single and len(values) > 0 and isinstance(values[0], (list, tuple))
+    if own_values and len(values) != len(label_list):
+        raise _lib.M355Error(f"region_stats: {len(values)} lists of values for {len(label_list)} subjects")
+    if not own_values and any(len(im) != len(image_lists[0]) for im in image_lists):
+        raise _lib.M355Error("region_stats: every subject needs the same number of images")
+    plans = [_rs_chunks(v) for v in values] if own_values else [_rs_chunks(values)] * len(label_list)
+    subjects = [_rs_subject(lab, im, i) for i, (lab, im) in enumerate(zip(label_list, image_lists))]
+    buf, records = _rs_enqueue(subjects, plans, bool(median), result, workspace)
+    if single:
+        return _rs_unpack(buf, records[0], plans[0], len(image_lists[0]))
+    host = buf.cpu()
+    per = [_rs_unpack(host, row, plan, len(im)) for row, plan, im in zip(records, plans, image_lists)]
+    return per if own_values else RegionStats(*(torch.stack(field) for field in zip(*per)))
