@@ -28,7 +28,7 @@ from ._lib import ACT_LEAKY_RELU, ACT_NONE, ACT_RELU, ConvDesc, NormDesc, check
 #                     only the conv kernels differ; results differ from "fp32" by summation-order noise.
 #   "bf16" / "fp16"   operands rounded to 16 bits, fp32 accumulate (BASELINE cfg3 / cfg5).
 # In the 16-bit modes the forward / data-gradient / weight-gradient kernels of the 3x3x3 stride-1 convolutions with
-# more than 4 channels on both sides read the c8 activation layout (include/m355seg.h; `H16_TRAIN_C8` below); the
+# more than 4 channels on both sides read the c8 activation layout (include/m355seg.h); the
 # edge layers go through the fp32-tensor entry points, which round the operands while staging them (Cin <= 4
 # forward) or take the vector-ALU fp32 path (Cout <= 4).  Normalisation, pooling, conv-transpose, softmax and loss
 # kernels always compute in fp32.
@@ -84,25 +84,41 @@ CONV_PROFILE_EVERY = 1
 _prof_seen = 0
 
 
-def _prof_gate(tag, desc=None, which=0):
-    """-> (CONV_PROFILE or None, plan) for a launch about to be issued"""
-    prof = CONV_PROFILE
-    if prof is None:
-        return None, None
-    plan = conv_plan(desc, which) if desc is not None else None
-    if CONV_PROFILE_KEYS is not None and (tag, plan) not in CONV_PROFILE_KEYS:
-        return None, plan
-    if CONV_PROFILE_EVERY > 1:
-        global _prof_seen
-        _prof_seen += 1
-        if _prof_seen % CONV_PROFILE_EVERY:
-            return None, plan
-    return prof, plan
-
-
 def _conv_bytes(N, Cin, Cout, voxels, taps, in_elem, out_elem):
     """algorithmic HBM bytes of one conv launch: input once + output once + weights once"""
     return float(N) * voxels * (Cin * in_elem + Cout * out_elem) + 4.0 * Cin * Cout * taps
+
+
+def _conv_launch(tag, d, which, in_elem, out_elem, fn, *args):
+    """THE launch of a convolution: `fn(*args)`, an entry point of the library, checked.  While CONV_PROFILE is a list and
+    the gates let this launch through, it is recorded between two events.  d: the descriptor before any flag is set, which
+    gives the shape of the record (N, Cin, Cout, k and the output voxels: flops and bytes) and its plan,
+    m355_conv3d_plan(d, which) -- which = None: the record carries no plan (the weight gradient from c8 operands);
+    in_elem / out_elem: bytes per element the flow reports.  With profiling off nothing of the record is computed."""
+    prof = CONV_PROFILE
+    if prof is not None:
+        plan = conv_plan(d, which) if which is not None else None
+        if CONV_PROFILE_KEYS is not None and (tag, plan) not in CONV_PROFILE_KEYS:
+            prof = None
+        elif CONV_PROFILE_EVERY > 1:
+            global _prof_seen
+            _prof_seen += 1
+            if _prof_seen % CONV_PROFILE_EVERY:
+                prof = None
+    if prof is not None:
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+    rc = fn(*args)
+    if rc:
+        check(rc, fn.__name__[len("m355_"):])
+    if prof is not None:
+        e1.record()
+        taps = d.k ** 3
+        voxels = 1
+        for n in (d.D, d.H, d.W):
+            voxels *= (n + 2 * d.pad - d.k) // d.stride + 1
+        prof.append((tag, 2.0 * taps * d.Cin * d.Cout * d.N * voxels, e0, e1, plan,
+                     _conv_bytes(d.N, d.Cin, d.Cout, voxels, taps, in_elem, out_elem)))
 
 
 # ----------------------------------------------------------------- helpers
@@ -354,11 +370,10 @@ def as_f32(x):
 # the 16-bit modes, flipped / transposed for the data gradient) and the library used to repack before every
 # launch (234 launches per profiled run).  Weights only change at optimizer.step(), which bumps `_version`.
 PACK_CACHE = True
-# 16-bit precision modes, training: pack the conv input / output gradient to c8 once in the autograd function and run
-# forward, data gradient and weight gradient on the c8 entry points (False: fp32 operands, staged inside the library)
-H16_TRAIN_C8 = True
-# ... and keep activations AND activation gradients of ModularUNet / Block3d only in c8 while training (round 3: the
-# fp32 tensors the twin flow keeps beside the c8 ones bound the 16-bit step); False: the round-2 twin flow
+# 16-bit precision modes, training: the conv input / output gradient is packed to c8 once in the autograd function, and
+# forward, data gradient and weight gradient run on the c8 entry points.  H16_TRAIN_C8ONLY: also keep activations AND
+# activation gradients of ModularUNet / Block3d only in c8 while training (round 3: the fp32 tensors the twin flow keeps
+# beside the c8 ones bound the 16-bit step); False: the round-2 twin flow
 H16_TRAIN_C8ONLY = os.environ.get("M355_TRAIN_C8ONLY", "1") != "0"
 _bn_sync_group = None      # (defined properly with batch_norm_sync below)
 
@@ -671,57 +686,80 @@ def _c8_channel_partials(x16: Act16, stats: dict):
     stats["partials"], stats["slots"] = part, slots
 
 
-def _conv3d_act16(x16: Act16, weight, bias, add, stats, c8_out=False, softmax=False, sigmoid=False):
-    """3x3x3 / s1 / p1 forward on a c8 input (no autograd: the c8 flow only exists under no_grad).  c8_out: the
-    result (a pre-norm tensor) is written by the conv epilogue as c8 too and returned as an Act16.  softmax:
-    nn.Softmax(dim=1) of the result (the conv's epilogue where the kernel variant has one, else a separate pass);
-    sigmoid: nn.Sigmoid of it, the same way."""
+def _head_flag(d, softmax, sigmoid):
+    """-> the descriptor flag of the hypothesis head the conv epilogue of `d` applies itself; 0: no head asked for, or the
+    kernel variant has no epilogue (`_head_fwd` then runs as a pass of its own)"""
+    L = _lib.lib()
+    if softmax and L.m355_conv3d_fuses_softmax(C.byref(d)) != 0:
+        return _lib.CONV_SOFTMAX
+    if sigmoid and L.m355_conv3d_fuses_sigmoid(C.byref(d)) != 0:
+        return _lib.CONV_SIGMOID
+    return 0
+
+
+def _head_fwd(x, softmax, inner=1, diag_bias=0.0):
+    """nn.Softmax(dim=1) of the logits `x` (softmax; inner / diag_bias: StochasticMatrix) or nn.Sigmoid of them, as a pass"""
+    x = x.contiguous()
+    y = torch.empty_like(x)
+    if softmax:
+        N, Ctot = x.shape[0], x.shape[1]
+        check(_lib.lib().m355_softmax_fwd(_p(x), _p(y), N, Ctot // inner, inner, x.numel() // (N * Ctot), float(diag_bias),
+                                          _stream()), "softmax_fwd")
+    else:
+        check(_lib.lib().m355_sigmoid_fwd(_p(x), _p(y), x.numel(), _stream()), "sigmoid_fwd")
+    return y
+
+
+def _head_bwd(y, dy, softmax, inner=1):
+    """dlogits from the saved head output: y * (dy - sum_c y dy) (softmax) or dy * y * (1 - y) (sigmoid)"""
+    y, dy = y.contiguous(), dy.contiguous()
+    dx = torch.empty_like(y)
+    if softmax:
+        N, Ctot = y.shape[0], y.shape[1]
+        check(_lib.lib().m355_softmax_bwd(_p(y), _p(dy), _p(dx), N, Ctot // inner, inner, y.numel() // (N * Ctot), _stream()),
+              "softmax_bwd")
+    else:
+        check(_lib.lib().m355_sigmoid_bwd(_p(y), _p(dy), _p(dx), y.numel(), _stream()), "sigmoid_bwd")
+    return dx
+
+
+def _conv3d_act16(x16: Act16, weight, bias, add, stats, out16: Optional[Act16], softmax=False, sigmoid=False):
+    """3x3x3 / s1 / p1 forward on a c8 input, the one launch sequence of the no-grad c8 flow and of `_Conv3dC8Fn`.
+    out16: the result (a pre-norm tensor) is written there by the conv epilogue, as c8 too; None: a fresh fp32 tensor,
+    with `add` fused and nn.Softmax(dim=1) / nn.Sigmoid applied (the conv's epilogue where the kernel variant has one and
+    neither `add` nor `stats` is in the way, else a separate pass).  `weight` is contiguous.  -> (result, descriptor)"""
     L = _lib.lib()
     _require(weight, bias, add)
-    weight = weight.contiguous()
     N, Cin, D, H, W = x16.shape
     Cout = weight.shape[0]
-    c8_out = c8_out and add is None
-    if add is not None:
-        add = add.contiguous()
     d = _conv_desc(N, Cin, Cout, D, H, W, 3, 1, 1, 0, 0, compute=x16.compute)
     wbuf, flags = _packed_weight(weight, d, 0)
-    fuse_sm = (softmax and not c8_out and add is None and stats is None
-               and L.m355_conv3d_fuses_softmax(C.byref(d)) != 0)
-    fuse_sg = (sigmoid and not c8_out and add is None and stats is None
-               and L.m355_conv3d_fuses_sigmoid(C.byref(d)) != 0)
-    d = _with_flags(d, flags | (_lib.CONV_SOFTMAX if fuse_sm else 0) | (_lib.CONV_SIGMOID if fuse_sg else 0))
+    head = softmax or sigmoid
+    fused = _head_flag(d, softmax, sigmoid) if (head and out16 is None and add is None and stats is None) else 0
+    dk = _with_flags(d, flags | fused)
     ws = _workspace(L.m355_conv3d_h16_workspace(C.byref(d), 0), x16.device)
-    prof, plan = _prof_gate("conv3d_fwd", d, 0)
-    if prof is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
     part = None
     slots = 0
     if stats is not None:
-        slots = L.m355_conv3d_stats_slots_c8(C.byref(d)) if c8_out else L.m355_conv3d_stats_slots(C.byref(d))
+        slots = L.m355_conv3d_stats_slots(C.byref(d)) if out16 is None else L.m355_conv3d_stats_slots_c8(C.byref(d))
     if slots > 0:
         part = torch.empty((N, slots, Cout, 2), dtype=torch.float32, device=x16.device)
         stats["partials"], stats["slots"] = part, slots
-    if c8_out:
-        y = Act16.empty(N, Cout, (D, H, W), x16.compute, x16.device)
-        check(L.m355_conv3d_fwd_h16_c8(C.byref(d), x16.ptr(), x16.batch_stride(), _p(wbuf), _p(bias), y.ptr(),
-                                       y.batch_stride(), _p(part), _p(ws), ws.numel(), _stream()), "conv3d_fwd_h16_c8")
-    else:
-        y = torch.empty((N, Cout, D, H, W), dtype=torch.float32, device=x16.device)
-        check(L.m355_conv3d_fwd_h16(C.byref(d), x16.ptr(), x16.batch_stride(), _p(wbuf), _p(bias), _p(add), _p(y),
-                                    _p(part), _p(ws), ws.numel(), _stream()), "conv3d_fwd_h16")
-    if prof is not None:
-        e1.record()
-        prof.append(("conv3d_fwd", 2.0 * 27 * Cin * Cout * N * D * H * W, e0, e1, plan,
-                     _conv_bytes(N, Cin, Cout, D * H * W, 27, 2, 2 if c8_out else 4)))
-    if c8_out and stats is not None and slots == 0:
-        _c8_channel_partials(y, stats)
-    if softmax and not fuse_sm:
-        y = softmax_channels(as_f32(y))
-    if sigmoid and not fuse_sg:
-        y = _SigmoidFn.apply(as_f32(y))
-    return y
+    if out16 is not None:
+        y = out16
+        _conv_launch("conv3d_fwd", d, 0, 2, 2, L.m355_conv3d_fwd_h16_c8, C.byref(dk), x16.ptr(),
+                     x16.batch_stride(), _p(wbuf), _p(bias), y.ptr(), y.batch_stride(), _p(part), _p(ws), ws.numel(), _stream())
+        if stats is not None and slots == 0:
+            _c8_channel_partials(y, stats)
+        return y, d
+    if add is not None:
+        add = add.contiguous()
+    y = torch.empty((N, Cout, D, H, W), dtype=torch.float32, device=x16.device)
+    _conv_launch("conv3d_fwd", d, 0, 2, 4, L.m355_conv3d_fwd_h16, C.byref(dk), x16.ptr(), x16.batch_stride(),
+                 _p(wbuf), _p(bias), _p(add), _p(y), _p(part), _p(ws), ws.numel(), _stream())
+    if head and not fused:
+        y = _head_fwd(y, softmax)
+    return y, d
 
 
 # ------------------------------------------------- c8-only TRAINING flow (16-bit modes, autograd on)
@@ -747,7 +785,7 @@ def _pack_scaled(x, compute, scale):
     x, xbs = _dense_channels(x)
     N, Cc = x.shape[:2]
     S = x.shape[2] * x.shape[3] * x.shape[4]
-    out = torch.empty((N, (Cc + 7) // 8, S, 8), dtype=_DT16[compute], device=x.device)
+    out = _c8_grad(N, Cc, S, compute, x.device)
     check(_lib.lib().m355_act16_pack_scaled(_p(x), _p(out), N, Cc, S, xbs, 0, compute, float(scale), _stream()),
           "act16_pack_scaled")
     return out
@@ -810,8 +848,7 @@ class _UnpackFn(torch.autograd.Function):
 class _C8ConvMeta:
     x16: "Act16"                      # the whole (possibly concatenated) conv input
     part_blocks: Sequence[int]        # channel blocks of each autograd part of it
-    out16: Optional["Act16"] = None   # c8 destination (None with f32_out)
-    f32_out: bool = False             # fp32 NCDHW result (the out conv), optionally with the fused softmax / sigmoid
+    out16: Optional["Act16"] = None   # c8 destination; None: fp32 NCDHW result (the out conv), optionally with its head
     softmax: bool = False
     sigmoid: bool = False
     stats: Optional[dict] = None
@@ -825,58 +862,17 @@ class _Conv3dC8Fn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, weight, bias, add, meta: _C8ConvMeta, *part_ts):
-        L = _lib.lib()
         x16 = meta.x16
-        _require(weight, bias, add)
         weight = weight.contiguous()
-        N, Cin, D, H, W = x16.shape
-        Cout = weight.shape[0]
-        d = _conv_desc(N, Cin, Cout, D, H, W, 3, 1, 1, 0, 0, compute=x16.compute)
-        wbuf, flags = _packed_weight(weight, d, 0)
-        fuse_sm = meta.softmax and add is None and L.m355_conv3d_fuses_softmax(C.byref(d)) != 0
-        fuse_sg = meta.sigmoid and add is None and L.m355_conv3d_fuses_sigmoid(C.byref(d)) != 0
-        dk = _with_flags(d, flags | (_lib.CONV_SOFTMAX if fuse_sm else 0) | (_lib.CONV_SIGMOID if fuse_sg else 0))
-        ws = _workspace(L.m355_conv3d_h16_workspace(C.byref(d), 0), x16.device)
-        prof, plan = _prof_gate("conv3d_fwd", d, 0)
-        if prof is not None:
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-        part = None
-        slots = 0
-        if meta.stats is not None:
-            slots = L.m355_conv3d_stats_slots(C.byref(d)) if meta.f32_out else L.m355_conv3d_stats_slots_c8(C.byref(d))
-        if slots > 0:
-            part = torch.empty((N, slots, Cout, 2), dtype=torch.float32, device=x16.device)
-            meta.stats["partials"], meta.stats["slots"] = part, slots
-        if meta.f32_out:
-            if add is not None:
-                add = add.contiguous()
-            y = torch.empty((N, Cout, D, H, W), dtype=torch.float32, device=x16.device)
-            check(L.m355_conv3d_fwd_h16(C.byref(dk), x16.ptr(), x16.batch_stride(), _p(wbuf), _p(bias), _p(add), _p(y),
-                                        _p(part), _p(ws), ws.numel(), _stream()), "conv3d_fwd_h16")
-            if meta.softmax and not fuse_sm:
-                logits, y = y, torch.empty_like(y)
-                check(L.m355_softmax_fwd(_p(logits), _p(y), N, Cout, 1, D * H * W, 0.0, _stream()), "softmax_fwd")
-            if meta.sigmoid and not fuse_sg:
-                logits, y = y, torch.empty_like(y)
-                check(L.m355_sigmoid_fwd(_p(logits), _p(y), y.numel(), _stream()), "sigmoid_fwd")
-            if x16.compute == _lib.COMPUTE_F16:     # the head of an fp16 pass: size-derived estimate (capture fallback)
-                _gs().auto = _auto_grad_scale(N * D * H * W)
-                _overflow_word(x16.device)
-            out = y
-        else:
-            y16 = meta.out16
-            check(L.m355_conv3d_fwd_h16_c8(C.byref(dk), x16.ptr(), x16.batch_stride(), _p(wbuf), _p(bias), y16.ptr(),
-                                           y16.batch_stride(), _p(part), _p(ws), ws.numel(), _stream()), "conv3d_fwd_h16_c8")
-            out = y16.alias()
-        if prof is not None:
-            e1.record()
-            prof.append(("conv3d_fwd", 2.0 * 27 * Cin * Cout * N * D * H * W, e0, e1, plan,
-                         _conv_bytes(N, Cin, Cout, D * H * W, 27, 2, 4 if meta.f32_out else 2)))
+        out, d = _conv3d_act16(x16, weight, bias, add, meta.stats, meta.out16, meta.softmax, meta.sigmoid)
+        if meta.out16 is not None:
+            out = meta.out16.alias()
+        elif x16.compute == _lib.COMPUTE_F16:     # the head of an fp16 pass: size-derived estimate (capture fallback)
+            _gs().auto = _auto_grad_scale(d.N * d.D * d.H * d.W)
+            _overflow_word(x16.device)
         ctx.meta, ctx.desc = meta, d
         ctx.gs = _gs()
         ctx.has_bias = bias is not None
-        ctx.x_info = (x16.C, x16.spatial, x16.compute)
         xa = x16.alias()
         if meta.softmax or meta.sigmoid:
             ctx.save_for_backward(xa, weight, out)
@@ -889,23 +885,13 @@ class _Conv3dC8Fn(torch.autograd.Function):
         L = _lib.lib()
         meta, d = ctx.meta, ctx.desc
         compute = d.compute
-        if meta.softmax:
+        if meta.softmax or meta.sigmoid:
             xa, weight, y = ctx.saved_tensors
-            dy = dy.contiguous()
-            dl = torch.empty_like(y)
-            check(L.m355_softmax_bwd(_p(y), _p(dy), _p(dl), d.N, d.Cout, 1, y.numel() // (d.N * d.Cout), _stream()),
-                  "softmax_bwd")
-            dy = dl
-        elif meta.sigmoid:
-            xa, weight, y = ctx.saved_tensors
-            dy = dy.contiguous()
-            dl = torch.empty_like(y)
-            check(L.m355_sigmoid_bwd(_p(y), _p(dy), _p(dl), y.numel(), _stream()), "sigmoid_bwd")
-            dy = dl
+            dy = _head_bwd(y, dy, meta.softmax)
         else:
             xa, weight = ctx.saved_tensors
         dadd = dy if (meta.has_add and ctx.needs_input_grad[2]) else None
-        if meta.f32_out:        # the gradient enters the c8 flow here: this node fixes the scale of the pass
+        if meta.out16 is None:   # the gradient enters the c8 flow here: this node fixes the scale of the pass
             key = (id(weight), tuple(dy.shape), "sigmoid") if meta.sigmoid else (id(weight), tuple(dy.shape))
             scale = ctx.gs.resolve(compute, dy, key)
             dy16 = _pack_scaled(dy, compute, scale)
@@ -916,40 +902,21 @@ class _Conv3dC8Fn(torch.autograd.Function):
         xa, xbs = _c8t(xa)
         need_w, need_b = ctx.needs_input_grad[0], ctx.needs_input_grad[1] and ctx.has_bias
         need_x = any(ctx.needs_input_grad[4:])
+        S = d.D * d.H * d.W
         dw = db = None
         if need_w or need_b:
             dw = torch.empty_like(weight)
             db = torch.empty(d.Cout, dtype=weight.dtype, device=weight.device) if ctx.has_bias else None
-            prof, _ = _prof_gate("conv3d_bwd_weight")
-            if prof is not None:
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
             ws = _workspace(L.m355_conv3d_bwd_weight_c8_workspace(C.byref(d)), weight.device)
-            check(L.m355_conv3d_bwd_weight_c8(C.byref(d), _p(xa), xbs, _p(dy16), dybs, _p(dw), _p(db), 1.0 / scale, _p(ws),
-                                              ws.numel(), _stream()), "conv3d_bwd_weight_c8")
-            if prof is not None:
-                e1.record()
-                vox = d.D * d.H * d.W
-                prof.append(("conv3d_bwd_weight", 2.0 * 27 * d.Cin * d.Cout * d.N * vox, e0, e1, None,
-                             _conv_bytes(d.N, d.Cin, d.Cout, vox, 27, 2, 2)))
+            _conv_launch("conv3d_bwd_weight", d, None, 2, 2, L.m355_conv3d_bwd_weight_c8, C.byref(d), _p(xa), xbs,
+                         _p(dy16), dybs, _p(dw), _p(db), 1.0 / scale, _p(ws), ws.numel(), _stream())
         dparts: List[Optional[torch.Tensor]] = [None] * len(meta.part_blocks)
         if need_x:
-            S = d.D * d.H * d.W
-            dx16 = torch.empty((d.N, (d.Cin + 7) // 8, S, 8), dtype=_DT16[compute], device=weight.device)
-            dd = _conv_desc(d.N, d.Cin, d.Cout, d.D, d.H, d.W, 3, 1, 1, 0, 0, compute=compute)
-            wbuf, flags = _packed_weight(weight, dd, 1)
-            ws = _workspace(L.m355_conv3d_h16_workspace(C.byref(dd), 1), weight.device)
-            prof, plan = _prof_gate("conv3d_bwd_data", dd, 1)
-            dd = _with_flags(dd, flags)
-            if prof is not None:
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-            check(L.m355_conv3d_bwd_data_h16_c8(C.byref(dd), _p(dy16), dybs, _p(wbuf), _p(dx16), 0, _p(ws), ws.numel(),
-                                                _stream()), "conv3d_bwd_data_h16_c8")
-            if prof is not None:
-                e1.record()
-                prof.append(("conv3d_bwd_data", 2.0 * 27 * d.Cin * d.Cout * d.N * S, e0, e1, plan,
-                             _conv_bytes(d.N, d.Cin, d.Cout, S, 27, 2, 2)))
+            dx16 = _c8_grad(d.N, d.Cin, S, compute, weight.device)
+            wbuf, flags = _packed_weight(weight, d, 1)
+            ws = _workspace(L.m355_conv3d_h16_workspace(C.byref(d), 1), weight.device)
+            _conv_launch("conv3d_bwd_data", d, 1, 2, 2, L.m355_conv3d_bwd_data_h16_c8, C.byref(_with_flags(d, flags)),
+                         _p(dy16), dybs, _p(wbuf), _p(dx16), 0, _p(ws), ws.numel(), _stream())
             b0 = 0
             for i, nb in enumerate(meta.part_blocks):
                 if ctx.needs_input_grad[4 + i]:
@@ -958,24 +925,16 @@ class _Conv3dC8Fn(torch.autograd.Function):
         return (dw if need_w else None, db if need_b else None, dadd, None, *dparts)
 
 
-def _conv3d_c8_train(x16: Act16, parts, weight, bias, add, stats, c8_out, softmax, out16=None, sigmoid=False):
-    """dispatch of `_conv3d_act16` while autograd records (c8 training flow)"""
+def _conv3d_c8_train(x16: Act16, parts, weight, bias, add, stats, out16, softmax, sigmoid):
+    """`_conv3d_act16` while autograd records (c8 training flow)"""
     if parts is None:
         parts = [x16]
     if any(p.C % 8 for p in parts[:-1]):
         raise _lib.M355Error("c8 training flow: concat parts must be whole channel blocks")
-    if c8_out and out16 is None:
-        N, _, D, H, W = x16.shape
-        out16 = Act16.empty(N, weight.shape[0], (D, H, W), x16.compute, x16.device)
-    meta = _C8ConvMeta(x16, [p.CB for p in parts], out16=out16, f32_out=not c8_out, softmax=softmax, sigmoid=sigmoid,
-                       stats=stats, has_add=add is not None)
+    meta = _C8ConvMeta(x16, [p.CB for p in parts], out16=out16, softmax=softmax, sigmoid=sigmoid, stats=stats,
+                       has_add=add is not None)
     out = _Conv3dC8Fn.apply(weight, bias, add, meta, *[p.t for p in parts])
-    if not c8_out:
-        return out
-    y16 = meta.out16
-    if stats is not None and "partials" not in stats:
-        _c8_channel_partials(y16, stats)
-    return Act16(y16.data, y16.C, y16.spatial, y16.compute, y16.cb0, out)
+    return out if out16 is None else out16.with_t(out)
 
 
 @dataclass
@@ -1133,10 +1092,6 @@ class _ConvTC8Fn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x_t, weight, bias, x: Act16, y16: Act16):
         weight = weight.contiguous()
-        N, Cin, D, H, W = x.shape
-        Cout = weight.shape[1]
-        if y16.shape != (N, Cout, 2 * D, 2 * H, 2 * W):
-            raise _lib.M355Error(f"c8 slot shape {y16.shape} != op output shape {(N, Cout, 2 * D, 2 * H, 2 * W)}")
         ctx.desc, ctx.compute, ctx.has_bias = _convt_c8_fwd(x, weight, bias, y16), x.compute, bias is not None
         ctx.gs = _gs()
         ctx.save_for_backward(x.alias(), weight)
@@ -1155,7 +1110,7 @@ class _ConvTC8Fn(torch.autograd.Function):
         dx16 = dw = db = None
         if L.m355_conv_transpose3d_h16_bwd_supported(C.byref(d)):
             if need_x:
-                dx16 = torch.empty((d.N, (d.Cin + 7) // 8, S, 8), dtype=_DT16[compute], device=weight.device)
+                dx16 = _c8_grad(d.N, d.Cin, S, compute, weight.device)
                 check(L.m355_conv_transpose3d_bwd_data_h16(C.byref(d), _p(dy16), dybs, _p(weight), _p(dx16), 0, compute,
                                                            _stream()), "conv_transpose3d_bwd_data_h16")
             if need_w:
@@ -1242,14 +1197,14 @@ class _Conv3dFn(torch.autograd.Function):
                                          "tensor and copy_into the slot instead)")
         d = _conv_desc(N, Cin, Cout, D, H, W, k, meta.stride, meta.pad, xbs, ybs, compute=_COMPUTE[_compute_mode])
         wbuf, flags = _packed_weight(weight, d, 0)
-        fuse_sm = meta.softmax and L.m355_conv3d_fuses_softmax(C.byref(d)) != 0
-        fuse_sg = meta.sigmoid and L.m355_conv3d_fuses_sigmoid(C.byref(d)) != 0
-        dk = _with_flags(d, flags | (_lib.CONV_SOFTMAX if fuse_sm else 0) | (_lib.CONV_SIGMOID if fuse_sg else 0))
+        head = meta.softmax or meta.sigmoid
+        fused = _head_flag(d, meta.softmax, meta.sigmoid) if head else 0
+        dk = _with_flags(d, flags | fused)
         # 16-bit training flow: the conv input is packed to c8 ONCE here (the library would stage the same copy
         # internally), consumed by the forward kernel and kept for the weight gradient (m355_conv3d_bwd_weight_h16
         # reads both operands as c8); the fp32 input is then not saved at all
         x16 = None
-        if (H16_TRAIN_C8 and d.compute in _DT16 and k == 3 and meta.stride == 1 and meta.pad == 1
+        if (d.compute in _DT16 and k == 3 and meta.stride == 1 and meta.pad == 1
                 and Cin > 4 and Cout > 4 and not meta.softmax and not meta.sigmoid and D * H * W * 64 < 2 ** 31
                 and ctx.needs_input_grad[0]):
             x16 = _c8_twin(x, d.compute)
@@ -1258,40 +1213,23 @@ class _Conv3dFn(torch.autograd.Function):
             meta.h16_train = d.compute
         ws = _workspace(L.m355_conv3d_h16_workspace(C.byref(d), 0) if x16 is not None
                         else L.m355_conv3d_fwd_workspace(C.byref(d)), x.device)
-        prof, plan = _prof_gate("conv3d_fwd", d, 0)
-        if prof is not None:
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
+        # statistics of the following normalisation fused into the conv epilogue (per-wave partials)
         slots = L.m355_conv3d_stats_slots(C.byref(d)) if meta.stats is not None else 0
-        if x16 is not None:
-            part = torch.empty((N, slots, Cout, 2), dtype=torch.float32, device=x.device) if slots > 0 else None
-            check(L.m355_conv3d_fwd_h16(C.byref(dk), x16.ptr(), x16.batch_stride(), _p(wbuf), _p(bias), _p(add), _p(y),
-                                        _p(part), _p(ws), ws.numel(), _stream()), "conv3d_fwd_h16")
-            if part is not None:
-                meta.stats["partials"], meta.stats["slots"] = part, slots
-        elif slots > 0:
-            # statistics of the following normalisation fused into the conv epilogue (per-wave partials)
+        part = None
+        if slots > 0:
             part = torch.empty((N, slots, Cout, 2), dtype=torch.float32, device=x.device)
-            check(L.m355_conv3d_fwd_stats(C.byref(dk), _p(x), _p(wbuf), _p(bias), _p(add), _p(y), _p(part), _p(ws),
-                                          ws.numel(), _stream()), "conv3d_fwd_stats")
             meta.stats["partials"], meta.stats["slots"] = part, slots
+        if x16 is not None:
+            _conv_launch("conv3d_fwd", d, 0, 4, 4, L.m355_conv3d_fwd_h16, C.byref(dk), x16.ptr(), x16.batch_stride(),
+                         _p(wbuf), _p(bias), _p(add), _p(y), _p(part), _p(ws), ws.numel(), _stream())
+        elif part is not None:
+            _conv_launch("conv3d_fwd", d, 0, 4, 4, L.m355_conv3d_fwd_stats, C.byref(dk), _p(x), _p(wbuf), _p(bias),
+                         _p(add), _p(y), _p(part), _p(ws), ws.numel(), _stream())
         else:
-            check(L.m355_conv3d_fwd(C.byref(dk), _p(x), _p(wbuf), _p(bias), _p(add), _p(y), _p(ws),
-                                    ws.numel(), _stream()), "conv3d_fwd")
-        if prof is not None:
-            e1.record()
-            flops = 2.0 * k ** 3 * Cin * Cout * N * oshape[2] * oshape[3] * oshape[4]
-            prof.append(("conv3d_fwd", flops, e0, e1, plan,
-                         _conv_bytes(N, Cin, Cout, oshape[2] * oshape[3] * oshape[4], k ** 3, 4, 4)))
-        if meta.softmax and not fuse_sm:   # kernel variants without the fused epilogue: a separate softmax pass
-            logits = y.contiguous()
-            y = torch.empty_like(logits)
-            check(L.m355_softmax_fwd(_p(logits), _p(y), N, Cout, 1, oshape[2] * oshape[3] * oshape[4], 0.0, _stream()),
-                  "softmax_fwd")
-        if meta.sigmoid and not fuse_sg:   # ... or a separate sigmoid pass
-            logits = y.contiguous()
-            y = torch.empty_like(logits)
-            check(L.m355_sigmoid_fwd(_p(logits), _p(y), y.numel(), _stream()), "sigmoid_fwd")
+            _conv_launch("conv3d_fwd", d, 0, 4, 4, L.m355_conv3d_fwd, C.byref(dk), _p(x), _p(wbuf), _p(bias), _p(add),
+                         _p(y), _p(ws), ws.numel(), _stream())
+        if head and not fused:   # kernel variants without the fused epilogue: a separate pass
+            y = _head_fwd(y, meta.softmax)
         ctx.meta, ctx.desc = meta, d
         ctx.has_bias, ctx.has_add = bias is not None, add is not None
         ctx.part_channels = [p.shape[1] for p in parts]
@@ -1311,19 +1249,9 @@ class _Conv3dFn(torch.autograd.Function):
         L = _lib.lib()
         meta = ctx.meta
         d = ctx.desc
-        if meta.softmax:   # dlogits = y * (dy - sum_c y dy)
+        if meta.softmax or meta.sigmoid:
             x, weight, y = ctx.saved_tensors
-            dy = dy.contiguous()
-            dl = torch.empty_like(y)
-            check(L.m355_softmax_bwd(_p(y.contiguous()), _p(dy), _p(dl), d.N, d.Cout, 1, y.numel() // (d.N * d.Cout),
-                                     _stream()), "softmax_bwd")
-            dy = dl
-        elif meta.sigmoid:   # dlogits = dy * y * (1 - y)
-            x, weight, y = ctx.saved_tensors
-            dy, y = dy.contiguous(), y.contiguous()
-            dl = torch.empty_like(y)
-            check(L.m355_sigmoid_bwd(_p(y), _p(dy), _p(dl), y.numel(), _stream()), "sigmoid_bwd")
-            dy = dl
+            dy = _head_bwd(y, dy, meta.softmax)
         else:
             x, weight = ctx.saved_tensors
         dy, dybs = _dense_channels(dy)
@@ -1342,50 +1270,33 @@ class _Conv3dFn(torch.autograd.Function):
                 dy16 = pack_act16(dy, x16.compute)
         else:
             x_dtype, x_device = x.dtype, x.device
+        # (the records of this function count 4-byte elements on both sides, whichever operands the kernels read)
         if need_w or (need_b and ctx.has_bias):
             dw = torch.empty_like(weight)
             db = torch.empty(d.Cout, dtype=weight.dtype, device=weight.device) if ctx.has_bias else None
-            prof, bplan = _prof_gate("conv3d_bwd_weight", d if x16 is None else None, 2)
-            if prof is not None:
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
             if x16 is not None:
                 ws = _workspace(L.m355_conv3d_bwd_weight_h16_workspace(C.byref(d)), x_device)
-                check(L.m355_conv3d_bwd_weight_h16(C.byref(d), x16.ptr(), x16.batch_stride(), dy16.ptr(), dy16.batch_stride(),
-                                                   _p(dy) if db is not None else None, _p(dw), _p(db), _p(ws), ws.numel(),
-                                                   _stream()), "conv3d_bwd_weight_h16")
+                _conv_launch("conv3d_bwd_weight", d, None, 4, 4, L.m355_conv3d_bwd_weight_h16, C.byref(d), x16.ptr(),
+                             x16.batch_stride(), dy16.ptr(), dy16.batch_stride(), _p(dy) if db is not None else None,
+                             _p(dw), _p(db), _p(ws), ws.numel(), _stream())
             else:
                 ws = _workspace(L.m355_conv3d_bwd_weight_workspace(C.byref(d)), x_device)
-                check(L.m355_conv3d_bwd_weight(C.byref(d), _p(x), _p(dy), _p(dw), _p(db), _p(ws), ws.numel(),
-                                               _stream()), "conv3d_bwd_weight")
-            if prof is not None:
-                e1.record()
-                vox = dy.shape[2] * dy.shape[3] * dy.shape[4]
-                prof.append(("conv3d_bwd_weight", 2.0 * d.k ** 3 * d.Cin * d.Cout * d.N * vox, e0, e1, bplan,
-                             _conv_bytes(d.N, d.Cin, d.Cout, vox, d.k ** 3, 4, 4)))
+                _conv_launch("conv3d_bwd_weight", d, 2, 4, 4, L.m355_conv3d_bwd_weight, C.byref(d), _p(x), _p(dy),
+                             _p(dw), _p(db), _p(ws), ws.numel(), _stream())
         if need_x:
             # gradient w.r.t. the (possibly concatenated) input, dense, then sliced per part
             dx = torch.empty((d.N, d.Cin, d.D, d.H, d.W), dtype=x_dtype, device=x_device)
             dd = _conv_desc(d.N, d.Cin, d.Cout, d.D, d.H, d.W, d.k, d.stride, d.pad, 0, d.y_batch_stride, compute=d.compute)
             wbuf, flags = _packed_weight(weight, dd, 1)
-            ws = _workspace(L.m355_conv3d_h16_workspace(C.byref(dd), 1) if dy16 is not None
-                            else L.m355_conv3d_bwd_data_workspace(C.byref(dd)), x_device)
-            prof, plan = _prof_gate("conv3d_bwd_data", dd, 1)
-            dd = _with_flags(dd, flags)
-            if prof is not None:
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
+            ddk = _with_flags(dd, flags)
             if dy16 is not None:
-                check(L.m355_conv3d_bwd_data_h16(C.byref(dd), dy16.ptr(), dy16.batch_stride(), _p(wbuf), _p(dx), _p(ws),
-                                                 ws.numel(), _stream()), "conv3d_bwd_data_h16")
+                ws = _workspace(L.m355_conv3d_h16_workspace(C.byref(dd), 1), x_device)
+                _conv_launch("conv3d_bwd_data", dd, 1, 4, 4, L.m355_conv3d_bwd_data_h16, C.byref(ddk), dy16.ptr(),
+                             dy16.batch_stride(), _p(wbuf), _p(dx), _p(ws), ws.numel(), _stream())
             else:
-                check(L.m355_conv3d_bwd_data(C.byref(dd), _p(dy), _p(wbuf), _p(dx), _p(ws), ws.numel(),
-                                             _stream()), "conv3d_bwd_data")
-            if prof is not None:
-                e1.record()
-                vox = dy.shape[2] * dy.shape[3] * dy.shape[4]
-                prof.append(("conv3d_bwd_data", 2.0 * d.k ** 3 * d.Cin * d.Cout * d.N * vox, e0, e1, plan,
-                             _conv_bytes(d.N, d.Cin, d.Cout, vox, d.k ** 3, 4, 4)))
+                ws = _workspace(L.m355_conv3d_bwd_data_workspace(C.byref(dd)), x_device)
+                _conv_launch("conv3d_bwd_data", dd, 1, 4, 4, L.m355_conv3d_bwd_data, C.byref(ddk), _p(dy), _p(wbuf),
+                             _p(dx), _p(ws), ws.numel(), _stream())
             c0 = 0
             for i, cc in enumerate(ctx.part_channels):
                 if ctx.needs_input_grad[4 + i]:
@@ -1418,12 +1329,12 @@ def conv3d(x, weight, bias=None, add=None, stride=1, padding=1, out: Optional[Ou
         return pack_act16(conv3d(x, weight, bias, add, stride, padding, None, stats), out.buf16.compute, out.act16())
     if isinstance(x, Act16):
         if k == 3 and stride == 1 and padding == 1:
+            # (a conv with a fused fp32 `add`, or with a head, keeps its result in fp32)
+            out16 = _c8_out_slot(x, None, x.spatial, C=weight.shape[0]) if (c8_out and not head and add is None) else None
+            add32 = as_f32(add) if add is not None else None
             if torch.is_grad_enabled() and (_tracks_any(weight, bias, add) or _act16_tracks(x, add, *(c8_parts or ()))):
-                # c8 training flow (a conv with a fused fp32 `add` keeps its result in fp32)
-                return _conv3d_c8_train(x, c8_parts, weight, bias, as_f32(add) if add is not None else None, stats,
-                                        c8_out and not head and add is None, softmax, sigmoid=sigmoid)
-            return _conv3d_act16(x, weight, bias, as_f32(add) if add is not None else None, stats, c8_out and not head,
-                                 softmax, sigmoid)
+                return _conv3d_c8_train(x, c8_parts, weight, bias, add32, stats, out16, softmax, sigmoid)   # c8 training flow
+            return _conv3d_act16(x, weight.contiguous(), bias, add32, stats, out16, softmax, sigmoid)[0]
         if c8_parts is not None and _act16_tracks(*c8_parts):
             raise NotImplementedError("c8 training flow: only 3x3x3 / stride 1 / padding 1 convolutions read a concat buffer")
         x = x.to_f32()
@@ -1493,17 +1404,10 @@ def conv_transpose3d(x, weight, bias=None, stride=2, padding=0, output_padding=0
     k = weight.shape[2]
     if isinstance(x, Act16):
         if k == 2 and stride == 2 and padding == 0 and output_padding == 0:   # c8 -> c8 kernel
+            D, H, W = x.spatial
+            y16 = _c8_out_slot(x, out, (2 * D, 2 * H, 2 * W), C=weight.shape[1])
             if torch.is_grad_enabled() and (_tracks_any(weight, bias) or x.requires_grad):
-                y16 = out.act16() if (out is not None and out.buf16 is not None) else None
-                if y16 is None:
-                    N, Cin, D, H, W = x.shape
-                    y16 = Act16.empty(N, weight.shape[1], (2 * D, 2 * H, 2 * W), x.compute, x.device)
-                t = _ConvTC8Fn.apply(x.t, weight, bias, x, y16)
-                return Act16(y16.data, y16.C, y16.spatial, y16.compute, y16.cb0, t)
-            y16 = out.act16() if (out is not None and out.buf16 is not None) else None
-            if y16 is None:
-                N, Cin, D, H, W = x.shape
-                y16 = Act16.empty(N, weight.shape[1], (2 * D, 2 * H, 2 * W), x.compute, x.device)
+                return y16.with_t(_ConvTC8Fn.apply(x.t, weight, bias, x, y16))
             _convt_c8_fwd(x, weight.contiguous(), bias, y16)
             return y16
         y = _ConvT3dFn.apply(x.to_f32(), weight, bias, (k, stride, padding, output_padding, None))
@@ -1525,7 +1429,7 @@ class NormCfg:
     out: Optional[OutSlot] = None
     stats: Optional[dict] = None   # partial sums from the producing conv (ops.conv3d(..., stats=...))
     c8: int = 0                    # 16-bit no-grad flow: emit the result ONLY in the c8 layout (compute code)
-    # 16-bit TRAINING flow (H16_TRAIN_C8), set by norm_act() / its autograd function:
+    # 16-bit TRAINING flow on fp32 tensors (the twin flow), set by norm_act() / its autograd function:
     dx_twin: int = 0               # compute code when the conv that produced x wants its output gradient as c8 too
     twin: Optional["Act16"] = None  # c8 twin of the fp32 result, handed from the forward to norm_act()
     sync: Optional[tuple] = None   # synchronised batch norm: (process group, device-side total element count)
@@ -1681,13 +1585,13 @@ class _NormActFn(torch.autograd.Function):
             add, abs_ = _dense_channels(add)
         d = NormDesc(N, Cc, S, cfg.groups, cfg.act, cfg.eps, cfg.slope, xbs, ybs, abs_)
         mean, rstd, use_batch = _norm_statistics(L, d, x, cfg, N, Cc)
-        # 16-bit training flow (H16_TRAIN_C8): a dense output also leaves as a c8 twin for the convolution that
+        # 16-bit training flow on fp32 tensors (the twin flow): a dense output also leaves as a c8 twin for the convolution that
         # usually consumes it (handed over through `cfg.twin`, attached to the returned tensor by norm_act());
         # ctx.dx_twin: the convolution that produced x wants its output gradient in c8 as well (see backward)
         compute = _COMPUTE[_compute_mode]
         ctx.dx_twin = cfg.dx_twin
         cfg.twin = None
-        if H16_TRAIN_C8 and compute in _DT16 and cfg.out is None and ybs == Cc * S and Cc > 4:
+        if compute in _DT16 and cfg.out is None and ybs == Cc * S and Cc > 4:
             cfg.twin = Act16.empty(N, Cc, tuple(x.shape[2:]), compute, x.device)
             check(L.m355_norm_act_fwd_h16(C.byref(d), _p(x), _p(mean), _p(rstd), _p(gamma), _p(beta), _p(add), _p(y),
                                           cfg.twin.ptr(), cfg.twin.batch_stride(), compute, _stream()), "norm_act_fwd_h16")
@@ -2128,46 +2032,30 @@ def upsample_trilinear2x_hp(x, out: Optional[OutSlot] = None):
 class _SoftmaxFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, inner, diag_bias):
-        L = _lib.lib()
         _require(x)
-        x = x.contiguous()
-        N, Ctot = x.shape[0], x.shape[1]
-        Cc = Ctot // inner
-        S = x.numel() // (N * Ctot)
-        y = torch.empty_like(x)
-        check(L.m355_softmax_fwd(_p(x), _p(y), N, Cc, inner, S, float(diag_bias), _stream()), "softmax_fwd")
-        ctx.dims = (N, Cc, inner, S)
+        y = _head_fwd(x, True, inner, diag_bias)
+        ctx.inner = inner
         ctx.save_for_backward(y)
         return y
 
     @staticmethod
     def backward(ctx, dy):
-        L = _lib.lib()
         (y,) = ctx.saved_tensors
-        N, Cc, inner, S = ctx.dims
-        dy = dy.contiguous()
-        dx = torch.empty_like(y)
-        check(L.m355_softmax_bwd(_p(y), _p(dy), _p(dx), N, Cc, inner, S, _stream()), "softmax_bwd")
-        return dx, None, None
+        return _head_bwd(y, dy, True, ctx.inner), None, None
 
 
 class _SigmoidFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x):
         _require(x)
-        x = x.contiguous()
-        y = torch.empty_like(x)
-        check(_lib.lib().m355_sigmoid_fwd(_p(x), _p(y), x.numel(), _stream()), "sigmoid_fwd")
+        y = _head_fwd(x, False)
         ctx.save_for_backward(y)
         return y
 
     @staticmethod
     def backward(ctx, dy):
         (y,) = ctx.saved_tensors
-        dy = dy.contiguous()
-        dx = torch.empty_like(y)
-        check(_lib.lib().m355_sigmoid_bwd(_p(y), _p(dy), _p(dx), y.numel(), _stream()), "sigmoid_bwd")
-        return dx
+        return _head_bwd(y, dy, False)
 
 
 def sigmoid(x):
