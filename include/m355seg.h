@@ -731,6 +731,45 @@ int m355_binary_loss_bwd(const float* x, const float* t, const float* sums, cons
                          int32_t N, int32_t C, int64_t S, float dice_weight, const float* class_weights,
                          const float* pos_weight, int32_t square_dice, int32_t from_logits, float* dx, void* stream);
 
+/* ------------------------------------------------ focal Tversky loss
+ * HybridFocalTverskyLoss (criterions/hybrid_focal_tversky_loss.py): a Tversky term that weighs false
+ * positives (alpha) and false negatives (beta) separately, raised to a power, plus a focal cross-entropy on the positive
+ * half.  x and the target t (values in [0, 1], soft targets allowed): dense fp32 [N, C, S], rows at nc * S for any S (no
+ * alignment requirement).  eps = 1e-8.
+ *   from_logits == 0   x = p (probabilities): q = 1 - p, lp = log((p + eps) / (1 + eps)); no expf is evaluated
+ *   from_logits != 0   x = z (logits), the log-softmax over the C channels of a voxel is taken here: m = max_c z_c,
+ *                      s = sum_c exp(z_c - m), lp_c = (z_c - m) - log s, p_c = exp(z_c - m) / s, q_c = -expm1(lp_c); no eps
+ *   TP = sum p t, FP = sum p (1 - t), FN = sum q t, each accumulated directly
+ *   TI = TP / (TP + alpha FP + beta FN + eps/2),  u = max(0, 1 - TI),  tversky_nc = v[c] * u^e   (e = tversky_power;
+ *        v = tversky_class_weights or 1; no powf for e == 1)
+ *   focal_nc = w[c] * sum(t q^gamma lp) / S   (w = focal_class_weights or 1; gamma = focal_gamma: 0 -- the factor is
+ *        exactly 1 --, 1, 2, 3 by multiplication, any other value >= 1 by powf, 0 at q == 0)
+ *   out3 = {loss, tversky_loss, focal_loss} = {(1 - tw) focal_loss + tw tversky_loss, mean(tversky_nc), mean(-focal_nc)}
+ * With alpha = beta = 0.5, e = 1, gamma = 0 and from_logits == 0 this is m355_hybrid_loss_fwd without square_dice.
+ * sums (kept for backward): [N*C*4] = {TP, FP, FN, sum t q^gamma lp}, unweighted.
+ * Deterministic (fp32 per lane, then fp64 block and cross-chunk sums in a fixed order, no float atomics); a misaligned
+ * view gives the bits of its aligned copy.  Errors: null pointer, non-positive size, alpha or beta negative or not
+ * finite, tversky_power <= 0, focal_gamma outside {0} u [1, inf) M355_EINVALID_ARG; N*C > 65535 M355_EUNSUPPORTED (no
+ * limit on C of its own); workspace M355_EWORKSPACE; nothing is launched then.  m355_focal_tversky_workspace is 0 for a
+ * non-positive size.
+ */
+size_t m355_focal_tversky_workspace(int32_t N, int32_t C, int64_t S);
+int m355_focal_tversky_fwd(const float* x, const float* t, int32_t N, int32_t C, int64_t S,
+                           float tversky_weight, float alpha, float beta, float tversky_power, float focal_gamma,
+                           const float* focal_class_weights /* [C] or NULL */, const float* tversky_class_weights /* [C] or NULL */,
+                           int32_t from_logits, float* out3, float* sums /* [N*C*4] */,
+                           void* workspace, size_t workspace_bytes, void* stream);
+/* dx = dloss * d(loss)/dx in one pass, closed form from the saved sums (the Tversky part is 0 where u == 0, for e < 1
+ * too): the gradient with respect to p, or with from_logits to z directly,
+ *   dz_k = g_k - p_k sum_c g_c + p_k (h_k - sum_c p_c h_c),   g the focal and h the Tversky gradient per channel,
+ * which stays alive at a voxel saturated on the wrong class, where a softmax's own backward multiplies by p_k = 0.
+ * Up to 16 channels the per-voxel values stay in registers between the sums over c and their use; above that the planes
+ * are read again.  Writes dx[0, N*C*S). */
+int m355_focal_tversky_bwd(const float* x, const float* t, const float* sums, const float* dloss /* device scalar */,
+                           int32_t N, int32_t C, int64_t S, float tversky_weight, float alpha, float beta,
+                           float tversky_power, float focal_gamma, const float* focal_class_weights,
+                           const float* tversky_class_weights, int32_t from_logits, float* dx, void* stream);
+
 /* ------------------------------------------------------------ elementwise
  * torch.cat([x_up, x_skip], dim=1) (models/modular_unet.py:97) when the
  * producer could not write into the concat buffer directly: strided copy of

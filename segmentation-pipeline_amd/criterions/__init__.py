@@ -1,3 +1,4 @@
 """Drop-in for `segmentation_pipeline.criterions` (reference criterions/__init__.py:1)."""
 from .hybrid_logistic_dice_loss import HybridLogisticDiceLoss
 from .hybrid_binary_logistic_dice_loss import HybridBinaryLogisticDiceLoss
+from .hybrid_focal_tversky_loss import HybridFocalTverskyLoss

@@ -2165,6 +2165,62 @@ def binary_logistic_dice_loss(x, target, dice_weight=0.5, class_weights=None, po
     return _BinaryLossFn.apply(x, target, dice_weight, class_weights, pos_weight, square_dice, from_logits)
 
 
+class _FocalTverskyLossFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, t, tversky_weight, alpha, beta, tversky_power, focal_gamma, focal_class_weights,
+                tversky_class_weights, from_logits):
+        L = _lib.lib()
+        # (the argument errors come before the device check, as in _BinaryLossFn)
+        for name, v in (("prediction", x), ("target", t), ("focal_class_weights", focal_class_weights),
+                        ("tversky_class_weights", tversky_class_weights)):
+            if v is not None and v.dtype != torch.float32:
+                raise _lib.M355Error(f"{name}: expected torch.float32, got {v.dtype}")
+        if x.dim() < 2 or x.shape != t.shape:
+            raise _lib.M355Error(f"prediction {tuple(x.shape)} and target {tuple(t.shape)}: expected one shape [N, C, ...]")
+        N, Cc = x.shape[0], x.shape[1]
+        for name, w in (("focal_class_weights", focal_class_weights), ("tversky_class_weights", tversky_class_weights)):
+            if w is not None and (w.dim() != 1 or w.numel() != Cc):
+                raise _lib.M355Error(f"{name} of shape {tuple(w.shape)} for {Cc} channels")
+        _require(x, t, focal_class_weights, tversky_class_weights)
+        x, t = x.contiguous(), t.contiguous()
+        fw = None if focal_class_weights is None else focal_class_weights.contiguous()
+        tw = None if tversky_class_weights is None else tversky_class_weights.contiguous()
+        S = x.numel() // (N * Cc)
+        out3 = torch.empty(3, dtype=torch.float32, device=x.device)
+        sums = torch.empty(N * Cc * 4, dtype=torch.float32, device=x.device)
+        ws = _workspace(L.m355_focal_tversky_workspace(N, Cc, S), x.device)
+        par = (float(tversky_weight), float(alpha), float(beta), float(tversky_power), float(focal_gamma))
+        fl = 1 if from_logits else 0
+        check(L.m355_focal_tversky_fwd(_p(x), _p(t), N, Cc, S, *par, _p(fw), _p(tw), fl, _p(out3), _p(sums), _p(ws),
+                                       ws.numel(), _stream()), "focal_tversky_fwd")
+        ctx.args = (N, Cc, S, par, fl)
+        ctx.save_for_backward(x, t, sums, fw, tw)
+        st = out3.untyped_storage()   # three tensors over one storage, as _HybridLossFn returns them
+        loss, tversky, focal = (torch.empty((), dtype=torch.float32, device=x.device).set_(st, i, ()) for i in range(3))
+        ctx.mark_non_differentiable(tversky, focal)
+        return loss, tversky, focal
+
+    @staticmethod
+    def backward(ctx, dloss, _d1, _d2):
+        L = _lib.lib()
+        x, t, sums, fw, tw = ctx.saved_tensors
+        N, Cc, S, par, fl = ctx.args
+        dloss = dloss.contiguous().to(torch.float32)
+        dx = torch.empty_like(x)
+        check(L.m355_focal_tversky_bwd(_p(x), _p(t), _p(sums), _p(dloss), N, Cc, S, *par, _p(fw), _p(tw), fl, _p(dx),
+                                       _stream()), "focal_tversky_bwd")
+        return (dx,) + (None,) * 9
+
+
+def focal_tversky_loss(x, target, tversky_weight=0.5, alpha=0.5, beta=0.5, tversky_power=1.0, focal_gamma=0.0,
+                       focal_class_weights=None, tversky_class_weights=None, from_logits=False):
+    """HybridFocalTverskyLoss.forward -> (loss, tversky_loss, focal_loss) of `x` [N, C, ...] fp32 -- probabilities, or
+    with from_logits the logits of an nn.Identity head, whose log-softmax over C is taken inside -- against `target` in
+    [0, 1].  The class weights: fp32 device tensors [C] or None.  The gradient flows through `loss`."""
+    return _FocalTverskyLossFn.apply(x, target, tversky_weight, alpha, beta, tversky_power, focal_gamma,
+                                     focal_class_weights, tversky_class_weights, from_logits)
+
+
 # ---------------------------------------------------------------- elementwise
 class _ChannelScaleFn(torch.autograd.Function):
     @staticmethod
