@@ -313,6 +313,30 @@ int m355_conv_transpose3d_bwd_weight(const m355_conv3d_desc* d, const float* x, 
  * Pure host function. */
 int m355_conv_transpose3d_plan(const m355_conv3d_desc* d, int32_t which, const void* y_side, int32_t* out4);
 
+/* The gradients of the k = 2 / stride 2 conv-transpose on the bf16 matrix pipe through the exact three-way operand split
+ * of M355_COMPUTE_F32X3 (fp32 tensors, fp32 accumulation, nothing rounded to 16 bits): entry points and queries of their
+ * own, with the argument meaning of m355_conv_transpose3d_bwd_data / _bwd_weight.  The three fp32 entry points above, their
+ * plan and their workspace query do not change with them.
+ * m355_conv_transpose3d_x3_bwd_supported(desc, y_side): bit 0 = the data gradient, bit 1 = the weight gradient has a split
+ * kernel for this descriptor and this dy pointer (NULL = aligned).  The weight gradient (convt_k2s2_bwd_weight_x3_kernel)
+ * needs desc->compute == M355_COMPUTE_F32X3, k 2 / stride 2 / pad 0 / out_pad 0, below 2^31 elements per sample, W even, dy
+ * 16-byte aligned with y_batch_stride a multiple of 4, x_batch_stride even, at least 512 voxels in the batch (the
+ * smallest level measured; smaller ones stay on the fp32-MFMA kernel), and M355_F32X3 / M355_F32X3_CONVT_BWD not 0.  The data
+ * gradient has no split kernel: bit 0 is never set.  A gradient whose bit is clear gets M355_EUNSUPPORTED from its entry
+ * point before any launch (so does an x pointer off an 8-byte boundary); the caller then takes the fp32 entry point.
+ * m355_conv_transpose3d_x3_bwd_workspace(desc): bytes for the supported gradients (slabs [split][Cin][Cout][8] fp32, then
+ * the bias partials [split][Cout] double, each rounded up to 256), 0 when none is.
+ * m355_conv_transpose3d_x3_bwd_plan(desc, which = 1 | 2, y_side, out4): out[0] = 2 (the split family of
+ * m355_conv_transpose3d_plan) or 5 (none: M355_EUNSUPPORTED); which = 2: out[1] = channel tiles MT (2 | 4) of
+ * convt_k2s2_bwd_weight_x3_kernel<MT>, out[2] = voxel-range splits (grid.x, slabs), out[3] = 0.  Pure host functions. */
+int32_t m355_conv_transpose3d_x3_bwd_supported(const m355_conv3d_desc* d, const void* y_side);
+size_t m355_conv_transpose3d_x3_bwd_workspace(const m355_conv3d_desc* d);
+int m355_conv_transpose3d_x3_bwd_plan(const m355_conv3d_desc* d, int32_t which, const void* y_side, int32_t* out4);
+int m355_conv_transpose3d_bwd_data_x3(const m355_conv3d_desc* d, const float* dy, const float* w, float* dx,
+                                      void* workspace, size_t workspace_bytes, void* stream);
+int m355_conv_transpose3d_bwd_weight_x3(const m355_conv3d_desc* d, const float* x, const float* dy, float* dw, float* dbias,
+                                        void* workspace, size_t workspace_bytes, void* stream);
+
 /* nn.ConvTranspose3d(kernel_size=2, stride=2) c8 -> c8 for the 16-bit modes (fp32 weights and arithmetic: the op
  * is HBM-bound): the output lands directly in its slot of the decoder's c8 concat buffer
  * (models/modular_unet.py:96-97).  Other geometries: M355_EUNSUPPORTED (unpack / fp32 / pack instead). */

@@ -13,6 +13,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("M355_LIB_PATH") or os.path.join(_HERE, "libm355seg.so")
 
 M355_OK = 0
+M355_EUNSUPPORTED = -2
 ACT_NONE, ACT_RELU, ACT_LEAKY_RELU = 0, 1, 2
 ACT_ELU, ACT_GELU, ACT_GELU_TANH, ACT_SILU = 3, 4, 5, 6   # smooth: evaluated in fp32 in every flow (csrc/activation.hpp)
 COMPUTE_F32, COMPUTE_BF16, COMPUTE_F16, COMPUTE_F32X3 = 0, 1, 2, 3
@@ -206,6 +207,11 @@ SIGNATURES = {
     "m355_conv_transpose3d_bwd_data": (C.c_int, [_CD, _P, _P, _P, _P, _sz, _P]),
     "m355_conv_transpose3d_bwd_weight": (C.c_int, [_CD, _P, _P, _P, _P, _P, _sz, _P]),
     "m355_conv_transpose3d_fwd_h16": (C.c_int, [_CD, _P, _i64, _P, _P, _P, _i64, _i32, _P]),
+    "m355_conv_transpose3d_x3_bwd_supported": (_i32, [_CD, _P]),
+    "m355_conv_transpose3d_x3_bwd_workspace": (_sz, [_CD]),
+    "m355_conv_transpose3d_x3_bwd_plan": (C.c_int, [_CD, _i32, _P, C.POINTER(C.c_int32)]),
+    "m355_conv_transpose3d_bwd_data_x3": (C.c_int, [_CD, _P, _P, _P, _P, _sz, _P]),
+    "m355_conv_transpose3d_bwd_weight_x3": (C.c_int, [_CD, _P, _P, _P, _P, _P, _sz, _P]),
     "m355_norm_num_stats": (_i64, [_ND]),
     "m355_norm_workspace": (_sz, [_ND]),
     "m355_norm_plan": (C.c_int, [_ND, _i32, C.POINTER(C.c_int32)]),

@@ -208,6 +208,9 @@ __device__ __forceinline__ void store_conv_tile16(const f32x4v (&acc)[NTW][2], f
 int convt_fwd_x3_nvt(int Cin);
 void launch_convt_fwd_x3(int nvt, dim3 grid, const float* x, const float* w, const float* bias, float* y, int Cin, int Cout,
                          int D, int H, int W, int64_t xbs, int64_t ybs, int mt_per_wg, hipStream_t st);
+// ... and its weight gradient (slabs, bias partials, then their fixed-order reduce); grid.x = the voxel-range splits
+void launch_convt_bww_x3(int mt, dim3 grid, const float* x, const float* dy, float* dw, float* dbias, float* slab, double* bslab,
+                         int N, int Cin, int Cout, int D, int H, int W, int64_t xbs, int64_t ybs, hipStream_t st);
 
 // ConvTranspose3d (convt.hip): the same contract.  `kind` names the kernel family of the call, the numbers are that
 // family's launch; the byte counts hold for every kind, so one workspace serves whichever side the pointers pick.

@@ -1,8 +1,9 @@
 // fp32 convolution on the bf16 matrix pipe: M355_COMPUTE_F32X3 -- forward, data gradient and weight gradient of the
 // 3x3x3 / stride 1 / pad 1 nn.Conv3d in Block3d (/root/reference/segmentation_pipeline/models/components.py:48-56) and the
 // forward of the k2 s2 nn.ConvTranspose3d (models/modular_unet.py:72-81).  In this file: conv3_f32x3_kernel (+ the 16-row
-// remainder tile conv3_f32x3_m16_kernel), conv3_bww_x3_kernel / conv3_bww_x3c_kernel, convt_k2s2_fwd_x3_kernel, the weight
-// packs and the planners of the weight gradient.
+// remainder tile conv3_f32x3_m16_kernel), conv3_bww_x3_kernel / conv3_bww_x3c_kernel, convt_k2s2_fwd_x3_kernel,
+// convt_k2s2_bwd_weight_x3_kernel with its reduce (the conv-transpose's weight gradient), the weight packs and the planners
+// of the weight gradient.
 //
 // The fp32 MFMA (v_mfma_f32_32x32x2_f32) runs at 1/16 of the bf16 rate and this chip clocks both down under load
 // (DESIGN 4.6), so the fp32 layers sit at the power ceiling of that instruction.  An fp32 number splits EXACTLY into three
@@ -1261,6 +1262,195 @@ void launch_convt_fwd_x3(int nvt, dim3 grid, const float* x, const float* w, con
     default: M355_CONVT_X3(32); break;
   }
 #undef M355_CONVT_X3
+}
+
+// ------------------------------------------------------------------------------------ ConvTranspose3d k2 s2, weight gradient
+// dW[c, (o, t)] = sum_v X[c, v] * dY[o, 2v + t]: M = Cin, N = 8 * Cout, K = voxels, both operands activations, both split
+// while they are staged.  The grid is that of convt_k2s2_bwd_weight_mfma_kernel (convt.hip): a persistent workgroup owns
+// 32 * MT input channels x 16 output channels (wave w: 4 o x 8 t = one 32-column tile) and walks 32-voxel tiles of its
+// split with the next tile's loads in flight; partial dW -> slab[split][Cin][Cout][8].  A staging thread owns a PAIR of
+// x-adjacent voxels (float2 of an x row, float4 of a dy row: the x parity of the output voxel is the tap's c bit), so the
+// two bf16 of a plane are one 32-bit LDS word -- x3_pack of the two voxels -- and the planes [plane][row][voxel] give
+// every lane its fragment (8 consecutive voxels of its row) as one 16-byte read.  Row stride 80 bytes: 16 consecutive
+// rows start on 16 different 4-bank groups.  The bias gradient is summed from the dy values in registers: the lanes of
+// wave w hold output channels w, w + 4, w + 8, w + 12 of the block, so one wave_sum per channel finishes it.
+// Host: W even (pairs stay in a row), dy 16-byte aligned with a batch stride that is a multiple of 4, x 8-byte aligned
+// with an even batch stride (route_convt_x3_bwd, convt.hip).
+template <int MT>
+__global__ __launch_bounds__(256, MT == 2 ? 3 : 2) void convt_k2s2_bwd_weight_x3_kernel(
+    const float* __restrict__ x, const float* __restrict__ dy, float* __restrict__ slab, double* __restrict__ bslab, int N,
+    int Cin, int Cout, int D, int H, int W, int64_t xbs, int64_t ybs, int nsplit) {
+  constexpr int NV = 32, CT = 32 * MT, RS = NV * 2 + 16, XJ = CT / 16;   // RS: bytes per row of a plane
+  __shared__ __attribute__((aligned(16))) unsigned char xs3[3 * CT * RS];
+  __shared__ __attribute__((aligned(16))) unsigned char dys3[3 * 128 * RS];
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int half = lane >> 5, l32 = lane & 31;
+  const int split = blockIdx.x, o0 = blockIdx.y * 16, c0 = blockIdx.z * CT;
+  const int S = D * H * W;
+  const int OH = 2 * H, OW = 2 * W;
+  const int64_t OS = (int64_t)S * 8;
+  const int64_t total = (int64_t)N * S;
+  const int64_t ntiles = (total + NV - 1) / NV;
+  const bool want_bias = bslab != nullptr && blockIdx.z == 0;
+
+  f32x16 acc[MT];
+#pragma unroll
+  for (int m = 0; m < MT; ++m)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[m][r] = 0.f;
+  float bsum[4] = {0.f, 0.f, 0.f, 0.f};
+
+  // staging: voxel pair vp, part (x rows part + 16 j; dy rows: output channel (part >> 2) + 4 j, (a, b) = part & 3)
+  const int vp = tid & 15, part = tid >> 4, ab = part & 3, oq = part >> 2;
+  float2 xpf[XJ];
+  float4 dpf[4];
+  bool tok = false;
+  auto fetch = [&](int64_t tile) __attribute__((always_inline)) {
+    const int64_t g = tile * NV + 2 * vp;     // total is even: a pair is inside the range or outside it
+    tok = g < total;
+    const int64_t nn = tok ? g / S : 0;
+    const int v = tok ? (int)(g - nn * S) : 0;
+    const float* xp = x + nn * xbs + v;
+#pragma unroll
+    for (int j = 0; j < XJ; ++j) {
+      const int c = c0 + part + 16 * j;
+      xpf[j] = *reinterpret_cast<const float2*>(xp + ((tok && c < Cin) ? (int64_t)c * S : 0));   // clamped address
+    }
+    const float* dp = dy + nn * ybs + ((int64_t)(2 * (v / (W * H)) + (ab >> 1)) * OH + 2 * ((v / W) % H) + (ab & 1)) * OW +
+                      2 * (v % W);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int o = o0 + oq + 4 * j;
+      dpf[j] = *reinterpret_cast<const float4*>(dp + ((tok && o < Cout) ? (int64_t)o * OS : 0));
+    }
+  };
+  // the three planes of the pair (a, b) as one word each: a = even voxel = low half
+  auto put = [&](unsigned char* row, float a, float b, int plane_bytes) __attribute__((always_inline)) {
+    unsigned ha, ma, la, hb, mb, lb;
+    x3_split(a, ha, ma, la);
+    x3_split(b, hb, mb, lb);
+    *reinterpret_cast<unsigned*>(row) = x3_pack(ha, hb);
+    *reinterpret_cast<unsigned*>(row + plane_bytes) = x3_pack(ma, mb);
+    *reinterpret_cast<unsigned*>(row + 2 * plane_bytes) = x3_pack(la, lb);
+  };
+  auto commit = [&]() __attribute__((always_inline)) {
+#pragma unroll
+    for (int j = 0; j < XJ; ++j) {
+      const int c = part + 16 * j;
+      const bool ok = tok && c0 + c < Cin;
+      put(xs3 + c * RS + vp * 4, ok ? xpf[j].x : 0.f, ok ? xpf[j].y : 0.f, CT * RS);
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int ol = oq + 4 * j;
+      const bool ok = tok && o0 + ol < Cout;
+      const float4 q = ok ? dpf[j] : make_float4(0.f, 0.f, 0.f, 0.f);
+      unsigned char* row = dys3 + (ol * 8 + ab * 2) * RS + vp * 4;
+      put(row, q.x, q.z, 128 * RS);          // c = 0: the even output voxels of the two pairs
+      put(row + RS, q.y, q.w, 128 * RS);     // c = 1
+      bsum[j] += (q.x + q.y) + (q.z + q.w);
+    }
+  };
+
+  if (split < ntiles) fetch(split);
+  for (int64_t tile = split; tile < ntiles; tile += nsplit) {
+    __syncthreads();
+    commit();
+    __syncthreads();
+    if (tile + nsplit < ntiles) fetch(tile + nsplit);
+    const unsigned char* xb = xs3 + l32 * RS + half * 16;
+    const unsigned char* db = dys3 + (wave * 32 + l32) * RS + half * 16;
+#pragma unroll
+    for (int s = 0; s < NV / 16; ++s) {
+      bf16x8 ah[MT], am[MT], al[MT];
+#pragma unroll
+      for (int m = 0; m < MT; ++m) {
+        ah[m] = *reinterpret_cast<const bf16x8*>(xb + (m * 32) * RS + s * 32);
+        am[m] = *reinterpret_cast<const bf16x8*>(xb + (CT + m * 32) * RS + s * 32);
+        al[m] = *reinterpret_cast<const bf16x8*>(xb + (2 * CT + m * 32) * RS + s * 32);
+      }
+      const bf16x8 bh = *reinterpret_cast<const bf16x8*>(db + s * 32);
+      const bf16x8 bm = *reinterpret_cast<const bf16x8*>(db + 128 * RS + s * 32);
+      const bf16x8 bl = *reinterpret_cast<const bf16x8*>(db + 2 * 128 * RS + s * 32);
+      // (the small terms of a product group first; consecutive MFMAs write different accumulators)
+#pragma unroll
+      for (int m = 0; m < MT; ++m) acc[m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[m], bh, acc[m], 0, 0, 0);
+#pragma unroll
+      for (int m = 0; m < MT; ++m) acc[m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am[m], bh, acc[m], 0, 0, 0);
+#pragma unroll
+      for (int m = 0; m < MT; ++m) acc[m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[m], bh, acc[m], 0, 0, 0);
+#pragma unroll
+      for (int m = 0; m < MT; ++m) acc[m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am[m], bm, acc[m], 0, 0, 0);
+#pragma unroll
+      for (int m = 0; m < MT; ++m) acc[m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[m], bm, acc[m], 0, 0, 0);
+#pragma unroll
+      for (int m = 0; m < MT; ++m) acc[m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[m], bl, acc[m], 0, 0, 0);
+    }
+  }
+  // D[i = ci][j = (o, t)]
+  const int o = o0 + wave * 4 + (l32 >> 3);
+  if (o < Cout) {
+    float* sl = slab + (int64_t)split * Cin * Cout * 8;
+#pragma unroll
+    for (int m = 0; m < MT; ++m)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int c = c0 + m * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
+        if (c < Cin) sl[((int64_t)c * Cout + o) * 8 + (l32 & 7)] = acc[m][r];
+      }
+  }
+  if (want_bias) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const float s = wave_sum(bsum[j]);
+      const int ob = o0 + wave + 4 * j;
+      if (lane == 0 && ob < Cout) bslab[(int64_t)split * Cout + ob] = (double)s;
+    }
+  }
+}
+
+// dW = sum over the splits, dbias likewise from bslab: 32 consecutive elements x 8 lanes per workgroup, lane q sums the
+// splits q, q + 8, ... in that order and the eight partial sums are added pairwise -- a fixed order, in double, with
+// nsplit / 8 dependent loads per thread where convt_slab_reduce_kernel has nsplit.  Workgroups past `eblocks` do dbias.
+__global__ __launch_bounds__(256) void convt_k2s2_slab_reduce_x3_kernel(
+    const float* __restrict__ slab, float* __restrict__ out, int64_t total, int nsplit, const double* __restrict__ bslab,
+    float* __restrict__ dbias, int Cout, int eblocks) {
+  __shared__ double red[8][33];
+  const int e = threadIdx.x & 31, q = threadIdx.x >> 5;
+  const bool bias = (int)blockIdx.x >= eblocks;
+  const int64_t n = bias ? Cout : total;
+  const int64_t i = (int64_t)(bias ? blockIdx.x - eblocks : blockIdx.x) * 32 + e;
+  double v = 0.0;
+  if (i < n) {
+    if (bias) {
+      for (int s = q; s < nsplit; s += 8) v += bslab[(int64_t)s * n + i];
+    } else {
+#pragma unroll 4
+      for (int s = q; s < nsplit; s += 8) v += (double)slab[(int64_t)s * n + i];
+    }
+  }
+  red[q][e] = v;
+  __syncthreads();
+  if (q == 0 && i < n) {
+    const double r = ((red[0][e] + red[1][e]) + (red[2][e] + red[3][e])) + ((red[4][e] + red[5][e]) + (red[6][e] + red[7][e]));
+    (bias ? dbias : out)[i] = (float)r;
+  }
+}
+
+void launch_convt_bww_x3(int mt, dim3 grid, const float* x, const float* dy, float* dw, float* dbias, float* slab, double* bslab,
+                         int N, int Cin, int Cout, int D, int H, int W, int64_t xbs, int64_t ybs, hipStream_t st) {
+  const int nsplit = (int)grid.x;
+  if (mt == 2)
+    hipLaunchKernelGGL(convt_k2s2_bwd_weight_x3_kernel<2>, grid, dim3(256), 0, st, x, dy, slab, bslab, N, Cin, Cout, D, H, W,
+                       xbs, ybs, nsplit);
+  else
+    hipLaunchKernelGGL(convt_k2s2_bwd_weight_x3_kernel<4>, grid, dim3(256), 0, st, x, dy, slab, bslab, N, Cin, Cout, D, H, W,
+                       xbs, ybs, nsplit);
+  const int64_t total = (int64_t)Cin * Cout * 8;
+  const int eblocks = (int)ceil_div(total, 32), bblocks = dbias ? (int)ceil_div(Cout, 32) : 0;
+  hipLaunchKernelGGL(convt_k2s2_slab_reduce_x3_kernel, dim3((unsigned)(eblocks + bblocks)), dim3(256), 0, st, slab, dw, total,
+                     nsplit, bslab, dbias, Cout, eblocks);
 }
 
 }  // namespace m355

@@ -10,7 +10,8 @@
 // flop/B in fp32 -> HBM-bound.  The three k2s2 ops run as
 // fp32-MFMA GEMMs with the voxel on the lane (coalesced x reads, float2-coalesced
 // y / dy accesses); any other geometry takes the generic direct kernels below.  (M355_COMPUTE_F32X3: the forward runs
-// on the bf16 matrix pipe through the exact three-way operand split -- convt_k2s2_fwd_x3_kernel, conv3d_f32x3.hip.)
+// on the bf16 matrix pipe through the exact three-way operand split -- convt_k2s2_fwd_x3_kernel, conv3d_f32x3.hip; so does
+// the weight gradient behind m355_conv_transpose3d_bwd_weight_x3 -- convt_k2s2_bwd_weight_x3_kernel, same file.)
 //
 // The device half comes first; the host half at the foot resolves each descriptor to one ConvtRoute
 // (conv3d_common.hpp) that the queries, the entry points and m355_conv_transpose3d_plan all read.
@@ -1369,6 +1370,40 @@ static void launch_convt_bww_c8(const ConvtRoute& r, const m355_conv3d_desc* d, 
                      d->Cout, r.split, grad_unscale, overflow_flag());
 }
 
+// ---- the split gradients (m355_conv_transpose3d_bwd_*_x3): a route of their own, so that route_convt and what it feeds
+// stay as they are.  which: 1 data gradient (no split kernel: always Unsupported), 2 weight gradient
+// (convt_k2s2_bwd_weight_x3_kernel, conv3d_f32x3.hip).  The kernel stages PAIRS of x-adjacent voxels with float2 / float4
+// loads: W even, dy 16-byte aligned with a batch stride that is a multiple of 4, an even x batch stride (the x pointer
+// itself is the entry point's check).  Shapes below CONVT_X3_BWW_MIN_VOXELS voxels per batch keep the fp32-MFMA kernel:
+// 320 -> 320 @8^3 is the smallest level measured (0.034 against 0.043 ms, profiles/convt_grad_x3_ab.txt); below it a
+// workgroup has a single tile and nothing was measured.
+constexpr int64_t CONVT_X3_BWW_MIN_VOXELS = 512;
+static ConvtRoute route_convt_x3_bwd(const m355_conv3d_desc* d, int which, const void* dy) {
+  ConvtRoute r{};
+  r.kind = ConvtKind::Unsupported;
+  convt_plan_code(r, 0, 0, 0);
+  if (which != 2 || !convt_dims_ok(d) || !is_k2s2(d) || !convt_fits_i32(d)) return r;
+  if (d->compute != M355_COMPUTE_F32X3 || !tuning().f32x3 || !tuning().f32x3_convt_bwd) return r;
+  const ConvtGeom g = convt_geom(d);
+  if (d->W % 2 || g.ybs % 4 || g.xbs % 2 || ((uintptr_t)dy & 15)) return r;
+  const int64_t S = (int64_t)d->D * d->H * d->W;
+  if (d->N * S < CONVT_X3_BWW_MIN_VOXELS && tuning().f32x3_convt_bwd < 2) return r;   // (2: the sweep hook, no floor)
+  r.kind = ConvtKind::X3;
+  r.mt = d->Cin > 64 ? 4 : 2;
+  const int64_t otiles = ceil_div(d->Cout, 16), ctiles = ceil_div(d->Cin, 32 * r.mt);
+  // persistent, one round: 45 KB (MT = 2) / 60 KB (MT = 4) of LDS per workgroup -> 3 / 2 workgroups per CU.  The reduce
+  // spreads the splits of an element over 8 lanes, so a few hundred of them cost it a few tens of loads per lane.
+  const int64_t per_cu = r.mt == 2 ? 3 : 2;
+  r.split = (int)std::min(std::max<int64_t>(1, per_cu * num_cus() / (ctiles * otiles)), ceil_div(d->N * S, 32));
+  r.grid = dim3((unsigned)r.split, (unsigned)otiles, (unsigned)ctiles);
+  r.slab_bytes = (size_t)round_up((int64_t)r.split * d->Cin * d->Cout * 8 * 4, 256);
+  r.dbias_offset = r.slab_bytes;
+  r.dbias_bytes = (size_t)round_up((int64_t)r.split * d->Cout * 8, 256);   // bslab[split][Cout], double
+  r.workspace_bytes = r.slab_bytes + r.dbias_bytes;
+  convt_plan_code(r, r.mt, r.split, 0);
+  return r;
+}
+
 }  // namespace m355
 
 using namespace m355;
@@ -1536,4 +1571,51 @@ extern "C" int m355_conv_transpose3d_bwd_weight_h16(const m355_conv3d_desc* d, c
       return rc;
   }
   return check_launch("conv_transpose3d_bwd_weight_h16");
+}
+
+
+// ---- the split gradients of M355_COMPUTE_F32X3: entry points and queries of their own (route_convt_x3_bwd) ----
+extern "C" int32_t m355_conv_transpose3d_x3_bwd_supported(const m355_conv3d_desc* d, const void* y_side) {
+  if (!d) return 0;
+  return (route_convt_x3_bwd(d, 1, y_side).kind == ConvtKind::X3 ? 1 : 0) | (route_convt_x3_bwd(d, 2, y_side).kind == ConvtKind::X3 ? 2 : 0);
+}
+extern "C" size_t m355_conv_transpose3d_x3_bwd_workspace(const m355_conv3d_desc* d) {
+  return d ? std::max(route_convt_x3_bwd(d, 1, nullptr).workspace_bytes, route_convt_x3_bwd(d, 2, nullptr).workspace_bytes) : 0;
+}
+extern "C" int m355_conv_transpose3d_x3_bwd_plan(const m355_conv3d_desc* d, int32_t which, const void* y_side, int32_t* out4) {
+  if (int rc = validate_convt(d, "conv_transpose3d_x3_bwd_plan")) return rc;
+  M355_REQUIRE(out4 && (which == 1 || which == 2), M355_EINVALID_ARG, "conv_transpose3d_x3_bwd_plan: null pointer or which not 1 | 2");
+  const ConvtRoute r = route_convt_x3_bwd(d, which, y_side);
+  std::copy_n(r.plan_code, 4, out4);
+  return M355_OK;
+}
+
+extern "C" int m355_conv_transpose3d_bwd_data_x3(const m355_conv3d_desc* d, const float* dy, const float* w, float* dx,
+                                                 void* workspace, size_t workspace_bytes, void* stream) {
+  const char* who = "conv_transpose3d_bwd_data_x3";
+  if (int rc = validate_convt(d, who)) return rc;
+  M355_REQUIRE(dy && w && dx, M355_EINVALID_ARG, "%s: null pointer", who);
+  (void)workspace; (void)workspace_bytes; (void)stream;
+  M355_REQUIRE(route_convt_x3_bwd(d, 1, dy).kind == ConvtKind::X3, M355_EUNSUPPORTED,
+               "%s: the data gradient has no split kernel (m355_conv_transpose3d_x3_bwd_supported bit 0): take "
+               "m355_conv_transpose3d_bwd_data", who);
+  return M355_EUNSUPPORTED;
+}
+
+extern "C" int m355_conv_transpose3d_bwd_weight_x3(const m355_conv3d_desc* d, const float* x, const float* dy, float* dw,
+                                                   float* dbias, void* workspace, size_t workspace_bytes, void* stream) {
+  const char* who = "conv_transpose3d_bwd_weight_x3";
+  if (int rc = validate_convt(d, who)) return rc;
+  M355_REQUIRE(x && dy && dw, M355_EINVALID_ARG, "%s: null pointer", who);
+  const ConvtRoute r = route_convt_x3_bwd(d, 2, dy);
+  M355_REQUIRE(r.kind == ConvtKind::X3 && ((uintptr_t)x & 7) == 0, M355_EUNSUPPORTED,
+               "%s: needs M355_COMPUTE_F32X3, kernel_size 2 / stride 2 / padding 0, even W, dy 16-byte and x 8-byte aligned, "
+               "batch strides that are multiples of 4 (dy) and 2 (x), and M355_F32X3_CONVT_BWD != 0 "
+               "(m355_conv_transpose3d_x3_bwd_supported bit 1): take m355_conv_transpose3d_bwd_weight", who);
+  M355_REQUIRE(workspace && workspace_bytes >= (dbias ? r.workspace_bytes : r.slab_bytes), M355_EWORKSPACE,
+               "%s: workspace too small (%zu < %zu)", who, workspace_bytes, dbias ? r.workspace_bytes : r.slab_bytes);
+  const ConvtGeom g = convt_geom(d);
+  launch_convt_bww_x3(r.mt, r.grid, x, dy, dw, dbias, (float*)workspace, dbias ? (double*)((char*)workspace + r.dbias_offset) : nullptr,
+                      d->N, d->Cin, d->Cout, d->D, d->H, d->W, g.xbs, g.ybs, (hipStream_t)stream);
+  return check_launch("convt_k2s2_bwd_weight_x3");
 }

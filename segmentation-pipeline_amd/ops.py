@@ -1393,9 +1393,18 @@ class _ConvT3dFn(torch.autograd.Function):
         if ctx.needs_input_grad[1] or (ctx.has_bias and ctx.needs_input_grad[2]):
             dw = torch.empty_like(weight)
             db = torch.empty(d.Cout, dtype=weight.dtype, device=weight.device) if ctx.has_bias else None
-            ws = _workspace(L.m355_conv_transpose3d_workspace(C.byref(d)), x.device)
-            check(L.m355_conv_transpose3d_bwd_weight(C.byref(d), _p(x), _p(dy), _p(dw), _p(db), _p(ws),
-                                                     ws.numel(), _stream()), "conv_transpose3d_bwd_weight")
+            # M355_COMPUTE_F32X3: the split kernel where the library has one for this descriptor and this dy (bit 1)
+            rc = _lib.M355_EUNSUPPORTED
+            if d.compute == _lib.COMPUTE_F32X3 and L.m355_conv_transpose3d_x3_bwd_supported(C.byref(d), _p(dy)) & 2:
+                ws = _workspace(L.m355_conv_transpose3d_x3_bwd_workspace(C.byref(d)), x.device)
+                rc = L.m355_conv_transpose3d_bwd_weight_x3(C.byref(d), _p(x), _p(dy), _p(dw), _p(db), _p(ws), ws.numel(),
+                                                           _stream())
+                if rc != _lib.M355_EUNSUPPORTED:
+                    check(rc, "conv_transpose3d_bwd_weight_x3")
+            if rc == _lib.M355_EUNSUPPORTED:
+                ws = _workspace(L.m355_conv_transpose3d_workspace(C.byref(d)), x.device)
+                check(L.m355_conv_transpose3d_bwd_weight(C.byref(d), _p(x), _p(dy), _p(dw), _p(db), _p(ws),
+                                                         ws.numel(), _stream()), "conv_transpose3d_bwd_weight")
         return dx, dw, db, None
 
 
