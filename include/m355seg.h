@@ -794,6 +794,28 @@ int m355_focal_tversky_bwd(const float* x, const float* t, const float* sums, co
                            float tversky_power, float focal_gamma, const float* focal_class_weights,
                            const float* tversky_class_weights, int32_t from_logits, float* dx, void* stream);
 
+/* ------------------------------------------------ target pyramid (deep supervision)
+ * The targets of the auxiliary heads of models.DeepSupervisionUNet (criterions.DeepSupervisionLoss): one
+ * launch reads a dense fp32 target y[N, C, D, H, W] once and writes its `levels` coarser levels, level j (1 <= j <= levels)
+ * of spatial size (D, H, W) / 2^j.
+ *   M355_PYRAMID_AREA     out_j[n, c, z, y, x] = mean of the 2^j cube of y that starts at (z, y, x) 2^j: the soft target of
+ *                         the coarse cell (F.avg_pool3d(y, 2^j)).  Level 1 is the pairwise sum of its 8 voxels times 0.125,
+ *                         level j the same of its 8 level j-1 cells; for a one-hot target every partial sum is an integer
+ *                         <= 4096 and every scale a power of two, so the result is exact.
+ *   M355_PYRAMID_NEAREST  out_j[n, c, z, y, x] = y[n, c, z 2^j, y 2^j, x 2^j]: F.interpolate(y, scale_factor=2^-j,
+ *                         mode='nearest'), a pure copy.
+ * out: the levels back to back, level 1 first, each dense NCDHW; m355_target_pyramid_elems floats in all (0 for arguments
+ * m355_target_pyramid refuses).  y and out need 4-byte alignment only: rows go as 16-byte loads where their address allows
+ * it, the result does not depend on it.  Element offsets are 64-bit.  No atomics, one summation order, no workspace: a call
+ * repeats bit for bit, and it can be captured in a graph.
+ * Errors, nothing is launched: null pointer, non-positive size, levels outside 1..4, mode other than the two above
+ * M355_EINVALID_ARG; D, H or W not divisible by 2^levels M355_EUNSUPPORTED (the message names the dimension).
+ */
+enum { M355_PYRAMID_AREA = 0, M355_PYRAMID_NEAREST = 1 };
+int64_t m355_target_pyramid_elems(int32_t N, int32_t C, int32_t D, int32_t H, int32_t W, int32_t levels);
+int m355_target_pyramid(const float* y, int32_t N, int32_t C, int32_t D, int32_t H, int32_t W, int32_t levels,
+                        int32_t mode, float* out, void* stream);
+
 /* ------------------------------------------------------------ elementwise
  * torch.cat([x_up, x_skip], dim=1) (models/modular_unet.py:97) when the
  * producer could not write into the concat buffer directly: strided copy of

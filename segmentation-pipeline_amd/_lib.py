@@ -262,6 +262,8 @@ SIGNATURES = {
     "m355_focal_tversky_workspace": (_sz, [_i32, _i32, _i64]),
     "m355_focal_tversky_fwd": (C.c_int, [_P, _P, _i32, _i32, _i64, _f32, _f32, _f32, _f32, _f32, _P, _P, _i32, _P, _P, _P, _sz, _P]),
     "m355_focal_tversky_bwd": (C.c_int, [_P, _P, _P, _P, _i32, _i32, _i64, _f32, _f32, _f32, _f32, _f32, _P, _P, _i32, _P, _P]),
+    "m355_target_pyramid_elems": (_i64, [_i32, _i32, _i32, _i32, _i32, _i32]),
+    "m355_target_pyramid": (C.c_int, [_P, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _P, _P]),
     "m355_copy_channels": (C.c_int, [_P, _P, _i32, _i32, _i64, _i64, _i64, _P]),
     "m355_channel_scale": (C.c_int, [_P, _P, _P, _i32, _i32, _i64, _P]),
     "m355_add": (C.c_int, [_P, _P, _P, _i64, _P]),

@@ -185,7 +185,7 @@ class ModularUNet(nn.Module):
         with ops.grad_scale_scope():
             return self._forward(x)
 
-    def _forward(self, x):
+    def _forward(self, x, levels=None):
         f = self._filters
         N, spatial = x.shape[0], tuple(x.shape[2:])
         # 16-bit precision mode under no_grad: activations live only in the c8 layout the conv kernels read
@@ -234,12 +234,23 @@ class ModularUNet(nn.Module):
             slot = ops.OutSlot(None, 0, c_up, buf16=buf) if flow else ops.OutSlot(buf, 0, c_up)
             x_up = _run_upsample(self.upsampling[i], x, out=slot)
             x = self.up_blocks[i](ops.Concat(buf, [x_up, x_skip]), c8_out=bool(flow))
+            if i:
+                self._decoder_level(i, x, levels)
 
-        if isinstance(self.hypothesis, nn.Softmax) and self.hypothesis.dim == 1 and isinstance(self.out_conv, nn.Conv3d):
+        return self._head(self.out_conv, x)
+
+    def _decoder_level(self, i, x, levels):
+        """hook of `_forward`: `x` is the output of up_blocks[i] for a coarser decoder level i >= 1 (what upsampling[i - 1]
+        reads next), `levels` what `forward` handed to `_forward`.  Nothing here: ModularUNet launches nothing per level."""
+
+    def _head(self, conv, x):
+        """hypothesis(conv(x)): the output convolution and the model's hypothesis on a decoder activation (an Act16 in the
+        16-bit flows)"""
+        if isinstance(self.hypothesis, nn.Softmax) and self.hypothesis.dim == 1 and isinstance(conv, nn.Conv3d):
             # out conv + Softmax(dim=1) (:99-100) as one op: the softmax runs in the conv epilogue
-            return run_conv(self.out_conv, x, softmax=True)
-        if type(self.hypothesis) is nn.Sigmoid and isinstance(self.out_conv, nn.Conv3d):
+            return run_conv(conv, x, softmax=True)
+        if type(self.hypothesis) is nn.Sigmoid and isinstance(conv, nn.Conv3d):
             # out conv + Sigmoid as one op, the same way
-            return run_conv(self.out_conv, x, sigmoid=True)
-        x = run_conv(self.out_conv, x)
+            return run_conv(conv, x, sigmoid=True)
+        x = run_conv(conv, x)
         return _run_hypothesis(self.hypothesis, ops.as_f32(x))

@@ -2230,6 +2230,42 @@ def focal_tversky_loss(x, target, tversky_weight=0.5, alpha=0.5, beta=0.5, tvers
                                      focal_class_weights, tversky_class_weights, from_logits)
 
 
+# ------------------------------------------------------------- target pyramid
+PYRAMID_MODES = {"area": 0, "nearest": 1}   # M355_PYRAMID_AREA, M355_PYRAMID_NEAREST
+PYRAMID_MAX_LEVELS = 4
+
+
+def target_pyramid(y, levels, mode='area'):
+    """The targets of `levels` auxiliary heads (criterions.DeepSupervisionLoss): [level 1, ..., level `levels`]
+    of the fp32 target `y` [N, C, D, H, W], level j of spatial size (D, H, W) / 2^j -- mode 'area' the mean of the 2^j cube
+    (F.avg_pool3d(y, 2**j)), 'nearest' the voxel at (z, y, x) * 2^j (F.interpolate(..., mode='nearest')).  One launch reads
+    `y` once and writes every level; the levels are views of one allocation and carry no autograd history."""
+    if mode not in PYRAMID_MODES:
+        raise ValueError(f"target_pyramid: mode {mode!r} is neither 'area' nor 'nearest'")
+    if y.dtype != torch.float32:
+        raise _lib.M355Error(f"target: expected torch.float32, got {y.dtype}")
+    if y.dim() != 5:
+        raise _lib.M355Error(f"target {tuple(y.shape)}: expected [N, C, D, H, W]")
+    levels = int(levels)
+    N, Cc, D, H, W = y.shape
+    if 1 <= levels <= PYRAMID_MAX_LEVELS:
+        for name, size in (("D", D), ("H", H), ("W", W)):
+            if size % (1 << levels):
+                raise _lib.M355Error(f"target_pyramid: {name} = {size} is not divisible by {1 << levels} (2^levels)")
+    _require(y)
+    L = _lib.lib()
+    y = y.detach().contiguous()
+    out = torch.empty(max(int(L.m355_target_pyramid_elems(N, Cc, D, H, W, levels)), 1), dtype=torch.float32, device=y.device)
+    check(L.m355_target_pyramid(_p(y), N, Cc, D, H, W, levels, PYRAMID_MODES[mode], _p(out), _stream()), "target_pyramid")
+    views, off = [], 0
+    for j in range(1, levels + 1):
+        shape = (N, Cc, D >> j, H >> j, W >> j)
+        n = N * Cc * shape[2] * shape[3] * shape[4]
+        views.append(out[off:off + n].view(shape))
+        off += n
+    return views
+
+
 # ---------------------------------------------------------------- elementwise
 class _ChannelScaleFn(torch.autograd.Function):
     @staticmethod

@@ -83,10 +83,15 @@ class StandardPredict:
         """batch: dict of stacked tensors (collate_subjects, utils/utils.py:75-85)."""
         batch = {k: (v.to(device) if torch.is_tensor(v) else v) for k, v in batch.items()}
         x = batch["X"]
-        if self.sagittal_split:
-            y_pred = reverse_split_and_flip(model(split_and_flip(x).contiguous()))
-        else:
-            y_pred = model(x)
+        y_pred = model(split_and_flip(x).contiguous()) if self.sagittal_split else model(x)
+        if isinstance(y_pred, (tuple, list)):
+            # a deep-supervision model in training mode (models.DeepSupervisionUNet): every level for the criterion, the
+            # full-resolution one where a tensor is expected (TrainLoop's training evaluators)
+            levels = tuple(reverse_split_and_flip(p) for p in y_pred) if self.sagittal_split else tuple(y_pred)
+            batch["y_pred_levels"] = levels
+            y_pred = levels[0]
+        elif self.sagittal_split:
+            y_pred = reverse_split_and_flip(y_pred)
         batch["y_pred"] = y_pred
         return batch
 

@@ -66,7 +66,8 @@ def train_step(model, criterion, optimizer, predictor, batch, device, timer: Opt
     batch = predictor.predict(model, device, batch)
     if timer:
         timer.stamp("model_forward")
-    loss_dict = criterion(batch["y_pred"], batch["y"])
+    # (a deep-supervision model hands the criterion every level: prediction.StandardPredict, criterions.DeepSupervisionLoss)
+    loss_dict = criterion(batch.get("y_pred_levels", batch["y_pred"]), batch["y"])
     if timer:
         timer.stamp("loss_function")
     if isinstance(model, D.PatchParallel):
