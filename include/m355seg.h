@@ -1329,6 +1329,89 @@ int m355_region_stats(const void* labels, int32_t label_dtype, const int32_t* si
                       int32_t K, const int32_t* values /* host */, int32_t L, int32_t median, int64_t* count,
                       int32_t* bounds, float* stats, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------ multi-tensor optimizer step: clipping, SGD / Adam / AdamW, poly LR, weight EMA
+ * The device half of segmentation_pipeline_amd.optim (FusedSGD, FusedAdam); stands in for the
+ * torch.optim.Adam / SGD a reference config names as its optimizer component (research/dmri_hippo/configs/main_config.py:128,
+ * research/msseg2/msseg2.py:94) and for what a training scheme composes around it: clip_grad_norm_,
+ * lr_scheduler.PolynomialLR, an EMA of the weights.  All tensors are float32 and contiguous; a tensor needs no alignment
+ * beyond 4 bytes (16-byte accesses are used where every tensor of an entry allows them).
+ *
+ * A step is   [ m355_optim_norm x ceil(T / CAP) ]  ->  m355_optim_prepare  ->  m355_optim_update x ceil(T / CAP)
+ * with the norm launches only when clipping is on.  T tensors are listed once, in any order; m355_optim_plan gives every
+ * tensor its run of blocks (blk0, nblk: ceil(n / chunk) blocks of `chunk` elements, numbered through the whole list) and
+ * the workspace size (one fp64 partial per block).  A launch takes at most m355_optim_capacity() consecutive tensors of
+ * the list; its table travels BY VALUE in the kernel arguments, so a launch captured into a hipGraph replays with the
+ * pointers of the capture, and the number of launches never depends on element counts.
+ *
+ *   m355_optim_norm     partial[blk0 + b] = sum of (double)g * g over block b's chunk, added in a fixed order; a non-finite
+ *                       gradient makes the partial NaN.  No floating-point atomics: the same call twice gives the same bits.
+ *   m355_optim_prepare  one block.  norm = sqrt(partials added in slot order, fp64) / grad_scale;
+ *                       clip_coef = min(1, max_norm / (norm + 1e-6)) (clip_grad_norm_'s expression);
+ *                       skip = (found_inf && *found_inf != 0) || norm not finite  -- the one difference from
+ *                       clip_grad_norm_, which would write NaN into the weights;  t advances unless skipped;
+ *                       lr[g] = group lr * (1 - min(t, total_steps) / total_steps)^power with t = 0 on the first step
+ *                       (total_steps == 0: no schedule); Adam: bc1 = 1 - beta1^(t + 1), bc2 likewise, step size lr / bc1;
+ *                       all in fp64, each value rounded to fp32 once.  Without clipping (desc.clip == 0) no partial is
+ *                       read, norm = NaN and clip_coef = 1.  found_inf / grad_scale: device floats or NULL (the GradScaler
+ *                       protocol of torch's fused optimizers).
+ *   m355_optim_update   reads the state record and returns at once when skip is set (parameters, state and EMA keep their
+ *                       bits).  The gradient is multiplied by clip_coef / grad_scale as it is read and never written back.
+ *                       SGD: g += wd * p; buf = momentum * buf + (1 - dampening) * g (`first`: buf = g); g = nesterov ? g +
+ *                       momentum * buf : buf; p -= lr * g.  Adam: g += wd * p; AdamW: p *= 1 - lr * wd; then m += (1 - beta1)
+ *                       * (g - m); v = beta2 * v + (1 - beta2) * g * g; p -= (lr / bc1) * m / (sqrt(v) / sqrt(bc2) + eps) --
+ *                       torch's own expressions.  ema_decay >= 0: ema += (1 - ema_decay) * (p_new - ema) in the same pass.
+ *                       state1 = momentum buffer / exp_avg (SGD without momentum: unused, may be NULL), state2 = exp_avg_sq.
+ *
+ * State record: M355_OPTIM_STATE_WORDS 4-byte words of device memory, zero before the first step, owned by the caller:
+ *   [0] norm f32  [1] clip_coef f32  [2] clip_coef / grad_scale f32  [3] bc1 f32  [4] bc2 f32 (group 0)  [5] skip i32
+ *   [6] t i32 (steps applied)  [7] reserved  [8 + g] lr f32  [24 + g] 1 - lr * wd f32  [40 + g] lr / bc1 f32
+ *   [56 + g] sqrt(bc2) f32,  g < M355_OPTIM_MAX_GROUPS.
+ * Every entry point checks its arguments on the host before any launch and returns M355_EINVALID_ARG with a message that
+ * names it: a null pointer, n < 1 or n > capacity, a negative count, a blk0 that does not continue the plan, a group out
+ * of range, non-finite or out-of-range hyper-parameters, a workspace too small for the partials.  Calls only enqueue. */
+#define M355_OPTIM_CAP 48
+#define M355_OPTIM_MAX_GROUPS 16
+#define M355_OPTIM_STATE_WORDS 72
+enum { M355_OPTIM_SGD = 0, M355_OPTIM_ADAM = 1, M355_OPTIM_ADAMW = 2 };
+typedef struct {
+  void* param;
+  const void* grad;
+  void* state1;
+  void* state2;
+  void* ema;
+  int64_t n;                   /* elements */
+  int64_t blk0;                /* m355_optim_plan's */
+  int32_t group;
+  int32_t first;               /* SGD: the momentum buffer holds nothing yet */
+} m355_optim_tensor;
+typedef struct {
+  double lr, weight_decay;
+  double momentum, dampening;  /* SGD */
+  double beta1, beta2, eps;    /* Adam, AdamW */
+  int32_t nesterov, reserved;
+} m355_optim_group;
+typedef struct {
+  int32_t rule;                /* M355_OPTIM_* */
+  int32_t groups;              /* 1 .. M355_OPTIM_MAX_GROUPS */
+  int32_t clip, reserved;      /* clip != 0: the norm pass ran, max_norm applies */
+  double max_norm;
+  int64_t total_steps;         /* 0: constant learning rate */
+  double power;
+  double ema_decay;            /* < 0: no EMA */
+  m355_optim_group group[M355_OPTIM_MAX_GROUPS];
+} m355_optim_desc;
+int32_t m355_optim_capacity(void);
+/* pure host: *chunk = elements of a block; blk0[i], nblk[i] = tensor i's blocks (a zero-element tensor owns none);
+ * *workspace_bytes = room for one fp64 partial per block */
+int m355_optim_plan(const int64_t* counts /* host */, int32_t T, int32_t* chunk, int64_t* blk0, int64_t* nblk,
+                    size_t* workspace_bytes);
+int m355_optim_norm(const m355_optim_tensor* tensors /* host */, int32_t n, void* workspace, size_t workspace_bytes,
+                    void* stream);
+int m355_optim_prepare(const m355_optim_desc* desc, int64_t nslots, const void* workspace, size_t workspace_bytes,
+                       const float* found_inf, const float* grad_scale, void* state, void* stream);
+int m355_optim_update(const m355_optim_desc* desc, const m355_optim_tensor* tensors /* host */, int32_t n, const void* state,
+                      void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -136,8 +136,35 @@ class SliceMosaicDesc(C.Structure):
                 ("first_tile", C.c_int32), ("pad", C.c_float)]
 
 
+OPTIM_SGD, OPTIM_ADAM, OPTIM_ADAMW = 0, 1, 2
+OPTIM_MAX_GROUPS = 16
+OPTIM_STATE_WORDS = 72
+# words of the optimizer state record (include/m355seg.h)
+OPTIM_ST_NORM, OPTIM_ST_CLIP, OPTIM_ST_SKIP, OPTIM_ST_T, OPTIM_ST_LR = 0, 1, 5, 6, 8
+
+
+class OptimTensor(C.Structure):
+    """m355_optim_tensor"""
+    _fields_ = [("param", C.c_void_p), ("grad", C.c_void_p), ("state1", C.c_void_p), ("state2", C.c_void_p),
+                ("ema", C.c_void_p), ("n", C.c_int64), ("blk0", C.c_int64), ("group", C.c_int32), ("first", C.c_int32)]
+
+
+class OptimGroup(C.Structure):
+    """m355_optim_group"""
+    _fields_ = [("lr", C.c_double), ("weight_decay", C.c_double), ("momentum", C.c_double), ("dampening", C.c_double),
+                ("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double), ("nesterov", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+class OptimDesc(C.Structure):
+    """m355_optim_desc"""
+    _fields_ = [("rule", C.c_int32), ("groups", C.c_int32), ("clip", C.c_int32), ("reserved", C.c_int32),
+                ("max_norm", C.c_double), ("total_steps", C.c_int64), ("power", C.c_double), ("ema_decay", C.c_double),
+                ("group", OptimGroup * OPTIM_MAX_GROUPS)]
+
+
 _P = C.c_void_p
-ABI_VERSION = 3   # M355_ABI_VERSION of include/m355seg.h this binding was written against
+ABI_VERSION = 3  # M355_ABI_VERSION of include/m355seg.h this binding was written against
 _i32, _i64, _f32, _sz = C.c_int32, C.c_int64, C.c_float, C.c_size_t
 _CD, _ND = C.POINTER(ConvDesc), C.POINTER(NormDesc)
 _I3, _D, _AS = C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(AugStage)
@@ -325,6 +352,11 @@ SIGNATURES = {
     "m355_region_stats_workspace": (_sz, [_i32, _i32, _i32]),
     "m355_region_stats_plan": (C.c_int, [_I3]),
     "m355_region_stats": (C.c_int, [_P, _i32, _I3, C.POINTER(RegionImage), _i32, _I3, _i32, _i32, _P, _P, _P, _P, _sz, _P]),
+    "m355_optim_capacity": (_i32, []),
+    "m355_optim_plan": (C.c_int, [C.POINTER(_i64), _i32, _I3, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_sz)]),
+    "m355_optim_norm": (C.c_int, [_P, _i32, _P, _sz, _P]),
+    "m355_optim_prepare": (C.c_int, [C.POINTER(OptimDesc), _i64, _P, _sz, _P, _P, _P, _P]),
+    "m355_optim_update": (C.c_int, [C.POINTER(OptimDesc), _P, _i32, _P, _P]),
 }
 
 
