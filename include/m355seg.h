@@ -1291,6 +1291,45 @@ int m355_surface_mask(const int32_t* x, int32_t value, const int32_t* size3, uin
 int m355_surface_gather(const uint8_t* border, const float* d2, int64_t nvox, float* out, int32_t* cursor,
                         int32_t capacity, void* stream);
 
+/* ------------------------------------------ boundary loss on a batched signed distance transform
+ * The device half of criterions.BoundaryLoss (Kervadec et al., "Boundary loss for highly unbalanced segmentation";
+ * DESIGN §4.27).  target, phi, p, dp: fp32 [planes = N * C][size3[0]][size3[1]][size3[2]], contiguous with the last axis
+ * fastest -- for a criterion's [N, C, D, H, W] tensors size3 = (D, H, W).  Every entry point enqueues on `stream`, never
+ * synchronises, uses no float atomics (a call repeats bit for bit) and checks its arguments on the host before any
+ * launch: a null pointer, a size or plane count < 1, 2^31 voxels per plane or more, or a spacing that is not finite
+ * and > 0 is M355_EINVALID_ARG; an axis above M355_EDT_MAX_DIM (m355_signed_distance) or N * C > 65535 (the loss) is
+ * M355_EUNSUPPORTED; a short workspace is M355_EWORKSPACE.
+ *   m355_signed_distance   A voxel is inside when target > 0.5 (a NaN is outside).  Per plane, with d the Euclidean
+ *                          distance under spacing3 (three host floats, one per axis of size3):
+ *                            outside voxel   phi = +d(v, nearest inside voxel)
+ *                            inside voxel    phi = -(d(v, nearest outside voxel) - 1)
+ *                            a plane that is all inside or all outside: phi = 0 everywhere
+ *                          (the convention of the published implementation; with unit spacing the inside voxels next to
+ *                          the border get 0).  plane_on: `planes` host bytes, or null for all planes; a plane whose byte
+ *                          is 0 is written as zeros and costs no transform.  One transform per plane -- every voxel
+ *                          needs the distance to the other membership only -- in three launches per 1024 planes (the
+ *                          last alone when none of them is on).  The arithmetic is m355_edt_sq's, term by term, the
+ *                          root correctly rounded and the subtraction from 1 rounded once: with unit spacing phi is the
+ *                          fp32 rounding of the exact value.  target is not modified and must not overlap phi.
+ *                          Workspace: m355_signed_distance_workspace(planes, size3) bytes (0 for invalid arguments).
+ *   m355_boundary_loss_fwd loss[0] = sum_n sum_c w_c sum_v p phi / (N S sum_c w_c), one fp32 device scalar; products and
+ *                          sums in fp64 in a fixed order.  class_weights: C device floats >= 0 with a positive sum, or
+ *                          null for all ones; rows with w_c == 0 are not read.  Two launches.  Workspace:
+ *                          m355_boundary_loss_workspace(N, C, S) bytes (0 for non-positive sizes).
+ *   m355_boundary_loss_bwd dp = dloss[0] (w_c / (N S sum_c w_c)) phi, the coefficient rounded to fp32 once and the product
+ *                          once; zeros for rows with w_c == 0.  dloss: one device float.  One launch.  The target gets
+ *                          no gradient.
+ */
+size_t m355_signed_distance_workspace(int32_t planes, const int32_t* size3);
+int m355_signed_distance(const float* target, int32_t planes, const int32_t* size3, const float* spacing3 /* host */,
+                         const uint8_t* plane_on /* host, may be null */, float* phi, void* workspace,
+                         size_t workspace_bytes, void* stream);
+size_t m355_boundary_loss_workspace(int32_t N, int32_t C, int64_t S);
+int m355_boundary_loss_fwd(const float* p, const float* phi, const float* class_weights, int32_t N, int32_t C, int64_t S,
+                           float* loss, void* workspace, size_t workspace_bytes, void* stream);
+int m355_boundary_loss_bwd(const float* phi, const float* dloss /* device scalar */, const float* class_weights, int32_t N,
+                           int32_t C, int64_t S, float* dp, void* stream);
+
 /* ------------------------------------------ statistics of image values grouped by the label of the voxel
  * The device half of ops.region_stats, evaluators.ImageRegionEvaluator and data_processing.dataset_fingerprint (DESIGN
  * §4.22).  One label volume [W, H, D] (contiguous, D fastest; any M355_EV_* type up to float32), K >= 0 images

@@ -349,6 +349,11 @@ SIGNATURES = {
     "m355_edt_sqrt": (C.c_int, [_P, _P, _i64, _P]),
     "m355_surface_mask": (C.c_int, [_P, _i32, _I3, _P, _P, _P]),
     "m355_surface_gather": (C.c_int, [_P, _P, _i64, _P, _P, _i32, _P]),
+    "m355_signed_distance_workspace": (_sz, [_i32, _I3]),
+    "m355_signed_distance": (C.c_int, [_P, _i32, _I3, C.POINTER(C.c_float), _P, _P, _P, _sz, _P]),
+    "m355_boundary_loss_workspace": (_sz, [_i32, _i32, _i64]),
+    "m355_boundary_loss_fwd": (C.c_int, [_P, _P, _P, _i32, _i32, _i64, _P, _P, _sz, _P]),
+    "m355_boundary_loss_bwd": (C.c_int, [_P, _P, _P, _i32, _i32, _i64, _P, _P]),
     "m355_region_stats_workspace": (_sz, [_i32, _i32, _i32]),
     "m355_region_stats_plan": (C.c_int, [_I3]),
     "m355_region_stats": (C.c_int, [_P, _i32, _I3, C.POINTER(RegionImage), _i32, _I3, _i32, _i32, _P, _P, _P, _P, _sz, _P]),

@@ -6,6 +6,7 @@
 //   edt_sqrt_kernel        correctly rounded elementwise square root
 //   surface_mask_kernel    the six-neighbour border of (x == value), and its voxel count
 //   surface_gather_kernel  sqrt(d2) of the border voxels, compacted
+//   sd_sweep_kernel, sd_line_kernel   the batched signed distance of criterions.BoundaryLoss (described where they stand)
 //
 // A volume is [W, H, D] with D fastest.  The transform is separable: d2[w, h, d] = min_w' ((sw (w - w'))^2 +
 // min_h' ((sh (h - h'))^2 + (sd kd[w', h', d])^2)) with kd the index distance to the nearest site of the row.
@@ -194,6 +195,168 @@ __global__ __launch_bounds__(ED_NT) void surface_gather_kernel(const uint8_t* __
   }
 }
 
+// ------------------------------------------------------------------------- batched signed distance
+// phi of every (n, c) plane of a target [planes][A0][A1][A2], A2 fastest, in one launch per pass: blockIdx carries the
+// plane, and a bit mask in the kernel arguments says which planes are transformed.  A voxel is inside when t > 0.5 (a NaN
+// is outside) and needs the distance to the nearest voxel of the OTHER membership only.  At every separable stage one of
+// a voxel's two partial distances (to inside, to outside) is zero -- the voxel is a site of its own class -- so one value
+// and the membership bit carry both, and the signed transform costs one transform:
+//   sd_sweep_kernel   along A2: index distance to the nearest voxel of the other membership in the row, uint16 with the
+//                     membership in bit 15; SD_NONE: the row has one membership only.  edt_d_kernel's wave scans, over
+//                     run starts and run ends instead of sites: the nearest other voxel to the left of i is the one before
+//                     the start of i's run, the nearest to the right the one after its end.
+//   sd_line_kernel    along A1, then along A0: the candidate of position q for a target at p is
+//                     (m[q] != m[p] ? 0 : g[q]) + (s (p - q))^2.  Effective candidate values are >= 0, so the pruning
+//                     argument of this file's header holds unchanged.  g > 0 or +inf for every voxel (a voxel is never
+//                     its own opposite), so the fp32 sign bit is free for the membership between the two passes.  The
+//                     last pass writes phi: 0 where g is infinite (exactly the planes without a boundary), sqrt_rn(g)
+//                     outside, 1 - sqrt_rn(g) inside; and zeros into the planes that are switched off.
+// The arithmetic is edt_line_kernel's, term by term: |phi| has the bits of the two-transform formulation through
+// m355_edt_sq.
+constexpr uint32_t SD_NONE = 0x7FFF;            // no voxel of the other membership in the row
+constexpr uint32_t SD_IN = 0x8000;              // membership bit of the sweep's code
+constexpr int SD_MASK_PLANES = 1024;            // planes per launch: the mask is 128 bytes of kernel arguments
+static_assert(M355_EDT_MAX_DIM <= (int)SD_NONE, "an index distance fits 15 bits");
+
+struct SdPlanes {
+  uint32_t on[SD_MASK_PLANES / 32];
+};
+__device__ __forceinline__ bool sd_on(const SdPlanes& m, uint32_t plane) { return (m.on[plane >> 5] >> (plane & 31)) & 1; }
+
+__global__ __launch_bounds__(ED_NT) void sd_sweep_kernel(const float* __restrict__ target, uint16_t* __restrict__ code,
+                                                         SdPlanes planes, size_t S, uint32_t rows, uint32_t D,
+                                                         uint32_t rows_per_wave) {
+  if (!sd_on(planes, blockIdx.y)) return;
+  const float* t = target + blockIdx.y * S;
+  uint16_t* kd = code + blockIdx.y * S;
+  const uint32_t lane = threadIdx.x & 63;
+  const uint32_t wave = blockIdx.x * (ED_NT / 64) + (threadIdx.x >> 6);
+  const uint32_t r0 = wave * rows_per_wave;
+  if (r0 >= rows) return;                            // (the whole wave, as in edt_d_kernel)
+  const uint32_t n = min(rows_per_wave, rows - r0) * D;   // <= ED_GROUP
+  const uint32_t base = r0 * D;                      // < 2^31 voxels per plane (checked on the host)
+  int run_start[ED_CHUNKS];
+  uint32_t in_bits = 0;
+  int carry = -1, prev = 0;                          // prev: the membership of the voxel before the chunk
+#pragma unroll
+  for (int c = 0; c < ED_CHUNKS; ++c) {
+    run_start[c] = -1;
+    if ((uint32_t)c * 64 < n) {                      // wave-uniform
+      const uint32_t i = c * 64 + lane;
+      const int m = i < n && t[base + i] > 0.5f;
+      int pm = __shfl_up(m, 1, 64);
+      if (lane == 0) pm = prev;
+      int v = (i == 0 || pm != m) ? (int)i : -1;     // the first voxel of a run of one membership
+#pragma unroll
+      for (int off = 1; off < 64; off <<= 1) {
+        const int o = __shfl_up(v, off, 64);
+        if ((int)lane >= off) v = max(v, o);
+      }
+      v = max(v, carry);
+      carry = __shfl(v, 63, 64);
+      prev = __shfl(m, 63, 64);
+      run_start[c] = v;
+      in_bits |= (uint32_t)m << c;
+    }
+  }
+  constexpr int BIG = 1 << 30;
+  carry = BIG;
+  int next = 0;                                      // the membership of the voxel after the chunk
+#pragma unroll
+  for (int c = ED_CHUNKS - 1; c >= 0; --c) {
+    if ((uint32_t)c * 64 < n) {
+      const uint32_t i = c * 64 + lane;
+      const int m = (in_bits >> c) & 1;
+      int nm = __shfl_down(m, 1, 64);
+      if (lane == 63) nm = next;
+      int v = i < n && (i == n - 1 || nm != m) ? (int)i : BIG;   // the last voxel of a run
+#pragma unroll
+      for (int off = 1; off < 64; off <<= 1) {
+        const int o = __shfl_down(v, off, 64);
+        if ((int)lane + off < 64) v = min(v, o);
+      }
+      v = min(v, carry);
+      carry = __shfl(v, 0, 64);
+      next = __shfl(m, 0, 64);
+      if (i < n) {
+        // the run is one sequence over the wave's rows: a neighbour found outside the voxel's own row is discarded
+        const int row_first = (int)(i / D * D), row_last = row_first + (int)D - 1;
+        const int kl = run_start[c] > row_first ? (int)i - run_start[c] + 1 : (int)SD_NONE;
+        const int kr = v < row_last ? v + 1 - (int)i : (int)SD_NONE;
+        kd[base + i] = (uint16_t)((uint32_t)min(kl, kr) | (m ? SD_IN : 0u));
+      }
+    }
+  }
+}
+
+// edt_line_kernel with the membership: lines (o, j) as there, blockIdx.z the plane.  FROM_CODE: the input is the sweep's
+// code and g = (s_in * k)^2; otherwise the previous pass's fp32 with the membership in the sign bit (`in` may be `out`).
+// LAST: phi is written, and zeros into a plane that is switched off; otherwise such a plane is left alone.
+template <bool FROM_CODE, bool LAST>
+__global__ __launch_bounds__(ED_NT) void sd_line_kernel(const void* in, float* out, SdPlanes planes, size_t S, uint32_t n,
+                                                        uint32_t inner, uint32_t line_stride, uint32_t outer_stride,
+                                                        float s_in, float s) {
+  extern __shared__ float g[];                       // [n][ED_DT], sign bit: inside
+  const uint32_t lane = threadIdx.x % ED_DT, ty = threadIdx.x / ED_DT;
+  const uint32_t j = blockIdx.x * ED_DT + lane;
+  const bool live = j < inner;
+  const uint32_t at = blockIdx.y * outer_stride + j;   // position 0 of the thread's line in its plane; < 2^31 when live
+  const size_t plane = blockIdx.z * S;
+  constexpr uint32_t ROWS = ED_NT / ED_DT;
+  if (!sd_on(planes, blockIdx.z)) {                  // (the whole block)
+    if (LAST && live)
+      for (uint32_t p = ty; p < n; p += ROWS) out[plane + at + p * line_stride] = 0.f;
+    return;
+  }
+  for (uint32_t p = ty; p < n; p += ROWS) {
+    float v = INFINITY;
+    if (live) {
+      if (FROM_CODE) {
+        const uint32_t c = ((const uint16_t*)in)[plane + at + p * line_stride], k = c & SD_NONE;
+        if (k != SD_NONE) {
+          const float t = __fmul_rn(s_in, (float)k);
+          v = __fmul_rn(t, t);
+        }
+        if (c & SD_IN) v = __uint_as_float(__float_as_uint(v) | 0x80000000u);
+      } else {
+        v = ((const float*)in)[plane + at + p * line_stride];
+      }
+    }
+    g[p * ED_DT + lane] = v;
+  }
+  __syncthreads();
+  if (!live) return;
+  // A line of +inf of one membership offers no candidate (every one is +inf + (s k)^2): its outputs are its inputs, and
+  // the search, which would walk the whole line from every position, is skipped.  Most lines of a sparse target are of
+  // that kind.  One walk over the line decides, and it ends at the first finite value or change of membership.
+  bool search = false;
+  const uint32_t first = __float_as_uint(g[lane]);
+  for (uint32_t q = 0; q < n && !search; ++q) {
+    const uint32_t u = __float_as_uint(g[q * ED_DT + lane]);
+    search = (u & 0x7FFFFFFFu) != 0x7F800000u || ((u ^ first) >> 31) != 0;
+  }
+  for (uint32_t p = ty; p < n; p += ROWS) {
+    const uint32_t me = __float_as_uint(g[p * ED_DT + lane]), sign = me & 0x80000000u;
+    float m = __uint_as_float(me ^ sign);
+    const uint32_t below = p, above = n - 1 - p, kmax = search ? max(below, above) : 0u;
+    for (uint32_t k = 1; k <= kmax; ++k) {
+      const float t = __fmul_rn(s, (float)k);
+      const float sq = __fmul_rn(t, t);
+      if (!(sq < m)) break;                          // nothing at distance >= k can be smaller (header of this file)
+      if (k <= below) {
+        const uint32_t u = __float_as_uint(g[(p - k) * ED_DT + lane]);
+        m = fminf(m, (u ^ sign) & 0x80000000u ? sq : __fadd_rn(__uint_as_float(u & 0x7FFFFFFFu), sq));
+      }
+      if (k <= above) {
+        const uint32_t u = __float_as_uint(g[(p + k) * ED_DT + lane]);
+        m = fminf(m, (u ^ sign) & 0x80000000u ? sq : __fadd_rn(__uint_as_float(u & 0x7FFFFFFFu), sq));
+      }
+    }
+    if (LAST) out[plane + at + p * line_stride] = isinf(m) ? 0.f : sign ? __fsub_rn(1.f, sqrt_rn(m)) : sqrt_rn(m);
+    else out[plane + at + p * line_stride] = __uint_as_float(__float_as_uint(m) | sign);
+  }
+}
+
 int check_volume(const char* what, const int32_t* s) {
   for (int a = 0; a < 3; ++a) M355_REQUIRE(s[a] >= 1, M355_EINVALID_ARG, "%s: size %d on axis %d", what, s[a], a);
   M355_REQUIRE((int64_t)s[0] * s[1] * s[2] < ((int64_t)1 << 31), M355_EINVALID_ARG, "%s: %lld voxels (fewer than 2^31)",
@@ -238,6 +401,64 @@ extern "C" int m355_edt_sq(const uint8_t* sites, const int32_t* size3, const flo
   hipLaunchKernelGGL(edt_line_kernel<false>, dim3((unsigned)m355::ceil_div((int64_t)H * D, ED_DT), 1), dim3(ED_NT),
                      (size_t)W * ED_DT * sizeof(float), st, (const void*)d2, d2, W, H * D, H * D, 0u, 0.f, spacing3[0]);
   return m355::check_launch("edt_sq: W pass");
+}
+
+extern "C" size_t m355_signed_distance_workspace(int32_t planes, const int32_t* size3) {
+  if (planes < 1 || !size3 || size3[0] < 1 || size3[1] < 1 || size3[2] < 1) return 0;
+  const int64_t S = (int64_t)size3[0] * size3[1] * size3[2];
+  return (size_t)m355::round_up((int64_t)planes * S * (int64_t)sizeof(uint16_t), 256);   // the sweep's codes
+}
+
+extern "C" int m355_signed_distance(const float* target, int32_t planes, const int32_t* size3, const float* spacing3,
+                                    const uint8_t* plane_on, float* phi, void* workspace, size_t workspace_bytes,
+                                    void* stream) {
+  M355_REQUIRE(target && size3 && spacing3 && phi && workspace, M355_EINVALID_ARG, "signed_distance: null pointer");
+  M355_REQUIRE(planes >= 1, M355_EINVALID_ARG, "signed_distance: %d planes", planes);
+  if (int rc = check_volume("signed_distance", size3)) return rc;
+  for (int a = 0; a < 3; ++a)
+    M355_REQUIRE(isfinite(spacing3[a]) && spacing3[a] > 0.f, M355_EINVALID_ARG,
+                 "signed_distance: spacing %g on axis %d (finite and > 0)", (double)spacing3[a], a);
+  for (int a = 0; a < 3; ++a)
+    M355_REQUIRE(size3[a] <= M355_EDT_MAX_DIM, M355_EUNSUPPORTED,
+                 "signed_distance: size %d on axis %d (at most M355_EDT_MAX_DIM = %d: a line is staged in LDS)", size3[a], a,
+                 M355_EDT_MAX_DIM);
+  M355_REQUIRE(workspace_bytes >= m355_signed_distance_workspace(planes, size3), M355_EWORKSPACE,
+               "signed_distance: workspace of %zu bytes, %zu needed", workspace_bytes,
+               m355_signed_distance_workspace(planes, size3));
+  const uint32_t A0 = size3[0], A1 = size3[1], A2 = size3[2], rows = A0 * A1;
+  const size_t S = (size_t)rows * A2;
+  hipStream_t st = (hipStream_t)stream;
+  const uint32_t rpw = std::max<uint32_t>(1, ED_GROUP / A2);
+  const unsigned sweep_blocks = (unsigned)m355::ceil_div(m355::ceil_div(rows, rpw), ED_NT / 64);
+  for (int32_t p0 = 0; p0 < planes; p0 += SD_MASK_PLANES) {
+    const int32_t np = std::min<int32_t>(SD_MASK_PLANES, planes - p0);
+    SdPlanes mask = {};
+    bool any = false;
+    for (int32_t i = 0; i < np; ++i)
+      if (!plane_on || plane_on[p0 + i]) {
+        mask.on[i >> 5] |= 1u << (i & 31);
+        any = true;
+      }
+    const float* t = target + (size_t)p0 * S;
+    uint16_t* code = (uint16_t*)workspace + (size_t)p0 * S;
+    float* out = phi + (size_t)p0 * S;
+    if (any) {
+      hipLaunchKernelGGL(sd_sweep_kernel, dim3(sweep_blocks, (unsigned)np), dim3(ED_NT), 0, st, t, code, mask, S, rows, A2,
+                         rpw);
+      if (int rc = m355::check_launch("signed_distance: sweep")) return rc;
+      // along A1: slab a0, lines (a0, a2) for a2 < A2, A2 apart
+      hipLaunchKernelGGL((sd_line_kernel<true, false>), dim3((unsigned)m355::ceil_div(A2, ED_DT), A0, (unsigned)np),
+                         dim3(ED_NT), (size_t)A1 * ED_DT * sizeof(float), st, (const void*)code, out, mask, S, A1, A2, A2,
+                         A1 * A2, spacing3[2], spacing3[1]);
+      if (int rc = m355::check_launch("signed_distance: first line pass")) return rc;
+    }
+    // along A0, in place: the lines are the A1 * A2 voxels of slab a0 = 0, A1 * A2 apart.  Also zeroes the planes that are off.
+    hipLaunchKernelGGL((sd_line_kernel<false, true>), dim3((unsigned)m355::ceil_div((int64_t)A1 * A2, ED_DT), 1, (unsigned)np),
+                       dim3(ED_NT), (size_t)A0 * ED_DT * sizeof(float), st, (const void*)out, out, mask, S, A0, A1 * A2,
+                       A1 * A2, 0u, 0.f, spacing3[0]);
+    if (int rc = m355::check_launch("signed_distance: last line pass")) return rc;
+  }
+  return M355_OK;
 }
 
 extern "C" int m355_edt_sqrt(const float* d2, float* d, int64_t n, void* stream) {

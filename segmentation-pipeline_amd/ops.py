@@ -2230,6 +2230,50 @@ def focal_tversky_loss(x, target, tversky_weight=0.5, alpha=0.5, beta=0.5, tvers
                                      focal_class_weights, tversky_class_weights, from_logits)
 
 
+class _BoundaryLossFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, p, phi, class_weights):
+        L = _lib.lib()
+        # (the argument errors come before the device check, as in _FocalTverskyLossFn)
+        for name, v in (("prediction", p), ("phi", phi), ("class_weights", class_weights)):
+            if v is not None and v.dtype != torch.float32:
+                raise _lib.M355Error(f"{name}: expected torch.float32, got {v.dtype}")
+        if p.dim() < 2 or p.shape != phi.shape:
+            raise _lib.M355Error(f"prediction {tuple(p.shape)} and phi {tuple(phi.shape)}: expected one shape [N, C, ...]")
+        N, Cc = p.shape[0], p.shape[1]
+        if class_weights is not None and (class_weights.dim() != 1 or class_weights.numel() != Cc):
+            raise _lib.M355Error(f"class_weights of shape {tuple(class_weights.shape)} for {Cc} channels")
+        _require(p, phi, class_weights)
+        p, phi = p.contiguous(), phi.contiguous()
+        cw = None if class_weights is None else class_weights.contiguous()
+        S = p.numel() // (N * Cc)
+        loss = torch.empty((), dtype=torch.float32, device=p.device)
+        ws = _workspace(L.m355_boundary_loss_workspace(N, Cc, S), p.device)
+        check(L.m355_boundary_loss_fwd(_p(p), _p(phi), _p(cw), N, Cc, S, _p(loss), _p(ws), ws.numel(), _stream()),
+              "boundary_loss_fwd")
+        ctx.args = (N, Cc, S)
+        ctx.save_for_backward(phi, cw)
+        return loss
+
+    @staticmethod
+    def backward(ctx, dloss):
+        L = _lib.lib()
+        phi, cw = ctx.saved_tensors
+        N, Cc, S = ctx.args
+        dloss = dloss.contiguous().to(torch.float32)
+        dp = torch.empty_like(phi)
+        check(L.m355_boundary_loss_bwd(_p(phi), _p(dloss), _p(cw), N, Cc, S, _p(dp), _stream()), "boundary_loss_bwd")
+        return dp, None, None
+
+
+def boundary_loss(p, phi, class_weights=None):
+    """The boundary loss of Kervadec et al.: sum_c w_c sum p phi / (N S sum_c w_c), a 0-dim tensor, of the
+    fp32 probabilities `p` [N, C, ...] and the signed distance map `phi` of the target (ops.signed_distance).
+    class_weights: an fp32 device tensor [C] of values >= 0 with a positive sum, or None for all ones; a channel with
+    weight 0 is not read and gets a zero gradient.  The gradient flows to `p` only."""
+    return _BoundaryLossFn.apply(p, phi, class_weights)
+
+
 # ------------------------------------------------------------- target pyramid
 PYRAMID_MODES = {"area": 0, "nearest": 1}   # M355_PYRAMID_AREA, M355_PYRAMID_NEAREST
 PYRAMID_MAX_LEVELS = 4
@@ -3097,6 +3141,37 @@ def edt_sqrt(d2, out=None):
     with torch.cuda.device(d2.device):
         check(_lib.lib().m355_edt_sqrt(_p(d2), _p(out), d2.numel(), _stream()), "edt_sqrt")
     return out
+
+
+def signed_distance(target, spacing=(1., 1., 1.), planes=None):
+    """The signed distance map of every (n, c) plane of `target` (float32 [N, C, D, H, W], contiguous, on the device;
+    a voxel is inside when target > 0.5), float32 of the same shape: +distance to the nearest inside voxel
+    outside, -(distance to the nearest outside voxel - 1) inside, 0 everywhere in a plane without a boundary.  spacing: a
+    number or three (D, H, W), used in fp32; exact (the fp32 rounding of the true value) for unit spacing.  planes: None
+    for all, or N * C host flags ([N][C] order) -- a plane that is off is written as zeros and costs no transform.  One
+    transform per plane, three launches for up to 1024 planes, no synchronisation.  Every axis at most _lib.EDT_MAX_DIM."""
+    if not isinstance(target, torch.Tensor) or target.dtype != torch.float32:
+        got = target.dtype if isinstance(target, torch.Tensor) else type(target).__name__
+        raise _lib.M355Error(f"signed_distance: target: element type {got} (expected torch.float32)")
+    if target.dim() != 5:
+        raise _lib.M355Error(f"signed_distance: target: expected [N, C, D, H, W], got shape {tuple(target.shape)}")
+    sp = (C.c_float * 3)(*_spacing3(spacing))
+    n_planes = target.shape[0] * target.shape[1]
+    on = None
+    if planes is not None:
+        flags = [bool(v) for v in (planes.flatten().tolist() if isinstance(planes, torch.Tensor) else planes)]
+        if len(flags) != n_planes:
+            raise _lib.M355Error(f"signed_distance: {len(flags)} plane flags for N * C = {n_planes} planes")
+        on = (C.c_uint8 * n_planes)(*flags)
+    _dist_arg(target, (torch.float32,), "signed_distance: target")
+    size3 = (C.c_int32 * 3)(*target.shape[2:])
+    L = _lib.lib()
+    with torch.cuda.device(target.device):
+        ws = _workspace(L.m355_signed_distance_workspace(n_planes, size3), target.device)
+        phi = torch.empty_like(target)
+        check(L.m355_signed_distance(_p(target), n_planes, size3, sp, on, _p(phi), _p(ws), ws.numel(), _stream()),
+              "signed_distance")
+    return phi
 
 
 def surface_mask(x_i32, value, border=None, count=None):
