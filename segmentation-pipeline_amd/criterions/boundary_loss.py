@@ -28,13 +28,13 @@ The result is `criterion`'s dict with 'loss' replaced by the total and 'boundary
 import math
 
 import torch
-from torch import nn
 
 from .. import ops
 from .._lib import M355Error
+from ._device_weights import DeviceWeightsCriterion
 
 
-class BoundaryLoss(nn.Module):
+class BoundaryLoss(DeviceWeightsCriterion):
     def __init__(self, criterion, boundary_weight=0.01, regional_weight=1.0, boundary_class_weights=None,
                  spacing=(1., 1., 1.)):
         super().__init__()
@@ -60,7 +60,6 @@ class BoundaryLoss(nn.Module):
         self.spacing = spacing
         self.register_buffer("regional_weight", torch.tensor(float(regional_weight), dtype=torch.float32))
         self.register_buffer("boundary_weight", torch.tensor(float(boundary_weight), dtype=torch.float32))
-        self._uploaded = None   # (values, device, tensor): the class weights on the device, uploaded once
 
     def set_weights(self, regional=None, boundary=None):
         """Fill the mixing weights in place (no synchronisation; the buffers keep their addresses)."""
@@ -75,16 +74,10 @@ class BoundaryLoss(nn.Module):
         values = self.boundary_class_weights
         if values is None:
             values = (0.0,) + (1.0,) * (channels - 1) if channels > 1 else (1.0,)
-        elif len(values) != channels:
-            raise M355Error(f"boundary_class_weights of {len(values)} values for {channels} channels")
-        held = self._uploaded
-        if held is None or held[0] != values or held[1] != device:
-            held = self._uploaded = (values, device, torch.tensor(values, dtype=torch.float32, device=device))
-        return values, held[2]
+        return values, self._device_weights("boundary_class_weights", channels, device, given=values)
 
-    def __getstate__(self):   # pickled losses hold no device tensor
-        state = self.__dict__.copy()
-        state["_uploaded"] = None
+    def __getstate__(self):   # pickled losses hold no device tensor: the buffers go to the host too
+        state = super().__getstate__()
         state["_buffers"] = {k: v.cpu() for k, v in self._buffers.items()}
         return state
 

@@ -9,14 +9,11 @@ backward multiplies by p (1 - p) = 0.
 
 Same dict of three scalars as HybridLogisticDiceLoss; the gradient flows through 'loss' only.
 """
-import torch
-from torch import nn
-
 from .. import ops
-from .._lib import M355Error
+from ._device_weights import DeviceWeightsCriterion
 
 
-class HybridBinaryLogisticDiceLoss(nn.Module):
+class HybridBinaryLogisticDiceLoss(DeviceWeightsCriterion):
     def __init__(self, dice_weight=0.5, logistic_class_weights=None, pos_weight=None, square_dice=True, from_logits=False):
         super().__init__()
         self.dice_weight = dice_weight
@@ -24,33 +21,10 @@ class HybridBinaryLogisticDiceLoss(nn.Module):
         self.pos_weight = pos_weight
         self.square_dice = square_dice
         self.from_logits = from_logits
-        self._uploaded = {}   # attribute name -> (values, device, tensor): the weights on the device, uploaded once
-
-    def _weights(self, name, channels, device):
-        """self.<name> as an fp32 device tensor [channels] or None, uploaded once per (values, device)"""
-        given = getattr(self, name)
-        if given is None:
-            return None
-        if isinstance(given, torch.Tensor):
-            if given.dim() != 1 or given.numel() != channels:
-                raise M355Error(f"{name} of shape {tuple(given.shape)} for {channels} channels")
-            return given.to(device=device, dtype=torch.float32)
-        values = tuple(float(v) for v in given)
-        if len(values) != channels:
-            raise M355Error(f"{name} of {len(values)} values for {channels} channels")
-        held = self._uploaded.get(name)
-        if held is None or held[0] != values or held[1] != device:
-            held = self._uploaded[name] = (values, device, torch.tensor(values, dtype=torch.float32, device=device))
-        return held[2]
-
-    def __getstate__(self):   # pickled losses hold no device tensor
-        state = self.__dict__.copy()
-        state["_uploaded"] = {}
-        return state
 
     def forward(self, prediction, target):
         channels = prediction.shape[1] if prediction.dim() >= 2 else 0
         loss, dice_loss, logistic_loss = ops.binary_logistic_dice_loss(
-            prediction, target, self.dice_weight, self._weights("logistic_class_weights", channels, prediction.device),
-            self._weights("pos_weight", channels, prediction.device), self.square_dice, self.from_logits)
+            prediction, target, self.dice_weight, self._device_weights("logistic_class_weights", channels, prediction.device),
+            self._device_weights("pos_weight", channels, prediction.device), self.square_dice, self.from_logits)
         return {'loss': loss, 'dice_loss': dice_loss, 'logistic_loss': logistic_loss}

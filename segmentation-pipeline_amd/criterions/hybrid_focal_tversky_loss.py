@@ -22,14 +22,11 @@ Same dict shape as the other criteria: {'loss', 'tversky_loss', 'focal_loss'}; t
 """
 import math
 
-import torch
-from torch import nn
-
 from .. import ops
-from .._lib import M355Error
+from ._device_weights import DeviceWeightsCriterion
 
 
-class HybridFocalTverskyLoss(nn.Module):
+class HybridFocalTverskyLoss(DeviceWeightsCriterion):
     def __init__(self, tversky_weight=0.5, alpha=0.5, beta=0.5, tversky_power=1.0, focal_gamma=0.0,
                  logistic_class_weights=None, tversky_class_weights=None, from_logits=False):
         super().__init__()
@@ -49,34 +46,11 @@ class HybridFocalTverskyLoss(nn.Module):
         self.logistic_class_weights = logistic_class_weights
         self.tversky_class_weights = tversky_class_weights
         self.from_logits = from_logits
-        self._uploaded = {}   # attribute name -> (values, device, tensor): the weights on the device, uploaded once
-
-    def _weights(self, name, channels, device):
-        """self.<name> as an fp32 device tensor [channels] or None, uploaded once per (values, device)"""
-        given = getattr(self, name)
-        if given is None:
-            return None
-        if isinstance(given, torch.Tensor):
-            if given.dim() != 1 or given.numel() != channels:
-                raise M355Error(f"{name} of shape {tuple(given.shape)} for {channels} channels")
-            return given.to(device=device, dtype=torch.float32)
-        values = tuple(float(v) for v in given)
-        if len(values) != channels:
-            raise M355Error(f"{name} of {len(values)} values for {channels} channels")
-        held = self._uploaded.get(name)
-        if held is None or held[0] != values or held[1] != device:
-            held = self._uploaded[name] = (values, device, torch.tensor(values, dtype=torch.float32, device=device))
-        return held[2]
-
-    def __getstate__(self):   # pickled losses hold no device tensor
-        state = self.__dict__.copy()
-        state["_uploaded"] = {}
-        return state
 
     def forward(self, prediction, target):
         channels = prediction.shape[1] if prediction.dim() >= 2 else 0
         loss, tversky_loss, focal_loss = ops.focal_tversky_loss(
             prediction, target, self.tversky_weight, self.alpha, self.beta, self.tversky_power, self.focal_gamma,
-            self._weights("logistic_class_weights", channels, prediction.device),
-            self._weights("tversky_class_weights", channels, prediction.device), self.from_logits)
+            self._device_weights("logistic_class_weights", channels, prediction.device),
+            self._device_weights("tversky_class_weights", channels, prediction.device), self.from_logits)
         return {'loss': loss, 'tversky_loss': tversky_loss, 'focal_loss': focal_loss}

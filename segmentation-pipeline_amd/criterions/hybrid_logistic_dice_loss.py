@@ -5,39 +5,20 @@ Mirror of segmentation_pipeline/criterions/hybrid_logistic_dice_loss.py:6-43
 (prediction, target) produces the four per-(n, c) sums, a finalize kernel turns them
 into the scalars, and the backward is closed-form from the saved sums.
 """
-import torch
-from torch import nn
-
 from .. import ops
+from ._device_weights import DeviceWeightsCriterion
 
 
-class HybridLogisticDiceLoss(nn.Module):
+class HybridLogisticDiceLoss(DeviceWeightsCriterion):
     def __init__(self, dice_weight=0.5, logistic_class_weights=None, square_dice=True):
         super().__init__()
         self.dice_weight = dice_weight
         self.logistic_class_weights = logistic_class_weights
         self.square_dice = square_dice
-        self._weights = None   # (values, device, tensor): the class weights on the device, uploaded once
-
-    def _class_weights(self, device):
-        """The reference builds the weight tensor every call (:23-25); from a Python list that is a blocking
-        host-to-device copy per step (~0.8 ms of a 12 ms step).  Uploaded once per (values, device)."""
-        if self.logistic_class_weights is None:
-            return None
-        if isinstance(self.logistic_class_weights, torch.Tensor):
-            return self.logistic_class_weights.to(device=device, dtype=torch.float32)
-        values = tuple(float(v) for v in self.logistic_class_weights)
-        if self._weights is None or self._weights[0] != values or self._weights[1] != device:
-            self._weights = (values, device, torch.tensor(values, dtype=torch.float32, device=device))
-        return self._weights[2]
-
-    def __getstate__(self):   # pickled losses stay as the reference's (no device tensor inside)
-        state = self.__dict__.copy()
-        state["_weights"] = None
-        return state
 
     def forward(self, prediction, target):
-        weights = self._class_weights(prediction.device)
+        # (the weights' length is not checked against the channels, as in the reference's constructor)
+        weights = self._device_weights("logistic_class_weights", None, prediction.device)
         loss, dice_loss, logistic_loss = ops.hybrid_logistic_dice_loss(
             prediction, target, self.dice_weight, weights, self.square_dice)
         return {'loss': loss, 'dice_loss': dice_loss, 'logistic_loss': logistic_loss}

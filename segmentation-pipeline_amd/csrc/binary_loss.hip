@@ -1,6 +1,7 @@
 // Binary cross-entropy + Dice loss for sigmoid heads (criterions/hybrid_binary_logistic_dice_loss.py):
-// the binary / multi-label counterpart of the hybrid loss in loss_patch_eval.hip, with the same structure -- a
-// partial-sum kernel over chunks of one (n, c) row, a one-block finalize kernel, a one-pass closed-form backward.
+// the binary / multi-label counterpart of the hybrid loss in hybrid_loss.hip, with the same structure -- a
+// partial-sum kernel over chunks of one (n, c) row, a one-block finalize kernel, a one-pass closed-form backward
+// (the shared pieces: loss_common.hpp).
 //
 //   PROB    x = p, probabilities (the Sigmoid head's output).  q = 1 - p (one fp32 subtraction, exact for p >= 0.5),
 //           lp = log((p + eps) / (1 + eps)), lq = log((q + eps) / (1 + eps)), eps = 1e-8 (1 + eps == 1.0f, as in the
@@ -9,11 +10,12 @@
 //           lq = -softplus(z), softplus(v) = max(v, 0) + log1p(exp(-|v|)): no eps, finite for every finite z.
 //
 // sums[nc * 5 + k] = {sum p t, sum p(^2), sum t(^2), sum t lp, sum (1 - t) lq}; class and positive weights enter in the
-// finalize step and in the backward only.  The first three sums are accumulated exactly as loss_partial_kernel does
-// (thread i of a chunk takes elements i, i + 256, ... in fp32, then fp64 in a fixed order), so the Dice term of a
-// PROB launch has the bits of m355_hybrid_loss_fwd's.  That fixes one element per lane and load: rows start at nc * S
+// finalize step and in the backward only.  The first three sums are accumulated by dice_accumulate in the order of
+// hybrid_loss.hip's partial-sum kernel (thread i of a chunk takes elements i, i + 256, ... in fp32, then fp64 in a fixed
+// order) and turned into the Dice term by the same dice_term, so the Dice term of a PROB launch has the bits of
+// m355_hybrid_loss_fwd's.  That fixes one element per lane and load: rows start at nc * S
 // for any S, and scalar loads need no alignment.  No float atomics: two launches give the same bits.
-#include "common.hpp"
+#include "loss_common.hpp"
 
 namespace m355 {
 
@@ -39,8 +41,6 @@ __global__ __launch_bounds__(256) void binary_loss_partial_kernel(const float* _
   const float* xp = x + nc * S;
   const float* tp = t + nc * S;
   const int64_t begin = (int64_t)b * BLOSS_CHUNK, end = min(S, begin + BLOSS_CHUNK);
-  const float eps = 1e-8f;
-  const float denom = (float)(1.0 + 1e-8);
   float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f, s4 = 0.f;
   // BLOSS_U elements of the lane's sequence are loaded before the first is used (two waves per SIMD at cfg2's output:
   // one load in flight per lane leaves the pass bound by memory latency); they are still added in sequence order
@@ -63,34 +63,19 @@ __global__ __launch_bounds__(256) void binary_loss_partial_kernel(const float* _
       } else {
         pv = xv;
         const float qv = 1.f - pv;
-        lp = logf((pv + eps) / denom);
-        lq = logf((qv + eps) / denom);
+        lp = safe_log_prob(pv);
+        lq = safe_log_prob(qv);
       }
-      s0 = fmaf(pv, tv, s0);
-      if (square_dice) {
-        s1 = fmaf(pv, pv, s1);
-        s2 = fmaf(tv, tv, s2);
-      } else {
-        s1 += pv;
-        s2 += tv;
-      }
+      dice_accumulate(pv, tv, square_dice, s0, s1, s2);
       s3 = fmaf(tv, lp, s3);
       s4 = fmaf(1.f - tv, lq, s4);
     }
   }
-  const double t0 = block_sum<double, 256>((double)s0, scratch);
-  const double t1 = block_sum<double, 256>((double)s1, scratch);
-  const double t2 = block_sum<double, 256>((double)s2, scratch);
-  const double t3 = block_sum<double, 256>((double)s3, scratch);
-  const double t4 = block_sum<double, 256>((double)s4, scratch);
-  if (threadIdx.x == 0) {
-    double* o = partial + (nc * nblk + b) * BLOSS_K;
-    o[0] = t0; o[1] = t1; o[2] = t2; o[3] = t3; o[4] = t4;
-  }
+  const float s[BLOSS_K] = {s0, s1, s2, s3, s4};
+  store_block_sums(s, partial, nc * nblk + b, scratch);
 }
 
-// single block: sums[nc*5+k], out3 = {loss, dice_loss, logistic_loss}.  The Dice expressions are those of
-// loss_finalize_kernel.
+// single block, one thread per row, its chunks added in order: sums[nc*5+k], out3 = {loss, dice_loss, logistic_loss}
 __global__ __launch_bounds__(256) void binary_loss_finalize_kernel(const double* __restrict__ partial,
                                                                    const float* __restrict__ class_w,
                                                                    const float* __restrict__ pos_w, float* __restrict__ sums,
@@ -104,9 +89,7 @@ __global__ __launch_bounds__(256) void binary_loss_finalize_kernel(const double*
     for (int b = 0; b < nblk; ++b)
       for (int k = 0; k < BLOSS_K; ++k) v[k] += partial[((int64_t)nc * nblk + b) * BLOSS_K + k];
     for (int k = 0; k < BLOSS_K; ++k) sums[nc * BLOSS_K + k] = (float)v[k];
-    const float overlap = (float)v[0], total = (float)v[1] + (float)v[2];
-    const float dice = 2.f * overlap / (total + 1e-8f);
-    dice_acc += (double)(1.f - dice);
+    dice_acc += (double)dice_term(v[0], v[1], v[2]);
     const double pw = pos_w ? (double)pos_w[nc % C] : 1.0;
     float logistic = (float)((pw * v[3] + v[4]) / (double)S);
     if (class_w) logistic *= class_w[nc % C];
@@ -114,16 +97,11 @@ __global__ __launch_bounds__(256) void binary_loss_finalize_kernel(const double*
   }
   const double d = block_sum<double, 256>(dice_acc, scratch);
   const double l = block_sum<double, 256>(log_acc, scratch);
-  if (threadIdx.x == 0) {
-    const float dice_loss = (float)(d / NC), logistic_loss = (float)(l / NC);
-    out3[0] = (1.f - dice_weight) * logistic_loss + dice_weight * dice_loss;
-    out3[1] = dice_loss;
-    out3[2] = logistic_loss;
-  }
+  if (threadIdx.x == 0) write_out3(out3, dice_weight, (float)(d / NC), (float)(l / NC));
 }
 
 // dx = dloss * [ (1-w) * d(logistic_loss)/dx + w * d(dice_loss)/dx ],   k = cw[c] / (N*C*S)
-//   d dice_loss / dp = -(1/(N*C)) * (2 t / (T+eps) - 2 O * dT/dp / (T+eps)^2),   dT/dp = 2p (square_dice) or 1
+//   d dice_loss / dp: dice_bwd_coeffs
 //   PROB    d logistic_loss / dp = -k * (pw t / (p + eps) - (1 - t) / (q + eps))
 //   LOGITS  d logistic_loss / dz =  k * (-pw t sigmoid(-z) + (1 - t) sigmoid(z));  dp/dz = p * sigmoid(-z)
 //           (sigmoid(-z) is evaluated, not 1 - sigmoid(z): that difference cancels where the loss has to pull hardest)
@@ -135,14 +113,11 @@ __global__ __launch_bounds__(256) void binary_loss_bwd_kernel(const float* __res
                                                               int C, int64_t S, float dice_weight, int square_dice) {
   const int64_t nc = blockIdx.y;
   const float g = dloss[0];
-  const float O = sums[nc * BLOSS_K + 0];
-  const float T = sums[nc * BLOSS_K + 1] + sums[nc * BLOSS_K + 2] + 1e-8f;
   const float inv_nc = 1.f / (float)(N * C);
+  const DiceBwd k = dice_bwd_coeffs(sums + nc * BLOSS_K, dice_weight, inv_nc, g);
   const float cw = class_w ? class_w[nc % C] : 1.f;
   const float pw = pos_w ? pos_w[nc % C] : 1.f;
   const float klog = (1.f - dice_weight) * cw * inv_nc / (float)S * g;
-  const float kd1 = -dice_weight * inv_nc * 2.f / T * g;          // * t
-  const float kd2 = dice_weight * inv_nc * 2.f * O / (T * T) * g;  // * dT/dp
   const float eps = 1e-8f;
   const float* xp = x + nc * S;
   const float* tp = t + nc * S;
@@ -152,15 +127,15 @@ __global__ __launch_bounds__(256) void binary_loss_bwd_kernel(const float* __res
     float d;
     if (LOGITS) {
       const float pv = sigmoid_f32(xv), nv = sigmoid_f32(-xv);
-      float dd = kd1 * tv;
-      dd = fmaf(kd2, square_dice ? 2.f * pv : 1.f, dd);
+      float dd = k.kd1 * tv;
+      dd = fmaf(k.kd2, square_dice ? 2.f * pv : 1.f, dd);
       d = klog * fmaf(-pw * tv, nv, (1.f - tv) * pv);
       d = fmaf(dd, pv * nv, d);
     } else {
       const float qv = 1.f - xv;
       d = -klog * (pw * tv / (xv + eps) - (1.f - tv) / (qv + eps));
-      d = fmaf(kd1, tv, d);
-      d = fmaf(kd2, square_dice ? 2.f * xv : 1.f, d);
+      d = fmaf(k.kd1, tv, d);
+      d = fmaf(k.kd2, square_dice ? 2.f * xv : 1.f, d);
     }
     op[i] = d;
   }
@@ -171,8 +146,7 @@ __global__ __launch_bounds__(256) void binary_loss_bwd_kernel(const float* __res
 using namespace m355;
 
 extern "C" size_t m355_binary_loss_workspace(int32_t N, int32_t C, int64_t S) {
-  if (N <= 0 || C <= 0 || S <= 0) return 0;
-  return (size_t)N * C * ceil_div(S, BLOSS_CHUNK) * BLOSS_K * sizeof(double) + 256;
+  return loss_workspace_bytes(N, C, S, BLOSS_CHUNK, BLOSS_K);
 }
 
 extern "C" int m355_binary_loss_fwd(const float* x, const float* t, int32_t N, int32_t C, int64_t S, float dice_weight,
@@ -180,8 +154,7 @@ extern "C" int m355_binary_loss_fwd(const float* x, const float* t, int32_t N, i
                                     int32_t from_logits, float* out3, float* sums, void* workspace, size_t workspace_bytes,
                                     void* stream) {
   M355_REQUIRE(x && t && out3 && sums && workspace, M355_EINVALID_ARG, "binary_loss_fwd: null pointer");
-  M355_REQUIRE(N > 0 && C > 0 && S > 0, M355_EINVALID_ARG, "binary_loss_fwd: non-positive size");
-  M355_REQUIRE((int64_t)N * C <= 65535, M355_EUNSUPPORTED, "binary_loss_fwd: N*C > 65535");
+  if (int rc = loss_check("binary_loss_fwd", N, C, S)) return rc;
   M355_REQUIRE(workspace_bytes >= m355_binary_loss_workspace(N, C, S), M355_EWORKSPACE,
                "binary_loss_fwd: workspace too small");
   hipStream_t st = (hipStream_t)stream;
@@ -202,9 +175,8 @@ extern "C" int m355_binary_loss_bwd(const float* x, const float* t, const float*
                                     const float* pos_weight, int32_t square_dice, int32_t from_logits, float* dx,
                                     void* stream) {
   M355_REQUIRE(x && t && sums && dloss && dx, M355_EINVALID_ARG, "binary_loss_bwd: null pointer");
-  M355_REQUIRE(N > 0 && C > 0 && S > 0, M355_EINVALID_ARG, "binary_loss_bwd: non-positive size");
-  M355_REQUIRE((int64_t)N * C <= 65535, M355_EUNSUPPORTED, "binary_loss_bwd: N*C > 65535");
-  const dim3 grid((unsigned)std::max<int64_t>(1, std::min<int64_t>(ceil_div(S, 1024), 2048)), (unsigned)(N * C));
+  if (int rc = loss_check("binary_loss_bwd", N, C, S)) return rc;
+  const dim3 grid = loss_bwd_grid(S, 1024, N * C);
   if (from_logits)
     hipLaunchKernelGGL(binary_loss_bwd_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, x, t, sums, dloss,
                        class_weights, pos_weight, dx, N, C, S, dice_weight, square_dice);

@@ -4,45 +4,17 @@
 //   loss = sum_n sum_c w_c sum_v p[n, c, v] phi[n, c, v] / (N S sum_c w_c)
 //   dp[n, c, v] = dloss (w_c / (N S sum_c w_c)) phi[n, c, v]
 //
-// Forward: a partial-sum kernel over chunks of one (n, c) row and a one-block finalize kernel, as in
-// focal_tversky_loss.hip.  Every product and every sum is fp64: an fp32 x fp32 product is exact there (48 bits), so the
+// Forward: a partial-sum kernel over chunks of one (n, c) row and a one-block finalize kernel (the shared pieces:
+// loss_common.hpp).  Every product and every sum is fp64: an fp32 x fp32 product is exact there (48 bits), so the
 // only rounding that matters is the one to the fp32 result.  phi takes both signs and the sum cancels; fp32 partial sums
 // would lose what the loss is about.  Lanes, waves, chunks and rows are added in a fixed order, no float atomics: a call
 // repeats bit for bit.  Rows with w_c == 0 are not read.
 // Backward: one pass; the row's coefficient is formed in fp64 and rounded once, the product once more.
-#include "common.hpp"
+#include "loss_common.hpp"
 
-namespace {
-
-using namespace m355;
+namespace m355 {
 
 constexpr int BL_CHUNK = 8192;   // elements of a row per block of the partial-sum kernel (32 per thread)
-
-// 4 consecutive floats of a row, the first `nv` of them inside it; one 16-byte access where the address allows it
-__device__ __forceinline__ void bl_load(const float* __restrict__ p, int nv, float (&v)[4]) {
-  if (nv >= 4 && ((uintptr_t)p & 15) == 0) {
-    const float4 r = *reinterpret_cast<const float4*>(p);
-    v[0] = r.x; v[1] = r.y; v[2] = r.z; v[3] = r.w;
-  } else {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) v[j] = j < nv ? p[j] : 0.f;
-  }
-}
-
-__device__ __forceinline__ void bl_store(float* __restrict__ p, int nv, const float (&v)[4]) {
-  if (nv >= 4 && ((uintptr_t)p & 15) == 0) {
-    *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
-  } else {
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-      if (j < nv) p[j] = v[j];
-  }
-}
-
-__device__ __forceinline__ int bl_valid(int64_t v0, int64_t end) {
-  const int64_t left = end - v0;
-  return left <= 0 ? 0 : left >= 4 ? 4 : (int)left;
-}
 
 // sum_c w_c in fp64, in channel order
 __device__ __forceinline__ double bl_weight_sum(const float* __restrict__ w, int C) {
@@ -66,15 +38,15 @@ __global__ __launch_bounds__(256) void bl_partial_kernel(const float* __restrict
   double acc = 0.0;
 #pragma unroll 4
   for (int64_t v0 = begin + threadIdx.x * 4; v0 < end; v0 += 1024) {
-    const int nv = bl_valid(v0, end);
+    const int nv = row_valid(v0, end, 4);
     float a[4], f[4];
-    bl_load(pp + v0, nv, a);
-    bl_load(fp + v0, nv, f);
+    row_load<4>(pp + v0, nv, a);
+    row_load<4>(fp + v0, nv, f);
 #pragma unroll
     for (int j = 0; j < 4; ++j) acc = fma((double)a[j], (double)f[j], acc);   // (elements past the row are 0 * 0)
   }
-  const double r = block_sum<double, 256>(acc, scratch);
-  if (threadIdx.x == 0) partial[nc * nblk + b] = r;
+  const double s[1] = {acc};
+  store_block_sums(s, partial, nc * nblk + b, scratch);
 }
 
 // single block.  Wave k takes the rows k, k + 4, ..: its lanes add the row's chunks l, l + 64, .. in fp64, then a butterfly.
@@ -104,34 +76,29 @@ __global__ __launch_bounds__(256) void bl_bwd_kernel(const float* __restrict__ p
   const float* fp = phi + nc * S;
   float* op = dp + nc * S;
   for (int64_t v0 = (blockIdx.x * 256ll + threadIdx.x) * 4; v0 < S; v0 += gridDim.x * 1024ll) {
-    const int nv = bl_valid(v0, S);
+    const int nv = row_valid(v0, S, 4);
     float f[4], o[4] = {0.f, 0.f, 0.f, 0.f};
     if (wc != 0.f) {                                 // (a row without weight gets zeros whatever dloss and phi hold)
-      bl_load(fp + v0, nv, f);
+      row_load<4>(fp + v0, nv, f);
 #pragma unroll
       for (int j = 0; j < 4; ++j) o[j] = __fmul_rn(k, f[j]);
     }
-    bl_store(op + v0, nv, o);
+    row_store<4>(op + v0, nv, o);
   }
 }
 
-int bl_check(const char* what, int32_t N, int32_t C, int64_t S) {
-  M355_REQUIRE(N > 0 && C > 0 && S > 0, M355_EINVALID_ARG, "%s: non-positive size", what);
-  M355_REQUIRE((int64_t)N * C <= 65535, M355_EUNSUPPORTED, "%s: N*C > 65535", what);
-  return M355_OK;
-}
+}  // namespace m355
 
-}  // namespace
+using namespace m355;
 
 extern "C" size_t m355_boundary_loss_workspace(int32_t N, int32_t C, int64_t S) {
-  if (N <= 0 || C <= 0 || S <= 0) return 0;
-  return (size_t)N * C * ceil_div(S, BL_CHUNK) * sizeof(double) + 256;
+  return loss_workspace_bytes(N, C, S, BL_CHUNK, 1);
 }
 
 extern "C" int m355_boundary_loss_fwd(const float* p, const float* phi, const float* class_weights, int32_t N, int32_t C,
                                       int64_t S, float* loss, void* workspace, size_t workspace_bytes, void* stream) {
   M355_REQUIRE(p && phi && loss && workspace, M355_EINVALID_ARG, "boundary_loss_fwd: null pointer");
-  if (int rc = bl_check("boundary_loss_fwd", N, C, S)) return rc;
+  if (int rc = loss_check("boundary_loss_fwd", N, C, S)) return rc;
   M355_REQUIRE(workspace_bytes >= m355_boundary_loss_workspace(N, C, S), M355_EWORKSPACE,
                "boundary_loss_fwd: workspace too small");
   hipStream_t st = (hipStream_t)stream;
@@ -147,8 +114,7 @@ extern "C" int m355_boundary_loss_fwd(const float* p, const float* phi, const fl
 extern "C" int m355_boundary_loss_bwd(const float* phi, const float* dloss, const float* class_weights, int32_t N, int32_t C,
                                       int64_t S, float* dp, void* stream) {
   M355_REQUIRE(phi && dloss && dp, M355_EINVALID_ARG, "boundary_loss_bwd: null pointer");
-  if (int rc = bl_check("boundary_loss_bwd", N, C, S)) return rc;
-  const dim3 grid((unsigned)std::max<int64_t>(1, std::min<int64_t>(ceil_div(S, 2048), 2048)), (unsigned)(N * C));
-  hipLaunchKernelGGL(bl_bwd_kernel, grid, dim3(256), 0, (hipStream_t)stream, phi, dloss, class_weights, dp, (int)N, (int)C, S);
+  if (int rc = loss_check("boundary_loss_bwd", N, C, S)) return rc;
+  hipLaunchKernelGGL(bl_bwd_kernel, loss_bwd_grid(S, 2048, N * C), dim3(256), 0, (hipStream_t)stream, phi, dloss, class_weights, dp, (int)N, (int)C, S);
   return check_launch("boundary_loss_bwd");
 }

@@ -2,8 +2,8 @@
 // weights for false positives and false negatives, raised to a power, plus a focal cross-entropy on the positive half.
 //
 //   PROB    x = p.  q = 1 - p, lp = log((p + eps) / (1 + eps)), eps = 1e-8 (1 + eps == 1.0f).  No expf is evaluated.
-//           Row-major like binary_loss.hip: a partial-sum kernel over chunks of one (n, c) row, a one-block finalize
-//           kernel, a one-pass closed-form backward.
+//           Row-major: a partial-sum kernel over chunks of one (n, c) row, a one-block finalize kernel, a one-pass
+//           closed-form backward (the shared pieces: loss_common.hpp).
 //   LOGITS  x = z, the log-softmax over the C channels of a voxel is taken here: m = max_c z_c, s = sum_c exp(z_c - m),
 //           lp_c = (z_c - m) - log s, p_c = exp(z_c - m) / s, q_c = -expm1(lp_c) (1 - p cancels near p = 1).  No eps.
 //           Voxel-major: a lane owns VPL consecutive voxels and walks the C channel planes, every plane read coalesced
@@ -13,11 +13,10 @@
 // sums[nc * 4 + k] = {TP = sum p t, FP = sum p (1 - t), FN = sum q t, sum t q^gamma lp}, each accumulated directly: the
 // class weights, alpha, beta and the power enter in the finalize step and in the backward only.
 //
-// Loads and stores: a lane's group of VPL consecutive elements goes as one 8- or 16-byte access where its address allows
-// it and the whole group is inside the row, and element by element otherwise.  Which lane adds which element does not
-// depend on the alignment (no peeled head), so a misaligned view gives the bits of its aligned clone.  fp32 per lane in
-// a fixed order, then fp64 across the block and across the chunks in a fixed order; no float atomics.
-#include "common.hpp"
+// Loads and stores: a lane's group of VPL consecutive elements goes through row_load / row_store, so a misaligned view
+// gives the bits of its aligned clone.  fp32 per lane in a fixed order, then fp64 across the block and across the chunks
+// in a fixed order; no float atomics.
+#include "loss_common.hpp"
 
 #include <cmath>
 
@@ -44,42 +43,6 @@ __device__ __forceinline__ void focal_pow_pair(float q, float gamma, int gi, flo
   qg = q * dq;
 }
 
-// V consecutive floats of a row, the first `nv` of them inside it
-template <int V>
-__device__ __forceinline__ void ft_load(const float* __restrict__ p, int nv, float (&v)[V]) {
-  static_assert(V == 2 || V == 4, "group of 2 or 4");
-  if (nv >= V && ((uintptr_t)p & (4 * V - 1)) == 0) {
-    if constexpr (V == 4) {
-      const float4 r = *reinterpret_cast<const float4*>(p);
-      v[0] = r.x; v[1] = r.y; v[2] = r.z; v[3] = r.w;
-    } else {
-      const float2 r = *reinterpret_cast<const float2*>(p);
-      v[0] = r.x; v[1] = r.y;
-    }
-  } else {
-#pragma unroll
-    for (int j = 0; j < V; ++j) v[j] = j < nv ? p[j] : 0.f;
-  }
-}
-
-template <int V>
-__device__ __forceinline__ void ft_store(float* __restrict__ p, int nv, const float (&v)[V]) {
-  static_assert(V == 2 || V == 4, "group of 2 or 4");
-  if (nv >= V && ((uintptr_t)p & (4 * V - 1)) == 0) {
-    if constexpr (V == 4) *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
-    else *reinterpret_cast<float2*>(p) = make_float2(v[0], v[1]);
-  } else {
-#pragma unroll
-    for (int j = 0; j < V; ++j)
-      if (j < nv) p[j] = v[j];
-  }
-}
-
-__device__ __forceinline__ int ft_valid(int64_t v0, int64_t end, int V) {
-  const int64_t left = end - v0;
-  return left <= 0 ? 0 : left >= V ? V : (int)left;
-}
-
 // one element's contribution to the four sums of its row
 template <int GM>
 __device__ __forceinline__ void ft_accumulate(float pv, float qv, float lp, float tv, float gamma, int gi, float& s0,
@@ -102,8 +65,6 @@ __global__ __launch_bounds__(256) void ft_prob_partial_kernel(const float* __res
   const float* xp = x + nc * S;
   const float* tp = t + nc * S;
   const int64_t begin = (int64_t)b * FT_PCHUNK, end = min(S, begin + FT_PCHUNK);
-  const float eps = 1e-8f;
-  const float denom = (float)(1.0 + 1e-8);
   float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
   // FT_U groups of x and of t are in flight per lane before the first is used; they are added in sequence order
   for (int64_t g0 = begin + threadIdx.x * 4; g0 < end; g0 += 256 * 4 * FT_U) {
@@ -112,9 +73,9 @@ __global__ __launch_bounds__(256) void ft_prob_partial_kernel(const float* __res
 #pragma unroll
     for (int u = 0; u < FT_U; ++u) {
       const int64_t v0 = g0 + 1024 * u;
-      nv[u] = ft_valid(v0, end, 4);
-      ft_load<4>(xp + v0, nv[u], xs[u]);
-      ft_load<4>(tp + v0, nv[u], ts[u]);
+      nv[u] = row_valid(v0, end, 4);
+      row_load<4>(xp + v0, nv[u], xs[u]);
+      row_load<4>(tp + v0, nv[u], ts[u]);
     }
 #pragma unroll
     for (int u = 0; u < FT_U; ++u) {
@@ -122,18 +83,12 @@ __global__ __launch_bounds__(256) void ft_prob_partial_kernel(const float* __res
       for (int j = 0; j < 4; ++j) {
         if (j >= nv[u]) break;
         const float pv = xs[u][j];
-        ft_accumulate<GM>(pv, 1.f - pv, logf((pv + eps) / denom), ts[u][j], gamma, gi, s0, s1, s2, s3);
+        ft_accumulate<GM>(pv, 1.f - pv, safe_log_prob(pv), ts[u][j], gamma, gi, s0, s1, s2, s3);
       }
     }
   }
-  const double t0 = block_sum<double, 256>((double)s0, scratch);
-  const double t1 = block_sum<double, 256>((double)s1, scratch);
-  const double t2 = block_sum<double, 256>((double)s2, scratch);
-  const double t3 = block_sum<double, 256>((double)s3, scratch);
-  if (threadIdx.x == 0) {
-    double* o = partial + (nc * nblk + b) * 4;
-    o[0] = t0; o[1] = t1; o[2] = t2; o[3] = t3;
-  }
+  const float s[4] = {s0, s1, s2, s3};
+  store_block_sums(s, partial, nc * nblk + b, scratch);
 }
 
 // -------------------------------------------------------------------------------------------------- LOGITS forward
@@ -154,11 +109,11 @@ __global__ __launch_bounds__(256) void ft_logits_partial_kernel(const float* __r
 #pragma unroll
     for (int k = 0; k < 4; ++k) acc[c][k] = 0.f;
   for (int64_t v0 = begin + threadIdx.x * VPL; v0 < end; v0 += 256 * VPL) {
-    const int nv = ft_valid(v0, end, VPL);
+    const int nv = row_valid(v0, end, VPL);
     float d[CR][VPL], e[CR][VPL], m[VPL], s[VPL];
 #pragma unroll
     for (int c = 0; c < CR; ++c)
-      if (c < C) ft_load<VPL>(zn + c * S + v0, nv, d[c]);
+      if (c < C) row_load<VPL>(zn + c * S + v0, nv, d[c]);
 #pragma unroll
     for (int j = 0; j < VPL; ++j) {
       m[j] = d[0][j];
@@ -187,7 +142,7 @@ __global__ __launch_bounds__(256) void ft_logits_partial_kernel(const float* __r
     for (int c = 0; c < CR; ++c)
       if (c < C) {
         float tt[VPL];
-        ft_load<VPL>(tn + c * S + v0, nv, tt);
+        row_load<VPL>(tn + c * S + v0, nv, tt);
 #pragma unroll
         for (int j = 0; j < VPL; ++j) {
           if (j >= nv) break;
@@ -232,17 +187,17 @@ __global__ __launch_bounds__(256) void ft_logits_partial_reread_kernel(const flo
 #pragma unroll
   for (int it = 0; it < FT_IT; ++it) {
     const int64_t v0 = begin + (it * 256 + threadIdx.x) * 4;
-    nv[it] = ft_valid(v0, end, 4);
+    nv[it] = row_valid(v0, end, 4);
     float v[4];
-    ft_load<4>(zn + v0, nv[it], m[it]);
+    row_load<4>(zn + v0, nv[it], m[it]);
     for (int c = 1; c < C; ++c) {
-      ft_load<4>(zn + c * S + v0, nv[it], v);
+      row_load<4>(zn + c * S + v0, nv[it], v);
 #pragma unroll
       for (int j = 0; j < 4; ++j) m[it][j] = fmaxf(m[it][j], v[j]);
     }
     float s[4] = {0.f, 0.f, 0.f, 0.f};
     for (int c = 0; c < C; ++c) {
-      ft_load<4>(zn + c * S + v0, nv[it], v);
+      row_load<4>(zn + c * S + v0, nv[it], v);
 #pragma unroll
       for (int j = 0; j < 4; ++j) s[j] += expf(v[j] - m[it][j]);
     }
@@ -258,8 +213,8 @@ __global__ __launch_bounds__(256) void ft_logits_partial_reread_kernel(const flo
     for (int it = 0; it < FT_IT; ++it) {
       const int64_t v0 = begin + (it * 256 + threadIdx.x) * 4;
       float zz[4], tt[4];
-      ft_load<4>(zn + c * S + v0, nv[it], zz);
-      ft_load<4>(tn + c * S + v0, nv[it], tt);
+      row_load<4>(zn + c * S + v0, nv[it], zz);
+      row_load<4>(tn + c * S + v0, nv[it], tt);
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         if (j >= nv[it]) break;
@@ -267,14 +222,8 @@ __global__ __launch_bounds__(256) void ft_logits_partial_reread_kernel(const flo
         ft_accumulate<GM>(expf(dd) * inv[it][j], -expm1f(lp), lp, tt[j], gamma, gi, s0, s1, s2, s3);
       }
     }
-    const double t0 = block_sum<double, 256>((double)s0, scratch);
-    const double t1 = block_sum<double, 256>((double)s1, scratch);
-    const double t2 = block_sum<double, 256>((double)s2, scratch);
-    const double t3 = block_sum<double, 256>((double)s3, scratch);
-    if (threadIdx.x == 0) {
-      double* o = partial + ((n * C + c) * nblk + b) * 4;
-      o[0] = t0; o[1] = t1; o[2] = t2; o[3] = t3;
-    }
+    const float s[4] = {s0, s1, s2, s3};
+    store_block_sums(s, partial, (n * C + c) * nblk + b, scratch);
   }
 }
 
@@ -318,12 +267,7 @@ __global__ __launch_bounds__(256) void ft_finalize_kernel(const double* __restri
   }
   const double tv = block_sum<double, 256>(tv_acc, scratch);
   const double fo = block_sum<double, 256>(fo_acc, scratch);
-  if (threadIdx.x == 0) {
-    const float tversky_loss = (float)(tv / NC), focal_loss = (float)(fo / NC);
-    out3[0] = (1.f - tversky_weight) * focal_loss + tversky_weight * tversky_loss;
-    out3[1] = tversky_loss;
-    out3[2] = focal_loss;
-  }
+  if (threadIdx.x == 0) write_out3(out3, tversky_weight, (float)(tv / NC), (float)(fo / NC));
 }
 
 // --------------------------------------------------------------------------------------------------------- backward
@@ -363,15 +307,14 @@ __global__ __launch_bounds__(256) void ft_prob_bwd_kernel(const float* __restric
   const FtCoef k = ft_coef(sums, nc, (int)(nc % C), focal_w, tversky_w, dloss[0], 1.f / (float)(N * C), 1.f / (float)S,
                            tversky_weight, alpha, beta, power);
   const float eps = 1e-8f;
-  const float denom = (float)(1.0 + 1e-8);
   const float* xp = x + nc * S;
   const float* tp = t + nc * S;
   float* op = dx + nc * S;
   for (int64_t v0 = (blockIdx.x * 256ll + threadIdx.x) * 4; v0 < S; v0 += gridDim.x * 1024ll) {
-    const int nv = ft_valid(v0, S, 4);
+    const int nv = row_valid(v0, S, 4);
     float xs[4], ts[4], o[4];
-    ft_load<4>(xp + v0, nv, xs);
-    ft_load<4>(tp + v0, nv, ts);
+    row_load<4>(xp + v0, nv, xs);
+    row_load<4>(tp + v0, nv, ts);
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       const float pv = xs[j], tv = ts[j];
@@ -381,11 +324,11 @@ __global__ __launch_bounds__(256) void ft_prob_bwd_kernel(const float* __restric
       } else {
         float qg, dq;
         focal_pow_pair<GM>(1.f - pv, gamma, gi, qg, dq);
-        f = qg / (pv + eps) - gamma * dq * logf((pv + eps) / denom);
+        f = qg / (pv + eps) - gamma * dq * safe_log_prob(pv);
       }
       o[j] = fmaf(k.kf * tv, f, fmaf(k.A, tv, k.B));
     }
-    ft_store<4>(op + v0, nv, o);
+    row_store<4>(op + v0, nv, o);
   }
 }
 
@@ -426,11 +369,11 @@ __global__ __launch_bounds__(256) void ft_logits_bwd_kernel(const float* __restr
   float* on = dz + n * C * S;
   const int64_t begin = (int64_t)blockIdx.x * FT_LCHUNK, end = min(S, begin + FT_LCHUNK);
   for (int64_t v0 = begin + threadIdx.x * VPL; v0 < end; v0 += 256 * VPL) {
-    const int nv = ft_valid(v0, end, VPL);
+    const int nv = row_valid(v0, end, VPL);
     float d[CR][VPL], a[CR][VPL], m[VPL], s[VPL], sum_a[VPL];
 #pragma unroll
     for (int c = 0; c < CR; ++c)
-      if (c < C) ft_load<VPL>(zn + c * S + v0, nv, d[c]);
+      if (c < C) row_load<VPL>(zn + c * S + v0, nv, d[c]);
 #pragma unroll
     for (int j = 0; j < VPL; ++j) {
       m[j] = d[0][j];
@@ -460,7 +403,7 @@ __global__ __launch_bounds__(256) void ft_logits_bwd_kernel(const float* __restr
     for (int c = 0; c < CR; ++c)
       if (c < C) {
         float tt[VPL];
-        ft_load<VPL>(tn + c * S + v0, nv, tt);
+        row_load<VPL>(tn + c * S + v0, nv, tt);
         const FtCoef k = coef[c];
 #pragma unroll
         for (int j = 0; j < VPL; ++j) {
@@ -476,7 +419,7 @@ __global__ __launch_bounds__(256) void ft_logits_bwd_kernel(const float* __restr
         float o[VPL];
 #pragma unroll
         for (int j = 0; j < VPL; ++j) o[j] = fmaf(-d[c][j], sum_a[j], a[c][j]);
-        ft_store<VPL>(on + c * S + v0, nv, o);
+        row_store<VPL>(on + c * S + v0, nv, o);
       }
   }
 }
@@ -501,17 +444,17 @@ __global__ __launch_bounds__(256) void ft_logits_bwd_reread_kernel(const float* 
 #pragma unroll
   for (int it = 0; it < FT_IT; ++it) {
     const int64_t v0 = begin + (it * 256 + threadIdx.x) * 4;
-    nv[it] = ft_valid(v0, end, 4);
+    nv[it] = row_valid(v0, end, 4);
     float v[4];
-    ft_load<4>(zn + v0, nv[it], m[it]);
+    row_load<4>(zn + v0, nv[it], m[it]);
     for (int c = 1; c < C; ++c) {
-      ft_load<4>(zn + c * S + v0, nv[it], v);
+      row_load<4>(zn + c * S + v0, nv[it], v);
 #pragma unroll
       for (int j = 0; j < 4; ++j) m[it][j] = fmaxf(m[it][j], v[j]);
     }
     float s[4] = {0.f, 0.f, 0.f, 0.f};
     for (int c = 0; c < C; ++c) {
-      ft_load<4>(zn + c * S + v0, nv[it], v);
+      row_load<4>(zn + c * S + v0, nv[it], v);
 #pragma unroll
       for (int j = 0; j < 4; ++j) s[j] += expf(v[j] - m[it][j]);
     }
@@ -529,8 +472,8 @@ __global__ __launch_bounds__(256) void ft_logits_bwd_reread_kernel(const float* 
       for (int it = 0; it < FT_IT; ++it) {
         const int64_t v0 = begin + (it * 256 + threadIdx.x) * 4;
         float zz[4], tt[4], o[4];
-        ft_load<4>(zn + c * S + v0, nv[it], zz);
-        ft_load<4>(tn + c * S + v0, nv[it], tt);
+        row_load<4>(zn + c * S + v0, nv[it], zz);
+        row_load<4>(tn + c * S + v0, nv[it], tt);
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
           const float dd = zz[j] - m[it][j];
@@ -539,7 +482,7 @@ __global__ __launch_bounds__(256) void ft_logits_bwd_reread_kernel(const float* 
           if (pass == 0) sum_a[it][j] += a;
           o[j] = fmaf(-p, sum_a[it][j], a);
         }
-        if (pass == 1) ft_store<4>(on + c * S + v0, nv[it], o);
+        if (pass == 1) row_store<4>(on + c * S + v0, nv[it], o);
       }
     }
 }
@@ -585,8 +528,7 @@ static FtBwdK ft_bwd_logits(int gm) {
 using namespace m355;
 
 extern "C" size_t m355_focal_tversky_workspace(int32_t N, int32_t C, int64_t S) {
-  if (N <= 0 || C <= 0 || S <= 0) return 0;
-  return (size_t)N * C * ceil_div(S, FT_LCHUNK) * 4 * sizeof(double) + 256;
+  return loss_workspace_bytes(N, C, S, FT_LCHUNK, 4);
 }
 
 extern "C" int m355_focal_tversky_fwd(const float* x, const float* t, int32_t N, int32_t C, int64_t S, float tversky_weight,
@@ -595,9 +537,9 @@ extern "C" int m355_focal_tversky_fwd(const float* x, const float* t, int32_t N,
                                       int32_t from_logits, float* out3, float* sums, void* workspace, size_t workspace_bytes,
                                       void* stream) {
   M355_REQUIRE(x && t && out3 && sums && workspace, M355_EINVALID_ARG, "focal_tversky_fwd: null pointer");
-  M355_REQUIRE(N > 0 && C > 0 && S > 0, M355_EINVALID_ARG, "focal_tversky_fwd: non-positive size");
+  // (the parameters before the sizes: both are M355_EINVALID_ARG, and the row count's M355_EUNSUPPORTED comes after them)
   if (int rc = ft_check_params("focal_tversky_fwd", alpha, beta, tversky_power, focal_gamma)) return rc;
-  M355_REQUIRE((int64_t)N * C <= 65535, M355_EUNSUPPORTED, "focal_tversky_fwd: N*C > 65535");
+  if (int rc = loss_check("focal_tversky_fwd", N, C, S)) return rc;
   M355_REQUIRE(workspace_bytes >= m355_focal_tversky_workspace(N, C, S), M355_EWORKSPACE,
                "focal_tversky_fwd: workspace too small");
   hipStream_t st = (hipStream_t)stream;
@@ -632,9 +574,9 @@ extern "C" int m355_focal_tversky_bwd(const float* x, const float* t, const floa
                                       float focal_gamma, const float* focal_class_weights, const float* tversky_class_weights,
                                       int32_t from_logits, float* dx, void* stream) {
   M355_REQUIRE(x && t && sums && dloss && dx, M355_EINVALID_ARG, "focal_tversky_bwd: null pointer");
-  M355_REQUIRE(N > 0 && C > 0 && S > 0, M355_EINVALID_ARG, "focal_tversky_bwd: non-positive size");
+  // (the parameters before the sizes: both are M355_EINVALID_ARG, and the row count's M355_EUNSUPPORTED comes after them)
   if (int rc = ft_check_params("focal_tversky_bwd", alpha, beta, tversky_power, focal_gamma)) return rc;
-  M355_REQUIRE((int64_t)N * C <= 65535, M355_EUNSUPPORTED, "focal_tversky_bwd: N*C > 65535");
+  if (int rc = loss_check("focal_tversky_bwd", N, C, S)) return rc;
   hipStream_t st = (hipStream_t)stream;
   int gi;
   const int gm = focal_mode(focal_gamma, gi);
@@ -645,7 +587,7 @@ extern "C" int m355_focal_tversky_bwd(const float* x, const float* t, const floa
     k = C <= 4 ? ft_bwd_logits<4, 4>(gm) : C <= 8 ? ft_bwd_logits<8, 4>(gm) : C <= FT_CREG ? ft_bwd_logits<16, 2>(gm)
         : gm == 0 ? ft_logits_bwd_reread_kernel<0> : gm == 1 ? ft_logits_bwd_reread_kernel<1> : ft_logits_bwd_reread_kernel<2>;
   } else {
-    grid = dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>(ceil_div(S, 2048), 2048)), (unsigned)(N * C));
+    grid = loss_bwd_grid(S, 2048, N * C);
     k = gm == 0 ? ft_prob_bwd_kernel<0> : gm == 1 ? ft_prob_bwd_kernel<1> : ft_prob_bwd_kernel<2>;
   }
   hipLaunchKernelGGL(k, grid, dim3(256), 0, st, x, t, sums, dloss, focal_class_weights, tversky_class_weights, dx, (int)N,

@@ -1,8 +1,8 @@
-// Hybrid logistic + Dice loss (fwd/bwd), sliding-window patch gather /
-// aggregation, and argmax + confusion counts.  All HBM-bound single-pass kernels.
+// Sliding-window patch gather / aggregation, argmax + confusion counts, and the device-side weighted patch sampler.
+// All HBM-bound single-pass kernels.  (The file's name is older than its contents: the hybrid loss it began with is in
+// hybrid_loss.hip.)
 //
 // Reference code replaced:
-//   HybridLogisticDiceLoss.forward  criterions/hybrid_logistic_dice_loss.py:13-43
 //   PatchPredict tiling/aggregation prediction.py:132-143 (torchio GridSampler /
 //     GridAggregator(overlap_mode='average'))
 //   CustomArgMax + SegmentationEvaluator counts
@@ -10,115 +10,6 @@
 #include "common.hpp"
 
 namespace m355 {
-
-constexpr int LOSS_CHUNK = 16384;
-
-// partial[((n*C + c)*nblk + b)*4 + k], k: 0 = sum p*t, 1 = sum p(^2), 2 = sum t(^2),
-// 3 = sum t*log(p_safe)
-__global__ __launch_bounds__(256) void loss_partial_kernel(const float* __restrict__ p,
-                                                           const float* __restrict__ t,
-                                                           double* __restrict__ partial, int64_t S,
-                                                           int square_dice, int nblk) {
-  __shared__ double scratch[4];
-  const int b = blockIdx.x;
-  const int64_t nc = blockIdx.y;
-  const float* pp = p + nc * S;
-  const float* tp = t + nc * S;
-  const int64_t begin = (int64_t)b * LOSS_CHUNK, end = min(S, begin + LOSS_CHUNK);
-  // reference: eps = 1e-8; prediction_safe = (prediction + eps) / (1 + eps), evaluated by
-  // torch in fp32 with the python scalars rounded to fp32 (1 + 1e-8 == 1.0f)
-  const float eps = 1e-8f;
-  const float denom = (float)(1.0 + 1e-8);
-  float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
-  for (int64_t i = begin + threadIdx.x; i < end; i += 256) {
-    const float pv = pp[i], tv = tp[i];
-    s0 = fmaf(pv, tv, s0);
-    if (square_dice) {
-      s1 = fmaf(pv, pv, s1);
-      s2 = fmaf(tv, tv, s2);
-    } else {
-      s1 += pv;
-      s2 += tv;
-    }
-    const float ps = (pv + eps) / denom;
-    s3 = fmaf(tv, logf(ps), s3);
-  }
-  const double t0 = block_sum<double, 256>((double)s0, scratch);
-  const double t1 = block_sum<double, 256>((double)s1, scratch);
-  const double t2 = block_sum<double, 256>((double)s2, scratch);
-  const double t3 = block_sum<double, 256>((double)s3, scratch);
-  if (threadIdx.x == 0) {
-    double* o = partial + (nc * nblk + b) * 4;
-    o[0] = t0; o[1] = t1; o[2] = t2; o[3] = t3;
-  }
-}
-
-// single block: sums[nc*4+k], out3 = {loss, dice_loss, logistic_loss}
-__global__ __launch_bounds__(256) void loss_finalize_kernel(const double* __restrict__ partial,
-                                                            const float* __restrict__ class_w,
-                                                            float* __restrict__ sums,
-                                                            float* __restrict__ out3, int N, int C,
-                                                            int64_t S, int nblk, float dice_weight) {
-  __shared__ double scratch[4];
-  const int NC = N * C;
-  double dice_acc = 0.0, log_acc = 0.0;
-  for (int nc = threadIdx.x; nc < NC; nc += 256) {
-    double v[4] = {0, 0, 0, 0};
-    for (int b = 0; b < nblk; ++b)
-      for (int k = 0; k < 4; ++k) v[k] += partial[((int64_t)nc * nblk + b) * 4 + k];
-    for (int k = 0; k < 4; ++k) sums[nc * 4 + k] = (float)v[k];
-    // dice_coeffs = 2*overlap / (total + eps)   (fp32 in the reference)
-    const float overlap = (float)v[0], total = (float)v[1] + (float)v[2];
-    const float dice = 2.f * overlap / (total + 1e-8f);
-    dice_acc += (double)(1.f - dice);
-    float logistic = (float)(v[3] / (double)S);  // torch.mean over spatial dims
-    if (class_w) logistic *= class_w[nc % C];
-    log_acc += (double)(-logistic);
-  }
-  const double d = block_sum<double, 256>(dice_acc, scratch);
-  const double l = block_sum<double, 256>(log_acc, scratch);
-  if (threadIdx.x == 0) {
-    const float dice_loss = (float)(d / NC), logistic_loss = (float)(l / NC);
-    out3[0] = (1.f - dice_weight) * logistic_loss + dice_weight * dice_loss;
-    out3[1] = dice_loss;
-    out3[2] = logistic_loss;
-  }
-}
-
-// dp = dloss * [ (1-w) * d(logistic_loss)/dp + w * d(dice_loss)/dp ]
-//   d logistic_loss / dp = -cw[c] * t / ((p + eps) ) / (N*C*S)          (denominator 1+eps == 1)
-//   d dice_loss / dp     = -(1/(N*C)) * (2 t / (T+eps) - 2 O * dT/dp / (T+eps)^2)
-//                          dT/dp = 2p (square_dice) or 1
-__global__ __launch_bounds__(256) void loss_bwd_kernel(const float* __restrict__ p,
-                                                       const float* __restrict__ t,
-                                                       const float* __restrict__ sums,
-                                                       const float* __restrict__ dloss,
-                                                       const float* __restrict__ class_w,
-                                                       float* __restrict__ dp, int N, int C,
-                                                       int64_t S, float dice_weight,
-                                                       int square_dice) {
-  const int64_t nc = blockIdx.y;
-  const float g = dloss[0];
-  const float O = sums[nc * 4 + 0];
-  const float T = sums[nc * 4 + 1] + sums[nc * 4 + 2] + 1e-8f;
-  const float inv_nc = 1.f / (float)(N * C);
-  const float cw = class_w ? class_w[nc % C] : 1.f;
-  const float klog = -(1.f - dice_weight) * cw * inv_nc / (float)S * g;
-  const float kd1 = -dice_weight * inv_nc * 2.f / T * g;          // * t
-  const float kd2 = dice_weight * inv_nc * 2.f * O / (T * T) * g;  // * dT/dp
-  const float denom = (float)(1.0 + 1e-8);
-  const float* pp = p + nc * S;
-  const float* tp = t + nc * S;
-  float* op = dp + nc * S;
-  for (int64_t i = blockIdx.x * 256ll + threadIdx.x; i < S; i += gridDim.x * 256ll) {
-    const float pv = pp[i], tv = tp[i];
-    const float ps = (pv + 1e-8f) / denom;
-    float d = klog * tv / (ps * denom);
-    d = fmaf(kd1, tv, d);
-    d = fmaf(kd2, square_dice ? 2.f * pv : 1.f, d);
-    op[i] = d;
-  }
-}
 
 // ------------------------------------------------------------------ patches
 __global__ __launch_bounds__(256) void patch_gather_kernel(const float* __restrict__ vol,
@@ -528,43 +419,6 @@ __global__ __launch_bounds__(64) void sampler_draw_kernel(const float* __restric
 }  // namespace m355
 
 using namespace m355;
-
-extern "C" size_t m355_hybrid_loss_workspace(int32_t N, int32_t C, int64_t S) {
-  if (N <= 0 || C <= 0 || S <= 0) return 0;
-  return (size_t)N * C * ceil_div(S, LOSS_CHUNK) * 4 * sizeof(double) + 256;
-}
-
-extern "C" int m355_hybrid_loss_fwd(const float* p, const float* t, int32_t N, int32_t C, int64_t S,
-                                    float dice_weight, const float* class_weights,
-                                    int32_t square_dice, float* out3, float* sums, void* workspace,
-                                    size_t workspace_bytes, void* stream) {
-  M355_REQUIRE(p && t && out3 && sums && workspace, M355_EINVALID_ARG, "hybrid_loss_fwd: null pointer");
-  M355_REQUIRE(N > 0 && C > 0 && S > 0, M355_EINVALID_ARG, "hybrid_loss_fwd: non-positive size");
-  M355_REQUIRE((int64_t)N * C <= 65535, M355_EUNSUPPORTED, "hybrid_loss_fwd: N*C > 65535");
-  M355_REQUIRE(workspace_bytes >= m355_hybrid_loss_workspace(N, C, S), M355_EWORKSPACE,
-               "hybrid_loss_fwd: workspace too small");
-  hipStream_t st = (hipStream_t)stream;
-  const int nblk = (int)ceil_div(S, LOSS_CHUNK);
-  double* partial = (double*)workspace;
-  hipLaunchKernelGGL(loss_partial_kernel, dim3((unsigned)nblk, (unsigned)(N * C)), dim3(256), 0, st,
-                     p, t, partial, S, square_dice, nblk);
-  hipLaunchKernelGGL(loss_finalize_kernel, dim3(1), dim3(256), 0, st, partial, class_weights, sums,
-                     out3, N, C, S, nblk, dice_weight);
-  return check_launch("hybrid_loss_fwd");
-}
-
-extern "C" int m355_hybrid_loss_bwd(const float* p, const float* t, const float* sums,
-                                    const float* dloss, int32_t N, int32_t C, int64_t S,
-                                    float dice_weight, const float* class_weights,
-                                    int32_t square_dice, float* dp, void* stream) {
-  M355_REQUIRE(p && t && sums && dloss && dp, M355_EINVALID_ARG, "hybrid_loss_bwd: null pointer");
-  M355_REQUIRE(N > 0 && C > 0 && S > 0, M355_EINVALID_ARG, "hybrid_loss_bwd: non-positive size");
-  M355_REQUIRE((int64_t)N * C <= 65535, M355_EUNSUPPORTED, "hybrid_loss_bwd: N*C > 65535");
-  const unsigned bx = (unsigned)std::max<int64_t>(1, std::min<int64_t>(ceil_div(S, 1024), 2048));
-  hipLaunchKernelGGL(loss_bwd_kernel, dim3(bx, (unsigned)(N * C)), dim3(256), 0, (hipStream_t)stream,
-                     p, t, sums, dloss, class_weights, dp, N, C, S, dice_weight, square_dice);
-  return check_launch("hybrid_loss_bwd");
-}
 
 static int check_patch_args(int32_t P, int32_t C, int32_t V0, int32_t V1, int32_t V2, int32_t ps0,
                             int32_t ps1, int32_t ps2, const char* who) {

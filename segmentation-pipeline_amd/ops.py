@@ -2078,6 +2078,41 @@ def softmax_channels(x, inner=1, diag_bias=0.0):
 
 
 # ----------------------------------------------------------------------- loss
+# The four criteria share one shape (csrc/loss_common.hpp): a forward that leaves the scalars and the per-row sums on the
+# device, and a closed-form backward from the saved sums.
+def _loss_operands(named_tensors, named_weights):
+    """The checked operands of a criterion.  named_tensors: (name, tensor) of the prediction and of its companion (the
+    target, or phi); named_weights: (name, tensor or None) of the per-channel weights.
+    -> (prediction, companion, [weights], N, C, S), the tensors contiguous.
+    (the argument errors come before the device check: they are the same on a host without a GPU)"""
+    (_, x), (other_name, t) = named_tensors
+    for name, v in (*named_tensors, *named_weights):
+        if v is not None and v.dtype != torch.float32:
+            raise _lib.M355Error(f"{name}: expected torch.float32, got {v.dtype}")
+    if x.dim() < 2 or x.shape != t.shape:
+        raise _lib.M355Error(f"prediction {tuple(x.shape)} and {other_name} {tuple(t.shape)}: expected one shape [N, C, ...]")
+    N, Cc = x.shape[0], x.shape[1]
+    for name, w in named_weights:
+        if w is not None and (w.dim() != 1 or w.numel() != Cc):
+            raise _lib.M355Error(f"{name} of shape {tuple(w.shape)} for {Cc} channels")
+    weights = [w for _, w in named_weights]
+    _require(x, t, *weights)
+    return (x.contiguous(), t.contiguous(), [None if w is None else w.contiguous() for w in weights], N, Cc,
+            x.numel() // (N * Cc))
+
+
+def _three_scalars(out3):
+    """out3 [3] -> three independent 0-dim tensors for autograd's sake: not views of `out3` (a Function must not return
+    views of one base) and not clones either (three 4-byte device copies of ~10 us each per step) -- fresh tensor objects
+    over the same storage, as ops._alloc_out makes them for concat slots"""
+    st = out3.untyped_storage()
+    return tuple(torch.empty((), dtype=torch.float32, device=out3.device).set_(st, i, ()) for i in range(3))
+
+
+def _dloss32(dloss):
+    return dloss.contiguous().to(torch.float32)
+
+
 class _HybridLossFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, p, t, dice_weight, class_weights, square_dice):
@@ -2096,11 +2131,7 @@ class _HybridLossFn(torch.autograd.Function):
                                      _stream()), "hybrid_loss_fwd")
         ctx.args = (N, Cc, S, float(dice_weight), 1 if square_dice else 0)
         ctx.save_for_backward(p, t, sums, class_weights)
-        # three independent 0-dim tensors for autograd's sake: not views of `out3` (a Function must not return views of one
-        # base) and not clones either (three 4-byte device copies of ~10 us each per step) -- fresh tensor objects over the
-        # same storage, as ops._alloc_out makes them for concat slots
-        st = out3.untyped_storage()
-        loss, dice, logistic = (torch.empty((), dtype=torch.float32, device=p.device).set_(st, i, ()) for i in range(3))
+        loss, dice, logistic = _three_scalars(out3)
         ctx.mark_non_differentiable(dice, logistic)
         return loss, dice, logistic
 
@@ -2109,9 +2140,8 @@ class _HybridLossFn(torch.autograd.Function):
         L = _lib.lib()
         p, t, sums, cw = ctx.saved_tensors
         N, Cc, S, dwt, sq = ctx.args
-        dloss = dloss.contiguous().to(torch.float32)
         dp = torch.empty_like(p)
-        check(L.m355_hybrid_loss_bwd(_p(p), _p(t), _p(sums), _p(dloss), N, Cc, S, dwt, _p(cw), sq, _p(dp),
+        check(L.m355_hybrid_loss_bwd(_p(p), _p(t), _p(sums), _p(_dloss32(dloss)), N, Cc, S, dwt, _p(cw), sq, _p(dp),
                                      _stream()), "hybrid_loss_bwd")
         return dp, None, None, None, None
 
@@ -2126,31 +2156,17 @@ class _BinaryLossFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, t, dice_weight, class_weights, pos_weight, square_dice, from_logits):
         L = _lib.lib()
-        # (the argument errors come before the device check: they are the same on a host without a GPU)
-        for name, v in (("prediction", x), ("target", t), ("class_weights", class_weights), ("pos_weight", pos_weight)):
-            if v is not None and v.dtype != torch.float32:
-                raise _lib.M355Error(f"{name}: expected torch.float32, got {v.dtype}")
-        if x.dim() < 2 or x.shape != t.shape:
-            raise _lib.M355Error(f"prediction {tuple(x.shape)} and target {tuple(t.shape)}: expected one shape [N, C, ...]")
-        N, Cc = x.shape[0], x.shape[1]
-        for name, w in (("class_weights", class_weights), ("pos_weight", pos_weight)):
-            if w is not None and (w.dim() != 1 or w.numel() != Cc):
-                raise _lib.M355Error(f"{name} of shape {tuple(w.shape)} for {Cc} channels")
-        _require(x, t, class_weights, pos_weight)
-        x, t = x.contiguous(), t.contiguous()
-        class_weights = None if class_weights is None else class_weights.contiguous()
-        pos_weight = None if pos_weight is None else pos_weight.contiguous()
-        S = x.numel() // (N * Cc)
+        x, t, (cw, pw), N, Cc, S = _loss_operands(
+            (("prediction", x), ("target", t)), (("class_weights", class_weights), ("pos_weight", pos_weight)))
         out3 = torch.empty(3, dtype=torch.float32, device=x.device)
         sums = torch.empty(N * Cc * 5, dtype=torch.float32, device=x.device)
         ws = _workspace(L.m355_binary_loss_workspace(N, Cc, S), x.device)
         sq, fl = (1 if square_dice else 0), (1 if from_logits else 0)
-        check(L.m355_binary_loss_fwd(_p(x), _p(t), N, Cc, S, float(dice_weight), _p(class_weights), _p(pos_weight), sq, fl,
+        check(L.m355_binary_loss_fwd(_p(x), _p(t), N, Cc, S, float(dice_weight), _p(cw), _p(pw), sq, fl,
                                      _p(out3), _p(sums), _p(ws), ws.numel(), _stream()), "binary_loss_fwd")
         ctx.args = (N, Cc, S, float(dice_weight), sq, fl)
-        ctx.save_for_backward(x, t, sums, class_weights, pos_weight)
-        st = out3.untyped_storage()   # three tensors over one storage, as _HybridLossFn returns them
-        loss, dice, logistic = (torch.empty((), dtype=torch.float32, device=x.device).set_(st, i, ()) for i in range(3))
+        ctx.save_for_backward(x, t, sums, cw, pw)
+        loss, dice, logistic = _three_scalars(out3)
         ctx.mark_non_differentiable(dice, logistic)
         return loss, dice, logistic
 
@@ -2159,10 +2175,9 @@ class _BinaryLossFn(torch.autograd.Function):
         L = _lib.lib()
         x, t, sums, cw, pw = ctx.saved_tensors
         N, Cc, S, dwt, sq, fl = ctx.args
-        dloss = dloss.contiguous().to(torch.float32)
         dx = torch.empty_like(x)
-        check(L.m355_binary_loss_bwd(_p(x), _p(t), _p(sums), _p(dloss), N, Cc, S, dwt, _p(cw), _p(pw), sq, fl, _p(dx),
-                                     _stream()), "binary_loss_bwd")
+        check(L.m355_binary_loss_bwd(_p(x), _p(t), _p(sums), _p(_dloss32(dloss)), N, Cc, S, dwt, _p(cw), _p(pw), sq, fl,
+                                     _p(dx), _stream()), "binary_loss_bwd")
         return dx, None, None, None, None, None, None
 
 
@@ -2179,22 +2194,9 @@ class _FocalTverskyLossFn(torch.autograd.Function):
     def forward(ctx, x, t, tversky_weight, alpha, beta, tversky_power, focal_gamma, focal_class_weights,
                 tversky_class_weights, from_logits):
         L = _lib.lib()
-        # (the argument errors come before the device check, as in _BinaryLossFn)
-        for name, v in (("prediction", x), ("target", t), ("focal_class_weights", focal_class_weights),
-                        ("tversky_class_weights", tversky_class_weights)):
-            if v is not None and v.dtype != torch.float32:
-                raise _lib.M355Error(f"{name}: expected torch.float32, got {v.dtype}")
-        if x.dim() < 2 or x.shape != t.shape:
-            raise _lib.M355Error(f"prediction {tuple(x.shape)} and target {tuple(t.shape)}: expected one shape [N, C, ...]")
-        N, Cc = x.shape[0], x.shape[1]
-        for name, w in (("focal_class_weights", focal_class_weights), ("tversky_class_weights", tversky_class_weights)):
-            if w is not None and (w.dim() != 1 or w.numel() != Cc):
-                raise _lib.M355Error(f"{name} of shape {tuple(w.shape)} for {Cc} channels")
-        _require(x, t, focal_class_weights, tversky_class_weights)
-        x, t = x.contiguous(), t.contiguous()
-        fw = None if focal_class_weights is None else focal_class_weights.contiguous()
-        tw = None if tversky_class_weights is None else tversky_class_weights.contiguous()
-        S = x.numel() // (N * Cc)
+        x, t, (fw, tw), N, Cc, S = _loss_operands(
+            (("prediction", x), ("target", t)),
+            (("focal_class_weights", focal_class_weights), ("tversky_class_weights", tversky_class_weights)))
         out3 = torch.empty(3, dtype=torch.float32, device=x.device)
         sums = torch.empty(N * Cc * 4, dtype=torch.float32, device=x.device)
         ws = _workspace(L.m355_focal_tversky_workspace(N, Cc, S), x.device)
@@ -2204,8 +2206,7 @@ class _FocalTverskyLossFn(torch.autograd.Function):
                                        ws.numel(), _stream()), "focal_tversky_fwd")
         ctx.args = (N, Cc, S, par, fl)
         ctx.save_for_backward(x, t, sums, fw, tw)
-        st = out3.untyped_storage()   # three tensors over one storage, as _HybridLossFn returns them
-        loss, tversky, focal = (torch.empty((), dtype=torch.float32, device=x.device).set_(st, i, ()) for i in range(3))
+        loss, tversky, focal = _three_scalars(out3)
         ctx.mark_non_differentiable(tversky, focal)
         return loss, tversky, focal
 
@@ -2214,10 +2215,9 @@ class _FocalTverskyLossFn(torch.autograd.Function):
         L = _lib.lib()
         x, t, sums, fw, tw = ctx.saved_tensors
         N, Cc, S, par, fl = ctx.args
-        dloss = dloss.contiguous().to(torch.float32)
         dx = torch.empty_like(x)
-        check(L.m355_focal_tversky_bwd(_p(x), _p(t), _p(sums), _p(dloss), N, Cc, S, *par, _p(fw), _p(tw), fl, _p(dx),
-                                       _stream()), "focal_tversky_bwd")
+        check(L.m355_focal_tversky_bwd(_p(x), _p(t), _p(sums), _p(_dloss32(dloss)), N, Cc, S, *par, _p(fw), _p(tw), fl,
+                                       _p(dx), _stream()), "focal_tversky_bwd")
         return (dx,) + (None,) * 9
 
 
@@ -2234,19 +2234,7 @@ class _BoundaryLossFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, p, phi, class_weights):
         L = _lib.lib()
-        # (the argument errors come before the device check, as in _FocalTverskyLossFn)
-        for name, v in (("prediction", p), ("phi", phi), ("class_weights", class_weights)):
-            if v is not None and v.dtype != torch.float32:
-                raise _lib.M355Error(f"{name}: expected torch.float32, got {v.dtype}")
-        if p.dim() < 2 or p.shape != phi.shape:
-            raise _lib.M355Error(f"prediction {tuple(p.shape)} and phi {tuple(phi.shape)}: expected one shape [N, C, ...]")
-        N, Cc = p.shape[0], p.shape[1]
-        if class_weights is not None and (class_weights.dim() != 1 or class_weights.numel() != Cc):
-            raise _lib.M355Error(f"class_weights of shape {tuple(class_weights.shape)} for {Cc} channels")
-        _require(p, phi, class_weights)
-        p, phi = p.contiguous(), phi.contiguous()
-        cw = None if class_weights is None else class_weights.contiguous()
-        S = p.numel() // (N * Cc)
+        p, phi, (cw,), N, Cc, S = _loss_operands((("prediction", p), ("phi", phi)), (("class_weights", class_weights),))
         loss = torch.empty((), dtype=torch.float32, device=p.device)
         ws = _workspace(L.m355_boundary_loss_workspace(N, Cc, S), p.device)
         check(L.m355_boundary_loss_fwd(_p(p), _p(phi), _p(cw), N, Cc, S, _p(loss), _p(ws), ws.numel(), _stream()),
@@ -2260,9 +2248,8 @@ class _BoundaryLossFn(torch.autograd.Function):
         L = _lib.lib()
         phi, cw = ctx.saved_tensors
         N, Cc, S = ctx.args
-        dloss = dloss.contiguous().to(torch.float32)
         dp = torch.empty_like(phi)
-        check(L.m355_boundary_loss_bwd(_p(phi), _p(dloss), _p(cw), N, Cc, S, _p(dp), _stream()), "boundary_loss_bwd")
+        check(L.m355_boundary_loss_bwd(_p(phi), _p(_dloss32(dloss)), _p(cw), N, Cc, S, _p(dp), _stream()), "boundary_loss_bwd")
         return dp, None, None
 
 

@@ -1,20 +1,13 @@
 """HybridBinaryLogisticDiceLoss in torch: the expected values of the binary-loss tests.  The formulas run in
 the dtype of their inputs -- fp64 for the expected values, fp32 for the "torch fp32 on the CPU" figures the tests print --
 and the gradients come from autograd.  Also the raw C-ABI wrappers of the three entry points."""
-import ctypes as C
-
 import torch
 
+from loss_ref_common import _chk, _dev, _per_channel, _stream
 from raw_ops import _p
 from segmentation_pipeline_amd import _lib
 
 EPS = 1e-8
-
-
-def _per_channel(w, C_, like):
-    if w is None:
-        return torch.ones(C_, dtype=like.dtype)
-    return torch.as_tensor(w, dtype=like.dtype)
 
 
 def binary_loss(x, t, dice_weight=0.5, class_weights=None, pos_weight=None, square_dice=True, from_logits=False):
@@ -64,22 +57,12 @@ def torch32(x, t, dloss, **cfg):
 
 
 # ---------------------------------------------------------------------------------------------- raw entry points
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _chk(rc, what):
-    if rc != 0:
-        raise RuntimeError(f"{what} -> {rc} {_lib.lib().m355_last_error().decode()}")
-
-
 def raw_fwd(x, t, dice_weight=0.5, class_weights=None, pos_weight=None, square_dice=True, from_logits=False):
     """m355_binary_loss_fwd on device tensors (x, t: any views whose rows are dense) -> (out3, sums)"""
     L = _lib.lib()
     N, C_ = x.shape[:2]
     S = x.numel() // (N * C_)
-    cw = None if class_weights is None else torch.tensor(class_weights, dtype=torch.float32, device="cuda")
-    pw = None if pos_weight is None else torch.tensor(pos_weight, dtype=torch.float32, device="cuda")
+    cw, pw = _dev(class_weights), _dev(pos_weight)
     out3 = torch.empty(3, device="cuda")
     sums = torch.empty(N * C_ * 5, device="cuda")
     ws = torch.empty(max(int(L.m355_binary_loss_workspace(N, C_, S)), 16), dtype=torch.uint8, device="cuda")
@@ -93,8 +76,7 @@ def raw_bwd(x, t, sums, dloss, dice_weight=0.5, class_weights=None, pos_weight=N
     L = _lib.lib()
     N, C_ = x.shape[:2]
     S = x.numel() // (N * C_)
-    cw = None if class_weights is None else torch.tensor(class_weights, dtype=torch.float32, device="cuda")
-    pw = None if pos_weight is None else torch.tensor(pos_weight, dtype=torch.float32, device="cuda")
+    cw, pw = _dev(class_weights), _dev(pos_weight)
     g = torch.tensor([dloss], dtype=torch.float32, device="cuda")
     dx = torch.empty(x.shape, device="cuda") if out is None else out
     _chk(L.m355_binary_loss_bwd(_p(x), _p(t), _p(sums), _p(g), N, C_, S, dice_weight, _p(cw), _p(pw), int(square_dice),

@@ -2,21 +2,14 @@
 dtype of their inputs -- fp64 for the expected values, fp32 for the "torch fp32 on the CPU" figures the tests print -- and
 the gradients come from autograd; `closed_form_bwd` is the backward the kernels implement, written out.  Also the raw
 C-ABI wrappers of the three entry points."""
-import ctypes as C
-
 import torch
 
+from loss_ref_common import _chk, _dev, _per_channel, _stream
 from raw_ops import _p
 from segmentation_pipeline_amd import _lib
 
 EPS = 1e-8
 TINY = 1e-300
-
-
-def _per_channel(w, C_, like):
-    if w is None:
-        return torch.ones(C_, dtype=like.dtype)
-    return torch.as_tensor(w, dtype=like.dtype)
 
 
 def _pow(base, exponent):
@@ -101,19 +94,6 @@ def closed_form_bwd(x, t, dloss, tversky_weight=0.5, alpha=0.5, beta=0.5, tversk
 
 
 # ---------------------------------------------------------------------------------------------- raw entry points
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _chk(rc, what):
-    if rc != 0:
-        raise RuntimeError(f"{what} -> {rc} {_lib.lib().m355_last_error().decode()}")
-
-
-def _dev(w):
-    return None if w is None else torch.tensor(w, dtype=torch.float32, device="cuda")
-
-
 def raw_fwd(x, t, tversky_weight=0.5, alpha=0.5, beta=0.5, tversky_power=1.0, focal_gamma=0.0, focal_class_weights=None,
             tversky_class_weights=None, from_logits=False):
     """m355_focal_tversky_fwd on device tensors (x, t: any views whose rows are dense) -> (out3, sums)"""

@@ -228,16 +228,16 @@ def test_pickled_state_holds_no_device_tensor(monkeypatch):
     crit = BoundaryLoss(HybridLogisticDiceLoss(logistic_class_weights=[1, 2]), 0.25, 0.75, [0, 3], (1.0, 1.0, 2.5))
     x = torch.zeros(1, 2, 2, 2, 2)
     crit(x, x)
-    assert crit._uploaded is not None
+    assert set(crit._uploaded) == {"boundary_class_weights"}
     state = crit.__getstate__()
-    assert state["_uploaded"] is None
+    assert state["_uploaded"] == {}
     assert all(v.device.type == "cpu" for v in state["_buffers"].values())
     assert not any(torch.is_tensor(v) for k, v in state.items() if not k.startswith("_"))
     back = pickle.loads(pickle.dumps(crit))
-    assert back._uploaded is None and back.boundary_class_weights == (0.0, 3.0) and back.spacing == (1.0, 1.0, 2.5)
+    assert back._uploaded == {} and back.boundary_class_weights == (0.0, 3.0) and back.spacing == (1.0, 1.0, 2.5)
     assert (back.boundary_weight.item(), back.regional_weight.item()) == (0.25, 0.75)
-    assert back.criterion.logistic_class_weights == [1, 2] and back.criterion._weights is None
-    assert crit._uploaded is not None        # pickling leaves the live object alone
+    assert back.criterion.logistic_class_weights == [1, 2] and back.criterion._uploaded == {}
+    assert set(crit._uploaded) == {"boundary_class_weights"}        # pickling leaves the live object alone
 
 
 # ----------------------------------------------------------------------------------- the reference against scipy

@@ -215,7 +215,7 @@ def test_loss_pickles_without_device_tensors(torch_pyramid):
     back = pickle.loads(pickle.dumps(crit))
     assert back.weights == [0.5, 0.5] and back.target_mode == "nearest"
     assert back.criterion.dice_weight == 0.3 and back.criterion.logistic_class_weights == [1, 2, 3]
-    assert back.criterion._weights is None
+    assert back.criterion._uploaded == {}
 
     def tensors(o, depth=0):
         if torch.is_tensor(o):
