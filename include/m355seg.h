@@ -794,6 +794,45 @@ int m355_focal_tversky_bwd(const float* x, const float* t, const float* sums, co
                            float tversky_power, float focal_gamma, const float* focal_class_weights,
                            const float* tversky_class_weights, int32_t from_logits, float* dx, void* stream);
 
+/* ------------------------------------------------ top-k cross-entropy + Dice loss
+ * HybridTopKDiceLoss (criterions/hybrid_topk_dice_loss.py): the Dice term of m355_hybrid_loss_fwd plus a
+ * cross-entropy averaged over the k largest per-voxel values of the whole batch only (online hard-example mining).  x and
+ * the target t: dense fp32 [N, C, S], rows at nc * S for any S (no alignment requirement).  eps = 1e-8, M = N * S.
+ *   from_logits == 0   x = p (probabilities): lp = log((p + eps) / (1 + eps))
+ *   from_logits != 0   x = z (logits), the log-softmax over the C channels of a voxel is taken here as in
+ *                      m355_focal_tversky_fwd; p = exp(lp) is formed in registers; no eps
+ *   e[n, s] = -sum_c w[c] t[n,c,s] lp[n,c,s]   (w = class_weights or 1, any sign)
+ *   tau = the k-th largest of the M values of e (a three-pass 11 / 11 / 10-bit radix select on keys that order like the
+ *         floats; every NaN orders above +inf, -0 is +0), n_gt = #{e > tau}, n_eq = #{e == tau}
+ *   logistic_loss = (sum_{e > tau} e + (k - n_gt) tau) / (C k): ties at tau share what is left of k, none is drawn
+ *   dice_loss: m355_hybrid_loss_fwd's, on p, with its square_dice
+ *   out3 = {loss, dice_loss, logistic_loss} = {(1 - dice_weight) logistic_loss + dice_weight dice_loss, ..}
+ * With k = M the log term is m355_hybrid_loss_fwd's (from_logits == 0) or m355_focal_tversky_fwd's at gamma 0.
+ * k: the count itself, 1 <= k <= M -- or, with k_device != NULL, a device int64 scalar read by the kernels (clamped to
+ * [1, M] there; `k` is ignored), so a captured launch follows a schedule of k.
+ * Kept for backward: sums [N*C*3] = the Dice sums {sum p t, sum p(^2), sum t(^2)}; e [N*S]; state [4 words] = {tau, r =
+ * (k - n_gt) / n_eq as fp32, k as int64}.
+ * Deterministic (integer atomics on the histograms only; fp32 per lane, then fp64 block and cross-chunk sums in a fixed
+ * order); a misaligned view gives the bits of its aligned copy.  Errors: null pointer, non-positive size, k outside
+ * [1, M] M355_EINVALID_ARG; N*C > 65535 or M > 2^32 - 1 M355_EUNSUPPORTED; workspace M355_EWORKSPACE; nothing is
+ * launched then.  m355_topk_loss_workspace is 0 for a non-positive size.
+ */
+size_t m355_topk_loss_workspace(int32_t N, int32_t C, int64_t S);
+int m355_topk_loss_fwd(const float* x, const float* t, int32_t N, int32_t C, int64_t S, int64_t k,
+                       const int64_t* k_device /* device scalar or NULL */, float dice_weight,
+                       const float* class_weights /* [C] or NULL */, int32_t square_dice, int32_t from_logits,
+                       float* out3, float* sums /* [N*C*3] */, float* e /* [N*S] */, void* state /* 16 bytes */,
+                       void* workspace, size_t workspace_bytes, void* stream);
+/* dx = dloss * d(loss)/dx in one pass from x, t, the saved e, sums and state.  A voxel's selection weight sel is 1 where
+ * e > tau, r where e == tau, 0 otherwise (sum sel == k); kl = dloss (1 - dice_weight) sel / (C k); h = the Dice gradient
+ * with respect to p.
+ *   from_logits == 0   dx_c = h_c - kl w_c t_c / (x_c + eps)
+ *   from_logits != 0   dz_c = p_c (h_c - sum_j p_j h_j + kl sum_j w_j t_j) - kl w_c t_c
+ * Up to 16 channels the per-voxel values stay in registers; above that the planes are read again.  Writes dx[0, N*C*S). */
+int m355_topk_loss_bwd(const float* x, const float* t, const float* e, const float* sums, const void* state,
+                       const float* dloss /* device scalar */, int32_t N, int32_t C, int64_t S, float dice_weight,
+                       const float* class_weights, int32_t square_dice, int32_t from_logits, float* dx, void* stream);
+
 /* ------------------------------------------------ target pyramid (deep supervision)
  * The targets of the auxiliary heads of models.DeepSupervisionUNet (criterions.DeepSupervisionLoss): one
  * launch reads a dense fp32 target y[N, C, D, H, W] once and writes its `levels` coarser levels, level j (1 <= j <= levels)

@@ -289,6 +289,9 @@ SIGNATURES = {
     "m355_focal_tversky_workspace": (_sz, [_i32, _i32, _i64]),
     "m355_focal_tversky_fwd": (C.c_int, [_P, _P, _i32, _i32, _i64, _f32, _f32, _f32, _f32, _f32, _P, _P, _i32, _P, _P, _P, _sz, _P]),
     "m355_focal_tversky_bwd": (C.c_int, [_P, _P, _P, _P, _i32, _i32, _i64, _f32, _f32, _f32, _f32, _f32, _P, _P, _i32, _P, _P]),
+    "m355_topk_loss_workspace": (_sz, [_i32, _i32, _i64]),
+    "m355_topk_loss_fwd": (C.c_int, [_P, _P, _i32, _i32, _i64, _i64, _P, _f32, _P, _i32, _i32, _P, _P, _P, _P, _P, _sz, _P]),
+    "m355_topk_loss_bwd": (C.c_int, [_P, _P, _P, _P, _P, _P, _i32, _i32, _i64, _f32, _P, _i32, _i32, _P, _P]),
     "m355_target_pyramid_elems": (_i64, [_i32, _i32, _i32, _i32, _i32, _i32]),
     "m355_target_pyramid": (C.c_int, [_P, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _P, _P]),
     "m355_copy_channels": (C.c_int, [_P, _P, _i32, _i32, _i64, _i64, _i64, _P]),

@@ -5,6 +5,7 @@ stream, and the autograd graph.  Every tensor op on the hot path is a call
 through the C ABI of libm355seg.so; nothing falls back to torch or to the CPU.
 """
 import ctypes as C
+import math
 import os
 import weakref
 from dataclasses import dataclass
@@ -2228,6 +2229,68 @@ def focal_tversky_loss(x, target, tversky_weight=0.5, alpha=0.5, beta=0.5, tvers
     [0, 1].  The class weights: fp32 device tensors [C] or None.  The gradient flows through `loss`."""
     return _FocalTverskyLossFn.apply(x, target, tversky_weight, alpha, beta, tversky_power, focal_gamma,
                                      focal_class_weights, tversky_class_weights, from_logits)
+
+
+def topk_count(N, S, top_k):
+    """k = max(1, floor(N * S * top_k)) for a fraction 0 < top_k <= 1 of the N * S voxels of a batch: the one place the
+    floor is taken (the criterion's schedule and the tests' reference call it too)"""
+    top_k = float(top_k)
+    if not (math.isfinite(top_k) and 0.0 < top_k <= 1.0):
+        raise ValueError(f"top_k = {top_k}: expected a fraction in (0, 1]")
+    M = int(N) * int(S)
+    if M < 1:
+        raise ValueError(f"N * S = {M}: expected at least one voxel")
+    return max(1, min(M, math.floor(M * top_k)))
+
+
+class _TopKLossFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, t, top_k, dice_weight, class_weights, square_dice, from_logits):
+        L = _lib.lib()
+        x, t, (cw,), N, Cc, S = _loss_operands((("prediction", x), ("target", t)), (("class_weights", class_weights),))
+        if torch.is_tensor(top_k):
+            # k itself on the device: read by the kernels, never here
+            if top_k.dim() != 0 or top_k.dtype != torch.int64:
+                raise _lib.M355Error(f"top_k: expected a fraction or a 0-dim torch.int64 tensor holding k, got "
+                                     f"{tuple(top_k.shape)} {top_k.dtype}")
+            _require(top_k, dtype=torch.int64)
+            k, k_dev = 0, top_k
+        else:
+            k, k_dev = topk_count(N, S, top_k), None
+        out3 = torch.empty(3, dtype=torch.float32, device=x.device)
+        sums = torch.empty(N * Cc * 3, dtype=torch.float32, device=x.device)
+        e = torch.empty(N * S, dtype=torch.float32, device=x.device)     # saved: not the workspace, which the next op reuses
+        state = torch.empty(4, dtype=torch.float32, device=x.device)    # {tau, r, k as int64}
+        ws = _workspace(L.m355_topk_loss_workspace(N, Cc, S), x.device)
+        sq, fl = (1 if square_dice else 0), (1 if from_logits else 0)
+        check(L.m355_topk_loss_fwd(_p(x), _p(t), N, Cc, S, k, _p(k_dev), float(dice_weight), _p(cw), sq, fl, _p(out3),
+                                   _p(sums), _p(e), _p(state), _p(ws), ws.numel(), _stream()), "topk_loss_fwd")
+        ctx.args = (N, Cc, S, float(dice_weight), sq, fl)
+        ctx.save_for_backward(x, t, e, sums, state, cw)
+        loss, dice, logistic = _three_scalars(out3)
+        threshold = torch.empty((), dtype=torch.float32, device=x.device).set_(state.untyped_storage(), 0, ())
+        ctx.mark_non_differentiable(dice, logistic, threshold)
+        return loss, dice, logistic, threshold
+
+    @staticmethod
+    def backward(ctx, dloss, _d1, _d2, _d3):
+        L = _lib.lib()
+        x, t, e, sums, state, cw = ctx.saved_tensors
+        N, Cc, S, dwt, sq, fl = ctx.args
+        dx = torch.empty_like(x)
+        check(L.m355_topk_loss_bwd(_p(x), _p(t), _p(e), _p(sums), _p(state), _p(_dloss32(dloss)), N, Cc, S, dwt, _p(cw),
+                                   sq, fl, _p(dx), _stream()), "topk_loss_bwd")
+        return (dx,) + (None,) * 6
+
+
+def topk_logistic_dice_loss(x, target, top_k, dice_weight=0.5, class_weights=None, square_dice=True, from_logits=False):
+    """HybridTopKDiceLoss.forward -> (loss, dice_loss, logistic_loss, threshold) of `x` [N, C, ...] fp32 -- probabilities,
+    or with from_logits the logits of an nn.Identity head -- against `target` in [0, 1]: the Dice term of
+    hybrid_logistic_dice_loss plus the cross-entropy averaged over the k hardest voxels of the whole batch.
+    top_k: the fraction of the voxels in (0, 1] (k = topk_count(N, S, top_k)), or a 0-dim int64 device tensor holding k
+    itself, which the kernels read -- a captured step follows it.  threshold: the k-th largest per-voxel cross-entropy.
+    class_weights: an fp32 device tensor [C] or None.  The gradient flows through `loss`."""
+    return _TopKLossFn.apply(x, target, top_k, dice_weight, class_weights, square_dice, from_logits)
 
 
 class _BoundaryLossFn(torch.autograd.Function):
