@@ -9,6 +9,7 @@ import math
 import os
 import weakref
 from dataclasses import dataclass
+from operator import itemgetter
 from typing import List, NamedTuple, Optional, Sequence
 
 import numpy as np
@@ -1046,35 +1047,6 @@ def _norm_act_c8_train(x: Act16, gamma, beta, add, cfg: "NormCfg", pool=False):
     return Act16(o.data, o.C, o.spatial, o.compute, o.cb0, res)
 
 
-class _PoolC8Fn(torch.autograd.Function):
-    """nn.AvgPool3d(2, 2) c8 -> c8; skip=True: also returns the input as it continues into the skip connection, so that
-    the backward receives both gradients and sums them in the pool-backward pass"""
-
-    @staticmethod
-    def forward(ctx, x_t, x: Act16, out16: Optional[Act16], skip: bool):
-        N, Cc, D, H, W = x.shape
-        y16 = out16 if out16 is not None else Act16.empty(N, Cc, (D // 2, H // 2, W // 2), x.compute, x.device)
-        check(_lib.lib().m355_avgpool3d_2x_fwd_h16(x.ptr(), y16.ptr(), N, Cc, D, H, W, x.batch_stride(), y16.batch_stride(),
-                                                   x.compute, _stream()), "avgpool3d_2x_fwd_h16")
-        ctx.info = (N, Cc, D, H, W, x.compute)
-        return (x_t.view_as(x_t), y16.alias()) if skip else y16.alias()
-
-    @staticmethod
-    def backward(ctx, *grads):
-        N, Cc, D, H, W, compute = ctx.info
-        g_skip, g_pool = (grads if len(grads) == 2 else (None, grads[0]))
-        if g_pool is None:
-            return g_skip, None, None, None
-        g_pool, pbs = _c8t(g_pool)
-        sbs = 0
-        if g_skip is not None:
-            g_skip, sbs = _c8t(g_skip)
-        dx16 = _c8_grad(N, Cc, D * H * W, compute, g_pool.device)
-        check(_lib.lib().m355_avgpool3d_2x_bwd_h16(_p(g_pool), _p(g_skip), _p(dx16), N, Cc, D, H, W, pbs, sbs, 0, compute,
-                                                   _stream()), "avgpool3d_2x_bwd_h16")
-        return dx16, None, None, None
-
-
 def _convt_c8_fwd(x: Act16, weight, bias, y16: Act16):
     """The c8 -> c8 launch of nn.ConvTranspose3d(kernel_size=2, stride=2) into y16; returns the descriptor."""
     _require(weight, bias)
@@ -1733,309 +1705,289 @@ def norm_act(x, gamma, beta, cfg: NormCfg, add=None, pool=False):
     return y
 
 
-# ------------------------------------------------------------- pool / upsample
-class _AvgPoolFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, out):
-        L = _lib.lib()
-        _require(x)
-        x, xbs = _dense_channels(x)
-        N, Cc, D, H, W = x.shape
-        y = _alloc_out(out, (N, Cc, D // 2, H // 2, W // 2), x)
-        y, ybs = _dense_channels(y)
-        check(L.m355_avgpool3d_2x_fwd(_p(x), _p(y), N, Cc, D, H, W, xbs, ybs, _stream()), "avgpool3d_2x_fwd")
-        ctx.shape = (N, Cc, D, H, W)
-        return y
+# ------------------------------------------- factor-2 resampling: pool / upsample / space-to-depth
+# One row per op says in data what its entry points are called and take; the fp32 flow and the c8 flow have one autograd
+# function body each (_Resample2xFn, _Resample2xC8Fn), and _resample_launch is the one place that builds a call.  The C
+# side's counterpart is the row per entry point of csrc/resample_host.hpp.
+class _Resample2x(NamedTuple):
+    fwd: str                      # the entry points m355_<fwd> / m355_<bwd>, in the c8 flow m355_<fwd>_h16 / m355_<bwd>_h16;
+    bwd: str                      # space-to-depth and depth-to-space: each is the other's backward
+    chan: tuple                   # output shape from the input's (N, C, D, H, W): C * chan[0] // chan[1] channels ...
+    up: bool                      # ... at twice (True) or half the spatial size
+    nodes: tuple                  # autograd function of the fp32 flow, of its *_with_skip form, of the c8 flow
+    full_out: bool = False        # the entry points take the (N, C, D, H, W) of the output, not of the input: depth-to-space,
+    #                               whose full-resolution side (the one the s2d pair's entry points describe) is its output
+    route: bool = False           # the forward writes a route byte per output element for the backward to gather through:
+    #                               uint8 [N, C, D/2, H/2, W/2], in c8 [N, CB, S_out, 8]; null when nothing will run backward
+    add: Optional[str] = None     # not None: the backward takes the skip gradient as `add`, with a batch stride of its own (null
+    #                               without one); the suffix of the fp32 entry point that does (avg pool: one of its own)
+    pairs: bool = False           # the fp32 kernels move x pairs of the full-resolution side: _pairs_in / _pairs_out
+    overflow: bool = False        # the c8 function installs the fp16 overflow word, in which its backward's sums report their
+    #                               saturation, itself: the op is also used on its own (pack -> op -> backward).  The others (avg
+    #                               pool, align_corners=True trilinear, the s2d pair, which sums nothing) leave that to a
+    #                               neighbouring node of the model (_UnpackFn, the c8 conv)
 
-    @staticmethod
-    def backward(ctx, dy):
-        L = _lib.lib()
-        N, Cc, D, H, W = ctx.shape
-        dy, dybs = _dense_channels(dy)
-        dx = torch.empty(ctx.shape, dtype=dy.dtype, device=dy.device)
-        check(L.m355_avgpool3d_2x_bwd(_p(dy), _p(dx), N, Cc, D, H, W, dybs, 0, _stream()), "avgpool3d_2x_bwd")
-        return dx, None
+
+# entry point -> (picks its pointer arguments, in its order, out of (tensor 0, tensor 1, tensor 2, route); its number of batch
+# strides; its symbol): the argument orders of the family are written down once, in _lib's mirror of the C table
+_RESAMPLE_ARGS = {name: (itemgetter(*order), nstrides, "m355_" + name)
+                  for name, order, nstrides, _ in _lib.RESAMPLE_OPS + list(_lib.UPSAMPLE2X_OPS.values())}
 
 
-class _PoolSkipFn(torch.autograd.Function):
-    """AvgPool3d(2, 2) of a tensor that ALSO continues as a skip connection (models/modular_unet.py:90-92).
-    Returns (skip alias, pooled); the backward receives both gradients together and sums them in the pool-backward
-    pass (m355_avgpool3d_2x_bwd_add) -- autograd would otherwise add them with a separate torch kernel."""
-
-    @staticmethod
-    def forward(ctx, x):
-        L = _lib.lib()
-        _require(x)
-        xd, xbs = _dense_channels(x)
-        N, Cc, D, H, W = xd.shape
-        y = torch.empty((N, Cc, D // 2, H // 2, W // 2), dtype=x.dtype, device=x.device)
-        check(L.m355_avgpool3d_2x_fwd(_p(xd), _p(y), N, Cc, D, H, W, xbs, 0, _stream()), "avgpool3d_2x_fwd")
-        ctx.shape = (N, Cc, D, H, W)
-        return x.view_as(x), y
-
-    @staticmethod
-    def backward(ctx, g_skip, g_pool):
-        L = _lib.lib()
-        N, Cc, D, H, W = ctx.shape
-        if g_pool is None:
-            return g_skip
-        g_pool, gpbs = _dense_channels(g_pool)
-        dx = torch.empty(ctx.shape, dtype=g_pool.dtype, device=g_pool.device)
-        if g_skip is None:
-            check(L.m355_avgpool3d_2x_bwd(_p(g_pool), _p(dx), N, Cc, D, H, W, gpbs, 0, _stream()), "avgpool3d_2x_bwd")
+def _resample_launch(row, bwd, c8, pointers, shape, strides, compute=0):
+    """Call the forward or backward entry point of `row`, c8: its _h16 form.  pointers: (tensor 0, tensor 1, tensor 2, route)
+    as c_void_p or None, the tensors in the order of their batch `strides`: (x, y) forward, (dy, dx) backward, (dy, add, dx)
+    where the backward takes an `add`.  shape: the (N, C, D, H, W) the entry point takes."""
+    name = row.bwd if bwd else row.fwd
+    if c8:
+        name += "_h16"
+    elif bwd and row.add:     # fp32 avg pool: the sum with `add` is an entry point of its own, the plain one has no such argument
+        if pointers[1] is None:
+            pointers, strides = (pointers[0], pointers[2]), (strides[0], strides[2])
         else:
-            g_skip, gsbs = _dense_channels(g_skip)
-            check(L.m355_avgpool3d_2x_bwd_add(_p(g_pool), _p(g_skip), _p(dx), N, Cc, D, H, W, gpbs, gsbs, 0, _stream()),
-                  "avgpool3d_2x_bwd_add")
-        return dx
+            name += row.add
+    pick, nstrides, symbol = _RESAMPLE_ARGS[name]
+    check(getattr(_lib.lib(), symbol)(*pick(pointers), *shape, *strides[:nstrides], *((compute,) if c8 else ()), _stream()),
+          name)
 
 
-def avgpool3d_2x_with_skip(x, out: Optional[OutSlot] = None):
-    """-> (x as it continues into the skip connection, AvgPool3d(2, 2)(x)); see _PoolSkipFn.  `out` (c8 flow): the pooled
-    tensor is written into this concat slot."""
-    if isinstance(x, Act16):
-        D, H, W = x.spatial
-        y16 = _c8_out_slot(x, out, (D // 2, H // 2, W // 2))
-        skip_t, pooled_t = _PoolC8Fn.apply(x.t, x, y16, True)
-        return x.with_t(skip_t), y16.with_t(pooled_t)
-    return _PoolSkipFn.apply(x)
-
-
-def avgpool3d_2x(x, out: Optional[OutSlot] = None):
-    """nn.AvgPool3d(kernel_size=2, stride=2, count_include_pad=False); c8 -> c8 in the 16-bit no-grad flow."""
-    if isinstance(x, Act16):
-        N, Cc, D, H, W = x.shape
-        y16 = out.act16() if out is not None else None
-        if y16 is None:
-            y16 = Act16.empty(N, Cc, (D // 2, H // 2, W // 2), x.compute, x.device)
-        if _act16_tracks(x):
-            return y16.with_t(_PoolC8Fn.apply(x.t, x, y16, False))
-        check(_lib.lib().m355_avgpool3d_2x_fwd_h16(x.ptr(), y16.ptr(), N, Cc, D, H, W, x.batch_stride(),
-                                                   y16.batch_stride(), x.compute, _stream()), "avgpool3d_2x_fwd_h16")
-        return y16
-    return _AvgPoolFn.apply(x, out)
-
-
-# nn.MaxPool3d(2, 2) (csrc/maxpool.hip): the forward leaves a route byte per pooled element (window position 0..7 of
-# torch's argmax, ties / NaN included), the backward is a gather through it.  The route tensor comes from the caching
-# allocator and lives on ctx; it is not allocated when nothing will run backward (no_grad, the c8 no-grad flow).
-def _maxpool_fwd(x, y, ybs, route):
-    xd, xbs = _dense_channels(x)
-    N, Cc, D, H, W = xd.shape
-    idx = torch.empty((N, Cc, D // 2, H // 2, W // 2), dtype=torch.uint8, device=x.device) if route else None
-    check(_lib.lib().m355_maxpool3d_2x_fwd(_p(xd), _p(y), _p(idx), N, Cc, D, H, W, xbs, ybs, _stream()), "maxpool3d_2x_fwd")
-    return idx
+def _out_shape(row, xshape):
+    N, Cc, D, H, W = xshape
+    Cc = Cc * row.chan[0] // row.chan[1]
+    return (N, Cc, 2 * D, 2 * H, 2 * W) if row.up else (N, Cc, D // 2, H // 2, W // 2)
 
 
 def _tracks(x):
     return torch.is_grad_enabled() and x.requires_grad
 
 
-def _maxpool_bwd(ctx, g_pool, g_skip):
-    N, Cc, D, H, W = ctx.shape
-    g_pool, gpbs = _dense_channels(g_pool)
-    gsbs = 0
-    if g_skip is not None:
-        g_skip, gsbs = _dense_channels(g_skip)
-    dx = torch.empty(ctx.shape, dtype=g_pool.dtype, device=g_pool.device)
-    check(_lib.lib().m355_maxpool3d_2x_bwd(_p(g_pool), _p(ctx.idx), _p(g_skip), _p(dx), N, Cc, D, H, W, gpbs, gsbs, 0,
-                                           _stream()), "maxpool3d_2x_bwd")
-    return dx
+class _Resample2xFn(torch.autograd.Function):
+    """The fp32 flow of the family: x -> y, a fresh tensor or the concat slot `out`.
+    with_skip: x ALSO continues as a skip connection (models/modular_unet.py:90-92).  Returns (skip alias, y), `out` is
+    ignored; the backward receives both gradients together and sums them in its one pass (`add`) -- autograd would
+    otherwise add them with a separate torch kernel.
+    route: autograd was recording at .apply and x carries a gradient (inside forward grad mode is always off, and
+    ctx.needs_input_grad stays True under no_grad for a tensor that requires grad).  The route tensor comes from the caching
+    allocator and lives on ctx; it is not allocated when nothing will run backward."""
 
-
-class _MaxPoolFn(torch.autograd.Function):
-    # route: autograd was recording at .apply and x carries a gradient (inside forward grad mode is always off, and
-    # ctx.needs_input_grad stays True under no_grad for a tensor that requires grad)
     @staticmethod
-    def forward(ctx, x, out, route):
+    def forward(ctx, x, row, out, with_skip, route):
         _require(x)
-        N, Cc, D, H, W = x.shape
-        y = _alloc_out(out, (N, Cc, D // 2, H // 2, W // 2), x)
+        xd, xbs = _dense_channels(x)
+        xshape = tuple(xd.shape)
+        oshape = _out_shape(row, xshape)
+        y = _alloc_out(None if with_skip else out, oshape, x)
         y, ybs = _dense_channels(y)
-        ctx.idx = _maxpool_fwd(x, y, ybs, route)
-        ctx.shape = (N, Cc, D, H, W)
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        return _maxpool_bwd(ctx, dy, None), None, None
-
-
-class _MaxPoolSkipFn(torch.autograd.Function):
-    """MaxPool3d(2, 2) of a tensor that ALSO continues as a skip connection: (skip alias, pooled), and one backward pass
-    for the sum of both gradients (m355_maxpool3d_2x_bwd with `add`), as _PoolSkipFn does for the average pool."""
-
-    @staticmethod
-    def forward(ctx, x, route):
-        _require(x)
-        N, Cc, D, H, W = x.shape
-        y = torch.empty((N, Cc, D // 2, H // 2, W // 2), dtype=x.dtype, device=x.device)
-        ctx.idx = _maxpool_fwd(x, y, 0, route)
-        ctx.shape = (N, Cc, D, H, W)
-        return x.view_as(x), y
-
-    @staticmethod
-    def backward(ctx, g_skip, g_pool):
-        if g_pool is None:
-            return g_skip, None
-        return _maxpool_bwd(ctx, g_pool, g_skip), None
-
-
-class _MaxPoolC8Fn(torch.autograd.Function):
-    """nn.MaxPool3d(2, 2) c8 -> c8 of the c8 training flow, modelled on _PoolC8Fn (skip=True: also returns the input as
-    it continues into the skip connection); the route is one byte per lane of the pooled items"""
-
-    @staticmethod
-    def forward(ctx, x_t, x: Act16, y16: Act16, skip: bool):
-        N, Cc, D, H, W = x.shape
-        idx8 = torch.empty((N, x.CB, y16.S, 8), dtype=torch.uint8, device=x.device)
-        check(_lib.lib().m355_maxpool3d_2x_fwd_h16(x.ptr(), y16.ptr(), _p(idx8), N, Cc, D, H, W, x.batch_stride(),
-                                                   y16.batch_stride(), x.compute, _stream()), "maxpool3d_2x_fwd_h16")
-        ctx.info = (N, Cc, D, H, W, x.compute)
-        ctx.idx8 = idx8
-        if x.compute == _lib.COMPUTE_F16:
-            # the backward's sum with the skip gradient reports its saturation in the overflow word.  _PoolC8Fn leaves
-            # installing it to a neighbouring node (_UnpackFn, the c8 conv); this op is also used on its own
-            # (pack -> pool -> backward), where no other node would
-            _overflow_word(x.device)
-        return (x_t.view_as(x_t), y16.alias()) if skip else y16.alias()
+        full = oshape if row.full_out else xshape
+        yw, ywbs = y, ybs
+        if row.pairs:     # (the FULL-resolution side must be 8-byte aligned with an even stride)
+            if row.full_out:
+                yw, ywbs = _pairs_out(y, ybs)
+            else:
+                xd, xbs = _pairs_in(xd, xbs)
+        idx = torch.empty(oshape, dtype=torch.uint8, device=x.device) if route else None
+        _resample_launch(row, False, False, (_p(xd), _p(yw), None, _p(idx)), full, (xbs, ywbs))
+        if yw is not y:
+            y.copy_(yw)
+        ctx.row, ctx.shape, ctx.full, ctx.route = row, xshape, full, idx
+        return (x.view_as(x), y) if with_skip else y
 
     @staticmethod
     def backward(ctx, *grads):
-        N, Cc, D, H, W, compute = ctx.info
-        g_skip, g_pool = (grads if len(grads) == 2 else (None, grads[0]))
-        if g_pool is None:
-            return g_skip, None, None, None
-        g_pool, pbs = _c8t(g_pool)
-        sbs = 0
-        if g_skip is not None:
-            g_skip, sbs = _c8t(g_skip)
-        dx16 = _c8_grad(N, Cc, D * H * W, compute, g_pool.device)
-        check(_lib.lib().m355_maxpool3d_2x_bwd_h16(_p(g_pool), _p(ctx.idx8), _p(g_skip), _p(dx16), N, Cc, D, H, W, pbs, sbs, 0,
-                                                   compute, _stream()), "maxpool3d_2x_bwd_h16")
-        return dx16, None, None, None
+        g_skip, g = grads if len(grads) == 2 else (None, grads[0])
+        if g is None:
+            return g_skip, None, None, None, None
+        row = ctx.row
+        g, gbs = _dense_channels(g)
+        dx = torch.empty(ctx.shape, dtype=g.dtype, device=g.device)
+        if row.add is None:
+            if row.pairs and row.full_out:    # the gradient is the full-resolution side
+                g, gbs = _pairs_in(g, gbs)
+            pointers, strides = (_p(g), _p(dx), None, None), (gbs, 0)
+        else:
+            sbs = 0
+            if g_skip is not None:
+                g_skip, sbs = _dense_channels(g_skip)
+            pointers, strides = (_p(g), _p(g_skip), _p(dx), _p(ctx.route)), (gbs, sbs, 0)
+        _resample_launch(row, True, False, pointers, ctx.full, strides)
+        return dx, None, None, None, None
+
+
+def _resample_c8_fwd(row, x: "Act16", y16: "Act16", route=None):
+    """the c8 -> c8 forward launch: of the no-grad flow as it is, and of _Resample2xC8Fn"""
+    _resample_launch(row, False, True, (x.ptr(), y16.ptr(), None, _p(route)), y16.shape if row.full_out else x.shape,
+                     (x.batch_stride(), y16.batch_stride()), x.compute)
+
+
+class _Resample2xC8Fn(torch.autograd.Function):
+    """The c8 training flow of the family: c8 -> c8 straight into `y16`, a fresh activation or a concat slot; the backward
+    runs the c8 kernel on the c8 gradient.  with_skip: also returns the input as it continues into the skip connection, so
+    that the backward receives both gradients and sums them in its one pass."""
+
+    @staticmethod
+    def forward(ctx, x_t, row, x: "Act16", y16: "Act16", with_skip):
+        route = torch.empty((x.shape[0], x.CB, y16.S, 8), dtype=torch.uint8, device=x.device) if row.route else None
+        _resample_c8_fwd(row, x, y16, route)
+        ctx.row, ctx.route = row, route
+        ctx.info = (x.shape, y16.shape if row.full_out else x.shape, x.compute)
+        if row.overflow and x.compute == _lib.COMPUTE_F16:
+            _overflow_word(x.device)
+        return (x_t.view_as(x_t), y16.alias()) if with_skip else y16.alias()
+
+    @staticmethod
+    def backward(ctx, *grads):
+        g_skip, g = grads if len(grads) == 2 else (None, grads[0])
+        if g is None:
+            return g_skip, None, None, None, None
+        row = ctx.row
+        (N, Cc, D, H, W), full, compute = ctx.info
+        g, gbs = _c8t(g)
+        dx16 = _c8_grad(N, Cc, D * H * W, compute, g.device)
+        if row.add is None:
+            pointers, strides = (_p(g), _p(dx16), None, None), (gbs, 0)
+        else:
+            sbs = 0
+            if g_skip is not None:
+                g_skip, sbs = _c8t(g_skip)
+            pointers, strides = (_p(g), _p(g_skip), _p(dx16), _p(ctx.route)), (gbs, sbs, 0)
+        _resample_launch(row, True, True, pointers, full, strides, compute)
+        return dx16, None, None, None, None
+
+
+# autograd names its nodes after the class: one name per op and flow, as the graphs of the models are read
+class _AvgPoolFn(_Resample2xFn):
+    """nn.AvgPool3d(2, 2)"""
+
+
+class _PoolSkipFn(_Resample2xFn):
+    """nn.AvgPool3d(2, 2) of a tensor that also continues as a skip connection"""
+
+
+class _PoolC8Fn(_Resample2xC8Fn):
+    """nn.AvgPool3d(2, 2) c8 -> c8, with or without the skip output"""
+
+
+class _MaxPoolFn(_Resample2xFn):
+    """nn.MaxPool3d(2, 2) (csrc/maxpool.hip): the route byte is the window position 0..7 of torch's argmax, ties / NaN
+    included; the backward is a gather through it"""
+
+
+class _MaxPoolSkipFn(_Resample2xFn):
+    """nn.MaxPool3d(2, 2) of a tensor that also continues as a skip connection"""
+
+
+class _MaxPoolC8Fn(_Resample2xC8Fn):
+    """nn.MaxPool3d(2, 2) c8 -> c8, with or without the skip output; the route is one byte per lane of the pooled items"""
+
+
+class _UpsampleFn(_Resample2xFn):
+    """nn.Upsample(scale_factor=2), all three conventions"""
+
+
+class _UpsampleC8Fn(_Resample2xC8Fn):
+    """nn.Upsample(scale_factor=2) c8 -> c8; backward: the gather-form kernel on the c8 gradient"""
+
+
+class _S2DFn(_Resample2xFn):
+    """space-to-depth or depth-to-space by 2"""
+
+
+class _S2DC8Fn(_Resample2xC8Fn):
+    """space-to-depth or depth-to-space by 2 on c8 activations"""
+
+
+_AVGPOOL = _Resample2x("avgpool3d_2x_fwd", "avgpool3d_2x_bwd", (1, 1), False, (_AvgPoolFn, _PoolSkipFn, _PoolC8Fn), add="_add")
+_MAXPOOL = _Resample2x("maxpool3d_2x_fwd", "maxpool3d_2x_bwd", (1, 1), False, (_MaxPoolFn, _MaxPoolSkipFn, _MaxPoolC8Fn),
+                       route=True, add="", overflow=True)
+# nn.Upsample(scale_factor=2) by `mode`: align_corners=True trilinear (csrc/elementwise.hip), nearest and half-pixel
+# (align_corners=False) trilinear (csrc/upsample.hip)
+_UPSAMPLE = {
+    mode: _Resample2x(stem + "_fwd", stem + "_bwd", (1, 1), True, (_UpsampleFn, None, _UpsampleC8Fn), overflow=overflow)
+    for mode, stem, overflow in (("trilinear", "upsample_trilinear2x", False), ("nearest", "upsample_nearest2x", True),
+                                 ("trilinear_hp", "upsample_trilinear2x_hp", True))}
+_S2D = _Resample2x("space_to_depth2", "depth_to_space2", (8, 1), False, (_S2DFn, None, _S2DC8Fn), pairs=True)
+_D2S = _Resample2x("depth_to_space2", "space_to_depth2", (1, 8), True, (_S2DFn, None, _S2DC8Fn), full_out=True, pairs=True)
+
+
+def _resample2x(row, x, out=None, with_skip=False):
+    """A public function of the family: pick the flow, obtain the output, then the autograd function -- or, for a c8
+    activation that does not track, the plain launch.  -> y, with_skip: (x as it continues into the skip connection, y)"""
+    if not isinstance(x, Act16):
+        return row.nodes[1 if with_skip else 0].apply(x, row, out, with_skip, row.route and _tracks(x))
+    tracks = _act16_tracks(x)
+    if with_skip and not tracks:
+        return x, _resample2x(row, x, out)
+    oshape = _out_shape(row, x.shape)
+    y16 = _c8_out_slot(x, out, oshape[2:], oshape[1])
+    if not tracks:
+        _resample_c8_fwd(row, x, y16)
+        return y16
+    res = row.nodes[2].apply(x.t, row, x, y16, with_skip)
+    return (x.with_t(res[0]), y16.with_t(res[1])) if with_skip else y16.with_t(res)
+
+
+def avgpool3d_2x_with_skip(x, out: Optional[OutSlot] = None):
+    """-> (x as it continues into the skip connection, AvgPool3d(2, 2)(x)); see _Resample2xFn.  `out` (c8 flow): the pooled
+    tensor is written into this concat slot."""
+    return _resample2x(_AVGPOOL, x, out, True)
+
+
+def avgpool3d_2x(x, out: Optional[OutSlot] = None):
+    """nn.AvgPool3d(kernel_size=2, stride=2, count_include_pad=False); c8 -> c8 in the 16-bit flows."""
+    return _resample2x(_AVGPOOL, x, out)
 
 
 def maxpool3d_2x_with_skip(x, out: Optional[OutSlot] = None):
-    """-> (x as it continues into the skip connection, MaxPool3d(2, 2)(x)); see _MaxPoolSkipFn.  `out` (c8 flow): the
+    """-> (x as it continues into the skip connection, MaxPool3d(2, 2)(x)); see _Resample2xFn.  `out` (c8 flow): the
     pooled tensor is written into this concat slot."""
-    if isinstance(x, Act16):
-        if not _act16_tracks(x):
-            return x, maxpool3d_2x(x, out)
-        D, H, W = x.spatial
-        y16 = _c8_out_slot(x, out, (D // 2, H // 2, W // 2))
-        skip_t, pooled_t = _MaxPoolC8Fn.apply(x.t, x, y16, True)
-        return x.with_t(skip_t), y16.with_t(pooled_t)
-    return _MaxPoolSkipFn.apply(x, _tracks(x))
+    return _resample2x(_MAXPOOL, x, out, True)
 
 
 def maxpool3d_2x(x, out: Optional[OutSlot] = None):
     """nn.MaxPool3d(kernel_size=2, stride=2), torch's tie / NaN routing; c8 -> c8 in the 16-bit flows."""
-    if isinstance(x, Act16):
-        N, Cc, D, H, W = x.shape
-        y16 = _c8_out_slot(x, out, (D // 2, H // 2, W // 2))
-        if _act16_tracks(x):
-            return y16.with_t(_MaxPoolC8Fn.apply(x.t, x, y16, False))
-        check(_lib.lib().m355_maxpool3d_2x_fwd_h16(x.ptr(), y16.ptr(), None, N, Cc, D, H, W, x.batch_stride(),
-                                                   y16.batch_stride(), x.compute, _stream()), "maxpool3d_2x_fwd_h16")
-        return y16
-    return _MaxPoolFn.apply(x, out, _tracks(x))
+    return _resample2x(_MAXPOOL, x, out)
 
 
-# nn.Upsample(scale_factor=2): the entry point family of each convention -- align_corners=True trilinear
-# (csrc/elementwise.hip), nearest and half-pixel (align_corners=False) trilinear (csrc/upsample.hip).  <family>_fwd / _bwd
-# are the fp32 pair, <family>_fwd_h16 / _bwd_h16 the c8 pair; all four take the same argument lists.
-_UPSAMPLE_FAMILY = {"trilinear": "upsample_trilinear2x", "nearest": "upsample_nearest2x", "trilinear_hp": "upsample_trilinear2x_hp"}
+def upsample_trilinear2x(x, out: Optional[OutSlot] = None, mode: str = "trilinear"):
+    """nn.Upsample(scale_factor=2, mode='trilinear', align_corners=True); c8 -> c8 in the 16-bit flows.
+    mode: 'trilinear' (this default), or 'nearest' / 'trilinear_hp' = upsample_nearest2x / upsample_trilinear2x_hp."""
+    if mode not in _UPSAMPLE:
+        raise ValueError(f"upsample mode {mode!r} not in {sorted(_UPSAMPLE)}")
+    return _resample2x(_UPSAMPLE[mode], x, out)
 
 
-def _upsample_call(family, suffix, *args):
-    name = family + suffix
-    check(getattr(_lib.lib(), "m355_" + name)(*args), name)
+def upsample_nearest2x(x, out: Optional[OutSlot] = None):
+    """nn.Upsample(scale_factor=2, mode='nearest') (= 'nearest-exact' at this factor): the forward copies bits, the
+    backward sums each 2x2x2 block; c8 -> c8 in the 16-bit flows."""
+    return _resample2x(_UPSAMPLE["nearest"], x, out)
 
 
-class _UpsampleFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, out, family="upsample_trilinear2x"):
-        _require(x)
-        x, xbs = _dense_channels(x)
-        N, Cc, D, H, W = x.shape
-        y = _alloc_out(out, (N, Cc, 2 * D, 2 * H, 2 * W), x)
-        y, ybs = _dense_channels(y)
-        _upsample_call(family, "_fwd", _p(x), _p(y), N, Cc, D, H, W, xbs, ybs, _stream())
-        ctx.shape = (N, Cc, D, H, W)
-        ctx.family = family
-        return y
+def upsample_trilinear2x_hp(x, out: Optional[OutSlot] = None):
+    """nn.Upsample(scale_factor=2, mode='trilinear', align_corners=False): the half-pixel convention (weights 0.25 / 0.75,
+    edges clamped); c8 -> c8 in the 16-bit flows."""
+    return _resample2x(_UPSAMPLE["trilinear_hp"], x, out)
 
-    @staticmethod
-    def backward(ctx, dy):
-        N, Cc, D, H, W = ctx.shape
-        dy, dybs = _dense_channels(dy)
-        dx = torch.empty(ctx.shape, dtype=dy.dtype, device=dy.device)
-        _upsample_call(ctx.family, "_bwd", _p(dy), _p(dx), N, Cc, D, H, W, dybs, 0, _stream())
-        return dx, None, None
+
+def space_to_depth2(x):
+    """[N, C, D, H, W] -> [N, 8C, D/2, H/2, W/2], channel c*8 + (pz*4 + py*2 + px).  A c8 activation stays c8 (the packed
+    channels of input channel c are exactly c8 block c)."""
+    if isinstance(x, Act16) and all(v % 2 == 0 for v in x.shape[2:]):
+        return _resample2x(_S2D, x)
+    return _resample2x(_S2D, as_f32(x))
+
+
+def depth_to_space2(x, out: Optional[OutSlot] = None):
+    if isinstance(x, Act16) and x.C % 8 == 0 and (out is None or out.buf16 is not None):
+        return _resample2x(_D2S, x, out)
+    if out is not None and out.buf16 is not None:
+        return pack_act16(_resample2x(_D2S, as_f32(x)), out.buf16.compute, out.act16())
+    return _resample2x(_D2S, as_f32(x), out)
 
 
 def _into_c8_slot(y32, out: Optional[OutSlot], compute):
     """c8 flow: a producer without a c8 epilogue (conv-transpose, trilinear upsampling) computed `y32`
     densely; pack it into its slot of the c8 concat buffer."""
     return pack_act16(y32, compute, out.act16() if out is not None else None)
-
-
-class _UpsampleC8Fn(torch.autograd.Function):
-    """x2 upsampling c8 -> c8 (straight into its concat slot); backward: the gather-form kernel on the c8 gradient"""
-
-    @staticmethod
-    def forward(ctx, x_t, x: Act16, y16: Act16, family="upsample_trilinear2x"):
-        N, Cc, D, H, W = x.shape
-        _upsample_call(family, "_fwd_h16", x.ptr(), y16.ptr(), N, Cc, D, H, W, x.batch_stride(), y16.batch_stride(),
-                       x.compute, _stream())
-        ctx.info = (N, Cc, D, H, W, x.compute)
-        ctx.family = family
-        if x.compute == _lib.COMPUTE_F16 and family != "upsample_trilinear2x":
-            # the backward's sums report their saturation in the overflow word; as in _MaxPoolC8Fn, the op installs it
-            # itself (it is also used on its own: pack -> upsample -> backward)
-            _overflow_word(x.device)
-        return y16.alias()
-
-    @staticmethod
-    def backward(ctx, dy16):
-        N, Cc, D, H, W, compute = ctx.info
-        dy16, dybs = _c8t(dy16)
-        dx16 = _c8_grad(N, Cc, D * H * W, compute, dy16.device)
-        _upsample_call(ctx.family, "_bwd_h16", _p(dy16), _p(dx16), N, Cc, D, H, W, dybs, 0, compute, _stream())
-        return dx16, None, None, None
-
-
-def _upsample2x(x, out, family):
-    if isinstance(x, Act16):
-        N, Cc, D, H, W = x.shape
-        y16 = _c8_out_slot(x, out, (2 * D, 2 * H, 2 * W))
-        if _act16_tracks(x):
-            return y16.with_t(_UpsampleC8Fn.apply(x.t, x, y16, family))
-        _upsample_call(family, "_fwd_h16", x.ptr(), y16.ptr(), N, Cc, D, H, W, x.batch_stride(), y16.batch_stride(),
-                       x.compute, _stream())
-        return y16
-    return _UpsampleFn.apply(x, out, family)
-
-
-def upsample_trilinear2x(x, out: Optional[OutSlot] = None, mode: str = "trilinear"):
-    """nn.Upsample(scale_factor=2, mode='trilinear', align_corners=True); c8 -> c8 in the 16-bit flows.
-    mode: 'trilinear' (this default), or 'nearest' / 'trilinear_hp' = upsample_nearest2x / upsample_trilinear2x_hp."""
-    if mode not in _UPSAMPLE_FAMILY:
-        raise ValueError(f"upsample mode {mode!r} not in {sorted(_UPSAMPLE_FAMILY)}")
-    return _upsample2x(x, out, _UPSAMPLE_FAMILY[mode])
-
-
-def upsample_nearest2x(x, out: Optional[OutSlot] = None):
-    """nn.Upsample(scale_factor=2, mode='nearest') (= 'nearest-exact' at this factor): the forward copies bits, the
-    backward sums each 2x2x2 block; c8 -> c8 in the 16-bit flows."""
-    return _upsample2x(x, out, "upsample_nearest2x")
-
-
-def upsample_trilinear2x_hp(x, out: Optional[OutSlot] = None):
-    """nn.Upsample(scale_factor=2, mode='trilinear', align_corners=False): the half-pixel convention (weights 0.25 / 0.75,
-    edges clamped); c8 -> c8 in the 16-bit flows."""
-    return _upsample2x(x, out, "upsample_trilinear2x_hp")
 
 
 # ------------------------------------------------------------------- softmax
@@ -2472,111 +2424,6 @@ def copy_into(x, out: OutSlot):
     if out.buf16 is not None:   # c8 flow: the slot lives in the c8 twin of the concat buffer
         return pack_act16(as_f32(x), out.buf16.compute, out.act16())
     return _CopyIntoFn.apply(as_f32(x), out)
-
-
-class _S2DFn(torch.autograd.Function):
-    """space-to-depth (to_depth=True) or depth-to-space by 2; each is the other's backward."""
-
-    @staticmethod
-    def forward(ctx, x, to_depth, out):
-        L = _lib.lib()
-        _require(x)
-        x, xbs = _dense_channels(x)
-        N, Cc, D, H, W = x.shape
-        if to_depth:
-            full = (N, Cc, D, H, W)
-            y = _alloc_out(out, (N, Cc * 8, D // 2, H // 2, W // 2), x)
-        else:
-            full = (N, Cc // 8, 2 * D, 2 * H, 2 * W)
-            y = _alloc_out(out, full, x)
-        y, ybs = _dense_channels(y)
-        # (the FULL-resolution side must be 8-byte aligned with an even stride: x of s2d, y of d2s)
-        yw, ywbs = y, ybs
-        if to_depth:
-            x, xbs = _pairs_in(x, xbs)
-        else:
-            yw, ywbs = _pairs_out(y, ybs)
-        fn = L.m355_space_to_depth2 if to_depth else L.m355_depth_to_space2
-        check(fn(_p(x), _p(yw), full[0], full[1], full[2], full[3], full[4], xbs, ywbs, _stream()),
-              "space_to_depth2" if to_depth else "depth_to_space2")
-        if yw is not y:
-            y.copy_(yw)
-        ctx.to_depth, ctx.full = to_depth, full
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        L = _lib.lib()
-        dy, dybs = _dense_channels(dy)
-        N, Cf, D, H, W = ctx.full
-        if ctx.to_depth:   # gradient of s2d is d2s
-            dx = torch.empty(ctx.full, dtype=dy.dtype, device=dy.device)
-            check(L.m355_depth_to_space2(_p(dy), _p(dx), N, Cf, D, H, W, dybs, 0, _stream()), "depth_to_space2")
-        else:
-            dx = torch.empty((N, Cf * 8, D // 2, H // 2, W // 2), dtype=dy.dtype, device=dy.device)
-            dy, dybs = _pairs_in(dy, dybs)
-            check(L.m355_space_to_depth2(_p(dy), _p(dx), N, Cf, D, H, W, dybs, 0, _stream()), "space_to_depth2")
-        return dx, None, None
-
-
-def _s2d_c8(src_ptr, sbs, dst_ptr, dbs, full_shape, compute, to_depth):
-    """c8 -> c8; `full_shape` = (N, C, D, H, W) of the FULL-resolution tensor"""
-    N, Cc, D, H, W = full_shape
-    L = _lib.lib()
-    fn = L.m355_space_to_depth2_h16 if to_depth else L.m355_depth_to_space2_h16
-    check(fn(src_ptr, dst_ptr, N, Cc, D, H, W, sbs, dbs, compute, _stream()),
-          "space_to_depth2_h16" if to_depth else "depth_to_space2_h16")
-
-
-class _S2DC8Fn(torch.autograd.Function):
-    """space-to-depth (to_depth=True) or depth-to-space by 2 on c8 activations; each is the other's backward (on the c8
-    gradient)"""
-
-    @staticmethod
-    def forward(ctx, x_t, x: Act16, y16: Act16, to_depth: bool):
-        full = x.shape if to_depth else y16.shape
-        _s2d_c8(x.ptr(), x.batch_stride(), y16.ptr(), y16.batch_stride(), full, x.compute, to_depth)
-        ctx.info = (full, x.compute, to_depth, x.shape)
-        return y16.alias()
-
-    @staticmethod
-    def backward(ctx, dy16):
-        full, compute, to_depth, xshape = ctx.info
-        dy16, dybs = _c8t(dy16)
-        dx16 = _c8_grad(xshape[0], xshape[1], xshape[2] * xshape[3] * xshape[4], compute, dy16.device)
-        _s2d_c8(_p(dy16), dybs, _p(dx16), 0, full, compute, not to_depth)
-        return dx16, None, None, None
-
-
-def _s2d_act16(x: Act16, to_depth: bool, out: Optional[OutSlot]):
-    N, Cc, D, H, W = x.shape
-    if to_depth:
-        oshape = (N, Cc * 8, D // 2, H // 2, W // 2)
-    else:
-        if Cc % 8:
-            raise _lib.M355Error(f"depth_to_space2: {Cc} channels are not 8 parities per output channel")
-        oshape = (N, Cc // 8, 2 * D, 2 * H, 2 * W)
-    y16 = _c8_out_slot(x, out, oshape[2:], oshape[1])
-    if _act16_tracks(x):
-        return y16.with_t(_S2DC8Fn.apply(x.t, x, y16, to_depth))
-    _s2d_c8(x.ptr(), x.batch_stride(), y16.ptr(), y16.batch_stride(), x.shape if to_depth else oshape, x.compute, to_depth)
-    return y16
-
-
-def space_to_depth2(x):
-    """[N, C, D, H, W] -> [N, 8C, D/2, H/2, W/2], channel c*8 + (pz*4 + py*2 + px).  A c8 activation stays c8 (the packed
-    channels of input channel c are exactly c8 block c)."""
-    if isinstance(x, Act16) and all(v % 2 == 0 for v in x.shape[2:]):
-        return _s2d_act16(x, True, None)
-    return _S2DFn.apply(as_f32(x), True, None)
-
-
-def depth_to_space2(x, out: Optional[OutSlot] = None):
-    if isinstance(x, Act16) and x.C % 8 == 0 and (out is None or out.buf16 is not None):
-        return _s2d_act16(x, False, out)
-    if out is not None and out.buf16 is not None:
-        return pack_act16(_S2DFn.apply(as_f32(x), False, None), out.buf16.compute, out.act16())
-    return _S2DFn.apply(as_f32(x), False, out)
 
 
 class _BlurWeightFn(torch.autograd.Function):

@@ -124,15 +124,23 @@ def test_fp32_kernels_are_bit_exact(fp32_refs, shape, layout):
 
 def test_fp32_ops_autograd_and_no_grad(monkeypatch):
     """ops.maxpool3d_2x / _with_skip: torch autograd's gradient bit for bit; under no_grad no route is allocated, also
-    for an input that requires grad (the launches are watched through ops._maxpool_fwd)"""
-    routes = []
-    fwd = ops._maxpool_fwd
+    for an input that requires grad (the forward launches are watched through ops._resample_launch: the route pointer they
+    pass; whether a route was asked for, through ops._tracks, where the public functions take that from)"""
+    routes, asked = [], []
+    launch, tracks = ops._resample_launch, ops._tracks
 
-    def watched(x, y, ybs, route):
-        idx = fwd(x, y, ybs, route)
-        routes.append((bool(route), idx is not None))
-        return idx
-    monkeypatch.setattr(ops, "_maxpool_fwd", watched)
+    def watched_tracks(x):
+        asked.append(tracks(x))
+        return asked[-1]
+
+    def watched(row, bwd, c8, pointers, *args):
+        launch(row, bwd, c8, pointers, *args)
+        if not bwd:
+            assert row.fwd == "maxpool3d_2x_fwd" and not c8
+            routes.append((bool(asked.pop()), pointers[3] is not None))
+            assert not asked
+    monkeypatch.setattr(ops, "_tracks", watched_tracks)
+    monkeypatch.setattr(ops, "_resample_launch", watched)
     x, _ = M.tie_heavy_input((2, 3, 4, 4, 8), seed=3)
     x = x.nan_to_num(0.0, 2.0, -2.0)
     g = torch.Generator().manual_seed(4)
