@@ -1369,6 +1369,66 @@ int m355_boundary_loss_fwd(const float* p, const float* phi, const float* class_
 int m355_boundary_loss_bwd(const float* phi, const float* dloss /* device scalar */, const float* class_weights, int32_t N,
                            int32_t C, int64_t S, float* dp, void* stream);
 
+/* ------------------------------------------ lesion-wise (blob) Dice loss on device connected components
+ * The device half of criterions.BlobLoss (Kofler et al., "blob loss: instance imbalance aware loss functions for semantic
+ * segmentation").  target, p, dp: fp32 [planes = N * C][D][H][W], contiguous.  plane_on: `planes` host
+ * bytes, or null for all planes; the P_on planes whose byte is not 0 are "on", in plane order they take the slots
+ * 0 .. P_on - 1.  In an on plane a voxel is a member when target > 0.5 (a NaN is none), the members fall into connected
+ * components (connectivity 1 | 2 | 3: 6, 18, 26 neighbours), and
+ *     S_k = sum_k p,  Q_k = sum_k p^2,  A_k = |k|,  B = sum over the plane's non-members of p (square_dice: of p^2)
+ *     d_k = 2 S_k / (A_k + S_k + B + 1e-8)          square_dice: 2 S_k / (A_k + Q_k + B + 1e-8)
+ *     loss = sum_{on planes with K > 0 components} w_c (1/K) sum_k (1 - d_k) / sum_{the same planes} w_c
+ * which is the Dice of m355_hybrid_loss_fwd per component with the other components masked out of prediction and target.
+ * The term is Dice only: there is no per-component log term.
+ * Every entry point enqueues on `stream`, never synchronises, uses no float atomics (a call repeats bit for bit) and
+ * checks its arguments on the host before any launch: a null pointer, a size or plane count < 1, no plane on, a
+ * connectivity outside 1..3, or on planes that stack to 2^31 voxels or more is M355_EINVALID_ARG; more than 1024 planes
+ * is M355_EUNSUPPORTED; a short workspace or table buffer is M355_EWORKSPACE.  The queries return 0 for such arguments.
+ *   m355_blob_capacity  The number of components the accumulators are sized for, a bound the host can compute:
+ *                       P_on ceil(D/2) ceil(H/2) ceil(W/2) with 26 neighbours (two members of one 2 x 2 x 2 cell of a
+ *                       plane are connected), P_on ceil(D H W / 2) otherwise (a checkerboard).
+ *   m355_blob_label     labels: int32 [P_on][D][H][W], 0 for a non-member, else the number of the voxel's component; the
+ *                       components of all planes are numbered 1 .. n in raster order of their first voxel in the stack,
+ *                       so those of slot s are the contiguous range ranges[2 s] .. ranges[2 s + 1] (last = first - 1: the
+ *                       plane has none).  count[0] = n, or -1 when a bounded find / union loop of the labelling hit its
+ *                       bound (ranges are undefined then).  The on planes are thresholded into one int32 volume
+ *                       [P_on * D][H][W] whose slot s holds the value s + 1 and m355_ccl_label labels it in mode 0, where
+ *                       only equal values connect: planes that touch across the stacking boundary stay apart.  Ten
+ *                       launches, nothing is read on the host.  Workspace: m355_blob_label_workspace bytes.
+ *   m355_blob_dice_fwd  loss[0]: one fp32 device scalar; total[0] = count[0].  One pass over (p, labels) of the on planes
+ *                       accumulates S and Q as 64-bit integers of round(p 2^f), round(p^2 2^f) and A as a count with
+ *                       integer atomics, f = min(60, 63 - bits of D H W) >= 32 the largest scale at which no sum can
+ *                       overflow (each sum is off by at most 2^-33 per voxel summed, whatever the arrival order);
+ *                       zeroing and finalize read count on the device and cost time in the components there are.  p must
+ *                       be a probability: a value that is not finite or outside [0, 1] in an on plane makes loss (and the
+ *                       gradient) NaN, as count = -1 does; nothing raises.  class_weights: C device floats >= 0, or null
+ *                       for all ones.  `tables` (m355_blob_dice_tables bytes) is what the backward needs besides labels:
+ *                       two fp64 coefficients per component, one per plane, a status word.  Four launches.  Workspace:
+ *                       m355_blob_dice_workspace bytes.
+ *   m355_blob_dice_bwd  dp = dloss[0] (a_k + b_k p) for a member of component k (b_k = 0 without square_dice),
+ *                       dloss[0] g_nc for a non-member (times 2 p with square_dice), formed in fp64 and rounded to fp32
+ *                       once; zeros in planes that are off.  p may be null without square_dice.  One launch.  The target
+ *                       gets no gradient.
+ */
+int64_t m355_blob_capacity(int32_t planes, const uint8_t* plane_on /* host, may be null */, int32_t D, int32_t H, int32_t W,
+                           int32_t connectivity);
+size_t m355_blob_label_workspace(int32_t planes, const uint8_t* plane_on, int32_t D, int32_t H, int32_t W);
+int m355_blob_label(const float* target, int32_t planes, const uint8_t* plane_on /* host, may be null */, int32_t D,
+                    int32_t H, int32_t W, int32_t connectivity, int32_t* labels, int32_t* ranges, int32_t* count,
+                    void* workspace, size_t workspace_bytes, void* stream);
+size_t m355_blob_dice_workspace(int32_t planes, const uint8_t* plane_on, int32_t D, int32_t H, int32_t W,
+                                int32_t connectivity);
+size_t m355_blob_dice_tables(int32_t planes, const uint8_t* plane_on, int32_t D, int32_t H, int32_t W,
+                             int32_t connectivity);
+int m355_blob_dice_fwd(const float* p, const int32_t* labels, const int32_t* ranges, const int32_t* count,
+                       const float* class_weights, int32_t N, int32_t C, const uint8_t* plane_on /* host, may be null */,
+                       int32_t D, int32_t H, int32_t W, int32_t connectivity, int32_t square_dice, float* loss,
+                       int32_t* total, void* tables, size_t tables_bytes, void* workspace, size_t workspace_bytes,
+                       void* stream);
+int m355_blob_dice_bwd(const float* p, const int32_t* labels, const void* tables, const float* dloss /* device scalar */,
+                       int32_t N, int32_t C, const uint8_t* plane_on /* host, may be null */, int32_t D, int32_t H,
+                       int32_t W, int32_t connectivity, int32_t square_dice, float* dp, void* stream);
+
 /* ------------------------------------------ statistics of image values grouped by the label of the voxel
  * The device half of ops.region_stats, evaluators.ImageRegionEvaluator and data_processing.dataset_fingerprint (DESIGN
  * §4.22).  One label volume [W, H, D] (contiguous, D fastest; any M355_EV_* type up to float32), K >= 0 images

@@ -357,6 +357,14 @@ SIGNATURES = {
     "m355_boundary_loss_workspace": (_sz, [_i32, _i32, _i64]),
     "m355_boundary_loss_fwd": (C.c_int, [_P, _P, _P, _i32, _i32, _i64, _P, _P, _sz, _P]),
     "m355_boundary_loss_bwd": (C.c_int, [_P, _P, _P, _i32, _i32, _i64, _P, _P]),
+    "m355_blob_capacity": (_i64, [_i32, _P, _i32, _i32, _i32, _i32]),
+    "m355_blob_label_workspace": (_sz, [_i32, _P, _i32, _i32, _i32]),
+    "m355_blob_label": (C.c_int, [_P, _i32, _P, _i32, _i32, _i32, _i32, _P, _P, _P, _P, _sz, _P]),
+    "m355_blob_dice_workspace": (_sz, [_i32, _P, _i32, _i32, _i32, _i32]),
+    "m355_blob_dice_tables": (_sz, [_i32, _P, _i32, _i32, _i32, _i32]),
+    "m355_blob_dice_fwd": (C.c_int, [_P, _P, _P, _P, _P, _i32, _i32, _P, _i32, _i32, _i32, _i32, _i32, _P, _P, _P, _sz, _P,
+                                     _sz, _P]),
+    "m355_blob_dice_bwd": (C.c_int, [_P, _P, _P, _P, _i32, _i32, _P, _i32, _i32, _i32, _i32, _i32, _P, _P]),
     "m355_region_stats_workspace": (_sz, [_i32, _i32, _i32]),
     "m355_region_stats_plan": (C.c_int, [_I3]),
     "m355_region_stats": (C.c_int, [_P, _i32, _I3, C.POINTER(RegionImage), _i32, _I3, _i32, _i32, _P, _P, _P, _P, _sz, _P]),

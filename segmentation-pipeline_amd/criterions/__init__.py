@@ -5,3 +5,4 @@ from .hybrid_focal_tversky_loss import HybridFocalTverskyLoss
 from .hybrid_topk_dice_loss import HybridTopKDiceLoss
 from .deep_supervision_loss import DeepSupervisionLoss
 from .boundary_loss import BoundaryLoss
+from .blob_loss import BlobLoss

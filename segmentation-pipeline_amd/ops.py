@@ -2276,6 +2276,136 @@ def boundary_loss(p, phi, class_weights=None):
     return _BoundaryLossFn.apply(p, phi, class_weights)
 
 
+# ------------------------------------------------------- blob (lesion-wise) Dice loss (csrc/blob_loss.hip)
+def _blob_planes(planes, n_planes, what):
+    """planes: None for all, or N * C flags ([N][C] order) -> (host byte array or None, tuple of flags)"""
+    if planes is None:
+        return None, (True,) * n_planes
+    flags = tuple(bool(v) for v in (planes.flatten().tolist() if isinstance(planes, torch.Tensor) else planes))
+    if len(flags) != n_planes:
+        raise _lib.M355Error(f"{what}: {len(flags)} plane flags for N * C = {n_planes} planes")
+    if not any(flags):
+        raise _lib.M355Error(f"{what}: no plane is on")
+    return (C.c_uint8 * n_planes)(*flags), flags
+
+
+def _blob_target(target, what):
+    if not isinstance(target, torch.Tensor) or target.dtype != torch.float32:
+        got = target.dtype if isinstance(target, torch.Tensor) else type(target).__name__
+        raise _lib.M355Error(f"{what}: target: element type {got} (expected torch.float32)")
+    if target.dim() != 5:
+        raise _lib.M355Error(f"{what}: target: expected [N, C, D, H, W], got shape {tuple(target.shape)}")
+
+
+def _blob_connectivity(connectivity, what):
+    if connectivity not in (1, 2, 3):
+        raise _lib.M355Error(f"{what}: connectivity {connectivity!r} not in (1, 2, 3): 6, 18 or 26 neighbours")
+    return int(connectivity)
+
+
+def _blob_label(target, on, n_on, connectivity):
+    L = _lib.lib()
+    n_planes, (D, H, W) = target.shape[0] * target.shape[1], target.shape[2:]
+    labels = torch.empty((n_on, D, H, W), dtype=torch.int32, device=target.device)
+    ranges = torch.empty((n_on, 2), dtype=torch.int32, device=target.device)
+    count = torch.empty((), dtype=torch.int32, device=target.device)
+    ws = _workspace(L.m355_blob_label_workspace(n_planes, on, D, H, W), target.device)
+    check(L.m355_blob_label(_p(target), n_planes, on, D, H, W, connectivity, _p(labels), _p(ranges), _p(count), _p(ws),
+                            ws.numel(), _stream()), "blob_label")
+    return labels, ranges, count
+
+
+def blob_labels(target, planes=None, connectivity=3):
+    """The connected components of every on plane of `target` (float32 [N, C, D, H, W], contiguous, on the device; a voxel
+    is a member when target > 0.5, a NaN is none) in one labelling, without a synchronisation.
+    planes: None for all, or N * C host flags ([N][C] order); the P_on planes that are on take the slots 0 .. P_on - 1 in
+    plane order.  connectivity 1 | 2 | 3: 6, 18, 26 neighbours.
+    -> (labels int32 [P_on, D, H, W]: 0 outside, else the component's number; ranges int32 [P_on, 2]: the components of
+    slot s are the numbers ranges[s, 0] .. ranges[s, 1] (last = first - 1: none), numbered in raster order of their first
+    voxel like scipy.ndimage.label's, shifted by first - 1; count: a 0-dim int32 device tensor, the number of components of
+    all planes, or -1 when the labelling hit a loop bound)."""
+    _blob_target(target, "blob_labels")
+    connectivity = _blob_connectivity(connectivity, "blob_labels")
+    on, flags = _blob_planes(planes, target.shape[0] * target.shape[1], "blob_labels")
+    _dist_arg(target, (torch.float32,), "blob_labels: target")
+    with torch.cuda.device(target.device):
+        return _blob_label(target, on, sum(flags), connectivity)
+
+
+class _BlobDiceLossFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, p, t, class_weights, flags, square_dice, connectivity):
+        L = _lib.lib()
+        p, t, (cw,), N, Cc, _ = _loss_operands((("prediction", p), ("target", t)), (("class_weights", class_weights),))
+        D, H, W = p.shape[2:]
+        on = None if all(flags) else (C.c_uint8 * (N * Cc))(*flags)
+        sq = 1 if square_dice else 0
+        with torch.cuda.device(p.device):
+            labels, ranges, count = _blob_label(t, on, sum(flags), connectivity)
+            loss = torch.empty((), dtype=torch.float32, device=p.device)
+            total = torch.empty((), dtype=torch.int32, device=p.device)
+            tables = torch.empty(int(L.m355_blob_dice_tables(N * Cc, on, D, H, W, connectivity)), dtype=torch.uint8,
+                                 device=p.device)             # saved: not the workspace, which the next op reuses
+            ws = _workspace(L.m355_blob_dice_workspace(N * Cc, on, D, H, W, connectivity), p.device)
+            check(L.m355_blob_dice_fwd(_p(p), _p(labels), _p(ranges), _p(count), _p(cw), N, Cc, on, D, H, W, connectivity,
+                                       sq, _p(loss), _p(total), _p(tables), tables.numel(), _p(ws), ws.numel(), _stream()),
+                  "blob_dice_fwd")
+        ctx.args = (N, Cc, D, H, W, on, connectivity, sq)
+        ctx.save_for_backward(p if sq else None, labels, tables)
+        ctx.mark_non_differentiable(total)
+        return loss, total
+
+    @staticmethod
+    def backward(ctx, dloss, _dtotal):
+        if not ctx.needs_input_grad[0]:
+            return (None,) * 6
+        p, labels, tables = ctx.saved_tensors
+        N, Cc, D, H, W, on, connectivity, sq = ctx.args
+        dp = torch.empty((N, Cc, D, H, W), dtype=torch.float32, device=labels.device)
+        with torch.cuda.device(labels.device):
+            check(_lib.lib().m355_blob_dice_bwd(_p(p), _p(labels), _p(tables), _p(_dloss32(dloss)), N, Cc, on, D, H, W,
+                                                connectivity, sq, _p(dp), _stream()), "blob_dice_bwd")
+        return (dp,) + (None,) * 5
+
+
+def blob_default_class_weights(channels):
+    """0 for channel 0 (the background) when there is more than one channel, 1 otherwise: BoundaryLoss's convention"""
+    return (0.0,) + (1.0,) * (channels - 1) if channels > 1 else (1.0,)
+
+
+def blob_dice_loss(prediction, target, class_weights=None, square_dice=True, connectivity=3, planes=None):
+    """The lesion-wise (blob) Dice of Kofler et al. -> (loss, count): the Dice term of
+    hybrid_logistic_dice_loss once per connected component of the target (target > 0.5; `connectivity` 1 | 2 | 3) with the
+    other components of its (n, c) plane masked out of prediction and target, averaged over the components of a plane and
+    over the planes by their channel weights; 0 when no plane has a component.  count: a 0-dim int32 device tensor, the
+    number of components (-1, with a NaN loss, when the labelling hit a loop bound).  prediction, target: fp32
+    [N, C, D, H, W] on the device; the prediction must hold probabilities: a value that is not finite or outside [0, 1] in
+    a plane that is on gives a NaN loss and gradient, nothing raises.
+    class_weights: None (0 for channel 0 when C > 1, else 1), a sequence of C host numbers >= 0 -- channels of weight 0 are
+    off: not labelled, not read, zero gradient --, or an fp32 device tensor [C], which is not read on the host: then
+    `planes` (N * C host flags, [N][C] order; None: all) says which planes are on.  The gradient flows to the prediction
+    only; nothing is read on the host."""
+    what = "blob_dice_loss"
+    _blob_target(target, what)
+    connectivity = _blob_connectivity(connectivity, what)
+    N, Cc = target.shape[0], target.shape[1]
+    if not isinstance(class_weights, torch.Tensor):
+        values = blob_default_class_weights(Cc) if class_weights is None else tuple(float(v) for v in class_weights)
+        if len(values) != Cc:
+            raise _lib.M355Error(f"{what}: class_weights of {len(values)} values for {Cc} channels")
+        if any(not (math.isfinite(v) and v >= 0) for v in values) or not sum(values) > 0:
+            raise _lib.M355Error(f"{what}: class_weights = {values}: expected finite values >= 0 with a positive sum")
+        if planes is not None:
+            raise _lib.M355Error(f"{what}: planes goes with a device tensor of class weights; host weights say which "
+                                 f"planes are on themselves")
+        flags = tuple(v > 0 for v in values) * N
+        _require(prediction, target)
+        class_weights = torch.tensor(values, dtype=torch.float32, device=prediction.device)
+    else:
+        _, flags = _blob_planes(planes, N * Cc, what)
+    return _BlobDiceLossFn.apply(prediction, target, class_weights, flags, bool(square_dice), connectivity)
+
+
 # ------------------------------------------------------------- target pyramid
 PYRAMID_MODES = {"area": 0, "nearest": 1}   # M355_PYRAMID_AREA, M355_PYRAMID_NEAREST
 PYRAMID_MAX_LEVELS = 4
