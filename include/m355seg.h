@@ -30,6 +30,8 @@
  *    allocator -- gets a library that makes no device allocation at all;
  *    otherwise the pool is hipMalloc'ed + hipMemset on first use (never inside
  *    a stream capture) and lives until the process exits.
+ *  - Workspace and output contents on entry are irrelevant unless an entry
+ *    point says "zeroed by the CALLER": the library initialises what it reads.
  *  - Every call only ENQUEUES work on `stream` (a hipStream_t passed as
  *    void*); no implicit synchronisation.
  *  - Return 0 (M355_OK) or a negative status; never throws, never aborts.
@@ -951,7 +953,8 @@ int m355_patch_aggregate_grid_weighted(const float* tiles, const int32_t* starts
  * points are the tensor-level part: gather P patches [P, C, ps0, ps1, ps2] from
  * a volume [C, V0, V1, V2] at integer corner locations loc[P,3] (i0,j0,k0), and
  * the aggregation out[c,v] = (sum over covering patches, in patch order) /
- * (number of covering patches).
+ * (number of covering patches).  m355_patch_accumulate ADDS to accum and count, so that a volume's patches may arrive in
+ * several batches: both are zeroed by the CALLER before the first batch.
  */
 int m355_patch_gather(const float* volume, const int32_t* loc, float* patches,
                       int32_t P, int32_t C, int32_t V0, int32_t V1, int32_t V2,
@@ -993,7 +996,8 @@ int m355_argmax_confusion(const float* prob, const int32_t* target, int32_t* arg
  *   m355_flip_permute        member input [N,C,size3[perm]] from x [N,C,size3], one gather pass
  *   m355_ensemble_accumulate reads a member prediction THROUGH the inverse transform (it is never mapped back or
  *                            stacked): mode 0: acc[N,C,S] (+)= pred; mode 1: votes[N,C,S] (int32) += 1 at the
- *                            member's argmax class (first maximum, as torch.argmax); first != 0 initialises
+ *                            member's argmax class (first maximum, as torch.argmax); first != 0 initialises (the
+ *                            accumulator's contents on entry are then irrelevant; with first == 0 they are the sum so far)
  *   m355_ensemble_finalize   mode 0: mean_out = acc / members; mode 1: onehot_out[N,C,S] (int64) of the class with
  *                            the most votes, ties -> the smallest class index (torch.mode on the CPU) */
 int m355_flip_permute(const float* x, float* member, int32_t N, int32_t C, const int32_t* size3, const int32_t* perm3,

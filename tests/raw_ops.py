@@ -116,6 +116,227 @@ class Slot:
         return self.result()
 
 
+SCRATCH_MODES = ("zeros", "stale", "ones", "nan")
+TAIL_BYTES, TAIL_CANARY = 256, 0xC3
+_SAME_SIZE_INT = {1: torch.uint8, 2: torch.int16, 4: torch.int32, 8: torch.int64}
+
+
+def canary_of(dtype):
+    """(integer view type, value) of the "nan" fill of a dtype: Slot.CANARY's quiet NaNs, a float64 quiet NaN, 0x7F bytes
+    for the integer types, True for bool"""
+    if dtype in Slot.CANARY:
+        return Slot.CANARY[dtype]
+    if dtype == torch.float64:
+        return torch.int64, 0x7FF80000C0DEBEEF
+    if dtype == torch.bool:
+        return torch.uint8, 1
+    size = dtype.itemsize
+    return _SAME_SIZE_INT[size], int.from_bytes(b"\x7f" * size, "little")
+
+
+def dirty(t, mode):
+    """fill tensor `t` (any strides) in place with what `mode` stands for ("zeros" | "ones" | "nan", and "first": 0x5A bytes,
+    what a "stale" buffer holds before its first use); -> t"""
+    size = t.element_size()
+    if size not in _SAME_SIZE_INT:
+        raise TypeError(f"no fill for {t.dtype}: elements of 1, 2, 4 or 8 bytes only")
+    if t.numel() == 0:
+        return t
+    with torch.no_grad():
+        if mode == "zeros":
+            t.view(_SAME_SIZE_INT[size]).zero_()
+        elif mode == "ones":
+            it = _SAME_SIZE_INT[size]
+            t.view(it).fill_(0xFF if it == torch.uint8 else -1)
+        elif mode == "nan":
+            it, v = canary_of(t.dtype)
+            t.view(it).fill_(v)
+        elif mode == "first":
+            t.view(_SAME_SIZE_INT[size]).fill_(int.from_bytes(b"\x5a" * size, "little"))
+        else:
+            raise ValueError(mode)
+    return t
+
+
+class Scratch:
+    """`with hip.scratch(mode) as s:` -- while active, every workspace and every output the RawOps wrappers allocate holds
+    what `mode` says on entry instead of whatever torch.empty returns:
+
+        None     torch.empty (nothing is tracked)
+        "zeros"  zeros
+        "stale"  the buffer the same call site got last time for the same size (0x5A bytes the first time), not refilled: the call
+                 sees what the previous call through that site left.  `s.rewind()` between two runs of the same sequence of
+                 calls makes the second run get the first run's buffers, allocation by allocation
+        "ones"   every byte 0xFF
+        "nan"    canary_of(dtype): quiet-NaN canaries, 0x7F bytes for integers, True for bool; a workspace holds the fp32
+                 canary in every word (0x7F bytes where its size is no multiple of 4)
+
+    In every mode but None a workspace is allocated TAIL_BYTES longer than declared, the tail holds TAIL_CANARY and the
+    wrapper still passes the declared size; leaving the context checks every tail (AssertionError).  Counters: `workspaces`
+    and `outputs` dirtied, `declared` = sum of the workspace bytes the library asked for."""
+
+    _HELPERS = ("_site", "_fresh", "output", "workspace", "empty", "_workspace", "_ws", "_out")
+
+    def __init__(self, ops, mode):
+        assert mode is None or mode in SCRATCH_MODES, mode
+        self.ops, self.mode = ops, mode
+        self.workspaces = self.outputs = self.declared = 0
+        self._tails = []            # (whole buffer, declared bytes, site)
+        self._stale, self._seen = {}, {}
+
+    def __enter__(self):
+        assert self.ops._scratch is None, "scratch() does not nest"
+        if self.mode is not None:
+            self.ops._scratch = self
+        return self
+
+    def __exit__(self, et, ev, tb):
+        self.ops._scratch = None
+        if et is None:
+            self.check_tails()
+        return False
+
+    def rewind(self):
+        """"stale": the next allocations start over at each call site's first buffer"""
+        self._seen.clear()
+
+    def check_tails(self):
+        if self.ops.device == "cuda":
+            torch.cuda.synchronize()
+        for buf, n, site in self._tails:
+            bad = (buf[n:] != TAIL_CANARY).nonzero().flatten()
+            assert bad.numel() == 0, (f"workspace of {site[0]} (line {site[1]}): {bad.numel()} bytes past the declared {n} were "
+                                      f"overwritten, first at +{int(bad[0])}")
+
+    def _site(self):
+        f = sys._getframe(0)
+        while f.f_code.co_filename == __file__ and f.f_code.co_name in self._HELPERS:
+            f = f.f_back
+        return f.f_code.co_name, f.f_lineno
+
+    def _fresh(self, kind, nbytes_or_shape, dtype, device, make):
+        """the buffer of this allocation: new (and filled), or in "stale" the one this site had for this size before"""
+        if self.mode != "stale":
+            return make(self.mode)
+        key = (kind, self._site(), nbytes_or_shape, dtype)
+        k = self._seen.get(key, 0)
+        self._seen[key] = k + 1
+        if (key, k) not in self._stale:
+            self._stale[(key, k)] = make("first")
+        return self._stale[(key, k)]
+
+    def output(self, shape, dtype, device):
+        self.outputs += 1
+        return self._fresh("out", shape, dtype, device,
+                           lambda mode: dirty(torch.zeros(shape, dtype=dtype, device=device), mode))
+
+    def workspace(self, n, asked, device):
+        self.workspaces += 1
+        self.declared += asked
+        site = self._site()
+
+        def make(mode):
+            buf = torch.zeros(n + TAIL_BYTES, dtype=torch.uint8, device=device)
+            assert buf.data_ptr() % 16 == 0
+            if mode == "nan" and n % 4 == 0:
+                dirty(buf[:n].view(torch.float32), "nan")
+            else:
+                buf[:n] = {"zeros": 0, "ones": 0xFF, "nan": 0x7F, "first": 0x5A}[mode]
+            buf[n:] = TAIL_CANARY
+            return buf
+        buf = self._fresh("ws", n, torch.uint8, device, make)
+        if not any(b is buf for b, _, _ in self._tails):
+            self._tails.append((buf, n, site))
+        return buf[:n]
+
+
+def bit_equal(a, b, mask=None):
+    """same shape, dtype and bits (NaN payloads and signed zeros included); mask: bool tensor of the defined elements"""
+    if a is None or b is None:
+        return a is None and b is None
+    if a.shape != b.shape or a.dtype != b.dtype:
+        return False
+    it = _SAME_SIZE_INT[a.element_size()]
+    ia, ib = a.contiguous().view(it), b.contiguous().view(it)
+    if mask is not None:
+        ia, ib = ia[mask.to(ia.device)], ib[mask.to(ib.device)]
+    return torch.equal(ia, ib)
+
+
+def assert_recycled(ops, run, other, reference, has_workspace=True, deterministic=True, masks=None, modes=SCRATCH_MODES[1:]):
+    """The recycled-memory protocol of one case.  `run()` -> {name: tensor} calls the entry point(s) under test on the
+    case's inputs through `ops`, `other()` does the same on other inputs of the same shapes, `reference(got)` asserts
+    that a result meets the case's oracle / fp64 reference at its parity test's tolerance.
+
+      (a) two runs on zeroed scratch are bit-identical (asserted unless deterministic=False)
+      (b) a run on "stale" (after other()), "ones" and "nan" scratch, in that order, is bit-identical to the clean run in
+          every returned tensor (masks: {name: bool tensor of the defined elements} for documented don't-care bytes)
+      (c) the "nan" run meets the reference; with deterministic=False every poisoned run does, in place of (b)
+      (d) every poisoned run went through at least one dirtied workspace of non-zero declared size (has_workspace; None:
+          where the clean run declared one), or else through at least one dirtied output
+    Leaving each scratch() checks the workspace tails.  modes: the poisoning modes to run (the harness self-test runs one)."""
+    masks = masks or {}
+    with ops.scratch("zeros") as s:
+        clean = run()
+    if has_workspace is None:       # (entry points whose workspace query is 0 on some routes: what the clean run declared)
+        has_workspace = s.declared > 0
+    with ops.scratch("zeros"):
+        again = run()
+    if deterministic:
+        diff = [k for k in clean if not bit_equal(clean[k], again[k], masks.get(k))]
+        assert not diff, f"(a) two runs on zeroed scratch differ in {diff}"
+    for mode in modes:
+        with ops.scratch(mode) as s:
+            if mode == "stale":
+                other()
+                s.rewind()
+            got = run()
+        if has_workspace:
+            assert s.workspaces >= 1 and s.declared > 0, f"(d) {mode}: {s.workspaces} workspaces of {s.declared} declared bytes"
+        else:
+            assert s.outputs >= 1, f"(d) {mode}: no output went through the harness"
+        if deterministic:
+            diff = [k for k in clean if not bit_equal(clean[k], got[k], masks.get(k))]
+            assert not diff, f"(b) on {mode!r} scratch {diff} differ from the run on zeroed scratch"
+        if mode == "nan" or not deterministic:
+            reference(got)
+
+
+class PoisonedEmpty:
+    """`with PoisonedEmpty(monkeypatch, mode) as p:` -- package-level twin of RawOps.scratch for code that allocates through
+    torch itself (ops.py): torch.empty, torch.empty_like, torch.empty_strided and Tensor.new_empty are wrapped (pytest's
+    monkeypatch, undone on exit, also after an exception) so that every result on a `device_type` device is filled as
+    `mode` says ("zeros" | "ones" | "nan"; there is no "stale": call the op once on other inputs first).  CPU and pinned
+    tensors are left alone.  torch.zeros / torch.full / tensor.clone are not touched, so whatever the package zero-fills
+    (work-queue pool, fp16 overflow word, optimizer state record, caller-zeroed counters) stays as it is.  `p.dirtied`
+    counts the allocations filled.  Capture no torch.cuda.graph inside: the fills would be recorded."""
+
+    def __init__(self, monkeypatch, mode, device_type="cuda"):
+        assert mode in ("zeros", "ones", "nan"), mode
+        self.monkeypatch, self.mode, self.device_type = monkeypatch, mode, device_type
+        self.dirtied = 0
+
+    def _wrap(self, orig):
+        def wrapped(*a, **k):
+            t = orig(*a, **k)
+            if (isinstance(t, torch.Tensor) and t.device.type == self.device_type and t.element_size() in _SAME_SIZE_INT
+                    and not (t.device.type == "cpu" and t.is_pinned())):      # (16-byte elements: left alone, not counted)
+                dirty(t, self.mode)
+                self.dirtied += 1
+            return t
+        return wrapped
+
+    def __enter__(self):
+        self._cm = self.monkeypatch.context()
+        m = self._cm.__enter__()
+        for owner, name in ((torch, "empty"), (torch, "empty_like"), (torch, "empty_strided"), (torch.Tensor, "new_empty")):
+            m.setattr(owner, name, self._wrap(getattr(owner, name)))
+        return self
+
+    def __exit__(self, *exc):
+        return self._cm.__exit__(*exc)
+
+
 def _p(t):
     if t is None:
         return None
@@ -137,6 +358,7 @@ class RawOps:
             self.prefix, self.device = "m355o_", "cpu"
         else:
             raise ValueError(backend)
+        self._scratch = None
 
     # ------------------------------------------------------------- plumbing
     def fn(self, name):
@@ -168,18 +390,33 @@ class RawOps:
         if out is not None:
             assert isinstance(out, Slot) and tuple(out.shape) == tuple(shape) and out.dtype == dtype, (out.shape, shape)
             return out
-        if fill is not None:
+        if fill is not None and self._scratch is None:
             return torch.full(tuple(shape), fill, dtype=dtype, device=self.device)
-        return torch.empty(tuple(shape), dtype=dtype, device=self.device)
+        return self.empty(*shape, dtype=dtype)   # (under hip.scratch(mode) the 0.0 / 7.0 pre-fills of c8 outputs become the mode's fill)
 
     def empty(self, *shape, dtype=torch.float32):
-        return torch.empty(shape, dtype=dtype, device=self.device)
+        """every output a wrapper allocates, main or auxiliary: torch.empty, or what the active scratch() mode holds"""
+        if self._scratch is None:
+            return torch.empty(shape, dtype=dtype, device=self.device)
+        return self._scratch.output(tuple(shape), dtype, self.device)
+
+    def _workspace(self, nbytes):
+        """every workspace a wrapper allocates: `nbytes` from the library's query (at least 16 are handed over).  The tensor's
+        numel() is the declared size the wrapper passes; under scratch(mode) it is a view of a buffer with a guarded tail."""
+        n = max(int(nbytes), 16)
+        if self._scratch is None:
+            return torch.empty(n, dtype=torch.uint8, device=self.device)
+        return self._scratch.workspace(n, int(nbytes), self.device)
 
     def _ws(self, qname, desc):
         n = 0
         if self.backend == "hip":
             n = getattr(self.lib, "m355_" + qname)(C.byref(desc))
-        return torch.empty(max(int(n), 16), dtype=torch.uint8, device=self.device)
+        return self._workspace(n)
+
+    def scratch(self, mode):
+        """Context manager (-> Scratch): what the workspaces and outputs of the wrappers hold on entry while it is active"""
+        return Scratch(self, mode)
 
     # ------------------------------------------------- fp16 overflow word
     def overflow_word(self):
@@ -340,7 +577,7 @@ class RawOps:
         return tuple(out)
 
     def conv3d_fwd_h16(self, x16, Cin, spatial, w, bias=None, add=None, compute=1, groups=None, eps=1e-5, softmax=False,
-                       out=None):
+                       out=None, partials=False):
         """forward on a c8 input; groups != None also returns the fused statistics (mean, rstd); softmax: the
         M355_CONV_SOFTMAX epilogue (asserts that the library offers it for this descriptor)"""
         w, bias, add = map(self.to, (w, bias, add))
@@ -353,7 +590,7 @@ class RawOps:
             assert self.lib.m355_conv3d_fuses_softmax(C.byref(d)) == 1
             d.flags |= 2
         n = self.lib.m355_conv3d_h16_workspace(C.byref(d), 0)
-        ws = torch.empty(max(int(n), 16), dtype=torch.uint8, device=self.device)
+        ws = self._workspace(n)
         part = None
         if groups is not None:
             slots = self.fn("conv3d_stats_slots")(C.byref(d))
@@ -370,7 +607,7 @@ class RawOps:
         self._chk(self.fn("norm_stats_from_partials")(C.byref(nd), _p(part), slots, _p(mean), _p(rstd), None, None,
                                                       0.1, _p(nws), nws.numel(), self._stream()),
                   "norm_stats_from_partials")
-        return y, mean, rstd
+        return (y, mean, rstd, part) if partials else (y, mean, rstd)
 
     def conv3d_fwd_h16_c8(self, x16, Cin, spatial, w, bias=None, compute=1, with_stats=False, out=None):
         """forward with c8 input AND c8 output; with_stats -> (y16, partials [N, P, Cout, 2])"""
@@ -380,7 +617,7 @@ class RawOps:
         d = self.conv_desc((N, Cin) + tuple(spatial), Cout, 3, 1, 1, compute=compute)
         y16 = self._out(out, (N, (Cout + 7) // 8, S, 8), x16.dtype, fill=0.0)
         n = self.lib.m355_conv3d_h16_workspace(C.byref(d), 0)
-        ws = torch.empty(max(int(n), 16), dtype=torch.uint8, device=self.device)
+        ws = self._workspace(n)
         part = None
         if with_stats:
             slots = self.fn("conv3d_stats_slots_c8")(C.byref(d))
@@ -414,7 +651,7 @@ class RawOps:
         dx = self._out(out, x_shape)
         d = self.conv_desc(x_shape, Cout, 3, 1, 1, xbs=_bs(dx), compute=compute)
         n = self.lib.m355_conv3d_h16_workspace(C.byref(d), 1)
-        ws = torch.empty(max(int(n), 16), dtype=torch.uint8, device=self.device)
+        ws = self._workspace(n)
         self._chk(self.fn("conv3d_bwd_data_h16")(C.byref(d), _p(dy16), _bs(dy16, CBp * S * 8), _p(w), _p(dx), _p(ws), ws.numel(),
                                                  self._stream()), "conv3d_bwd_data_h16")
         return dx
@@ -425,7 +662,7 @@ class RawOps:
         d = self.conv_desc((N, Cin) + tuple(spatial), Cout, 3, 1, 1, compute=compute)
         dw, db = self.empty(Cout, Cin, 3, 3, 3), (self.empty(Cout) if with_bias else None)
         n = self.lib.m355_conv3d_bwd_weight_h16_workspace(C.byref(d))
-        ws = torch.empty(max(int(n), 16), dtype=torch.uint8, device=self.device)
+        ws = self._workspace(n)
         d.y_batch_stride = _bs(dy) if with_bias else 0
         self._chk(self.fn("conv3d_bwd_weight_h16")(C.byref(d), _p(x16), _bs(x16), _p(dy16), _bs(dy16), _p(self.to(dy)) if with_bias else None,
                                                    _p(dw), _p(db), _p(ws), ws.numel(), self._stream()),
@@ -466,7 +703,7 @@ class RawOps:
         d = self.conv_desc(x_shape, Cout, 3, 1, 1, compute=compute)
         dx16 = self._out(out, (N, (x_shape[1] + 7) // 8, S, 8), dy16.dtype, fill=7.0)
         n = self.lib.m355_conv3d_h16_workspace(C.byref(d), 1)
-        ws = torch.empty(max(int(n), 16), dtype=torch.uint8, device=self.device)
+        ws = self._workspace(n)
         self._chk(self.fn("conv3d_bwd_data_h16_c8")(C.byref(d), _p(dy16), _bs(dy16, CBp * S * 8), _p(w), _p(dx16), _bs(dx16), _p(ws), ws.numel(),
                                                     self._stream()), "conv3d_bwd_data_h16_c8")
         return dx16
@@ -476,7 +713,7 @@ class RawOps:
         d = self.conv_desc((N, Cin) + tuple(spatial), Cout, 3, 1, 1, compute=compute)
         dw, db = self.empty(Cout, Cin, 3, 3, 3), (self.empty(Cout) if with_bias else None)
         n = self.lib.m355_conv3d_bwd_weight_c8_workspace(C.byref(d))
-        ws = torch.empty(max(int(n), 16), dtype=torch.uint8, device=self.device)
+        ws = self._workspace(n)
         self._chk(self.fn("conv3d_bwd_weight_c8")(C.byref(d), _p(x16), _bs(x16), _p(dy16), _bs(dy16), _p(dw), _p(db), float(unscale), _p(ws),
                                                   ws.numel(), self._stream()), "conv3d_bwd_weight_c8")
         return dw, db
@@ -572,15 +809,15 @@ class RawOps:
         dw = self.empty(x_shape[1], Cout, 2, 2, 2)
         db = self.empty(Cout) if with_bias else None
         n = self.lib.m355_conv_transpose3d_h16_bwd_workspace(C.byref(d))
-        ws = torch.empty(max(int(n), 16), dtype=torch.uint8, device=self.device)
+        ws = self._workspace(n)
         self._chk(self.fn("conv_transpose3d_bwd_weight_h16")(C.byref(d), _p(x16), _bs(x16), _p(dy16), _bs(dy16), _p(dw), _p(db), float(unscale),
                                                              compute, _p(ws), ws.numel(), self._stream()),
                   "conv_transpose3d_bwd_weight_h16")
         return dw, db
 
-    def conv3d_fwd_stats(self, x, w, bias=None, groups=0, eps=1e-5, compute=0, out=None):
+    def conv3d_fwd_stats(self, x, w, bias=None, groups=0, eps=1e-5, compute=0, out=None, partials=False):
         """fused conv + statistics: returns (y, mean, rstd) of the normalisation that follows the conv, or
-        None when this backend has no fused statistics for the shape"""
+        None when this backend has no fused statistics for the shape; partials: (y, mean, rstd, partials [N, P, Cout, 2])"""
         x, w = self.to(x), self.to(w)
         bias = self.to(bias) if bias is not None else None
         N, Cin, D, H, W = x.shape
@@ -601,7 +838,19 @@ class RawOps:
         self._chk(self.fn("norm_stats_from_partials")(C.byref(nd), _p(part), slots, _p(mean), _p(rstd), None, None,
                                                       0.1, _p(nws), nws.numel(), self._stream()),
                   "norm_stats_from_partials")
-        return y, mean, rstd
+        return (y, mean, rstd, part) if partials else (y, mean, rstd)
+
+    def norm_stats_from_partials(self, part, x_shape, groups, eps=1e-5):
+        """(mean, rstd) from the partials [N, P, C, 2] of a conv epilogue or of act16_channel_partials"""
+        part = self.to(part)
+        N, Cc = x_shape[:2]
+        nd = NormDesc(N, Cc, torch.Size(x_shape).numel() // (N * Cc), groups, 0, eps, 0.01, 0, 0, 0)
+        ns = self.fn("norm_num_stats")(C.byref(nd))
+        mean, rstd = self.empty(ns), self.empty(ns)
+        nws = self._ws("norm_workspace", nd)
+        self._chk(self.fn("norm_stats_from_partials")(C.byref(nd), _p(part), part.shape[1], _p(mean), _p(rstd), None, None,
+                                                      0.1, _p(nws), nws.numel(), self._stream()), "norm_stats_from_partials")
+        return mean, rstd
 
     def conv3d_bwd_data(self, dy, w, x_shape, stride=1, pad=1, compute=0, packed=None, out=None):
         dy, w = self.to(dy), self.to(w)
@@ -655,6 +904,22 @@ class RawOps:
         self._chk(self.fn("conv_transpose3d_bwd_weight")(C.byref(d), _p(x), _p(dy), _p(dw), _p(db), _p(ws),
                                                          ws.numel(), self._stream()), "convt_bwd_weight")
         return dw, db
+
+    def convt_bwd_weight_x3(self, x, dy, with_bias=True):
+        """m355_conv_transpose3d_bwd_weight_x3 (k2 s2, the split pipe) on dense tensors -> (dw, dbias, voxel-range splits of
+        the plan); asserts that the library has the split kernel for the descriptor -- HIP library only"""
+        x, dy = self.to(x), self.to(dy)
+        Cout = dy.shape[1]
+        d = self.conv_desc(x.shape, Cout, 2, 2, 0, compute=3)
+        plan = (C.c_int32 * 4)()
+        self._chk(self.lib.m355_conv_transpose3d_x3_bwd_plan(C.byref(d), 2, _p(dy), plan), "conv_transpose3d_x3_bwd_plan")
+        assert plan[0] == 2 and self.lib.m355_conv_transpose3d_x3_bwd_supported(C.byref(d), _p(dy)) == 2, tuple(plan)
+        dw = self.empty(x.shape[1], Cout, 2, 2, 2)
+        db = self.empty(Cout) if with_bias else None
+        ws = self._workspace(self.lib.m355_conv_transpose3d_x3_bwd_workspace(C.byref(d)))
+        self._chk(self.lib.m355_conv_transpose3d_bwd_weight_x3(C.byref(d), _p(x), _p(dy), _p(dw), _p(db), _p(ws), ws.numel(),
+                                                               self._stream()), "conv_transpose3d_bwd_weight_x3")
+        return dw, db, plan[2]
 
     # ------------------------------------------------------------------ norm
     @staticmethod
@@ -717,6 +982,19 @@ class RawOps:
         self._chk(self.fn("norm_act_bwd")(C.byref(d), _p(x), _p(dy), _p(mean), _p(rstd), _p(gamma), _p(beta),
                                           _p(dx), _p(dg), _p(db), training, _p(ws), ws.numel(), self._stream()),
                   "norm_act_bwd")
+        return dx, dg, db
+
+    def norm_act_bwd_pool(self, x, dskip, dpool, mean, rstd, gamma, beta, groups, act, training=1, eps=1e-5, slope=0.01):
+        """norm backward whose incoming gradient is dskip (may be None) + the un-pooled dpool -> (dx, dgamma, dbeta);
+        dense tensors -- HIP library only"""
+        x, dskip, dpool, mean, rstd, gamma, beta = map(self.to, (x, dskip, dpool, mean, rstd, gamma, beta))
+        N, Cc, D, H, W = x.shape
+        d = self.norm_desc(x, groups, act, eps, slope)
+        dx, dg, db = self.empty(*x.shape), self.empty(Cc), self.empty(Cc)
+        ws = self._ws("norm_workspace", d)
+        self._chk(self.fn("norm_act_bwd_pool")(C.byref(d), _p(x), _p(dskip), 0, _p(dpool), 0, D, H, W, _p(mean), _p(rstd),
+                                               _p(gamma), _p(beta), _p(dx), _p(dg), _p(db), training, _p(ws), ws.numel(),
+                                               self._stream()), "norm_act_bwd_pool")
         return dx, dg, db
 
     def norm_act_pool_fwd(self, x, mean, rstd, gamma, beta, groups, act, eps=1e-5, slope=0.01, out=None, out_pooled=None):
@@ -859,7 +1137,7 @@ class RawOps:
         N, Cc, D, H, W = x.shape
         oshape = (N, Cc, D // 2, H // 2, W // 2)
         y = self._out(out, oshape)
-        idx = torch.full(oshape, 255, dtype=torch.uint8, device=self.device) if route else None
+        idx = self._out(None, oshape, torch.uint8, fill=255) if route else None
         self._chk(self.fn("maxpool3d_2x_fwd")(_p(x), _p(y), _p(idx), N, Cc, D, H, W, _bs(x), _bs(y), self._stream()), "maxpool_fwd")
         return y, idx
 
@@ -876,7 +1154,7 @@ class RawOps:
         D, H, W = spatial
         N, CB = x16.shape[0], (Cc + 7) // 8
         y16 = self._out(out, (N, CB, D * H * W // 8, 8), x16.dtype, fill=7.0)
-        idx8 = torch.full((N, CB, D * H * W // 8, 8), 255, dtype=torch.uint8, device=self.device) if route else None
+        idx8 = self._out(None, (N, CB, D * H * W // 8, 8), torch.uint8, fill=255) if route else None
         self._chk(self.fn("maxpool3d_2x_fwd_h16")(_p(x16), _p(y16), _p(idx8), N, Cc, D, H, W, _bs(x16), _bs(y16), compute,
                                                   self._stream()), "maxpool_fwd_h16")
         return y16, idx8
@@ -950,7 +1228,7 @@ class RawOps:
     def blur_weight_bwd(self, dwexp, w, scale, ms, standardize, transposed):
         dwexp, w, scale, ms = map(self.to, (dwexp, w, scale, ms))
         A, B = w.shape[:2]
-        dw = torch.empty_like(w)
+        dw = self.empty(*w.shape, dtype=w.dtype)
         self._chk(self.fn("blur_weight_bwd")(_p(dwexp), _p(w), _p(scale), _p(ms), _p(dw), A, B, int(standardize),
                                              int(transposed), self._stream()), "blur_weight_bwd")
         return dw
@@ -958,13 +1236,13 @@ class RawOps:
     def weight_standardize_fwd(self, w):
         w = self.to(w)
         A, n = w.shape[0], w[0].numel()
-        wn, ms = torch.empty_like(w), self.empty(A, 2)
+        wn, ms = self.empty(*w.shape, dtype=w.dtype), self.empty(A, 2)
         self._chk(self.fn("weight_standardize_fwd")(_p(w), _p(wn), _p(ms), A, n, self._stream()), "weight_standardize_fwd")
         return wn, ms
 
     def weight_standardize_bwd(self, dwn, w, ms):
         dwn, w, ms = map(self.to, (dwn, w, ms))
-        dw = torch.empty_like(w)
+        dw = self.empty(*w.shape, dtype=w.dtype)
         self._chk(self.fn("weight_standardize_bwd")(_p(dwn), _p(w), _p(ms), _p(dw), w.shape[0], w[0].numel(),
                                                     self._stream()), "weight_standardize_bwd")
         return dw
@@ -1032,7 +1310,7 @@ class RawOps:
         x = self.to(x)
         N, Ct = x.shape[:2]
         S = x.numel() // (N * Ct)
-        y = torch.empty_like(x)
+        y = self.empty(*x.shape, dtype=x.dtype)
         self._chk(self.fn("softmax_fwd")(_p(x), _p(y), N, Ct // inner, inner, S, diag_bias, self._stream()),
                   "softmax_fwd")
         return y
@@ -1041,7 +1319,7 @@ class RawOps:
         y, dy = self.to(y), self.to(dy)
         N, Ct = y.shape[:2]
         S = y.numel() // (N * Ct)
-        dx = torch.empty_like(y)
+        dx = self.empty(*y.shape, dtype=y.dtype)
         self._chk(self.fn("softmax_bwd")(_p(y), _p(dy), _p(dx), N, Ct // inner, inner, S, self._stream()),
                   "softmax_bwd")
         return dx
@@ -1053,7 +1331,7 @@ class RawOps:
         S = p.numel() // (N * Cc)
         out3, sums = self.empty(3), self.empty(N * Cc * 4)
         nws = self.lib.m355_hybrid_loss_workspace(N, Cc, S) if self.backend == "hip" else 16
-        ws = torch.empty(max(nws, 16), dtype=torch.uint8, device=self.device)
+        ws = self._workspace(nws)
         self._chk(self.fn("hybrid_loss_fwd")(_p(p), _p(t), N, Cc, S, dice_weight, _p(cw), int(square), _p(out3),
                                              _p(sums), _p(ws), ws.numel(), self._stream()), "loss_fwd")
         return out3, sums
@@ -1063,7 +1341,7 @@ class RawOps:
         N, Cc = p.shape[:2]
         S = p.numel() // (N * Cc)
         g = torch.tensor([dloss], dtype=torch.float32, device=self.device)
-        dp = torch.empty_like(p)
+        dp = self.empty(*p.shape, dtype=p.dtype)
         self._chk(self.fn("hybrid_loss_bwd")(_p(p), _p(t), _p(sums), _p(g), N, Cc, S, dice_weight, _p(cw),
                                              int(square), _p(dp), self._stream()), "loss_bwd")
         return dp
@@ -1086,7 +1364,7 @@ class RawOps:
         count = torch.zeros(tuple(vshape), device=self.device)
         self._chk(self.fn("patch_accumulate")(_p(patches), _p(loc), _p(accum), _p(count), P, Cc, *vshape, *ps,
                                               self._stream()), "patch_accumulate")
-        out = torch.empty_like(accum)
+        out = self.empty(*accum.shape, dtype=accum.dtype)
         self._chk(self.fn("patch_finalize")(_p(accum), _p(count), _p(out), Cc, count.numel(), self._stream()),
                   "patch_finalize")
         return out, count
@@ -1095,8 +1373,8 @@ class RawOps:
         prob, target = self.to(prob), self.to(target.to(torch.int32))
         N, Cc = prob.shape[:2]
         S = prob.numel() // (N * Cc)
-        am = torch.empty(target.shape, dtype=torch.int32, device=self.device)
-        counts = torch.empty((N, Cc, 4), dtype=torch.int64, device=self.device)
+        am = self.empty(*target.shape, dtype=torch.int32)
+        counts = self.empty(N, Cc, 4, dtype=torch.int64)
         self._chk(self.fn("argmax_confusion")(_p(prob), _p(target), _p(am), _p(counts), N, Cc, S, self._stream()),
                   "argmax_confusion")
         return am, counts
