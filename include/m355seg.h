@@ -835,6 +835,68 @@ int m355_topk_loss_bwd(const float* x, const float* t, const float* e, const flo
                        const float* dloss /* device scalar */, int32_t N, int32_t C, int64_t S, float dice_weight,
                        const float* class_weights, int32_t square_dice, int32_t from_logits, float* dx, void* stream);
 
+/* ------------------------------------------------ segmented radix sort
+ * R segments of M 32-bit keys each, dense [R, M], sorted ascending segment by segment (csrc/segmented_sort.hip, DESIGN
+ * §4.30): an LSD radix sort over the bits [0, end_bit) in ceil(end_bit / 8) passes of 8-bit digits; the bits above end_bit
+ * travel with their key and do not order it.  Key-only.  `keys` is not written; `out` must not overlap it.
+ * Every pass is stable: within a workgroup a key's rank comes from wave-wide digit matching (64-bit ballots) and per-wave
+ * digit counts in LDS, added in wave order and, by a scan kernel, in tile order.  Integer atomics count a tile's digits;
+ * none decides a position, so a call repeats bit for bit.  No allocation, synchronisation or host read: it can be
+ * captured in a graph.
+ *   workspace = round_up(4 R M, 256) + 4 * 256 * R * (ceil(M / tile) + 1) + 256 bytes (the second key buffer, the digit
+ *   counts of the tiles and of the segments), tile = m355_segmented_sort_tile() keys per workgroup;
+ *   m355_segmented_sort_workspace is 0 for a non-positive size.
+ * Errors, nothing is launched: null pointer, non-positive size, end_bit outside [1, 32], keys == out M355_EINVALID_ARG;
+ * R > 65535 or M > 2^31 - 1 M355_EUNSUPPORTED; workspace M355_EWORKSPACE.
+ */
+size_t m355_segmented_sort_workspace(int64_t R, int64_t M);
+int32_t m355_segmented_sort_tile(void);
+int m355_segmented_sort_u32(const uint32_t* keys, uint32_t* out, int64_t R, int64_t M, int32_t end_bit, void* workspace,
+                            size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------ Lovasz-softmax loss
+ * LovaszLoss (criterions/lovasz_loss.py; Berman et al., CVPR 2018): the convex surrogate of the Jaccard
+ * index.  p (probabilities) and the target t: dense fp32 [N, C, S], rows at nc * S for any S (no alignment requirement).
+ *   segments   per_image == 0: one per channel over the M = N S voxels of the batch, R = C; per_image != 0: one per
+ *              (n, c), M = S, R = N C
+ *   element    fg = (t >= 0.5), e = |fg - p| in one fp32 subtraction, G = the segment's foreground count
+ *   sorted by e, descending: F(i) = the foreground elements among the first i, I(i) = G - F(i), U(i) = G + i - F(i),
+ *              J(0) = 0, J(i) = 1 - I(i) / U(i);  L_r = sum_i e_(i) (J(i) - J(i - 1))
+ *   ties       the elements of one value of e are a group [lo, hi) of the sorted order and each gets
+ *              dL_r/de = (J(hi) - J(lo)) / (hi - lo), the mean of the subgradients of every order of the group;
+ *              J(hi) - J(lo) = (I(lo) U(hi) - I(hi) U(lo)) / (U(lo) U(hi)) from 64-bit integer products and one fp64
+ *              division (J(hi) for lo = 0);  de/dp = -1 for foreground, +1 for background, also at e = 0
+ *   reduction  a segment takes part when all_classes != 0 or G > 0, with weight class_weights[c] (NULL: 1, expected
+ *              >= 0).  per_image == 0: loss = sum_c w_c L_c / sum_c w_c over them; per_image != 0: that mean per image
+ *              first (0 for an image without a segment), then the mean over the N images.  Nothing to average: loss 0,
+ *              gradient 0.  The decision is taken on the device.
+ *   out2 = {loss, the number of segments of non-zero weight that took part}
+ * A NaN or a prediction outside [0, 1] gives a NaN loss and gradient; the key pass clamps such an e to [0, 1] and raises a
+ * status word that the finalize kernel reads, so no access leaves the buffers.
+ * Kept for backward: sorted_keys [R, M] (key = ~((bits(e) << 1) | fg) & 0x7fffffff, ascending: 31 bits, since e <= 1
+ * means bits(e) < 2^30), F [R, M] (F(i) for i = 0 .. M - 1) and state [R x 2 words] = {G, the segment's coefficient
+ * dloss/dL_r as fp32}: 8 bytes per (class, voxel).
+ *   workspace = round_up(4 R M, 256) + round_up(m355_segmented_sort_workspace(R, M), 256) + round_up(4 R T, 256) + 8 R T
+ *   + 8 R + 256 bytes, T = ceil(M / tile), tile = m355_lovasz_loss_tile(): the unsorted keys, the sort's workspace, the
+ *   tiles' foreground counts and fp64 partial losses, L_r, the status word.  0 for sizes the entry points refuse.
+ * Deterministic: the sort decides no position by an atomic and equal keys are equal elements; the sums are fp64, per
+ * lane in index order, then block and tile sums in a fixed order; the one atomic is the OR into the status word.  A
+ * misaligned view gives the bits of its aligned copy.  Errors: null pointer, non-positive size M355_EINVALID_ARG;
+ * N*C > 65535 or M > 2^31 - 1 M355_EUNSUPPORTED; workspace M355_EWORKSPACE; nothing is launched then.
+ */
+size_t m355_lovasz_loss_workspace(int32_t N, int32_t C, int64_t S, int32_t per_image);
+int32_t m355_lovasz_loss_tile(void);
+int m355_lovasz_loss_fwd(const float* p, const float* t, int32_t N, int32_t C, int64_t S, int32_t per_image,
+                         int32_t all_classes, const float* class_weights /* [C] or NULL */, float* out2,
+                         uint32_t* sorted_keys /* [R*M] */, uint32_t* F /* [R*M] */, void* state /* 8 R bytes */,
+                         void* workspace, size_t workspace_bytes, void* stream);
+/* dx = dloss * d(loss)/dp in one launch: every element recomputes its key, finds its group [lo, hi) by two binary
+ * searches on key >> 1 in its segment's sorted keys, reads F(lo) and F(hi) and writes
+ * dx = dloss * coefficient * sign * (J(hi) - J(lo)) / (hi - lo).  Writes dx[0, N*C*S). */
+int m355_lovasz_loss_bwd(const float* p, const float* t, const uint32_t* sorted_keys, const uint32_t* F,
+                         const void* state, const float* dloss /* device scalar */, int32_t N, int32_t C, int64_t S,
+                         int32_t per_image, float* dx, void* stream);
+
 /* ------------------------------------------------ target pyramid (deep supervision)
  * The targets of the auxiliary heads of models.DeepSupervisionUNet (criterions.DeepSupervisionLoss): one
  * launch reads a dense fp32 target y[N, C, D, H, W] once and writes its `levels` coarser levels, level j (1 <= j <= levels)

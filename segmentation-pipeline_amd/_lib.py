@@ -292,6 +292,13 @@ SIGNATURES = {
     "m355_topk_loss_workspace": (_sz, [_i32, _i32, _i64]),
     "m355_topk_loss_fwd": (C.c_int, [_P, _P, _i32, _i32, _i64, _i64, _P, _f32, _P, _i32, _i32, _P, _P, _P, _P, _P, _sz, _P]),
     "m355_topk_loss_bwd": (C.c_int, [_P, _P, _P, _P, _P, _P, _i32, _i32, _i64, _f32, _P, _i32, _i32, _P, _P]),
+    "m355_segmented_sort_workspace": (_sz, [_i64, _i64]),
+    "m355_segmented_sort_tile": (_i32, []),
+    "m355_segmented_sort_u32": (C.c_int, [_P, _P, _i64, _i64, _i32, _P, _sz, _P]),
+    "m355_lovasz_loss_workspace": (_sz, [_i32, _i32, _i64, _i32]),
+    "m355_lovasz_loss_tile": (_i32, []),
+    "m355_lovasz_loss_fwd": (C.c_int, [_P, _P, _i32, _i32, _i64, _i32, _i32, _P, _P, _P, _P, _P, _P, _sz, _P]),
+    "m355_lovasz_loss_bwd": (C.c_int, [_P, _P, _P, _P, _P, _P, _i32, _i32, _i64, _i32, _P, _P]),
     "m355_target_pyramid_elems": (_i64, [_i32, _i32, _i32, _i32, _i32, _i32]),
     "m355_target_pyramid": (C.c_int, [_P, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _P, _P]),
     "m355_copy_channels": (C.c_int, [_P, _P, _i32, _i32, _i64, _i64, _i64, _P]),

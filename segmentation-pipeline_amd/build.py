@@ -11,7 +11,7 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libm355seg.so")
-SOURCES = ["abi.cpp", "conv3d.hip", "conv3d_host.hip", "conv3d_f32x3.hip", "conv3d_h16.hip", "act16.hip", "train16.hip", "norm.hip", "elementwise.hip", "convt.hip", "loss_patch_eval.hip", "hybrid_loss.hip", "binary_loss.hip", "focal_tversky_loss.hip", "topk_loss.hip", "boundary_loss.hip", "blob_loss.hip", "target_pyramid.hip", "ensemble.hip",
+SOURCES = ["abi.cpp", "conv3d.hip", "conv3d_host.hip", "conv3d_f32x3.hip", "conv3d_h16.hip", "act16.hip", "train16.hip", "norm.hip", "elementwise.hip", "convt.hip", "loss_patch_eval.hip", "hybrid_loss.hip", "binary_loss.hip", "focal_tversky_loss.hip", "topk_loss.hip", "segmented_sort.hip", "lovasz_loss.hip", "boundary_loss.hip", "blob_loss.hip", "target_pyramid.hip", "ensemble.hip",
            "blur_weights.hip", "components.hip", "augment.hip", "preprocess.hip", "evaluate.hip",
            "dwi.hip", "contour.hip", "maxpool.hip", "upsample.hip", "distance.hip", "region_stats.hip", "optimizer.hip"]
 HEADERS = [os.path.join(CSRC, h) for h in ("common.hpp", "h16.hpp", "norm_host.hpp", "activation.hpp", "resample_host.hpp", "conv3d_common.hpp", "conv3d_route.hpp", "h16_epilogue.hpp", "ev_load.hpp", "loss_common.hpp")] + \

@@ -6,3 +6,4 @@ from .hybrid_topk_dice_loss import HybridTopKDiceLoss
 from .deep_supervision_loss import DeepSupervisionLoss
 from .boundary_loss import BoundaryLoss
 from .blob_loss import BlobLoss
+from .lovasz_loss import LovaszLoss

@@ -2245,6 +2245,75 @@ def topk_logistic_dice_loss(x, target, top_k, dice_weight=0.5, class_weights=Non
     return _TopKLossFn.apply(x, target, top_k, dice_weight, class_weights, square_dice, from_logits)
 
 
+# ------------------------------------- segmented sort and the Lovasz-softmax loss (csrc/lovasz_loss.hip)
+def segmented_sort(keys):
+    """The rows of `keys` (int32 [R, M] on the device, values >= 0) sorted ascending, each row by itself: a stable LSD
+    radix sort over the 31 value bits (csrc/segmented_sort.hip).  Returns a new tensor; nothing is read on the host, a
+    call repeats bit for bit and can be captured in a graph.  A negative value keeps its sign bit but is ordered by its
+    low 31 bits."""
+    if not isinstance(keys, torch.Tensor) or keys.dtype != torch.int32:
+        got = keys.dtype if isinstance(keys, torch.Tensor) else type(keys).__name__
+        raise _lib.M355Error(f"segmented_sort: keys: element type {got} (expected torch.int32)")
+    if keys.dim() != 2 or keys.numel() == 0:
+        raise _lib.M355Error(f"segmented_sort: keys of shape {tuple(keys.shape)}: expected a non-empty [R, M]")
+    _require(keys, dtype=torch.int32)
+    L = _lib.lib()
+    keys = keys.contiguous()
+    R, M = keys.shape
+    out = torch.empty_like(keys)
+    with torch.cuda.device(keys.device):
+        ws = _workspace(L.m355_segmented_sort_workspace(R, M), keys.device)
+        check(L.m355_segmented_sort_u32(_p(keys), _p(out), R, M, 31, _p(ws), ws.numel(), _stream()), "segmented_sort_u32")
+    return out
+
+
+LOVASZ_CLASSES = ("present", "all")
+
+
+class _LovaszLossFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, p, t, classes, per_image, class_weights):
+        L = _lib.lib()
+        p, t, (cw,), N, Cc, S = _loss_operands((("prediction", p), ("target", t)), (("class_weights", class_weights),))
+        pi = 1 if per_image else 0
+        R, M = (N * Cc, S) if pi else (Cc, N * S)
+        out2 = torch.empty(2, dtype=torch.float32, device=p.device)
+        # saved: not the workspace, which the next op reuses -- 8 bytes per (class, voxel)
+        skeys = torch.empty(R * M, dtype=torch.int32, device=p.device)
+        F = torch.empty(R * M, dtype=torch.int32, device=p.device)
+        state = torch.empty(2 * R, dtype=torch.int32, device=p.device)   # {G, coefficient} per segment
+        ws = _workspace(L.m355_lovasz_loss_workspace(N, Cc, S, pi), p.device)
+        check(L.m355_lovasz_loss_fwd(_p(p), _p(t), N, Cc, S, pi, 1 if classes == "all" else 0, _p(cw), _p(out2), _p(skeys),
+                                     _p(F), _p(state), _p(ws), ws.numel(), _stream()), "lovasz_loss_fwd")
+        ctx.args = (N, Cc, S, pi)
+        ctx.save_for_backward(p, t, skeys, F, state)
+        return torch.empty((), dtype=torch.float32, device=p.device).set_(out2.untyped_storage(), 0, ())
+
+    @staticmethod
+    def backward(ctx, dloss):
+        L = _lib.lib()
+        p, t, skeys, F, state = ctx.saved_tensors
+        N, Cc, S, pi = ctx.args
+        dx = torch.empty_like(p)
+        check(L.m355_lovasz_loss_bwd(_p(p), _p(t), _p(skeys), _p(F), _p(state), _p(_dloss32(dloss)), N, Cc, S, pi, _p(dx),
+                                     _stream()), "lovasz_loss_bwd")
+        return dx, None, None, None, None
+
+
+def lovasz_loss(prediction, target, classes='present', per_image=False, class_weights=None):
+    """The Lovasz-softmax loss of Berman et al., a 0-dim tensor: the convex surrogate of the Jaccard index
+    of the fp32 probabilities `prediction` [N, C, ...] against `target` (a voxel is foreground of channel c where
+    target >= 0.5), one binary problem per channel -- so it serves a softmax and a sigmoid head alike.
+    per_image=False: one Jaccard surrogate per channel over the whole batch; True: per (n, c), averaged per image first.
+    classes: 'present' averages the channels that have a foreground voxel, 'all' every channel; class_weights: an fp32
+    device tensor [C] of values >= 0 or None; nothing to average gives 0.  Elements with equal errors share the mean of
+    their subgradients, so loss and gradient repeat bit for bit.  A NaN or a prediction outside [0, 1] gives a NaN loss and
+    gradient.  Nothing is read on the host.  The gradient flows to the prediction only."""
+    if classes not in LOVASZ_CLASSES:
+        raise ValueError(f"lovasz_loss: classes = {classes!r}: expected 'present' or 'all'")
+    return _LovaszLossFn.apply(prediction, target, classes, bool(per_image), class_weights)
+
+
 class _BoundaryLossFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, p, phi, class_weights):
