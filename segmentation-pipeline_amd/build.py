@@ -3,6 +3,7 @@
 hipcc cross-compiles without a GPU, so this runs in the build container; the
 resulting .so travels to the GPU box with the repo snapshot.
 """
+import glob
 import os
 import subprocess
 import sys
@@ -14,8 +15,7 @@ LIB = os.path.join(HERE, "libm355seg.so")
 SOURCES = ["abi.cpp", "conv3d.hip", "conv3d_host.hip", "conv3d_f32x3.hip", "conv3d_h16.hip", "act16.hip", "train16.hip", "norm.hip", "elementwise.hip", "convt.hip", "loss_patch_eval.hip", "hybrid_loss.hip", "binary_loss.hip", "focal_tversky_loss.hip", "topk_loss.hip", "segmented_sort.hip", "lovasz_loss.hip", "boundary_loss.hip", "blob_loss.hip", "target_pyramid.hip", "ensemble.hip",
            "blur_weights.hip", "components.hip", "augment.hip", "preprocess.hip", "evaluate.hip",
            "dwi.hip", "contour.hip", "maxpool.hip", "upsample.hip", "distance.hip", "region_stats.hip", "optimizer.hip"]
-HEADERS = [os.path.join(CSRC, h) for h in ("common.hpp", "h16.hpp", "norm_host.hpp", "activation.hpp", "resample_host.hpp", "conv3d_common.hpp", "conv3d_route.hpp", "h16_epilogue.hpp", "ev_load.hpp", "loss_common.hpp")] + \
-    [os.path.join(HERE, "..", "include", "m355seg.h")]
+HEADERS = sorted(glob.glob(os.path.join(CSRC, "*.hpp"))) + [os.path.join(HERE, "..", "include", "m355seg.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
 
 

@@ -6,21 +6,20 @@
 //                         displacement of a control grid held in LDS; nearest / trilinear / cubic B-spline, element
 //                         sizes 1 / 4 / 8 (nearest only for 1 and 8), pad value per channel from device memory
 //   aug_prefilter_kernel  cubic B-spline coefficients, in place, one thread per line (scipy spline_filter, mode mirror)
-//   aug_hist_kernel       radix select of exact order statistics (3 passes of 11 / 11 / 10 bits on order-preserving
-//   aug_pick_kernel       keys, LDS-privatised histograms, one-workgroup pick between passes), or one min / max pass
+//   aug_hist_kernel       exact order statistics by the radix select of radix_select.hpp: up to RADIX_Q ranks at once,
+//   aug_pick_kernel       one wave of the one-workgroup pick per rank; or one min / max pass
 //   aug_intensity_kernel  fused intensity program: bias field, clip + rescale, gamma, noise (Philox4x32-10)
 //   aug_blur_kernel       one axis of the separable Gaussian (scipy gaussian_filter, mode reflect), program epilogue
 //   aug_otsu_kernel       Otsu border pad value, one workgroup per channel
 //   aug_channel_minmax_kernel  per-channel min or max (the 'minimum' pad value) of all channels in one pass
 // Statistics a stage needs (percentile cutoffs, min / max) are written to device memory by the select kernels and read
 // there by the kernel that applies the stage: no host round trip.  Only integer atomics: results are deterministic.
-#include "common.hpp"
+#include "radix_select.hpp"
 
 namespace m355 {
 
 constexpr int AUG_NT = 256;
 constexpr int AUG_MAX_GRID = 4096;       // floats of the control grid in LDS (7x7x4x3 = 588)
-constexpr int RADIX_BINS = 2048;
 constexpr int RADIX_Q = 4;               // keys selected at once: floor / ceil rank of two percentiles
 constexpr int OTSU_BINS = 128;
 constexpr int OTSU_NT = 1024;
@@ -36,14 +35,6 @@ struct Program {
 };
 
 // ------------------------------------------------------------------------------------------------ helpers
-__device__ __forceinline__ uint32_t f2key(float f) {
-  const uint32_t u = __float_as_uint(f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float key2f(uint32_t k) {
-  return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
-}
-
 __device__ __forceinline__ void philox_round(uint32_t c[4], uint32_t k0, uint32_t k1) {
   const uint32_t M0 = 0xD2511F53u, M1 = 0xCD9E8D57u;
   const uint32_t hi0 = __umulhi(M0, c[0]), lo0 = M0 * c[0];
@@ -348,14 +339,13 @@ __global__ __launch_bounds__(AUG_NT) void aug_hist_kernel(const float* __restric
                                                           int pass, int nq, RadixState* __restrict__ st,
                                                           uint32_t* __restrict__ hist) {
   __shared__ uint32_t lh[RADIX_Q][RADIX_BINS];
-  const int shift = pass == 0 ? 21 : pass == 1 ? 10 : 0;
-  const uint32_t mask = pass == 2 ? 1023u : 2047u;
+  const RadixDigit dg = radix_digit(pass);
   if (pass >= 0) {
-    for (int i = threadIdx.x; i < RADIX_Q * RADIX_BINS; i += AUG_NT) (&lh[0][0])[i] = 0u;
+    radix_hist_clear<AUG_NT>(&lh[0][0], RADIX_Q * RADIX_BINS);
     __syncthreads();
   }
   uint32_t pre[RADIX_Q];
-  for (int j = 0; j < RADIX_Q; ++j) pre[j] = pass > 0 && j < nq ? st->prefix[j] >> (shift + (pass == 2 ? 10 : 11)) : 0u;
+  for (int j = 0; j < RADIX_Q; ++j) pre[j] = pass > 0 && j < nq ? st->prefix[j] >> dg.upper : 0u;
   uint32_t kmin = 0u, kmax = 0u;
   for (int64_t i = blockIdx.x * (int64_t)AUG_NT + threadIdx.x; i < n; i += (int64_t)gridDim.x * AUG_NT) {
     const uint32_t key = f2key(run_program(x[i], i, P, upto));
@@ -364,8 +354,8 @@ __global__ __launch_bounds__(AUG_NT) void aug_hist_kernel(const float* __restric
       kmax = max(kmax, key);
       continue;
     }
-    const uint32_t hi = pass == 0 ? 0u : key >> (shift + (pass == 2 ? 10 : 11));
-    const uint32_t d = (key >> shift) & mask;
+    const uint32_t hi = pass == 0 ? 0u : key >> dg.upper;
+    const uint32_t d = radix_digit_of(key, dg);
     for (int j = 0; j < nq; ++j)
       if (hi == pre[j]) atomicAdd(&lh[j][d], 1u);
   }
@@ -378,10 +368,7 @@ __global__ __launch_bounds__(AUG_NT) void aug_hist_kernel(const float* __restric
     return;
   }
   __syncthreads();
-  for (int i = threadIdx.x; i < nq * RADIX_BINS; i += AUG_NT) {
-    const uint32_t c = (&lh[0][0])[i];
-    if (c) atomicAdd(&hist[i], c);
-  }
+  radix_hist_flush<AUG_NT>(&lh[0][0], hist, nq * RADIX_BINS);
 }
 
 // numpy's _lerp: a + (b - a) t, or b - (b - a)(1 - t) when t >= 0.5
@@ -400,33 +387,16 @@ struct PickArgs {
 __global__ __launch_bounds__(AUG_NT) void aug_pick_kernel(int pass, int nq, RadixState* __restrict__ st,
                                                           uint32_t* __restrict__ hist, PickArgs pa, double* out,
                                                           int nout) {
-  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int shift = pass == 0 ? 21 : pass == 1 ? 10 : 0;
+  const int w = threadIdx.x >> 6;
   if (w < nq) {
-    uint32_t* h = hist + w * RADIX_BINS;
-    const uint32_t k = st->rank[w];
-    uint32_t part = 0;
-    for (int i = 0; i < 32; ++i) part += h[lane * 32 + i];
-    uint32_t incl = part;   // inclusive scan over lanes
-    for (int off = 1; off < 64; off <<= 1) {
-      const uint32_t o = (uint32_t)__shfl_up((int)incl, off, 64);
-      if (lane >= off) incl += o;
-    }
-    const uint32_t excl = incl - part;
-    if (k >= excl && k < incl) {   // exactly one lane
-      uint32_t cum = excl;
-      int d = 0;
-      for (; d < 32; ++d) {
-        const uint32_t c = h[lane * 32 + d];
-        if (k < cum + c) break;
-        cum += c;
-      }
-      st->prefix[w] |= (uint32_t)(lane * 32 + d) << shift;
-      st->rank[w] = k - cum;
+    uint32_t digit, rest;
+    if (radix_pick_wave(hist + w * RADIX_BINS, st->rank[w], digit, rest)) {   // exactly one lane
+      st->prefix[w] |= digit << radix_digit(pass).shift;
+      st->rank[w] = rest;
     }
   }
   __syncthreads();
-  for (int i = threadIdx.x; i < nq * RADIX_BINS; i += AUG_NT) hist[i] = 0u;
+  radix_hist_clear<AUG_NT>(hist, nq * RADIX_BINS);
   if (pass == 2 && threadIdx.x == 0) {
     for (int q = 0; q < nout; ++q)
       out[q] = np_lerp((double)key2f(st->prefix[2 * q]), (double)key2f(st->prefix[2 * q + 1]), pa.fr[q]);

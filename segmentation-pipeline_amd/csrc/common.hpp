@@ -47,6 +47,17 @@ __device__ __forceinline__ T wave_sum(T v) {
   return v;
 }
 
+// inclusive prefix sum over the 64 lanes of a wave
+__device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v) {
+  const int lane = threadIdx.x & 63;
+#pragma unroll
+  for (int off = 1; off < 64; off <<= 1) {
+    const uint32_t o = (uint32_t)__shfl_up((int)v, off, 64);
+    if (lane >= off) v += o;
+  }
+  return v;
+}
+
 // block-wide sum for blockDim.x == NT (multiple of 64); result valid in thread 0
 // (and broadcast to all when BCAST).  `scratch` must hold NT/64 elements.
 template <typename T, int NT, bool BCAST = false>

@@ -148,12 +148,7 @@ __global__ __launch_bounds__(LV_THREADS) void lv_totals_kernel(const uint32_t* _
 // exclusive scan of `v` over the block, `total` in every thread; sh: LV_THREADS / 64 words
 __device__ __forceinline__ uint32_t lv_block_excl(uint32_t v, uint32_t& total, uint32_t* sh) {
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  uint32_t incl = v;
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const uint32_t o = (uint32_t)__shfl_up((int)incl, off, 64);
-    if (lane >= off) incl += o;
-  }
+  const uint32_t incl = wave_incl_scan(v);
   __syncthreads();   // sh may still be read from the round before
   if (lane == 63) sh[w] = incl;
   __syncthreads();

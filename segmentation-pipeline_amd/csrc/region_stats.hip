@@ -24,10 +24,10 @@
 // turn before a butterfly over the lanes: a fixed order again.  Min / max keys and histograms are integers and use
 // integer atomics as well.  No floating-point atomic anywhere: two calls give the same bits.
 //
-// The select is augment.hip's: keys f2key(x) that order like the floats, three passes of 11 / 11 / 10 bits, histograms
-// privatised in LDS.  RS_HG histograms of 2048 bins fit a block, so a pass runs ceil((L + 2) / RS_HG) region groups as
-// grid.y; each group reads the volume and counts only its own regions.
-#include "common.hpp"
+// The median is the radix select of radix_select.hpp, one query per region.  RS_HG histograms of RADIX_BINS bins fit a
+// block, so a pass runs ceil((L + 2) / RS_HG) region groups as grid.y; each group reads the volume and counts only its
+// own regions.
+#include "radix_select.hpp"
 #include <hip/hip_fp16.h>
 #include <limits.h>
 #include <math.h>
@@ -39,7 +39,6 @@ using namespace m355;
 constexpr int RS_NT = 256;          // threads of a block
 constexpr int RS_U = 8;             // voxels a lane loads ahead per step of the grid-stride loop
 constexpr int RS_GRID_CAP = 1024;   // blocks along x: four per CU
-constexpr int RS_BINS = 2048;
 constexpr int RS_HG = 7;            // histograms (regions) of one block of a select pass: 56 KB of LDS
 constexpr int RS_MAX_L = 64;
 constexpr int RS_MAX_R = RS_MAX_L + 2;
@@ -49,17 +48,6 @@ struct Keys {
   int32_t k[RS_MAX_L];   // the label values as keys of the map's element type
   int32_t L, nokey;
 };
-
-// the key transform of augment.hip: unsigned keys that order like the floats (-nan < -inf < ... < +inf < +nan)
-__device__ __forceinline__ uint32_t f2key(float f) {
-  const uint32_t u = __float_as_uint(f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float key2f(uint32_t k) {
-  return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
-}
-constexpr uint32_t KEY_PINF = 0xff800000u;   // f2key(+inf): every larger key is a NaN
-constexpr uint32_t KEY_NINF = 0x007fffffu;   // f2key(-inf): every smaller key is a NaN
 
 __host__ __device__ __forceinline__ int32_t fkey(float f, int32_t nokey) {
   return (f == truncf(f) && fabsf(f) < 2147483520.f) ? (int32_t)f : nokey;
@@ -389,21 +377,18 @@ __global__ __launch_bounds__(RS_NT) void rs_scan_kernel(const void* __restrict__
   __shared__ double sdev[RS_NT / 64][RS_MAX_L];
   __shared__ uint32_t spre[RS_MAX_R];
   __shared__ double scratch[RS_NT / 64];
-  __shared__ uint32_t lh[HIST ? RS_HG : 1][RS_BINS];
+  __shared__ uint32_t lh[HIST ? RS_HG : 1][RADIX_BINS];
   const int R = K.L + 2;
   const int g0 = blockIdx.y * gsize, g1 = min(R, g0 + gsize);
-  const int shift = pass == 0 ? 21 : pass == 1 ? 10 : 0;
-  const int upper = shift + (pass == 2 ? 10 : 11);   // bits below the digits already fixed
-  const uint32_t mask = pass == 2 ? 1023u : 2047u;
+  const RadixDigit dg = radix_digit(pass);
   stage_keys(skeys, K);
   for (int r = threadIdx.x; r < RS_MAX_R; r += RS_NT) {
     smean[r] = DEV && r < R ? mean[r] : 0.0;
-    spre[r] = HIST && pass > 0 && r < R ? prefix[r] >> upper : 0u;
+    spre[r] = HIST && pass > 0 && r < R ? prefix[r] >> dg.upper : 0u;
   }
   if (DEV)
     for (int j = threadIdx.x; j < (RS_NT / 64) * RS_MAX_L; j += RS_NT) (&sdev[0][0])[j] = 0.0;
-  if (HIST)
-    for (int j = threadIdx.x; j < RS_HG * RS_BINS; j += RS_NT) (&lh[0][0])[j] = 0u;
+  if (HIST) radix_hist_clear<RS_NT>(&lh[0][0], RS_HG * RADIX_BINS);
   __syncthreads();
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const bool has_all = K.L >= g0 && K.L < g1, has_whole = K.L + 1 >= g0 && K.L + 1 < g1;
@@ -441,11 +426,11 @@ __global__ __launch_bounds__(RS_NT) void rs_scan_kernel(const void* __restrict__
         }
         if (HIST) {
           const uint32_t key = f2key(xs[u]);
-          const uint32_t hi = pass == 0 ? 0u : key >> upper;
-          const uint32_t dg = (key >> shift) & mask;
-          if (idx >= 0 && hi == spre[idx]) atomicAdd(&lh[idx - g0][dg], 1u);
-          if (in_all && hi == p_all) atomicAdd(&lh[K.L - g0][dg], 1u);
-          if (in_whole && hi == p_whole) atomicAdd(&lh[K.L + 1 - g0][dg], 1u);
+          const uint32_t hi = pass == 0 ? 0u : key >> dg.upper;
+          const uint32_t d = radix_digit_of(key, dg);
+          if (idx >= 0 && hi == spre[idx]) atomicAdd(&lh[idx - g0][d], 1u);
+          if (in_all && hi == p_all) atomicAdd(&lh[K.L - g0][d], 1u);
+          if (in_whole && hi == p_whole) atomicAdd(&lh[K.L + 1 - g0][d], 1u);
         }
       }
     }
@@ -468,45 +453,25 @@ __global__ __launch_bounds__(RS_NT) void rs_scan_kernel(const void* __restrict__
   }
   if (HIST) {
     __syncthreads();
-    const int n = (g1 - g0) * RS_BINS;
-    for (int j = threadIdx.x; j < n; j += RS_NT) {
-      const uint32_t cnt = (&lh[0][0])[j];
-      if (cnt) atomicAdd(&hist[(int64_t)g0 * RS_BINS + j], cnt);
-    }
+    radix_hist_flush<RS_NT>(&lh[0][0], hist + (int64_t)g0 * RADIX_BINS, (g1 - g0) * RADIX_BINS);
   }
 }
 
-// one wave per region (augment.hip's pick): the bucket of rank[r] extends prefix[r]; the histogram is cleared
+// one wave per region: the bucket of rank[r] extends prefix[r]; the histogram is cleared
 __global__ __launch_bounds__(64) void rs_pick_kernel(int pass, const int64_t* __restrict__ count,
                                                      uint32_t* __restrict__ prefix, uint32_t* __restrict__ rank,
                                                      uint32_t* __restrict__ hist) {
-  const int r = blockIdx.x, lane = threadIdx.x;
-  const int shift = pass == 0 ? 21 : pass == 1 ? 10 : 0;
-  uint32_t* h = hist + (int64_t)r * RS_BINS;
+  const int r = blockIdx.x;
+  uint32_t* h = hist + (int64_t)r * RADIX_BINS;
   if (count[r] > 0) {
-    const uint32_t k = rank[r];
-    uint32_t partial = 0;
-    for (int i = 0; i < 32; ++i) partial += h[lane * 32 + i];
-    uint32_t incl = partial;
-    for (int off = 1; off < 64; off <<= 1) {
-      const uint32_t o = (uint32_t)__shfl_up((int)incl, off, 64);
-      if (lane >= off) incl += o;
-    }
-    const uint32_t excl = incl - partial;
-    if (k >= excl && k < incl) {   // exactly one lane
-      uint32_t cum = excl;
-      int d = 0;
-      for (; d < 31; ++d) {
-        const uint32_t c = h[lane * 32 + d];
-        if (k < cum + c) break;
-        cum += c;
-      }
-      prefix[r] |= (uint32_t)(lane * 32 + d) << shift;
-      rank[r] = k - cum;
+    uint32_t digit, rest;
+    if (radix_pick_wave(h, rank[r], digit, rest)) {   // exactly one lane
+      prefix[r] |= digit << radix_digit(pass).shift;
+      rank[r] = rest;
     }
   }
   __syncthreads();
-  for (int i = lane; i < RS_BINS; i += 64) h[i] = 0u;
+  radix_hist_clear<64>(h, RADIX_BINS);
 }
 
 // one wave per region: stats[r][k][0..5) = mean, std, median, min, max of image k, and the min / max keys reset for
@@ -564,7 +529,7 @@ Layout layout_of(int L, int median) {
   o.rank = take(R * sizeof(uint32_t));
   o.kmm = take(2 * R * sizeof(uint32_t));
   o.part = take((size_t)RS_GRID_CAP * R * sizeof(double));
-  o.hist = take(median ? R * RS_BINS * sizeof(uint32_t) : 0);
+  o.hist = take(median ? R * RADIX_BINS * sizeof(uint32_t) : 0);
   o.total = at;
   return o;
 }
@@ -634,7 +599,7 @@ extern "C" int m355_region_stats(const void* labels, int32_t label_dtype, const 
   uint32_t* kmm = K ? (uint32_t*)(ws + lo.kmm) : nullptr;
   double* part = K ? (double*)(ws + lo.part) : nullptr;
   uint32_t* hist = K && median ? (uint32_t*)(ws + lo.hist) : nullptr;
-  const int64_t nhist = hist ? (int64_t)R * RS_BINS : 0;
+  const int64_t nhist = hist ? (int64_t)R * RADIX_BINS : 0;
   const unsigned nblk = (unsigned)std::max<int64_t>(1, std::min<int64_t>(ceil_div(S, RS_TILE), RS_GRID_CAP));
 
   hipLaunchKernelGGL(rs_init_kernel, dim3((unsigned)std::max<int64_t>(1, ceil_div(nhist, 4 * RS_NT))), dim3(RS_NT), 0, st,

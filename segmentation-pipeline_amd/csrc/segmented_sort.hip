@@ -46,17 +46,6 @@ __global__ __launch_bounds__(SS_THREADS) void ss_hist_kernel(const uint32_t* __r
   hist[(r * SS_BINS + threadIdx.x) * nblk + blockIdx.x] = lh[threadIdx.x];
 }
 
-// inclusive scan over the 64 lanes of a wave
-__device__ __forceinline__ uint32_t ss_wave_incl(uint32_t v) {
-  const int lane = threadIdx.x & 63;
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const uint32_t o = (uint32_t)__shfl_up((int)v, off, 64);
-    if (lane >= off) v += o;
-  }
-  return v;
-}
-
 // The scan, two launches of one wave per (digit, segment) row of hist: the row's total -> dtot[segment][digit]; then the
 // row's start -- the totals of the digits below it -- and the running prefix along the row, 64 tiles at a time.
 __global__ __launch_bounds__(64) void ss_rowsum_kernel(const uint32_t* __restrict__ hist, uint32_t* __restrict__ dtot,
@@ -83,7 +72,7 @@ __global__ __launch_bounds__(64) void ss_scan_kernel(uint32_t* __restrict__ hist
   for (int b0 = 0; b0 < nblk; b0 += 64) {
     const int b = b0 + lane;
     const uint32_t v = b < nblk ? row[b] : 0u;
-    const uint32_t in = ss_wave_incl(v);
+    const uint32_t in = wave_incl_scan(v);
     if (b < nblk) row[b] = run + in - v;
     run += (uint32_t)__shfl((int)in, 63, 64);
   }
@@ -141,7 +130,7 @@ __global__ __launch_bounds__(SS_THREADS) void ss_scatter_kernel(const uint32_t* 
     whist[i][threadIdx.x] = total;
     total += c;
   }
-  const uint32_t incl = ss_wave_incl(total);
+  const uint32_t incl = wave_incl_scan(total);
   if (lane == 63) wtot[w] = incl;
   gbase[threadIdx.x] = hist[(r * SS_BINS + threadIdx.x) * nblk + blockIdx.x];
   __syncthreads();

@@ -1,5 +1,6 @@
 // Top-k cross-entropy + Dice criterion (criterions/hybrid_topk_dice_loss.py): the log term averages only the
-// k largest per-voxel cross-entropies of the whole batch; the k-th largest is found by a radix select, not a sort.
+// k largest per-voxel cross-entropies of the whole batch; the k-th largest is found by the radix select of
+// radix_select.hpp (keys, digits, histograms and the descending block pick are there), not a sort.
 //
 //   e[n, s] = -sum_c w_c t[n,c,s] lp[n,c,s]      PROB    lp = log((x + eps) / (1 + eps)), p = x
 //                                                LOGITS  lp = log_softmax(x) over C, p = exp(lp) formed in registers
@@ -18,10 +19,10 @@
 // thousand words out of L2), which saves three one-wave launches.  k is a kernel argument or, with k_device, a device
 // int64 scalar clamped to [1, N*S]; only the picks and the backward depend on it.
 //
-// Histograms: LDS-privatised, flushed with integer atomics (they commute: the counts do not depend on the order).  Sums:
-// fp32 per lane in a fixed order, then fp64 across the block and across the chunks in a fixed order; no float atomics.
+// Sums: fp32 per lane in a fixed order, then fp64 across the block and across the chunks in a fixed order; no float atomics.
 // Loads and stores go through row_load / row_store, so a misaligned view gives the bits of its aligned clone.
 #include "loss_common.hpp"
+#include "radix_select.hpp"
 
 #include <cmath>
 
@@ -31,19 +32,15 @@ constexpr int TK_CHUNK = 4096;    // voxels per block of the first pass and of t
 constexpr int TK_CREG = 16;       // most channels whose per-voxel values are held in registers
 constexpr int TK_IT = TK_CHUNK / 1024;   // groups of 4 voxels per lane in the kernels that walk the planes
 constexpr int TK_ECHUNK = 4096;   // elements of e per block of the two select passes (8192 measured 4 us slower at 1 x 4 x 128^3)
-constexpr int TK_BINS = 2048;     // bins of one histogram (the last pass uses 1024 of them)
 constexpr int TK_K = 3;           // Dice sums per row
 
-// keys that order like the floats (augment.hip's f2key), with the two cases a loss has to pin down: every NaN is the
-// largest key, whatever its sign bit, so a NaN is selected first as torch.topk does; -0 is +0
+// f2key after the two cases a loss has to pin down: every NaN is the largest key, whatever its sign bit, so a NaN is
+// selected first as torch.topk does; -0 is +0 (bits2key is f2key on the float's bits, which these cases edit)
 __device__ __forceinline__ uint32_t tk_key(float f) {
   uint32_t u = __float_as_uint(f);
   if ((u & 0x7fffffffu) > 0x7f800000u) return 0xffffffffu;
   if (u == 0x80000000u) u = 0u;
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float tk_key2f(uint32_t k) {
-  return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
+  return bits2key(u);
 }
 
 // k of this call: the host's, or the device scalar's clamped to [1, M] (whatever it holds, the picks stay inside the
@@ -53,84 +50,18 @@ __device__ __forceinline__ int64_t tk_k(const int64_t* __restrict__ k_device, in
   return k < 1 ? 1 : k > M ? M : k;
 }
 
-// the select so far: the digits found, the 1-based rank among the keys that share them, how many keys lie above them and
-// how many are in the bin picked last
-struct TkSel {
-  uint32_t prefix, rank, n_eq;
-  uint64_t n_gt;
-};
-
-// One digit, by every thread of the block (256) with the same result: thread i owns BINS / 256 bins from the top down,
-// a scan over the threads finds the one whose bins hold rank `s.rank` counted from the largest key.  sh: 8 words of LDS.
-template <int BINS>
-__device__ __forceinline__ void tk_pick(const uint32_t* __restrict__ hist, int shift, TkSel& s, uint32_t* sh) {
-  constexpr int PER = BINS / 256;
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const int top = BINS - 1 - (int)threadIdx.x * PER;
-  uint32_t c[PER], part = 0;
-#pragma unroll
-  for (int i = 0; i < PER; ++i) {
-    c[i] = hist[top - i];
-    part += c[i];
-  }
-  uint32_t incl = part;
-  for (int off = 1; off < 64; off <<= 1) {
-    const uint32_t o = (uint32_t)__shfl_up((int)incl, off, 64);
-    if (lane >= off) incl += o;
-  }
-  if (lane == 63) sh[w] = incl;
-  if (threadIdx.x == 0) sh[4] = sh[5] = sh[6] = 0u;
-  __syncthreads();
-  uint32_t cum = incl - part;
-  for (int i = 0; i < w; ++i) cum += sh[i];
-  if (s.rank > cum && s.rank <= cum + part) {   // exactly one thread
-    uint32_t digit = 0, ceq = 0;
-    bool found = false;
-#pragma unroll
-    for (int i = 0; i < PER; ++i)
-      if (!found) {
-        if (s.rank <= cum + c[i]) {
-          found = true;
-          digit = (uint32_t)(top - i);
-          ceq = c[i];
-        } else {
-          cum += c[i];
-        }
-      }
-    sh[4] = digit;
-    sh[5] = cum;
-    sh[6] = ceq;
-  }
-  __syncthreads();
-  s.prefix |= sh[4] << shift;
-  s.n_gt += sh[5];
-  s.rank -= sh[5];
-  s.n_eq = sh[6];
-  __syncthreads();   // sh is written again by the next pick
-}
-
 // the first `passes` digits of the k-th largest key from the finished histograms hist[0 .. passes)
-__device__ __forceinline__ TkSel tk_select(const uint32_t* __restrict__ hist, int passes, int64_t k, uint32_t* sh) {
-  TkSel s;
+__device__ __forceinline__ RadixSel tk_select(const uint32_t* __restrict__ hist, int passes, int64_t k, uint32_t* sh) {
+  constexpr RadixDigit D0 = radix_digit(0), D1 = radix_digit(1), D2 = radix_digit(2);
+  RadixSel s;
   s.prefix = 0u;
   s.rank = (uint32_t)k;
   s.n_eq = 0u;
   s.n_gt = 0;
-  if (passes >= 1) tk_pick<TK_BINS>(hist, 21, s, sh);
-  if (passes >= 2) tk_pick<TK_BINS>(hist + TK_BINS, 10, s, sh);
-  if (passes >= 3) tk_pick<1024>(hist + 2 * TK_BINS, 0, s, sh);
+  if (passes >= 1) radix_pick_block<D0.bins>(hist, D0.shift, s, sh);
+  if (passes >= 2) radix_pick_block<D1.bins>(hist + RADIX_BINS, D1.shift, s, sh);
+  if (passes >= 3) radix_pick_block<D2.bins>(hist + 2 * RADIX_BINS, D2.shift, s, sh);
   return s;
-}
-
-__device__ __forceinline__ void tk_hist_clear(uint32_t* lh) {
-  for (int i = threadIdx.x; i < TK_BINS; i += 256) lh[i] = 0u;
-}
-// after the __syncthreads that ends the block's LDS atomics
-__device__ __forceinline__ void tk_hist_flush(const uint32_t* lh, uint32_t* __restrict__ hist) {
-  for (int i = threadIdx.x; i < TK_BINS; i += 256) {
-    const uint32_t c = lh[i];
-    if (c) atomicAdd(&hist[i], c);
-  }
 }
 
 // ------------------------------------------------------------------------------------------------- forward, pass 1
@@ -141,9 +72,9 @@ __global__ __launch_bounds__(256) void tk_fwd_kernel(const float* __restrict__ x
                                                      double* __restrict__ partial, uint32_t* __restrict__ hist, int C,
                                                      int64_t S, int nblk, int square_dice) {
   __shared__ double red[4][CR * TK_K];
-  __shared__ uint32_t lh[TK_BINS];
+  __shared__ uint32_t lh[RADIX_BINS];
   __shared__ float cw[CR];
-  tk_hist_clear(lh);
+  radix_hist_clear<256>(lh, RADIX_BINS);
   if ((int)threadIdx.x < CR) cw[threadIdx.x] = (class_w && (int)threadIdx.x < C) ? class_w[threadIdx.x] : 1.f;
   __syncthreads();
   const int b = blockIdx.x;
@@ -214,7 +145,7 @@ __global__ __launch_bounds__(256) void tk_fwd_kernel(const float* __restrict__ x
     row_store<VPL>(en + v0, nv, ev);
 #pragma unroll
     for (int j = 0; j < VPL; ++j)
-      if (j < nv) atomicAdd(&lh[tk_key(ev[j]) >> 21], 1u);
+      if (j < nv) atomicAdd(&lh[radix_digit_of(tk_key(ev[j]), radix_digit(0))], 1u);
   }
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
 #pragma unroll
@@ -231,7 +162,7 @@ __global__ __launch_bounds__(256) void tk_fwd_kernel(const float* __restrict__ x
     const double r = ((red[0][threadIdx.x] + red[1][threadIdx.x]) + red[2][threadIdx.x]) + red[3][threadIdx.x];
     partial[((n * C + c) * nblk + b) * TK_K + k] = r;
   }
-  tk_hist_flush(lh, hist);
+  radix_hist_flush<256>(lh, hist, RADIX_BINS);
 }
 
 // C > TK_CREG: the max and the log-sum of every voxel of the chunk first (LOGITS: two reads of the planes, which are in
@@ -242,8 +173,8 @@ __global__ __launch_bounds__(256) void tk_fwd_reread_kernel(const float* __restr
                                                             double* __restrict__ partial, uint32_t* __restrict__ hist,
                                                             int C, int64_t S, int nblk, int square_dice) {
   __shared__ double scratch[4];
-  __shared__ uint32_t lh[TK_BINS];
-  tk_hist_clear(lh);
+  __shared__ uint32_t lh[RADIX_BINS];
+  radix_hist_clear<256>(lh, RADIX_BINS);
   const int b = blockIdx.x;
   const int64_t n = blockIdx.y;
   const float* xn = x + n * C * S;
@@ -313,10 +244,10 @@ __global__ __launch_bounds__(256) void tk_fwd_reread_kernel(const float* __restr
     row_store<4>(en + v0, nv[it], ev[it]);
 #pragma unroll
     for (int j = 0; j < 4; ++j)
-      if (j < nv[it]) atomicAdd(&lh[tk_key(ev[it][j]) >> 21], 1u);
+      if (j < nv[it]) atomicAdd(&lh[radix_digit_of(tk_key(ev[it][j]), radix_digit(0))], 1u);
   }
   __syncthreads();
-  tk_hist_flush(lh, hist);
+  radix_hist_flush<256>(lh, hist, RADIX_BINS);
 }
 
 // --------------------------------------------------------------------------------------------------- select passes
@@ -326,13 +257,13 @@ template <int PASS>
 __global__ __launch_bounds__(256) void tk_select_kernel(const float* __restrict__ e, int64_t M,
                                                         const int64_t* __restrict__ k_device, int64_t k_host,
                                                         uint32_t* __restrict__ hist, double* __restrict__ esum) {
-  __shared__ uint32_t lh[TK_BINS];
+  __shared__ uint32_t lh[RADIX_BINS];
   __shared__ uint32_t sh[8];
   __shared__ double scratch[4];
-  tk_hist_clear(lh);
-  const TkSel sel = tk_select(hist, PASS, tk_k(k_device, k_host, M), sh);   // (its barriers publish the cleared bins)
-  constexpr int HSHIFT = PASS == 1 ? 21 : 10;
-  const uint32_t pre = sel.prefix >> HSHIFT;
+  radix_hist_clear<256>(lh, RADIX_BINS);
+  const RadixSel sel = tk_select(hist, PASS, tk_k(k_device, k_host, M), sh);   // (its barriers publish the cleared bins)
+  constexpr RadixDigit DG = radix_digit(PASS);
+  const uint32_t pre = sel.prefix >> DG.upper;
   const int64_t begin = (int64_t)blockIdx.x * TK_ECHUNK, end = min(M, begin + TK_ECHUNK);
   float above = 0.f;
   for (int64_t v0 = begin + threadIdx.x * 4; v0 < end; v0 += 1024) {
@@ -342,8 +273,8 @@ __global__ __launch_bounds__(256) void tk_select_kernel(const float* __restrict_
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       if (j >= nv) break;
-      const uint32_t key = tk_key(v[j]), hi = key >> HSHIFT;
-      if (hi == pre) atomicAdd(&lh[PASS == 1 ? (key >> 10) & 2047u : key & 1023u], 1u);
+      const uint32_t key = tk_key(v[j]), hi = key >> DG.upper;
+      if (hi == pre) atomicAdd(&lh[radix_digit_of(key, DG)], 1u);
       else if (PASS == 2 && hi > pre) above += v[j];
     }
   }
@@ -352,7 +283,7 @@ __global__ __launch_bounds__(256) void tk_select_kernel(const float* __restrict_
     store_block_sums(s, esum, blockIdx.x, scratch);
   }
   __syncthreads();
-  tk_hist_flush(lh, hist + PASS * TK_BINS);
+  radix_hist_flush<256>(lh, hist + PASS * RADIX_BINS, RADIX_BINS);
 }
 
 // --------------------------------------------------------------------------------------------------------- finalize
@@ -368,7 +299,7 @@ __global__ __launch_bounds__(256) void tk_finalize_kernel(const double* __restri
   __shared__ uint32_t sh[8];
   const int NC = N * C;
   const int64_t k = tk_k(k_device, k_host, (int64_t)N * S);
-  const TkSel sel = tk_select(hist, 3, k, sh);
+  const RadixSel sel = tk_select(hist, 3, k, sh);
   const int per = 256 / lanes, sub = threadIdx.x % lanes, slot = threadIdx.x / lanes;
   double dice_acc = 0.0;
   for (int nc0 = 0; nc0 < NC; nc0 += per) {
@@ -387,16 +318,17 @@ __global__ __launch_bounds__(256) void tk_finalize_kernel(const double* __restri
   // everything above tau: the chunks' sums in index order per thread, then the keys of tau's last histogram above it
   double top_acc = 0.0;
   for (int64_t i = threadIdx.x; i < nsb; i += 256) top_acc += esum[i];
-  const uint32_t digit = sel.prefix & 1023u;
-  for (uint32_t i = threadIdx.x; i < 1024u; i += 256u)
+  constexpr RadixDigit LAST = radix_digit(2);
+  const uint32_t digit = sel.prefix & LAST.mask;
+  for (uint32_t i = threadIdx.x; i < (uint32_t)LAST.bins; i += 256u)
     if (i > digit) {
-      const uint32_t c = hist[2 * TK_BINS + i];
-      if (c) top_acc += (double)c * (double)tk_key2f((sel.prefix & ~1023u) | i);
+      const uint32_t c = hist[2 * RADIX_BINS + i];
+      if (c) top_acc += (double)c * (double)key2f((sel.prefix & ~LAST.mask) | i);
     }
   const double dice = block_sum<double, 256>(dice_acc, scratch);
   const double top = block_sum<double, 256>(top_acc, scratch);
   if (threadIdx.x == 0) {
-    const float tau = tk_key2f(sel.prefix);
+    const float tau = key2f(sel.prefix);
     const double share = (double)((uint64_t)k - sel.n_gt);   // >= 1: the k-th largest itself is not above tau
     const double total = top + share * (double)tau;
     write_out3(out3, dice_weight, (float)(dice / NC), (float)(total / ((double)C * (double)k)));
@@ -619,7 +551,7 @@ static inline TkLayout tk_layout(int32_t N, int32_t C, int64_t S) {
   l.nsb = ceil_div((int64_t)N * S, TK_ECHUNK);
   l.esum = (size_t)N * C * l.nblk * TK_K * sizeof(double);
   l.hist = l.esum + (size_t)l.nsb * sizeof(double);
-  l.bytes = l.hist + 3 * TK_BINS * sizeof(uint32_t) + 256;
+  l.bytes = l.hist + 3 * RADIX_BINS * sizeof(uint32_t) + 256;
   return l;
 }
 
@@ -668,7 +600,7 @@ extern "C" int m355_topk_loss_fwd(const float* x, const float* t, int32_t N, int
   double* partial = (double*)workspace;
   double* esum = (double*)((char*)workspace + l.esum);
   uint32_t* hist = (uint32_t*)((char*)workspace + l.hist);
-  if (hipMemsetAsync(hist, 0, 3 * TK_BINS * sizeof(uint32_t), st) != hipSuccess) return check_launch("topk_loss_fwd: memset");
+  if (hipMemsetAsync(hist, 0, 3 * RADIX_BINS * sizeof(uint32_t), st) != hipSuccess) return check_launch("topk_loss_fwd: memset");
   const TkFwdK k1 = from_logits ? tk_fwd_for<true>(C) : tk_fwd_for<false>(C);
   hipLaunchKernelGGL(k1, dim3((unsigned)l.nblk, (unsigned)N), dim3(256), 0, st, x, t, class_weights, e, partial, hist, (int)C,
                      S, l.nblk, (int)square_dice);
