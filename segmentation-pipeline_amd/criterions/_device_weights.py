@@ -12,6 +12,23 @@ from torch import nn
 from .._lib import M355Error
 
 
+def require_probabilities(wrapper, criterion):
+    """BoundaryLoss, BlobLoss and LovaszLoss hand the prediction they are given to a term of their own that needs
+    probabilities; a wrapped criterion with from_logits=True -- at any depth of `.criterion` -- says the prediction holds
+    logits, on which the boundary term is an unbounded `mean(logit * phi)` and the blob and Lovasz terms are NaN.  Refused
+    where the nest is built (a ValueError), not found in a loss curve."""
+    inner, seen = criterion, set()
+    while inner is not None and id(inner) not in seen:
+        seen.add(id(inner))
+        if getattr(inner, "from_logits", False):
+            raise ValueError(
+                f"{type(wrapper).__name__} around {type(inner).__name__}(from_logits=True): the "
+                f"{type(wrapper).__name__} term takes probabilities, not logits.  Give the model a softmax or sigmoid "
+                f"head and the criterion from_logits=False, or keep the logits criterion outside "
+                f"{type(wrapper).__name__} (DeepSupervisionLoss forwards either kind)")
+        inner = getattr(inner, "criterion", None)
+
+
 class DeviceWeightsCriterion(nn.Module):
     def __init__(self):
         super().__init__()

@@ -21,8 +21,11 @@ and a captured step picks the new value up on its next replay.
 channel, BoundaryLoss's convention.  A voxel is a member when target > 0.5, which serves the soft 'area' targets of
 DeepSupervisionLoss; compose as DeepSupervisionLoss(BlobLoss(inner)): a tuple prediction is not this wrapper's business.
 The prediction must hold probabilities (a softmax or sigmoid head): a value outside [0, 1] or not finite in a weighted
-channel gives a NaN blob term, which the fused optimizers skip like any non-finite step.  The blob term is Dice only;
-a per-blob log term is not part of it.
+channel gives a NaN blob term, which the fused optimizers skip like any non-finite step.  A wrapped criterion with
+from_logits=True, at any depth, is therefore refused at construction (ValueError): use a softmax or sigmoid head with
+from_logits=False, or keep the logits criterion outside this wrapper -- DeepSupervisionLoss forwards either kind.  The
+blob term is Dice only; a per-blob log term is not part of it.  (A coarse cell of exactly 0.5 is no member here and in
+BoundaryLoss, and foreground in LovaszLoss: DESIGN §4.30.)
 
 The result is `criterion`'s dict with 'loss' replaced by the total and 'blob_loss', 'global_loss' (detached), 'blob_count'
 (a device int32: the number of components; -1 if the labelling gave up, with a NaN term), 'blob_weight' and
@@ -34,7 +37,7 @@ import torch
 
 from .. import ops
 from .._lib import M355Error
-from ._device_weights import DeviceWeightsCriterion
+from ._device_weights import DeviceWeightsCriterion, require_probabilities
 
 
 class BlobLoss(DeviceWeightsCriterion):
@@ -54,6 +57,7 @@ class BlobLoss(DeviceWeightsCriterion):
                 raise ValueError(f"blob_class_weights = {blob_class_weights}: expected finite values >= 0")
             if not sum(blob_class_weights) > 0:
                 raise ValueError(f"blob_class_weights = {blob_class_weights}: at least one channel needs a positive weight")
+        require_probabilities(self, criterion)
         if connectivity not in (1, 2, 3):
             raise ValueError(f"connectivity = {connectivity!r}: expected 1, 2 or 3 (6, 18 or 26 neighbours)")
         self.criterion = criterion

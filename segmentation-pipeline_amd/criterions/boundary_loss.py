@@ -19,8 +19,14 @@ synchronisation, so both published schedules are one line between steps -- "reba
 "increase": set_weights(boundary=a) with a growing -- and a captured step picks the new value up on its next replay.
 
 `boundary_class_weights=None` weighs every channel 1, except channel 0 (the background) 0 when there is more than one
-channel, the published default.  A membership threshold of 0.5 serves the soft 'area' targets of DeepSupervisionLoss;
+channel, the published default.  A voxel is inside when target > 0.5, which serves the soft 'area' targets of
+DeepSupervisionLoss (a coarse cell of exactly 0.5 is outside here and in BlobLoss, foreground in LovaszLoss: DESIGN §4.30);
 compose as DeepSupervisionLoss(BoundaryLoss(inner)): a tuple prediction is not this wrapper's business.
+
+The prediction must hold probabilities (a softmax or sigmoid head): on logits `mean(p * phi)` is unbounded.  A wrapped
+criterion with from_logits=True, at any depth, is therefore refused at construction (ValueError): use a softmax or
+sigmoid head with from_logits=False, or keep the logits criterion outside this wrapper -- DeepSupervisionLoss forwards
+either kind.
 
 The result is `criterion`'s dict with 'loss' replaced by the total and 'boundary_loss', 'regional_loss' (detached),
 'boundary_weight' and 'regional_weight' added; the gradient flows through 'loss' only.
@@ -31,7 +37,7 @@ import torch
 
 from .. import ops
 from .._lib import M355Error
-from ._device_weights import DeviceWeightsCriterion
+from ._device_weights import DeviceWeightsCriterion, require_probabilities
 
 
 class BoundaryLoss(DeviceWeightsCriterion):
@@ -52,6 +58,7 @@ class BoundaryLoss(DeviceWeightsCriterion):
             if not sum(boundary_class_weights) > 0:
                 raise ValueError(f"boundary_class_weights = {boundary_class_weights}: at least one channel needs a "
                                  f"positive weight")
+        require_probabilities(self, criterion)
         spacing = ops._spacing3(spacing)
         if any(not (math.isfinite(s) and s > 0) for s in spacing):
             raise ValueError(f"spacing = {spacing}: expected finite values > 0")

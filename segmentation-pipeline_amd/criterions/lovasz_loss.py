@@ -19,10 +19,13 @@ buffers): `set_weights` fills them in place without a synchronisation -- train o
 in -- and a captured step picks the new value up on its next replay.
 
 classes='present' (Berman's default) averages the channels that have a foreground voxel, 'all' every channel;
-per_image=True takes the mean per image first; `lovasz_class_weights` weighs the channels (None: all ones).  A membership
-threshold of 0.5 serves the soft 'area' targets of DeepSupervisionLoss; compose as DeepSupervisionLoss(LovaszLoss(inner)):
-a tuple prediction is not this wrapper's business.  The prediction must hold probabilities: a NaN or a value outside
-[0, 1] gives a NaN loss.
+per_image=True takes the mean per image first; `lovasz_class_weights` weighs the channels (None: all ones).  A voxel is
+foreground when target >= 0.5, which serves the soft 'area' targets of DeepSupervisionLoss (a coarse cell of exactly 0.5
+is foreground here and outside in BoundaryLoss and BlobLoss, which take target > 0.5: DESIGN §4.30); compose as
+DeepSupervisionLoss(LovaszLoss(inner)): a tuple prediction is not this wrapper's business.  The prediction must hold
+probabilities: a NaN or a value outside [0, 1] gives a NaN loss.  A wrapped criterion with from_logits=True, at any depth,
+is therefore refused at construction (ValueError): use a softmax or sigmoid head with from_logits=False, or keep the
+logits criterion outside this wrapper -- DeepSupervisionLoss forwards either kind.
 
 The result is `criterion`'s dict (or an empty one) with 'loss' replaced by the total and 'lovasz_loss', 'regional_loss'
 (detached), 'lovasz_weight' and 'regional_weight' added; the gradient flows through 'loss' only.
@@ -33,7 +36,7 @@ import torch
 
 from .. import ops
 from .._lib import M355Error
-from ._device_weights import DeviceWeightsCriterion
+from ._device_weights import DeviceWeightsCriterion, require_probabilities
 
 
 class LovaszLoss(DeviceWeightsCriterion):
@@ -43,6 +46,7 @@ class LovaszLoss(DeviceWeightsCriterion):
         for name, v in (("lovasz_weight", lovasz_weight), ("regional_weight", regional_weight)):
             if not math.isfinite(v):
                 raise ValueError(f"{name} = {v}: expected a finite value")
+        require_probabilities(self, criterion)
         if classes not in ops.LOVASZ_CLASSES:
             raise ValueError(f"classes = {classes!r}: expected 'present' or 'all'")
         if lovasz_class_weights is not None:
