@@ -1069,6 +1069,35 @@ int m355_ensemble_accumulate(const float* pred, float* acc, int32_t* votes, int3
 int m355_ensemble_finalize(const float* acc, const int32_t* votes, float* mean_out, int64_t* onehot_out, int32_t N,
                            int32_t C, int64_t S, int32_t members, int32_t mode, void* stream);
 
+/* ------------------------------------------ uncertainty maps (csrc/uncertainty.hip)
+ * Entropies of probability volumes, in float32, natural logarithm.  One expression for all three entry points, so
+ * equal probabilities give equal bits:
+ *   term(p)  = p > 0 ? p * logf(p) : 0      (0 at p <= 0; a NaN passes through and makes its voxel NaN, no other)
+ *   M355_UQ_CATEGORICAL  h(p[0..C)) = -(term(p_0) + term(p_1) + ...), summed in channel order: K = 1 map per volume
+ *   M355_UQ_BINARY       h(p) = -(term(p) + term(1 - p)) of every channel on its own, 1 - p in float32, the two
+ *                        products and their sum formed exactly and rounded once: K = C maps
+ *   m355_predictive_entropy            probs [N, C, S] float32 / bfloat16 / float16 (M355_EV_* codes, 16-bit values
+ *                                      widened exactly) -> entropy [N, K, S] float32 and, unless NULL, confidence
+ *                                      [N, 1, S]: the maximum channel value (a NaN is the maximum).  One pass.
+ *   m355_ensemble_entropy_accumulate   reads a member prediction through the inverse transform of
+ *                                      m355_ensemble_accumulate (size3, perm3, flip_mask as there) and adds the member's
+ *                                      entropy to eacc [N, K, S] in canonical orientation; first != 0 initialises (the
+ *                                      accumulator's contents on entry are then irrelevant).
+ *   m355_ensemble_uncertainty_finalize from acc [N, C, S] (the running sum of m355_ensemble_accumulate, mode 0), eacc
+ *                                      and the member count: entropy = h(acc * (1 / members)), the product being the one
+ *                                      m355_ensemble_finalize writes as the mean, so entropy has the bits of
+ *                                      m355_predictive_entropy of that mean; expected_entropy = eacc / members;
+ *                                      mutual_information = max(entropy - expected_entropy, 0), a NaN staying NaN;
+ *                                      confidence [N, 1, S] = max_c of the mean.  The first three are [N, K, S]. */
+enum { M355_UQ_CATEGORICAL = 0, M355_UQ_BINARY = 1 };
+int m355_predictive_entropy(const void* probs, int32_t dtype, float* entropy, float* confidence /* or NULL */, int32_t N,
+                            int32_t C, int64_t S, int32_t kind, void* stream);
+int m355_ensemble_entropy_accumulate(const float* pred, float* eacc, int32_t N, int32_t C, const int32_t* size3,
+                                     const int32_t* perm3, int32_t flip_mask, int32_t kind, int32_t first, void* stream);
+int m355_ensemble_uncertainty_finalize(const float* acc, const float* eacc, float* entropy, float* expected_entropy,
+                                       float* mutual_information, float* confidence, int32_t N, int32_t C, int64_t S,
+                                       int32_t members, int32_t kind, void* stream);
+
 /* ------------------------------------------ connected components + post-processing
  * skimage.morphology.label / remove_small_holes / dilation and the np.unique / torch.unique counts under
  * post_processing.py (keep_components, remove_holes, remove_small_components) and
@@ -1301,6 +1330,51 @@ typedef struct {
 int m355_eval_multilabel(const m355_eval_multilabel_desc* descs, int32_t n, void* dev_descs, int32_t scores_dtype,
                          int32_t C, const float* thresholds /* host, [C] */,
                          uint64_t* counts /* device [n][C][3], zeroed here */, void* stream);
+
+/* Calibration of probabilities (csrc/calibration.hip): reliability tables, Brier score and negative
+ * log-likelihood per subject, every subject of whatever size in one pass (descriptors as for m355_eval_multilabel: copied
+ * to `dev_descs` on the stream, no synchronisation).  Per subject: scores [C, S] float32, bfloat16 or float16 (widened
+ * exactly), 1 <= C <= M355_EV_MAX_CHANNELS, holding PROBABILITIES (the output of a softmax or sigmoid head), and a target,
+ * of one `target_kind` for all subjects:
+ *   M355_EV_TARGET_ONEHOT  a one-hot or soft map [C, S] of any M355_EV_* type: channel c is positive where `!= 0` (a NaN
+ *                          is, -0.0 is not); the categorical class is the first maximum over the channels (a NaN is the
+ *                          maximum), the rule of m355_eval_scores;
+ *   M355_EV_TARGET_MAP     a map [S] of channel indices of an integer M355_EV_* type; an index outside [0, C) makes the
+ *                          voxel invalid.  Channel c is positive where the index is c.
+ * Definitions:
+ *   bin         a confidence q (float32, 0 <= q <= 1) falls into bin min((int)(q * (float)bins), bins - 1): one float32
+ *               multiply and a truncation; 1 <= bins <= M355_CAL_MAX_BINS.
+ *   entry       {count, hits, conf_sum}, three uint64; conf_sum = sum of rint((double)q * 2^32), a 2^-32 fixed point
+ *               (the product is an integer for q >= 2^-8): exact and independent of order.
+ *   M355_CAL_CATEGORICAL (softmax).  A voxel is valid when every channel value lies in [0, 1] (so none is NaN, and the
+ *               top-label confidence lies there) and the target index is in range.  Invalid voxels are counted in
+ *               invalid[subject][0] and enter no table and no sum.  top[subject][bin]: q = the first maximum over the
+ *               channels, hit = that channel is the target's class.  classwise[subject][c][bin]: q = p_c, hit = the target
+ *               is positive in c.  brier = sum over valid voxels and channels of ((double)p_c - y_c)^2, y_c = 1 where the
+ *               target is positive in c, else 0.  nll = sum over valid voxels of -log(((double)p_t + 1e-8) / (1 + 1e-8)),
+ *               t the target's class (the reference criterion's prediction_safe shift; fp64 log).
+ *   M355_CAL_BINARY (sigmoid).  Every channel a problem of its own: (voxel, c) is valid when p_c lies in [0, 1] and the
+ *               target index is in range; invalid pairs are counted in invalid[subject][c].  classwise as above; top stays
+ *               zero.  brier as above over the valid pairs; nll = sum over them of -log(ps(p_c)) where the target is
+ *               positive and -log(ps(1 - (double)p_c)) where it is not, ps(x) = (x + 1e-8) / (1 + 1e-8).
+ *   sums[subject] = {brier, nll} in fp64: per-workgroup partials added in a fixed order, so a repeated call gives the same
+ *               bits.  voxels[subject] = S.
+ * Invalid values never index a table.  `workspace`: m355_eval_calibration_workspace(n) bytes, contents irrelevant.  The
+ * tables, invalid counts, sums and voxel counts are written in full by the call (their contents on entry are irrelevant). */
+#define M355_CAL_MAX_BINS 32
+enum { M355_CAL_CATEGORICAL = 0, M355_CAL_BINARY = 1 };
+typedef struct {
+  const void* scores;          /* [C, S] */
+  const void* target;          /* [C, S] (ONEHOT) or [S] (MAP) */
+  int64_t S;
+  int32_t target_dtype;
+} m355_eval_calibration_desc;
+size_t m355_eval_calibration_workspace(int32_t n);
+int m355_eval_calibration(const m355_eval_calibration_desc* descs, int32_t n, void* dev_descs, int32_t scores_dtype,
+                          int32_t target_kind /* of every subject */, int32_t C, int32_t bins, int32_t kind, uint64_t* top /* device [n][bins][3] */,
+                          uint64_t* classwise /* device [n][C][bins][3] */, uint64_t* invalid /* device [n][C] */,
+                          double* sums /* device [n][2] */, int64_t* voxels /* device [n] */, void* workspace,
+                          size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------ contour images
  * The device half of the reference's FindInterestingSlice and ContourImageEvaluator (evaluators.py).

@@ -112,6 +112,16 @@ class EvalMultilabelDesc(C.Structure):
     _fields_ = [("scores", C.c_void_p), ("target", C.c_void_p), ("S", C.c_int64), ("target_dtype", C.c_int32)]
 
 
+CAL_MAX_BINS = 32
+CAL_CATEGORICAL, CAL_BINARY = 0, 1
+UQ_CATEGORICAL, UQ_BINARY = 0, 1
+
+
+class EvalCalibrationDesc(C.Structure):
+    """m355_eval_calibration_desc"""
+    _fields_ = [("scores", C.c_void_p), ("target", C.c_void_p), ("S", C.c_int64), ("target_dtype", C.c_int32)]
+
+
 class SliceCountsDesc(C.Structure):
     """m355_slice_counts_desc"""
     _fields_ = [("data", C.c_void_p), ("counts_offset", C.c_int64), ("size3", C.c_int32 * 3), ("dtype", C.c_int32),
@@ -351,6 +361,13 @@ SIGNATURES = {
     "m355_eval_scores": (C.c_int, [C.POINTER(EvalScoresDesc), _i32, _P, _i32, _i32, _I3, _i32, _i32, _i32, _I3, _i32,
                                    _i32, _P, _P]),
     "m355_eval_multilabel": (C.c_int, [C.POINTER(EvalMultilabelDesc), _i32, _P, _i32, _i32, C.POINTER(C.c_float), _P, _P]),
+    "m355_eval_calibration_workspace": (_sz, [_i32]),
+    "m355_eval_calibration": (C.c_int, [C.POINTER(EvalCalibrationDesc), _i32, _P, _i32, _i32, _i32, _i32, _i32, _P, _P, _P, _P,
+                                        _P, _P, _sz, _P]),
+    "m355_predictive_entropy": (C.c_int, [_P, _i32, _P, _P, _i32, _i32, _i64, _i32, _P]),
+    "m355_ensemble_entropy_accumulate": (C.c_int, [_P, _P, _i32, _i32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _i32,
+                                                   _i32, _i32, _P]),
+    "m355_ensemble_uncertainty_finalize": (C.c_int, [_P, _P, _P, _P, _P, _P, _i32, _i32, _i64, _i32, _i32, _P]),
     "m355_slice_counts": (C.c_int, [C.POINTER(SliceCountsDesc), _i32, _P, _P, _P]),
     "m355_slice_rank": (C.c_int, [_P, C.POINTER(SliceSeg), _i32, _P, _P, _P, _P, _P]),
     "m355_slice_mosaic": (C.c_int, [C.POINTER(SliceMosaicDesc), _i32, C.POINTER(SliceTileDesc), _i32, _P, _P]),

@@ -14,7 +14,8 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libm355seg.so")
 SOURCES = ["abi.cpp", "conv3d.hip", "conv3d_host.hip", "conv3d_f32x3.hip", "conv3d_h16.hip", "act16.hip", "train16.hip", "norm.hip", "elementwise.hip", "convt.hip", "loss_patch_eval.hip", "hybrid_loss.hip", "binary_loss.hip", "focal_tversky_loss.hip", "topk_loss.hip", "segmented_sort.hip", "lovasz_loss.hip", "boundary_loss.hip", "blob_loss.hip", "target_pyramid.hip", "ensemble.hip",
            "blur_weights.hip", "components.hip", "augment.hip", "preprocess.hip", "evaluate.hip",
-           "dwi.hip", "contour.hip", "maxpool.hip", "upsample.hip", "distance.hip", "region_stats.hip", "optimizer.hip"]
+           "dwi.hip", "contour.hip", "maxpool.hip", "upsample.hip", "distance.hip", "region_stats.hip", "optimizer.hip",
+           "calibration.hip", "uncertainty.hip"]
 HEADERS = sorted(glob.glob(os.path.join(CSRC, "*.hpp"))) + [os.path.join(HERE, "..", "include", "m355seg.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
 

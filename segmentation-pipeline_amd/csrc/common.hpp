@@ -95,6 +95,7 @@ struct Tuning {
   int f32x3_convt_bwd = 1;   // ... and convt_k2s2_bwd_weight_x3_kernel behind m355_conv_transpose3d_bwd_weight_x3 (0: that entry point refuses; 2: also below the router's small-level floor)
   int convt_wgs = 0;     // c8 conv-transpose kernels: workgroups per CU of the persistent grids (0 = built-in)
   int h16_stagger = 2;   // 16-bit conv kernel: start offset of the odd workgroup of a CU, in units of 1024 cycles
+  int cal_blocks = 0;    // m355_eval_calibration: workgroups per subject (M355_CAL_BLOCKS; 0 = built-in, at most 2048)
 };
 const Tuning& tuning();
 

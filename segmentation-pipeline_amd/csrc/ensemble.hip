@@ -11,34 +11,9 @@
 //     what torch.mode returns on the CPU) and writes the int64 one-hot mask the reference returns.
 // All HBM-bound; the canonical (output) side is always the coalesced one.
 #include "common.hpp"
+#include "axis_map.hpp"
 
 namespace m355 {
-
-struct AxisMap {
-  int size[3];      // canonical spatial size (i0, i1, i2)
-  int64_t mstride[3];  // stride, in the MEMBER tensor, of canonical axis k (negative when that axis is flipped)
-  int64_t moff;     // member offset of canonical voxel (0, 0, 0)
-};
-
-// perm[j] in {0,1,2}: member axis j is canonical axis perm[j]; flip bit j: member axis j is reversed
-static AxisMap make_axis_map(const int32_t* size, const int32_t* perm, int flip_mask) {
-  AxisMap m{};
-  int msize[3];
-  for (int j = 0; j < 3; ++j) msize[j] = size[perm[j]];
-  int64_t mst[3] = {(int64_t)msize[1] * msize[2], msize[2], 1};
-  m.moff = 0;
-  for (int k = 0; k < 3; ++k) m.size[k] = size[k];
-  for (int j = 0; j < 3; ++j) {
-    const int k = perm[j];
-    if ((flip_mask >> j) & 1) {
-      m.mstride[k] = -mst[j];
-      m.moff += (int64_t)(msize[j] - 1) * mst[j];
-    } else {
-      m.mstride[k] = mst[j];
-    }
-  }
-  return m;
-}
 
 // member[n, c, a] = x[n, c, i(a)]: one thread per MEMBER element (coalesced writes), gathered reads
 __global__ __launch_bounds__(256) void flip_permute_kernel(const float* __restrict__ x, float* __restrict__ y, int NC,
@@ -110,21 +85,6 @@ __global__ __launch_bounds__(256) void ensemble_finalize_kernel(const float* __r
     for (int c = 0; c < C; ++c) o[(int64_t)c * S] = c == best ? 1 : 0;
   }
 }
-
-static int check_map_args(const char* who, const int32_t* size3, const int32_t* perm3, int flip_mask) {
-  M355_REQUIRE(size3 && perm3, M355_EINVALID_ARG, "%s: null shape / permutation", who);
-  M355_REQUIRE(size3[0] > 0 && size3[1] > 0 && size3[2] > 0, M355_EINVALID_ARG, "%s: non-positive size", who);
-  int seen = 0;
-  for (int j = 0; j < 3; ++j) {
-    M355_REQUIRE(perm3[j] >= 0 && perm3[j] <= 2, M355_EINVALID_ARG, "%s: permutation entry %d out of range", who, perm3[j]);
-    seen |= 1 << perm3[j];
-  }
-  M355_REQUIRE(seen == 7, M355_EINVALID_ARG, "%s: not a permutation of (0, 1, 2)", who);
-  M355_REQUIRE(flip_mask >= 0 && flip_mask <= 7, M355_EINVALID_ARG, "%s: flip mask out of range", who);
-  return M355_OK;
-}
-
-static unsigned grid_of(int64_t total) { return (unsigned)std::max<int64_t>(1, std::min<int64_t>(ceil_div(total, 256), 16384)); }
 
 }  // namespace m355
 

@@ -26,7 +26,8 @@ from ._lib import M355Error, check
 from .post_processing import _DTYPE_CODE, _OP_COPY, _OP_POSITIVE, _ccl, _connectivity, _device_volume, _histogram, _to_i32
 
 __all__ = ["overlap_histogram", "msseg_detection_test", "instance_segmentation_stats", "MAX_OVERLAP_ENTRIES", "STAT_NAMES",
-           "LabeledTensor", "LabelMap", "Evaluator", "SegmentationEvaluator", "MultiLabelEvaluator", "LabelMapEvaluator",
+           "LabeledTensor", "LabelMap", "Evaluator", "SegmentationEvaluator", "MultiLabelEvaluator", "CalibrationEvaluator",
+           "calibration_stats", "LabelMapEvaluator",
            "InstanceSegmentationEvaluator", "label_counts", "ScalarImage", "find_interesting_slices",
            "FindInterestingSlice", "ContourImageEvaluator", "render_contours", "SurfaceDistanceEvaluator",
            "surface_distances", "SURFACE_STAT_NAMES", "ImageRegionEvaluator", "IMAGE_REGION_STAT_NAMES"]
@@ -426,6 +427,83 @@ class MultiLabelEvaluator(Evaluator):
                 for stat_name in self.stats_to_output:
                     table[subject['name'], name, stat_name] = stats[stat_name].item()
         return _finish(table, self.summary_stats_to_output)
+
+
+def calibration_stats(table, bins_total=None):
+    """ece, mce, confidence, accuracy and the per-bin (count, accuracy, confidence) of one reliability table: `table`
+    int [B, 3] of (count, hits, conf_sum in 2^-32 fixed point), Python fp64 from the integers.  ece = sum_b (n_b / n)
+    |acc_b - conf_b| over the non-empty bins, mce the largest gap; an empty table gives NaN."""
+    rows = [(int(c), int(h), int(f)) for c, h, f in table]
+    n = sum(c for c, _, _ in rows)
+    per_bin = [(c, h / c, f / 4294967296.0 / c) if c else (0, float('nan'), float('nan')) for c, h, f in rows]
+    if n == 0:
+        nan = float('nan')
+        return {'ece': nan, 'mce': nan, 'confidence': nan, 'accuracy': nan}, per_bin
+    gaps = [(c, abs(a - q)) for c, a, q in per_bin if c]
+    return {'ece': sum(c / n * g for c, g in gaps), 'mce': max(g for _, g in gaps),
+            'confidence': sum(f for _, _, f in rows) / 4294967296.0 / n, 'accuracy': sum(h for _, h, _ in rows) / n}, per_bin
+
+
+class CalibrationEvaluator(Evaluator):
+    """Can the probabilities be trusted?  Per subject: expected and maximum calibration error ('ece', 'mce'), mean
+    'confidence' and 'accuracy', Brier score and negative log-likelihood ('brier', 'nll'), and the reliability table.
+    subject[prediction_name]: probabilities [C, W, H, D] (an image with `.data` or a bare tensor; float32 / bfloat16 /
+    float16); subject[target_name]: a one-hot or soft map of the same shape, or a map of channel indices ([W, H, D] or
+    [1, W, H, D], an integer type).  kind 'categorical' (softmax head): the label keys are 'top' (the top-label table:
+    confidence = the largest probability, hit = it is the target's class) followed by `channel_names` (default "0" ..
+    "C-1"), whose rows hold the classwise statistics (confidence = p_c, hit = the target is positive in c); 'binary'
+    (sigmoid head): the channel rows only, every channel a problem of its own.  'brier' and 'nll' are the subject's sums
+    over all channels divided by its valid voxels (binary: by its valid (voxel, channel) pairs) and stand in every row
+    of the subject.  A subject with no valid voxel gets NaN.  One ops.eval_calibration call and one copy back; the
+    statistics are Python fp64 on the integers.  The output has SegmentationEvaluator's layout ('subject_stats',
+    'summary_stats') and also 'reliability': a LabeledTensor [subject, label, bin, {count, accuracy, confidence}]
+    (float64; empty bins NaN)."""
+
+    def __init__(self, prediction_name: str, target_name: str, channel_names: Optional[Sequence[str]] = None,
+                 bins: int = 15, kind: str = 'categorical',
+                 stats_to_output: Sequence[str] = ('ece', 'mce', 'brier', 'nll', 'confidence', 'accuracy'),
+                 summary_stats_to_output: Sequence[str] = ('mean', 'std', 'min', 'max')):
+        if kind not in ('categorical', 'binary'):
+            raise ValueError(f"kind must be 'categorical' or 'binary', not {kind!r}")
+        self.prediction_name = prediction_name
+        self.target_name = target_name
+        self.channel_names = channel_names
+        self.bins = bins
+        self.kind = kind
+        self.stats_to_output = stats_to_output
+        self.summary_stats_to_output = summary_stats_to_output
+
+    _data = staticmethod(MultiLabelEvaluator._data)
+    _channel_names = MultiLabelEvaluator._channel_names
+
+    def __call__(self, subjects):
+        scores = [self._data(s[self.prediction_name]) for s in subjects]
+        targets = [self._data(s[self.target_name]) for s in subjects]
+        dev = next((t.device for t in scores if t.is_cuda), None)
+        if dev is None and torch.cuda.is_available():      # (without a device the op itself refuses host tensors)
+            dev = torch.device("cuda", torch.cuda.current_device())
+        channels, n = scores[0].shape[0], len(subjects)
+        names = (['top'] if self.kind == 'categorical' else []) + self._channel_names(channels)
+        table = _subject_table(subjects, self.stats_to_output, names)
+        reliability = LabeledTensor(dim_names=['subject', 'label', 'bin', 'stat'],
+                                    dim_keys=[[s['name'] for s in subjects], names, [str(b) for b in range(self.bins)],
+                                              ['count', 'accuracy', 'confidence']])
+        reliability.data = reliability.data.double()
+        device_counts = ops.eval_calibration([s.to(dev) for s in scores], [t.to(dev) for t in targets], self.bins, self.kind)
+        counts = ops.CalibrationCounts.unpack(device_counts.packed.cpu(), n, channels, self.bins, self.kind)
+        top, classwise = counts.top.numpy(), counts.classwise.numpy()
+        for i, subject in enumerate(subjects):
+            tables = ([top[i]] if self.kind == 'categorical' else []) + [classwise[i, c] for c in range(channels)]
+            valid = int(top[i, :, 0].sum()) if self.kind == 'categorical' else int(classwise[i, :, :, 0].sum())
+            sums = {'brier': counts.brier[i].item() / valid, 'nll': counts.nll[i].item() / valid} if valid else \
+                {'brier': float('nan'), 'nll': float('nan')}
+            for l, name in enumerate(names):
+                stats, per_bin = calibration_stats(tables[l])
+                stats.update(sums)
+                for stat_name in self.stats_to_output:
+                    table[subject['name'], name, stat_name] = stats[stat_name]
+                reliability.data[i, l] = torch.tensor(per_bin, dtype=torch.float64)
+        return dict(_finish(table, self.summary_stats_to_output), reliability=reliability)
 
 
 CURVE_STATS = ('error', 'absolute_error', 'squared_error', 'percent_diff')

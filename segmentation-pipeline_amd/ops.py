@@ -3022,6 +3022,130 @@ def eval_multilabel(scores, targets, thresholds=0.5):
     return counts
 
 
+# ----------------------------------------------------------------- calibration (csrc/calibration.hip)
+_EV_INDEX_DTYPE = {k: v for k, v in _EV_MAP_DTYPE.items() if k != torch.float32}
+_CAL_KINDS = {'categorical': _lib.CAL_CATEGORICAL, 'binary': _lib.CAL_BINARY}
+
+
+class CalibrationCounts(NamedTuple):
+    """ops.eval_calibration's result, device tensors that are views of one buffer (`packed`, int64 words): top
+    [n, B, 3] and classwise [n, C, B, 3] int64 entries (count, hits, conf_sum in 2^-32 fixed point); invalid int64 [n]
+    (categorical: voxels) or [n, C] (binary: per channel); brier, nll float64 [n] (sums, not means); voxels int64 [n]."""
+    top: torch.Tensor
+    classwise: torch.Tensor
+    invalid: torch.Tensor
+    brier: torch.Tensor
+    nll: torch.Tensor
+    voxels: torch.Tensor
+    packed: torch.Tensor
+
+    @staticmethod
+    def unpack(packed, n, channels, bins, kind):
+        """the views of a packed buffer (on whatever device it lies: the evaluator copies `packed` back once)"""
+        sizes = (n * bins * 3, n * channels * bins * 3, n * channels, n * 2, n)
+        top, cls, inv, sums, vox = torch.split(packed, sizes)
+        sums = sums.view(torch.float64).view(n, 2)
+        inv = inv.view(n, channels)
+        return CalibrationCounts(top.view(n, bins, 3), cls.view(n, channels, bins, 3),
+                                 inv if kind == 'binary' else inv[:, 0], sums[:, 0], sums[:, 1], vox, packed)
+
+
+def eval_calibration(scores, targets, bins=15, kind='categorical'):
+    """Reliability tables, Brier and NLL sums of probabilities against targets, every subject of whatever size in one
+    pass (include/m355seg.h states the definitions).  scores[i]: device tensors [C, *spatial] of PROBABILITIES (float32 /
+    bfloat16 / float16, one type and one C for all).  targets[i]: all of one form -- the shape of scores[i] (a one-hot or
+    soft map of any evaluation element type or a 16-bit float: channel c is positive where `!= 0`, the class is the first
+    maximum), or one value per voxel ([*spatial] or [1, *spatial], an integer type: the channel index; outside [0, C) the
+    voxel is invalid).  kind 'categorical' (softmax: top-label and classwise tables) or 'binary' (sigmoid: classwise
+    only, every channel a problem of its own).  -> CalibrationCounts; nothing synchronises."""
+    n = len(scores)
+    if n == 0 or len(targets) != n:
+        raise _lib.M355Error(f"eval_calibration: {n} score maps and {len(targets)} targets; one target per subject, at "
+                             "least one subject")
+    if kind not in _CAL_KINDS:
+        raise _lib.M355Error(f"eval_calibration: kind {kind!r} (one of {tuple(_CAL_KINDS)})")
+    bins = int(bins)
+    if not 1 <= bins <= _lib.CAL_MAX_BINS:
+        raise _lib.M355Error(f"eval_calibration: {bins} bins (1 .. {_lib.CAL_MAX_BINS})")
+    Cc = scores[0].shape[0] if scores[0].dim() >= 1 else 0
+    if not 1 <= Cc <= _lib.EV_MAX_CHANNELS:
+        raise _lib.M355Error(f"eval_calibration: {Cc} channels (1 .. {_lib.EV_MAX_CHANNELS})")
+    sd = _ev_code(scores[0], _EV_SCORE_DTYPE, "eval_calibration: scores")
+    descs = (_lib.EvalCalibrationDesc * n)()
+    keep = []
+    dev = scores[0].device
+    one_hot = None
+    for i, (s, t) in enumerate(zip(scores, targets)):
+        if s.dim() < 2 or s.shape[0] != Cc or s.dtype != scores[0].dtype or s.device != dev:
+            raise _lib.M355Error(f"eval_calibration: subject {i}: scores {tuple(s.shape)} {s.dtype} on {s.device}; expected "
+                                 f"[{Cc}, ...] {scores[0].dtype} on {dev}")
+        sp = tuple(s.shape[1:])
+        form = None
+        if t is not None and t.device == dev:
+            if tuple(t.shape) == tuple(s.shape):   # (with one channel [1, *spatial] is a map: pass an index as [*spatial])
+                form = True
+            elif tuple(t.shape) in (sp, (1,) + sp):
+                form = False
+        if form is None or (one_hot is not None and form != one_hot):
+            raise _lib.M355Error(f"eval_calibration: subject {i}: target "
+                                 f"{None if t is None else (tuple(t.shape), t.device)} for scores {tuple(s.shape)} on {dev}"
+                                 "; all targets one-hot maps or all index maps")
+        one_hot = form
+        s, t = s.contiguous(), t.contiguous()
+        keep += [s, t]
+        d = descs[i]
+        d.scores, d.target, d.S = s.data_ptr(), t.data_ptr(), s[0].numel()
+        d.target_dtype = _ev_code(t, _EV_TARGET_DTYPE if one_hot else _EV_INDEX_DTYPE,
+                                  f"eval_calibration: subject {i}: {'target' if one_hot else 'index map'}")
+    with torch.cuda.device(dev):
+        L = _lib.lib()
+        dev_descs = torch.empty(C.sizeof(descs), dtype=torch.uint8, device=dev)
+        packed = torch.empty(n * (bins * 3 * (1 + Cc) + Cc + 3), dtype=torch.int64, device=dev)
+        out = CalibrationCounts.unpack(packed, n, Cc, bins, kind)
+        nbytes = L.m355_eval_calibration_workspace(n)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        base = packed.data_ptr()
+        off = [0, n * bins * 3, n * bins * 3 * (1 + Cc), n * bins * 3 * (1 + Cc) + n * Cc, n * bins * 3 * (1 + Cc) + n * Cc + 2 * n]
+        ptr = [C.c_void_p(base + 8 * o) for o in off]
+        check(L.m355_eval_calibration(descs, n, _p(dev_descs), sd, _lib.EV_TARGET_ONEHOT if one_hot else _lib.EV_TARGET_MAP,
+                                      Cc, bins, _CAL_KINDS[kind], ptr[0], ptr[1], ptr[2], ptr[3], ptr[4], _p(ws), nbytes,
+                                      _stream()), "eval_calibration")
+    return out
+
+
+# ----------------------------------------------------------------- uncertainty maps (csrc/uncertainty.hip, DESIGN §4.31)
+_UQ_KINDS = {'categorical': _lib.UQ_CATEGORICAL, 'binary': _lib.UQ_BINARY}
+
+
+def _uq_kind(kind, what):
+    if kind not in _UQ_KINDS:
+        raise _lib.M355Error(f"{what}: kind {kind!r} (one of {tuple(_UQ_KINDS)})")
+    return _UQ_KINDS[kind]
+
+
+def predictive_entropy(probs, kind='categorical', confidence=False):
+    """Entropy map of probabilities [N, C, D, H, W] (float32 / bfloat16 / float16, on the device), natural logarithm,
+    float32: 'categorical' -sum_c p_c log p_c -> [N, 1, D, H, W]; 'binary' -p log p - (1 - p) log(1 - p) of every
+    channel -> [N, C, D, H, W].  0 log 0 is 0; a NaN makes its voxel NaN and no other.  confidence=True: -> (entropy,
+    the maximum channel value [N, 1, D, H, W]).  One pass.  The same expression the ensembles' uncertainty maps use, so
+    `predictive_entropy(mean)` has the bits of their 'entropy'.  On a blended PatchPredict volume this is the tool for an
+    uncertainty map: the member-wise terms (expected entropy, mutual information) are not aggregated over tiles."""
+    k = _uq_kind(kind, "predictive_entropy")
+    if probs.dim() < 3:
+        raise _lib.M355Error(f"predictive_entropy: probabilities {tuple(probs.shape)}; expected [N, C, *spatial]")
+    sd = _ev_code(probs, _EV_SCORE_DTYPE, "predictive_entropy")
+    probs = probs.contiguous()
+    N, Cc = probs.shape[:2]
+    sp = tuple(probs.shape[2:])
+    S = math.prod(sp)
+    with torch.cuda.device(probs.device):
+        ent = torch.empty((N, Cc if kind == 'binary' else 1) + sp, dtype=torch.float32, device=probs.device)
+        conf = torch.empty((N, 1) + sp, dtype=torch.float32, device=probs.device) if confidence else None
+        check(_lib.lib().m355_predictive_entropy(_p(probs), sd, _p(ent), _p(conf), N, Cc, S, k, _stream()),
+              "predictive_entropy")
+    return (ent, conf) if confidence else ent
+
+
 # ----------------------------------------------------------------- contour images (csrc/contour.hip, DESIGN §4.13)
 PLANES = ("Saggital", "Coronal", "Axial")   # by the axis of [W, H, D] a plane fixes; the reference's spelling
 _SLICE_DTYPE = {**_EV_MAP_DTYPE, **_EV_SCORE_DTYPE}
